@@ -2,9 +2,12 @@
 """bench.py — particle-updates/s of the push + deposit + solve cycle on MI355X.
 
 Contract (one JSON line on rank 0):
-  python bench.py --gpus N --steps K --warmup W
+  python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
   N > 1 is launched by the driver as
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+A plain run sets up, runs W warm-up steps, times K steps and prints the headline's line (ms_per_step = one timed
+step).  --dump-outputs DIR writes what the last timed step computed (dump_outputs).  --full measures the rest as
+well: the CPU baselines, the extensions at N=1 and the strong_c4 block.
 
 Workload (BASELINE.json configs[1]): axisymmetric (r,z) grid 1024 x 1024, 1e8 particles
 per GPU, fp32, single species, synthetic uniform plasma: uniform in the
@@ -692,6 +695,37 @@ def measured_traffic(config):
     return best
 
 
+DUMP_SAMPLE = 1 << 18          # particles written by --dump-outputs (7 MB with their masks; the grids are 20 MB each at 1024^2)
+
+
+def dump_outputs(sim, out_dir, seed=0x5EEDF051):
+    """--dump-outputs: what a caller of the timed frame receives after its last step, as float32 .npy files.  The grids in full
+    (readDensity: moments01_avgA, readMoments: this frame's moments; both (nz, nr, 4)); the particles in the library's particle
+    order (fpic_get_particles undoes the re-binning) at DUMP_SAMPLE sorted indices drawn from a fixed seed, or all of them when
+    there are fewer.
+    The reference's frame makes NaNs of its own: a particle re-injected through a NaN site of the inverse
+    CDF has NaN coordinates, poisons the moments of the cells it lands in, and the running average keeps that NaN.  Every file
+    stays finite: a non-finite value is written as 0, and <name>_nonfinite.npy marks it, one number per cell or particle whose
+    bit k is set when channel k was not finite."""
+    os.makedirs(out_dir, exist_ok=True)
+    shape = (sim.nz, sim.nr, 4)
+    outs = {"density": sim.readDensity(np.float32).reshape(shape), "moments": sim.readMoments(np.float32).reshape(shape)}
+    parts = sim.getParticles(np.float32, rand=False)
+    n = parts["alive"].size
+    idx = np.sort(np.random.default_rng(seed).choice(n, DUMP_SAMPLE, replace=False)) if n > DUMP_SAMPLE else np.arange(n)
+    outs["position"] = parts["position"][idx]
+    outs["velocity"] = parts["velocity"][idx]
+    alive = parts["alive"][idx]
+    del parts
+    for name in list(outs):
+        bad = ~np.isfinite(outs[name])
+        outs[name + "_nonfinite"] = (bad * (1 << np.arange(bad.shape[-1]))).sum(axis=-1)
+        outs[name] = np.where(bad, 0, outs[name])
+    outs["alive"] = alive
+    for name, a in outs.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -728,7 +762,15 @@ def main():
     ap.add_argument("--c4-ghost", type=int, default=4)
     ap.add_argument("--no-sink", action="store_true", help="development: no sink cells, hence no re-injected particles (ablation of the re-binning trigger)")
     ap.add_argument("--sort-interval", type=int, default=0, help="development: fixed re-binning period in frames (0 = the adaptive trigger)")
-    ap.add_argument("--no-extensions", action="store_true", help="skip the extension measurements at N=1 (counter RNG, dense solver)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure everything beside the headline as well: the CPU baselines, the extensions at N=1 (counter RNG, CIC "
+                         "deposit, Node host, dense solver, c3, em, c5_one_gpu) and the strong_c4 block.  Off by default: a plain run "
+                         "sets up, warms up, times the headline's steps and prints its line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the headline's last step computed as DIR/<name>.npy (float32): "
+                         "density and moments on the (r,z) grid, position / velocity / alive of a fixed, seeded sample of rank 0's particles; "
+                         "every file finite, the reference's NaNs marked in <name>_nonfinite.npy")
+    ap.add_argument("--no-extensions", action="store_true", help="with --full: skip the extension measurements at N=1 (counter RNG, dense solver)")
     ap.add_argument("--no-c5", action="store_true", help="skip extensions.c5_one_gpu (BASELINE configs[4] at full size on one GPU: about a minute)")
     ap.add_argument("--no-strong-c4", action="store_true", help="development: skip the strong_c4 block (BASELINE configs[3] as one decomposed run over the ranks)")
     ap.add_argument("--bootstrap", choices=["nccl", "gloo"], default="nccl",
@@ -737,6 +779,10 @@ def main():
                          "LOCAL_RANK %% device_count, so that N processes can share one GPU with a stand-in bound through FPIC_RCCL_LIBRARY "
                          "(tests/fake_rccl/fake_rccl_shm.cpp) and run the exact process topology of the N-GPU launch; its line says so and is no measurement")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs and (args.workload != "rz" or args.only_c3 or args.only_c4 or args.only_em):
+        ap.error("--dump-outputs writes the headline's outputs: not with --workload box or --only-*")
 
     import torch
     import fusionpic as fp
@@ -927,6 +973,8 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device=args.reduce_device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(sim, args.dump_outputs)
 
     if rank == 0:
         n_total = int(args.total_particles) if strong else n_local * world
@@ -995,12 +1043,12 @@ def main():
                 out["roofline"]["traffic_rate_frac_of_peak"] = rate / HBM_PEAK_GBS
         if args.rng == "counter":
             out["config"]["workload"] += "; EXTENSION: counter-based RNG (Philox4x32-10) instead of the reference's entropy-table generator"
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(spec)
             out["cpu_baseline"]["gpu_over_cpu"] = out["value"] / out["cpu_baseline"]["value"]
 
     sim.destroy()
-    if rank == 0 and world == 1 and not distributed and args.rng == "reference" and not args.no_extensions:
+    if rank == 0 and world == 1 and not distributed and args.rng == "reference" and args.full and not args.no_extensions:
         # Extension, reported beside the headline and never as it: same scene, same frame, with
         # the counter-based generator (no entropy table, no per-particle random state).
         ext = build("counter")
@@ -1072,10 +1120,10 @@ def main():
             except Exception as e:
                 out["extensions"]["c5_one_gpu"] = {"value": None, "error": "%s: %s" % (type(e).__name__, e)}
             torch.cuda.empty_cache()
-    if not args.no_strong_c4:
+    if args.full and not args.no_strong_c4:
         # north_star's scaling target lives on another workload than the parity-pinned headline: BASELINE configs[3]
         # (512^3 nodes, 2e9 particles, two species) as ONE decomposed run over the launcher's ranks — a fixed total, so
-        # N = 1, 2, 4, 8 of the driver's plain `bench.py --gpus N` trace the strong-scaling curve in this block, over the
+        # N = 1, 2, 4, 8 of `bench.py --gpus N --full` trace the strong-scaling curve in this block, over the
         # library's own RCCL communicator (there is no other transport here: a failure to set it up ends the run).
         torch.cuda.empty_cache()
         # A rank that fails inside this block leaves the others waiting in a collective of the library, rank 0 possibly

@@ -142,12 +142,12 @@ def test_bench_box_workload_under_the_launcher(tmp_path, world, solver):
 
 
 def test_bench_default_command_under_the_launcher(tmp_path):
-    """The driver's plain `bench.py --gpus 2` (the (r,z) headline sharded over the library's communicator with the all-reduce
+    """`bench.py --gpus 2 --full` (the (r,z) headline sharded over the library's communicator with the all-reduce
     on the side stream, then the strong_c4 block) as two processes on this one GPU, at a reduced size."""
     env = dict(os.environ, FPIC_RCCL_LIBRARY=fake_lib("procs"), MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port", str(free_port()),
            os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "5", "--warmup", "1", "--bootstrap", "gloo", "--no-cpu-baseline", "--side", "1000", "--grid", "256",
-           "--c4-grid", "64", "--c4-particles", "4e6", "--c4-ghost", "2"]
+           "--c4-grid", "64", "--c4-particles", "4e6", "--c4-ghost", "2", "--full"]
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=420)
     assert p.returncode == 0, p.stderr.decode()[-3000:]
     lines = [ln for ln in p.stdout.decode().splitlines() if ln.strip()]
