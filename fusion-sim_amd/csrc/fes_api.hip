@@ -19,8 +19,11 @@
 //   fes_host_io.inc.hpp     uploads, downloads, creation of the state
 //   fes_checkpoint.inc.hpp  checkpoint files (box, rank of a decomposition)
 //   fes_domain.inc.hpp      the z-slab decomposition: message lists, both transports, migration, decomposed solves and cycles
+//   fes_diag.inc.hpp        the energy diagnostics: the reductions, the recording ring, the ranks' combination
 #include "fes_api.hpp"
 #include "fes_kernels.hpp"
+#include "fes_diag_kernels.hpp"
+#include "fes_diag_core.hpp"
 #include "fes_fft.hpp"
 #include "fes_tri.hpp"
 #include "fpic_comm.hpp"
@@ -99,6 +102,7 @@ void release(fpic_handle* h)
     State* st = h->es;
     if (!st) return;
     for (Species& s : st->sp) free_species(s);
+    diag_release(st->diag);
     if (Domain* d = st->dom) {
         for (void* p : { static_cast<void*>(d->ghost_recv[0]), static_cast<void*>(d->ghost_recv[1]), d->mig_send[0], d->mig_send[1], d->mig_recv[0],
                          d->mig_recv[1], static_cast<void*>(d->counts_dev), static_cast<void*>(d->j_recv[0]), static_cast<void*>(d->j_recv[1]) })
@@ -328,6 +332,8 @@ namespace {
 
 } // namespace
 
+#include "fes_diag.inc.hpp"
+
 int precalc(fpic_handle* h)
 {
     if (h->es->dom) {
@@ -378,17 +384,23 @@ int substeps(fpic_handle* h, int nsub)
     if (h->es->dom) {
         Ranks rk;
         if (int e = dom_ranks_of(h, rk)) return e;
-        for (int k = 0; k < nsub; ++k)
+        for (int k = 0; k < nsub; ++k) {
             if (int rc = h->prec == FPIC_F32 ? dom_substep<float>(rk) : dom_substep<double>(rk)) return rc;
+            if (int rc = diag_after_substep(h)) return rc;
+        }
         return FPIC_OK;
     }
     if (h->es->solver == FPIC_SOLVER_YEE) {
-        for (int k = 0; k < nsub; ++k)
+        for (int k = 0; k < nsub; ++k) {
             if (int rc = h->prec == FPIC_F32 ? em_substep<float>(h) : em_substep<double>(h)) return rc;
+            if (int rc = diag_after_substep(h)) return rc;
+        }
         return FPIC_OK;
     }
-    for (int k = 0; k < nsub; ++k)
+    for (int k = 0; k < nsub; ++k) {
         if (int rc = h->prec == FPIC_F32 ? substep<float>(h) : substep<double>(h)) return rc;
+        if (int rc = diag_after_substep(h)) return rc;
+    }
     return FPIC_OK;
 }
 
@@ -695,8 +707,11 @@ int group_run(fpic_handle** hs, int n, int what, int ncalls)
     for (int r = 0; r < n; ++r) hs[r]->err.clear();
     if (what == 0) return report(h0->prec == FPIC_F32 ? dom_precalc<float>(rk) : dom_precalc<double>(rk));
     if (what == 2) return report(h0->es->solver != FPIC_SOLVER_YEE ? FPIC_OK : (h0->prec == FPIC_F32 ? dom_density<float>(rk) : dom_density<double>(rk)));
-    for (int k = 0; k < 2 * ncalls; ++k)
+    for (int k = 0; k < 2 * ncalls; ++k) {
         if (int rc = h0->prec == FPIC_F32 ? dom_substep<float>(rk) : dom_substep<double>(rk)) return report(rc);
+        for (fpic_handle* h : rk.hs) // (every member records its own rows, on the group's stream)
+            if (int rc = diag_after_substep(h)) return report(rc);
+    }
     return FPIC_OK;
 }
 

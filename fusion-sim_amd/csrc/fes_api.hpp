@@ -31,6 +31,10 @@ int domain_stats(fpic_handle* h, uint64_t* migrated, uint64_t* lost);
 bool is_decomposed(const fpic_handle* h);
 int group_run(fpic_handle** hs, int n, int what /* 0 precalc, 1 step, 2 density */, int ncalls);
 uint64_t particle_count(const fpic_handle* h);
+// energy diagnostics (fes_diag.inc.hpp)
+int energy_now(fpic_handle* h, int scope, fpic_energy* out);
+int energy_record(fpic_handle* h, int every, uint32_t capacity);
+int energy_history(fpic_handle* h, int scope, fpic_energy* rows, uint64_t capacity, uint64_t* n, uint64_t* dropped);
 uint64_t last_spill(const fpic_handle* h); // out-of-window deposits of the sub-step before last (lagged read-back)
 
 } // namespace fes

@@ -1201,6 +1201,18 @@ __global__ __launch_bounds__(256) void em_nodes_kernel(const T* __restrict__ Ey,
 }
 
 // B -= cb * curl E (em_update_b) on the planes k0 .. k0 + nk - 1 (they and the one above them are held)
+// half a step of curl E on the faces of held node (i, j, k) whose upper neighbours are ip, jp, kp (held places): B loses
+// (cx, cy, cz).  Shared by the B half step and the energy diagnostics, which form B of the integer time from the half-time
+// array without storing it (fes_diag_kernels.hpp)
+template <typename T>
+__device__ __forceinline__ void em_half_curl(const T* __restrict__ Ey, size_t sy, size_t sz, int i, int j, int k, int ip, int jp, int kp, T cbx, T cby,
+                                             T cbz, T& cx, T& cy, T& cz)
+{
+    cx = (FES_AT(Ey, i, jp, k, 2) - FES_AT(Ey, i, j, k, 2)) * cby - (FES_AT(Ey, i, j, kp, 1) - FES_AT(Ey, i, j, k, 1)) * cbz;
+    cy = (FES_AT(Ey, i, j, kp, 0) - FES_AT(Ey, i, j, k, 0)) * cbz - (FES_AT(Ey, ip, j, k, 2) - FES_AT(Ey, i, j, k, 2)) * cbx;
+    cz = (FES_AT(Ey, ip, j, k, 1) - FES_AT(Ey, i, j, k, 1)) * cbx - (FES_AT(Ey, i, jp, k, 0) - FES_AT(Ey, i, j, k, 0)) * cby;
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void em_update_b_kernel(T* By, const T* __restrict__ Ey, int nx, int ny, int nz, T cbx, T cby, T cbz, int k0,
                                                           int nk, Held held, const T* Bin = nullptr)
@@ -1214,9 +1226,8 @@ __global__ __launch_bounds__(256) void em_update_b_kernel(T* By, const T* __rest
     if ((k | kp) < 0) return;
     const size_t c = i + sy * j + sz * k;
     const int ip = (i + 1 == nx) ? 0 : i + 1, jp = (j + 1 == ny) ? 0 : j + 1;
-    const T cx = (FES_AT(Ey, i, jp, k, 2) - FES_AT(Ey, i, j, k, 2)) * cby - (FES_AT(Ey, i, j, kp, 1) - FES_AT(Ey, i, j, k, 1)) * cbz;
-    const T cy = (FES_AT(Ey, i, j, kp, 0) - FES_AT(Ey, i, j, k, 0)) * cbz - (FES_AT(Ey, ip, j, k, 2) - FES_AT(Ey, i, j, k, 2)) * cbx;
-    const T cz = (FES_AT(Ey, ip, j, k, 1) - FES_AT(Ey, i, j, k, 1)) * cbx - (FES_AT(Ey, i, jp, k, 0) - FES_AT(Ey, i, j, k, 0)) * cby;
+    T cx, cy, cz;
+    em_half_curl(Ey, sy, sz, i, j, k, ip, jp, kp, cbx, cby, cbz, cx, cy, cz);
     By[4 * c] = Bin[4 * c] - cx;
     By[4 * c + 1] = Bin[4 * c + 1] - cy;
     By[4 * c + 2] = Bin[4 * c + 2] - cz;

@@ -35,6 +35,24 @@ struct Species {
     void* em_args = nullptr;           // EmPushArgs of the last full-EM launch, resident for the kernel's out-of-line paths
 };
 
+// the energy diagnostics (fes_diag.inc.hpp): the sub-step counter of fpic_energy, the recording ring, the reduction's buffers
+struct Diag {
+    uint64_t substep = 0;              // sub-steps advanced since create
+    int every = 0;                     // record after every `every`-th sub-step; 0: off
+    fesdiag::Ring ring;
+    fpic_energy* ring_dev = nullptr;   // [ring.cap] rows
+    double* partial = nullptr;         // partial rows of the species passes and of the field pass
+    fpic_energy* row_dev = nullptr;    // the row of fpic_energy_now
+    void* gather = nullptr;            // the ranks' rows of a collective call
+    size_t gather_bytes = 0;
+};
+inline void diag_release(Diag& g)
+{
+    for (void* p : { static_cast<void*>(g.ring_dev), static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather })
+        if (p) (void)hipFree(p);
+    g = Diag();
+}
+
 struct State {
     int nx = 0, ny = 0, nz = 0;
     double lx = 0, ly = 0, lz = 0, W = 1;
@@ -82,6 +100,7 @@ struct State {
     void* fft_tw[3] = {};   // twiddle tables exp(-2 pi i t / n) of the three axes (T pairs)
     std::vector<Species> sp;
     struct Domain* dom = nullptr; // z-slab decomposition over several GPUs (fpic_domain_init)
+    Diag diag;
 };
 
 // Spatial decomposition: rank r of `world` owns the particles whose cell lies in the

@@ -1381,6 +1381,24 @@ int fpic_group_step(fpic_handle** handles, int n, int ncalls)
     if (ncalls < 0 || ncalls > (1 << 29)) return fail(handles[0], FPIC_ERR_INVALID_ARG, ".ncalls <- out of range");
     return fes::group_run(handles, n, 1, ncalls);
 }
+int fpic_energy_now(fpic_handle* h, int scope, fpic_energy* out)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_energy_now");
+    return fes::energy_now(h, scope, out);
+}
+int fpic_energy_record(fpic_handle* h, int every, uint32_t capacity)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_energy_record");
+    return fes::energy_record(h, every, capacity);
+}
+int fpic_energy_history(fpic_handle* h, int scope, fpic_energy* rows, uint64_t capacity, uint64_t* n, uint64_t* dropped)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_energy_history");
+    return fes::energy_history(h, scope, rows, capacity, n, dropped);
+}
 int fpic_get_particles_of(fpic_handle* h, int species, void* pos_aos, void* vel_aos, int dtype)
 {
     CHECK_HANDLE(h);

@@ -43,6 +43,7 @@ ABI_FUNCTIONS = [
     "fpic_comm_unique_id", "fpic_comm_init", "fpic_comm_destroy", "fpic_comm_info", "fpic_comm_set_overlap",
     "fpic_domain_init", "fpic_domain_set_particles", "fpic_domain_get_particles", "fpic_domain_stats",
     "fpic_group_precalc", "fpic_group_step", "fpic_group_density",
+    "fpic_energy_now", "fpic_energy_record", "fpic_energy_history",
 ]
 
 
@@ -77,6 +78,50 @@ class Stats(ctypes.Structure):
 
     def as_dict(self):
         return {name: getattr(self, name) for name, _ in self._fields_ if name != "reserved"}
+
+
+ENERGY_SPECIES = 16
+DIAG_LOCAL, DIAG_GLOBAL = 0, 1
+
+
+class Energy(ctypes.Structure):
+    """mirror of fpic_energy (include/fusionpic.h)"""
+    _fields_ = [
+        ("substep", ctypes.c_uint64), ("nspecies", ctypes.c_int32), ("reserved_i32", ctypes.c_int32),
+        ("field_e", ctypes.c_double), ("field_b", ctypes.c_double), ("field_b_external", ctypes.c_double),
+        ("count", ctypes.c_uint64 * ENERGY_SPECIES), ("kinetic", ctypes.c_double * ENERGY_SPECIES),
+        ("momentum", (ctypes.c_double * 3) * ENERGY_SPECIES), ("speed_max", ctypes.c_double * ENERGY_SPECIES),
+        ("reserved", ctypes.c_double * 8),
+    ]
+
+
+# one fpic_energy row as a numpy record (energyHistory); the same bytes as Energy
+ENERGY_DTYPE = np.dtype([
+    ("substep", "<u8"), ("nspecies", "<i4"), ("reserved_i32", "<i4"), ("field_e", "<f8"), ("field_b", "<f8"),
+    ("field_b_external", "<f8"), ("count", "<u8", (ENERGY_SPECIES,)), ("kinetic", "<f8", (ENERGY_SPECIES,)),
+    ("momentum", "<f8", (ENERGY_SPECIES, 3)), ("speed_max", "<f8", (ENERGY_SPECIES,)), ("reserved", "<f8", (8,)),
+])
+
+
+def _energy_dict(row, nspecies=None):
+    """{substep, field_e, field_b, field_b_external, count, kinetic, momentum, speed_max} of one row (a numpy record of
+    ENERGY_DTYPE); the per-species entries cut to the box's species"""
+    ns = int(row["nspecies"]) if nspecies is None else nspecies
+    return {"substep": int(row["substep"]), "nspecies": ns, "field_e": float(row["field_e"]), "field_b": float(row["field_b"]),
+            "field_b_external": float(row["field_b_external"]), "count": np.array(row["count"][:ns], dtype=np.uint64),
+            "kinetic": np.array(row["kinetic"][:ns]), "momentum": np.array(row["momentum"][:ns]),
+            "speed_max": np.array(row["speed_max"][:ns])}
+
+
+def _energy_sum(rows):
+    """the rows of several handles (one sub-step of one box) combined in the given order, as the library combines ranks:
+    sums left to right, speed_max the largest"""
+    out = rows[0].copy()
+    for r in rows[1:]:
+        for key in ("field_e", "field_b", "field_b_external", "count", "kinetic", "momentum"):
+            out[key] = out[key] + r[key]
+        out["speed_max"] = np.maximum(out["speed_max"], r["speed_max"])
+    return out
 
 
 _lib = None
@@ -152,6 +197,9 @@ def load_library(path=None):
     lib.fpic_add_b.argtypes = [vp, ctypes.c_double, ctypes.c_double, ctypes.c_double]
     lib.fpic_set_field3.argtypes = [vp, ci, vp, ci, ci, ci, ci]
     lib.fpic_read_field3.argtypes = [vp, ci, vp, ci]
+    lib.fpic_energy_now.argtypes = [vp, ci, ctypes.POINTER(Energy)]
+    lib.fpic_energy_record.argtypes = [vp, ci, ctypes.c_uint32]
+    lib.fpic_energy_history.argtypes = [vp, ci, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -594,6 +642,33 @@ class ElectrostaticBoxPusher:
         self._check(self._lib.fpic_read_field3(self._h, which, out.ctypes.data, code))
         return out.reshape(self.nodes, 4) if four else out
 
+    # ---- energy and momentum diagnostics (fpic_energy_*), reduced on the device
+    def _energy_row(self, scope):
+        e = Energy()
+        self._check(self._lib.fpic_energy_now(self._h, {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope], ctypes.byref(e)))
+        return np.frombuffer(bytes(e), dtype=ENERGY_DTYPE)[0]
+
+    def energy(self, scope="global"):
+        """{substep, field_e, field_b, field_b_external (J), count, kinetic (J), momentum (kg m/s), speed_max (c)} now;
+        per-species entries are arrays over the species.  'global' on a rank with a communicator is collective; on a
+        member of an in-process group it is an error (BoxGroup.energy sums the members)."""
+        return _energy_dict(self._energy_row(scope))
+
+    def recordEnergy(self, every, capacity=4096):
+        """after every `every`-th sub-step the same reduction goes into a device ring of `capacity` rows (0: off)"""
+        self._check(self._lib.fpic_energy_record(self._h, int(every), int(capacity)))
+
+    def energyHistory(self, scope="global"):
+        """(rows, dropped): the rows recorded since the last call, oldest first, as a numpy structured array of
+        ENERGY_DTYPE, and how many older rows the ring overwrote"""
+        sc = {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope]
+        n, dropped = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self._lib.fpic_energy_history(self._h, sc, None, 0, ctypes.byref(n), ctypes.byref(dropped)))
+        rows = np.zeros(n.value, dtype=ENERGY_DTYPE)
+        self._check(self._lib.fpic_energy_history(self._h, sc, rows.ctypes.data if n.value else None, n.value,
+                                                  ctypes.byref(n), ctypes.byref(dropped)))
+        return rows, int(dropped.value)
+
 
 class BoxGroup:
     """All ranks of a z-slab decomposition as handles of this process on one GPU (fpic_group_*): the in-process
@@ -617,6 +692,10 @@ class BoxGroup:
     def density(self):
         """density() of every member of a full-EM group: the charge grid of the current positions, complete on own planes"""
         self._check(self._lib.fpic_group_density(self._arr, len(self.sims)))
+
+    def energy(self):
+        """the whole box: the members' LOCAL values (each its own particles and planes) combined in rank order"""
+        return _energy_dict(_energy_sum([s._energy_row("local") for s in self.sims]))
 
 
 def commUniqueId(library=None):

@@ -33,7 +33,7 @@
  * geometry 'cart3d' (+ ny, length_y, solver 'poisson_fft'|'none', macro_weight) selects the self-consistent
  * electrostatic box — an extension with no reference counterpart (include/fusionpic.h): radius, height are
  * then the box lengths along x and z, nr, nz the node counts; same method names, plus addSpecies, addB,
- * readField.  Multi-GPU (one process per GPU): empic.commUniqueId() on rank 0, simulation.commInit(id,
+ * readField, energy, recordEnergy, energyHistory.  Multi-GPU (one process per GPU): empic.commUniqueId() on rank 0, simulation.commInit(id,
  * rank, world) on every rank; density() then sums the per-cell sums over the ranks inside the library (RCCL).
  */
 'use strict';
@@ -227,6 +227,12 @@ function makeBox(spec, lib) {
         return { n: n, position: position.subarray(0, 3 * n), velocity: velocity.subarray(0, 3 * n), ids: ids.subarray(0, n) };
     };
     out.domainStats = function () { return lib.domainStats(h); };
+    // energy and momentum diagnostics, reduced on the GPU (fpic_energy_*): scope 'global' (default; collective on a rank
+    // with a communicator) or 'local' (this rank's particles and planes)
+    const scopeOf = (scope) => (scope === 'local' ? 0 : 1);
+    out.energy = function (scope) { return lib.energy(h, scopeOf(scope)); };
+    out.recordEnergy = function (every, capacity) { lib.recordEnergy(h, every, capacity === undefined ? 4096 : capacity); };  // every 0: off
+    out.energyHistory = function (scope) { return lib.energyHistory(h, scopeOf(scope)); };  // { rows (oldest first), dropped }
     out.saveCheckpoint = function (path) { lib.saveCheckpoint(h, String(path)); };   // fpic_save_checkpoint: particles of every species + fields
     out.loadCheckpoint = function (path) { lib.loadCheckpoint(h, String(path)); };
     out.sort = function () { lib.sort(h); };

@@ -720,6 +720,94 @@ static napi_value n_domain_stats(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* ---- energy and momentum diagnostics (fpic_energy_*).  One row as an object: the scalars as numbers, the per-species
+ * values as Float64Arrays over the box's species (momentum: 3 per species). */
+static napi_value energy_object(napi_env env, const fpic_energy* e)
+{
+    napi_value o, v;
+    const int ns = e->nspecies < 0 ? 0 : (e->nspecies > FPIC_ENERGY_SPECIES ? FPIC_ENERGY_SPECIES : e->nspecies);
+    NAPI_OK(env, napi_create_object(env, &o));
+    struct { const char* k; double v; } f[] = {
+        { "substep", (double)e->substep }, { "field_e", e->field_e }, { "field_b", e->field_b }, { "field_b_external", e->field_b_external },
+    };
+    for (size_t i = 0; i < sizeof f / sizeof f[0]; ++i) {
+        NAPI_OK(env, napi_create_double(env, f[i].v, &v));
+        NAPI_OK(env, napi_set_named_property(env, o, f[i].k, v));
+    }
+    const char* names[4] = { "count", "kinetic", "momentum", "speed_max" };
+    for (int a = 0; a < 4; ++a) {
+        const size_t len = (size_t)ns * (a == 2 ? 3 : 1);
+        napi_value buf, arr;
+        void* data = NULL;
+        NAPI_OK(env, napi_create_arraybuffer(env, len * sizeof(double), &data, &buf));
+        double* d = (double*)data;
+        for (int s = 0; s < ns; ++s) {
+            if (a == 0) d[s] = (double)e->count[s];
+            else if (a == 1) d[s] = e->kinetic[s];
+            else if (a == 2) { d[3 * s] = e->momentum[s][0]; d[3 * s + 1] = e->momentum[s][1]; d[3 * s + 2] = e->momentum[s][2]; }
+            else d[s] = e->speed_max[s];
+        }
+        NAPI_OK(env, napi_create_typedarray(env, napi_float64_array, len, buf, 0, &arr));
+        NAPI_OK(env, napi_set_named_property(env, o, names[a], arr));
+    }
+    return o;
+}
+
+static int get_scope(napi_env env, napi_value v, int* scope)
+{
+    double d;
+    if (!get_double(env, v, &d)) return 0;
+    if (d != FPIC_DIAG_LOCAL && d != FPIC_DIAG_GLOBAL) { napi_throw_range_error(env, NULL, ".scope <- must be 0 (local) or 1 (global)"); return 0; }
+    *scope = (int)d;
+    return 1;
+}
+
+/* energy(h, scope) -> row */
+static napi_value n_energy(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2]; fpic_handle* h; int scope;
+    if (!get_args(env, info, 2, argv, &h) || !get_scope(env, argv[1], &scope)) return NULL;
+    fpic_energy e;
+    if (fpic_energy_now(h, scope, &e) != FPIC_OK) return throw_fpic(env, h);
+    return energy_object(env, &e);
+}
+
+/* recordEnergy(h, every, capacity) */
+static napi_value n_record_energy(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3]; fpic_handle* h; double every, cap;
+    if (!get_args(env, info, 3, argv, &h) || !get_double(env, argv[1], &every) || !get_double(env, argv[2], &cap)) return NULL;
+    if (every < 0 || every > 2147483647.0 || cap < 0 || cap > 4294967295.0) { napi_throw_range_error(env, NULL, ".every <- out of range"); return NULL; }
+    if (fpic_energy_record(h, (int)every, (uint32_t)cap) != FPIC_OK) return throw_fpic(env, h);
+    return undefined(env);
+}
+
+/* energyHistory(h, scope) -> { rows: [row, ...], dropped } (the rows recorded since the last call, oldest first) */
+static napi_value n_energy_history(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2]; fpic_handle* h; int scope;
+    if (!get_args(env, info, 2, argv, &h) || !get_scope(env, argv[1], &scope)) return NULL;
+    uint64_t n = 0, dropped = 0;
+    if (fpic_energy_history(h, scope, NULL, 0, &n, &dropped) != FPIC_OK) return throw_fpic(env, h);
+    fpic_energy* rows = NULL;
+    if (n) {
+        rows = (fpic_energy*)calloc((size_t)n, sizeof(fpic_energy));
+        if (!rows) { napi_throw_error(env, NULL, "host allocation failed"); return NULL; }
+        if (fpic_energy_history(h, scope, rows, n, &n, &dropped) != FPIC_OK) { free(rows); return throw_fpic(env, h); }
+    }
+    napi_value out, arr, v;
+    if (napi_create_object(env, &out) != napi_ok || napi_create_array_with_length(env, (size_t)n, &arr) != napi_ok) { free(rows); return NULL; }
+    for (uint64_t i = 0; i < n; ++i) {
+        napi_value row = energy_object(env, rows + i);
+        if (!row || napi_set_element(env, arr, (uint32_t)i, row) != napi_ok) { free(rows); return NULL; }
+    }
+    free(rows);
+    NAPI_OK(env, napi_set_named_property(env, out, "rows", arr));
+    NAPI_OK(env, napi_create_double(env, (double)dropped, &v));
+    NAPI_OK(env, napi_set_named_property(env, out, "dropped", v));
+    return out;
+}
+
 static napi_value n_build_arch(napi_env env, napi_callback_info info)
 {
     (void)info;
@@ -745,6 +833,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "commUniqueId", n_comm_unique_id }, { "commInit", n_comm_init }, { "commDestroy", n_comm_destroy },
         { "domainInit", n_domain_init }, { "domainSetParticles", n_domain_set_particles }, { "domainGetParticles", n_domain_get_particles },
         { "domainStats", n_domain_stats },
+        { "energy", n_energy }, { "recordEnergy", n_record_energy }, { "energyHistory", n_energy_history },
     };
     for (size_t i = 0; i < sizeof table / sizeof table[0]; ++i) {
         napi_value fn;

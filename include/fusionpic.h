@@ -392,6 +392,40 @@ int fpic_sort(fpic_handle* h);
 int fpic_save_checkpoint(fpic_handle* h, const char* path);
 int fpic_load_checkpoint(fpic_handle* h, const char* path);
 
+/* ---- CART3D energy and momentum diagnostics, reduced on the device (the oracle's field_energy, em_field_energy and
+ * kinetic_energy; the reference has no counterpart).  Sums are accumulated in double whatever the precision of the state,
+ * in a fixed order (no float atomics): the same state gives the same bits. */
+#define FPIC_ENERGY_SPECIES 16          /* = the decomposition's species limit; a box with more species gets FPIC_ERR_STATE */
+typedef struct fpic_energy {
+    uint64_t substep;                   /* sub-steps this handle has advanced since create when the values were taken */
+    int32_t  nspecies, reserved_i32;
+    double   field_e;                   /* J: 0.5 eps0 sum |E|^2 dV.  Electrostatic: node E (E4.xyz); full EM: the lattice E */
+    double   field_b;                   /* J: 0.5/mu0 sum |B|^2 dV of the lattice B at the integer time (full EM; 0 otherwise),
+                                           with the uniform external part included, as oracle em_field_energy */
+    double   field_b_external;          /* J: 0.5/mu0 |B0|^2 dV over the nodes summed (full EM; 0 otherwise): the external part of
+                                           field_b.  A rank counts its own planes, so the ranks' sum counts the box volume once */
+    uint64_t count[FPIC_ENERGY_SPECIES];
+    double   kinetic[FPIC_ENERGY_SPECIES];      /* J: 0.5 m W c^2 sum |v|^2 of the stored velocities (as oracle kinetic_energy) */
+    double   momentum[FPIC_ENERGY_SPECIES][3];  /* kg m/s: m W c sum v */
+    double   speed_max[FPIC_ENERGY_SPECIES];    /* max |v| in units of c */
+    double   reserved[8];
+} fpic_energy;
+
+#define FPIC_DIAG_LOCAL  0   /* this handle's particles and the planes it owns */
+#define FPIC_DIAG_GLOBAL 1   /* the whole simulation; with a communicator this is collective (every rank calls it) */
+
+/* Enqueues the reduction on the handle's stream, waits, fills *out.  GLOBAL on a decomposed handle without a communicator
+ * (a member of an in-process group) is FPIC_ERR_STATE: the host adds up the members' LOCAL values. */
+int fpic_energy_now(fpic_handle* h, int scope, fpic_energy* out);
+/* After every `every`-th sub-step the same reduction is enqueued behind the sub-step and its row written into a device ring
+ * of `capacity` rows: no host synchronisation, no collective.  every = 0 turns recording off and frees the ring; a new
+ * call starts an empty ring. */
+int fpic_energy_record(fpic_handle* h, int every, uint32_t capacity);
+/* The rows recorded since the last drain, oldest first (rows = NULL: *n receives how many there are, nothing is drained).
+ * If the ring wrapped, the newest `capacity` rows are returned and *dropped counts the others.  GLOBAL with a communicator
+ * is collective: every rank must hold the same number of rows (else FPIC_ERR_STATE on every rank). */
+int fpic_energy_history(fpic_handle* h, int scope, fpic_energy* rows, uint64_t capacity, uint64_t* n, uint64_t* dropped);
+
 int fpic_sync(fpic_handle* h);
 int fpic_profile(fpic_handle* h, int enable);
 int fpic_get_stats(fpic_handle* h, fpic_stats* out);
