@@ -517,7 +517,8 @@ int solve_distributed(Ranks& rk)
         Domain& d = *st->dom;
         if (st->solver == FPIC_SOLVER_YEE) { // the initial E on the edges of the slab and of its H halo planes on either side
             const int count = d.nzl + 2 * d.H;
-            em_edge_gradient_kernel<T><<<node_launch(st->nx, st->ny, count).grid, node_launch(st->nx, st->ny, count).block, 0, h->stream>>>(
+            const NodeLaunch nl = node_launch(st->nx, st->ny, count);
+            em_edge_gradient_kernel<T><<<nl.grid, nl.block, 0, h->stream>>>(
                 static_cast<const T*>(st->phi), st->nx, st->ny, st->nz, static_cast<T>(1.0 / (st->lx / st->nx)), static_cast<T>(1.0 / (st->ly / st->ny)),
                 static_cast<T>(1.0 / (st->lz / st->nz)), static_cast<T*>(st->Ey), ((d.z0 - d.H) % st->nz + st->nz) % st->nz, count, held_of(st));
             HIP_TRY(h, hipGetLastError());

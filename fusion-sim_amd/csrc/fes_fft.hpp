@@ -3,7 +3,8 @@
 // transform, k-space factor, inverse transform fused).  No reference counterpart (the reference has no field solve in its
 // step loop, empic.js:1436-1505): PARITY UNPINNED, the definition is oracle/es3d_oracle_impl.h
 // (es3d_poisson: phi_hat = rho_hat / (eps0 K^2), K^2 the eigenvalues of the 3-point Laplacian, mean mode 0), which these
-// kernels meet within the solve's tolerance (2e-5 fp32 / 1e-10 fp64), not bit for bit — exactly as rocFFT did.
+// kernels meet within the solve's tolerance (2e-5 fp32 / 1e-12 fp64 of max |phi|, tests/test_gpu_field_solve.py), not bit for
+// bit — exactly as rocFFT does.
 //
 // Why not rocFFT here: its strided-column kernels run a 512-point pass at 1.7 TB/s on this part
 // (profiles/r02_c4_kernel_stats.csv: fft_rtc_*_len512_*_sbcc, 610 us for 1.07 GB), and the conversion, k-space and
@@ -415,8 +416,11 @@ __global__ __launch_bounds__(kFftThreads) void fft_columns_kernel(T* __restrict_
             const int i = i0 + c;
             const double K2 = (k2x[i] + k2y[j]) + k2z[k];
             // 1 / K2 by the hardware's reciprocal and one Newton step (an IEEE double division is ~40 instructions, and eight of
-            // them per thread and tile were a quarter of this sweep's arithmetic): within 2 ulp of the quotient in double, i.e.
-            // the same float in all but boundary cases — inside the solve's tolerance either way (2e-5 / 1e-10)
+            // them per thread and tile were a quarter of this sweep's arithmetic): the same float as the quotient in all but
+            // boundary cases.  In double it is not the quotient to 2 ulp, but measured (tests/test_gpu_field_solve.py) the
+            // fp64 solve of a single mode meets phi = rho / (eps0 K^2) within 6e-16 of max |phi| (2.4e-16 with a second Newton
+            // step), and of a charge cloud numpy's solve within 1.2e-14, with a second step or without (that error grows with
+            // 256- and 512-point columns: the transform's, not this factor's) — far inside the solve's 1e-12
             double r = __builtin_amdgcn_rcp(K2);
             r = __builtin_fma(__builtin_fma(-K2, r, 1.0), r, r);
             const T g = (i | j | k) ? static_cast<T>(inv_eps0_n * r) : static_cast<T>(0);

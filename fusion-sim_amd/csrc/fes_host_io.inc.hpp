@@ -188,7 +188,8 @@ int create_state(fpic_handle* h)
             return rc;
     }
     // power-of-two grids (8 .. 512 nodes per axis): the library's own FFT passes; FPIC_POISSON_FFT=rocfft keeps rocFFT (a
-    // development switch: the two agree within the solve's tolerance, tests/test_gpu_es3d.py)
+    // development switch: the two agree within the solve's tolerance, 2e-5 (fp32) / 1e-12 (fp64) of max |phi|, and each
+    // meets numpy's double-precision solve within it: tests/test_gpu_field_solve.py::test_own_fft_and_rocfft_against_numpy)
     {
         const char* force = std::getenv("FPIC_POISSON_FFT");
         st->own_fft = fft_supported(st->nx) && fft_supported(st->ny) && fft_supported(st->nz) && !(force && std::strcmp(force, "rocfft") == 0);

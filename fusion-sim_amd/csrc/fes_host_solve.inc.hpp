@@ -120,13 +120,14 @@ int launch_solve(fpic_handle* h, bool convert = true)
             (rc = fft_x_inverse<T>(h, hat, rows, static_cast<T*>(st->phi))))
             return rc;
         if (convert) st->rho_fresh = false;
+        const NodeLaunch nl = node_launch(st->nx, st->ny, st->nz);
         if (st->solver == FPIC_SOLVER_YEE) {
-            em_edge_gradient_kernel<T><<<node_launch(st->nx, st->ny, st->nz).grid, node_launch(st->nx, st->ny, st->nz).block, 0, h->stream>>>(static_cast<const T*>(st->phi), st->nx, st->ny, st->nz,
+            em_edge_gradient_kernel<T><<<nl.grid, nl.block, 0, h->stream>>>(static_cast<const T*>(st->phi), st->nx, st->ny, st->nz,
                                                                                    static_cast<T>(1.0 / (st->lx / st->nx)), static_cast<T>(1.0 / (st->ly / st->ny)),
                                                                                    static_cast<T>(1.0 / (st->lz / st->nz)), static_cast<T*>(st->Ey), 0, st->nz, held_of(st));
             HIP_TRY(h, hipGetLastError());
         } else {
-            gradient_kernel<T><<<node_launch(st->nx, st->ny, st->nz).grid, node_launch(st->nx, st->ny, st->nz).block, 0, h->stream>>>(
+            gradient_kernel<T><<<nl.grid, nl.block, 0, h->stream>>>(
                 static_cast<const T*>(st->phi), st->nx, st->ny, st->nz, static_cast<T>(1.0 / (2.0 * (st->lx / st->nx))),
                 static_cast<T>(1.0 / (2.0 * (st->ly / st->ny))), static_cast<T>(1.0 / (2.0 * (st->lz / st->nz))), static_cast<T*>(st->E4));
             HIP_TRY(h, hipGetLastError());
@@ -157,12 +158,13 @@ int launch_solve(fpic_handle* h, bool convert = true)
         void* in_i[1] = { st->hat };
         void* out_i[1] = { st->phi };
         if (int rc = fft_status(h, ff.execute(st->inv, in_i, out_i, st->info_i), "rocfft_execute (inverse)")) return rc;
+        const NodeLaunch nl = node_launch(st->nx, st->ny, st->nz);
         if (st->solver == FPIC_SOLVER_YEE) // the field on the lattice's edges: Gauss's law holds exactly there
-            em_edge_gradient_kernel<T><<<node_launch(st->nx, st->ny, st->nz).grid, node_launch(st->nx, st->ny, st->nz).block, 0, h->stream>>>(static_cast<const T*>(st->phi), st->nx, st->ny, st->nz,
+            em_edge_gradient_kernel<T><<<nl.grid, nl.block, 0, h->stream>>>(static_cast<const T*>(st->phi), st->nx, st->ny, st->nz,
                                                                                    static_cast<T>(1.0 / (st->lx / st->nx)), static_cast<T>(1.0 / (st->ly / st->ny)),
                                                                                    static_cast<T>(1.0 / (st->lz / st->nz)), static_cast<T*>(st->Ey), 0, st->nz, held_of(st));
         else
-            gradient_kernel<T><<<node_launch(st->nx, st->ny, st->nz).grid, node_launch(st->nx, st->ny, st->nz).block, 0, h->stream>>>(
+            gradient_kernel<T><<<nl.grid, nl.block, 0, h->stream>>>(
                 static_cast<const T*>(st->phi), st->nx, st->ny, st->nz, static_cast<T>(1.0 / (2.0 * (st->lx / st->nx))),
                 static_cast<T>(1.0 / (2.0 * (st->ly / st->ny))), static_cast<T>(1.0 / (2.0 * (st->lz / st->nz))), static_cast<T*>(st->E4));
         HIP_TRY(h, hipGetLastError());

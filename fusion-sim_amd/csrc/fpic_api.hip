@@ -796,6 +796,14 @@ int validate_spec(const fpic_spec* s)
     if (s->raster_subpixel_bits < 0 || s->raster_subpixel_bits > 8) return fail(nullptr, FPIC_ERR_INVALID_ARG, ".raster_subpixel_bits <- must be 0 (ideal sprites) or 1..8");
     if (s->raster_subpixel_bits && s->shape != FPIC_SHAPE_REF11) return fail(nullptr, FPIC_ERR_INVALID_ARG, ".raster_subpixel_bits <- only the reference's point sprites are rasterised (shape 0)");
     if (s->geometry != FPIC_GEOM_CYL_RZ && s->geometry != FPIC_GEOM_CART3D) return fail(nullptr, FPIC_ERR_INVALID_ARG, ".geometry <- must be 0 (cyl_rz) or 1 (cart3d)");
+    // the box's tile windows map a node by wrap_near (fes_groups.hpp), defined for -n < d < 2n: a float tile's halo of two
+    // nodes reaches d = 2 on an axis of one node, and no length-1 rocFFT plan is exercised; so an axis has two nodes or more
+    if (s->geometry == FPIC_GEOM_CART3D) {
+        const char* names[3] = { "nr", "ny", "nz" };
+        const int nodes[3] = { s->nr, s->ny, s->nz };
+        for (int a = 0; a < 3; ++a)
+            if (nodes[a] < 2) return fail(nullptr, FPIC_ERR_INVALID_ARG, ".%s <- an axis of the periodic box needs at least 2 nodes (got %d)", names[a], nodes[a]);
+    }
     return FPIC_OK;
 }
 

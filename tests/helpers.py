@@ -26,6 +26,51 @@ def same_bits(a, b):
     return a.shape == b.shape and bool(np.all((a == b) | (np.isnan(a) & np.isnan(b))))
 
 
+EPS0 = 8.8541878128e-12
+
+
+def numpy_poisson(rho, L):
+    """phi of the 3-point-Laplacian Poisson problem in double with numpy's FFT: phi_hat = rho_hat / (eps0 K^2),
+    K^2 = sum_axis (2/d sin(pi m/n))^2, mean mode 0 (the definition in oracle/es3d_oracle_impl.h, not its code).
+    rho is [nz][ny][nx] (x fastest), L = (Lx, Ly, Lz)."""
+    nz, ny, nx = rho.shape
+    hat = np.fft.rfftn(rho)
+    k2 = 0.0
+    for axis, (n, length, half) in enumerate(((nz, L[2], False), (ny, L[1], False), (nx, L[0], True))):
+        m = np.arange(n // 2 + 1) if half else np.arange(n)
+        term = (2.0 * n / length * np.sin(np.pi * m / n)) ** 2
+        shape = [1, 1, 1]
+        shape[axis] = term.size
+        k2 = k2 + term.reshape(shape)
+    k2[0, 0, 0] = 1.0
+    hat /= EPS0 * k2
+    hat[0, 0, 0] = 0.0
+    return np.fft.irfftn(hat, s=rho.shape, axes=(0, 1, 2))
+
+
+# one factor of a separable eigenvector of the periodic 3-point Laplacian on n nodes: its values on the nodes 0 .. n-1
+# (-1, 0 or 1) and its Fourier mode m (eigenvalue term (2 n / L sin(pi m / n))^2)
+NODE_FACTORS = {
+    "one": (lambda n: np.ones(n), lambda n: 0),
+    "nyq": (lambda n: (-1.0) ** np.arange(n), lambda n: n // 2),
+    "qc": (lambda n: np.array([1.0, 0.0, -1.0, 0.0])[np.arange(n) % 4], lambda n: n // 4),
+    "qs": (lambda n: np.array([0.0, 1.0, 0.0, -1.0])[np.arange(n) % 4], lambda n: n // 4),
+}
+
+
+def node_mode(shape, L, pattern):
+    """rho = c_x(i) c_y(j) c_z(k), each factor one of NODE_FACTORS, laid down by unit charges ON the nodes: returns the
+    pattern [nz][ny][nx], its K^2 (phi = rho / (eps0 K^2) exactly), and the positions (x, y, z) = node (i dx, j dy, k dz) of
+    the nodes of value +1 and of value -1.  (A coordinate within 2^-15 of a cell of a node puts all its charge on that
+    node: the weight rounding of es3d_axis, oracle/es3d_oracle_impl.h.)"""
+    cx, cy, cz = (NODE_FACTORS[f][0](n) for f, n in zip(pattern, shape))
+    ideal = cz[:, None, None] * cy[None, :, None] * cx[None, None, :]
+    K2 = sum((2.0 * n / length * np.sin(np.pi * NODE_FACTORS[f][1](n) / n)) ** 2 for f, n, length in zip(pattern, shape, L))
+    d = [L[a] / shape[a] for a in range(3)]
+    at = lambda kji: np.stack([kji[:, 2] * d[0], kji[:, 1] * d[1], kji[:, 0] * d[2]], axis=1)
+    return ideal, K2, at(np.argwhere(ideal > 0)), at(np.argwhere(ideal < 0))
+
+
 DEMO_PROTON = dict(dt=2e-9, particle_mass=1.67e-27, particle_charge=1.602e-19)
 
 

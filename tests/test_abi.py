@@ -132,6 +132,17 @@ def test_c_level_validation_precedes_device_probe(fp):
     assert lib.fpic_create(None, ctypes.byref(h)) == -1
 
 
+def test_box_refuses_an_axis_of_one_node(fp):
+    """the periodic box needs two nodes or more per axis (its tile windows and the rocFFT plan are not made for one); the
+    spec check says so before any device is probed"""
+    box = dict(radius=1.0, length_y=1.0, height=1.0, nr=8, ny=8, nz=8, dt=1e-10, nparticles=0, count=10, particle_mass=1.0,
+               particle_charge=1.0, geometry="cart3d", solver="poisson_fft")
+    for key in ("nr", "ny", "nz"):
+        with pytest.raises(fp.FusionPicError) as e:
+            fp.makeCylindricalParticlePusher(dict(box, **{key: 1}))
+        assert str(e.value) == ".%s <- an axis of the periodic box needs at least 2 nodes (got 1)" % key
+
+
 @pytest.mark.skipif(has_gpu(), reason="a GPU is present")
 def test_no_cpu_fallback_without_a_device(fp):
     with pytest.raises(fp.FusionPicError) as e:

@@ -4,13 +4,14 @@ C ABI, against the build's own CPU oracle (oracle/es3d_oracle.c) and analytic kn
 PARITY UNPINNED — the reference has no self-consistent mode: what is
 compared here is the HIP path with the oracle that defines the mode.  Bar: particles, cell
 indices and the fixed-point charge grid bit-exact for a given field; the FFT solve within 2e-5
-(fp32) / 1e-10 (fp64) of the oracle's double-precision solve; Poisson single mode to 1e-6; cold
+(fp32) / 1e-10 (fp64) of the oracle's double-precision solve; Poisson single mode to 1e-6 (fp32) /
+1e-12 (fp64); cold
 plasma oscillation within 1 % of omega_p; total charge exact.
 """
 import numpy as np
 import pytest
 
-from helpers import same_bits
+from helpers import EPS0, node_mode, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -95,7 +96,8 @@ def test_push_and_deposit_bit_exact_in_a_given_field(fp, eo, precision, shape, n
 @pytest.mark.parametrize("shape", [(16, 16, 16), (32, 8, 12), (24, 20, 16), (64, 64, 64)])
 def test_poisson_solve_matches_oracle_and_single_mode(fp, eo, precision, shape):
     """rho from a random particle cloud: phi and E within tolerance of the oracle's double-precision solve;
-    and the discrete operator's eigenvector: rho = cos(k.x) gives phi = rho / (eps0 K^2) to 1e-6"""
+    and the discrete operator's eigenvector: rho = cos(k.x) gives phi = rho / (eps0 K^2) to 1e-6 (fp32) / 1e-12 (fp64)
+    — unit charges on the nodes (helpers.node_mode), rho = cos(pi i / 2) cos(pi j) sin(pi k / 2)"""
     rng = np.random.default_rng(sum(shape))
     n = 30000
     L = (0.7, 1.3, 0.9)
@@ -113,6 +115,17 @@ def test_poisson_solve_matches_oracle_and_single_mode(fp, eo, precision, shape):
     e4, w4 = sim.readField(fp.F3_E, np.float64), ora.E4.reshape(-1, 4).astype(np.float64)
     assert np.abs(e4[:, :3] - w4[:, :3]).max() <= 20 * tol * np.abs(w4[:, :3]).max()
     assert same_bits(e4[:, 3], phi)
+    sim.destroy()
+    ideal, K2, plus, minus = node_mode(shape, L, ("qc", "nyq", "qs"))
+    sim = fp.makeCylindricalParticlePusher(box_spec(shape, L, count=len(plus), macro_weight=1e9), precision=precision)
+    assert sim.addSpecies(MP, -QE, len(minus)) == 1
+    sim.set(position=plus, velocity=np.zeros_like(plus))
+    sim.set(position=minus, velocity=np.zeros_like(minus), species=1)
+    sim.precalc()
+    assert np.array_equal(sim.readField(fp.F3_RHO_FIXED), ideal.ravel().astype(np.int64) * eo.FIXED_ONE)
+    want = sim.readField(fp.F3_RHO, np.float64) / (EPS0 * K2)
+    ratio = np.abs(sim.readField(fp.F3_PHI, np.float64) - want).max() / np.abs(want).max()
+    assert ratio <= (1e-6 if precision == "fp32" else 1e-12), ratio
     sim.destroy()
 
 

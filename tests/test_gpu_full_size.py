@@ -17,7 +17,7 @@ import sys
 import numpy as np
 import pytest
 
-from helpers import ROOT, same_bits
+from helpers import ROOT, numpy_poisson, same_bits
 
 pytestmark = pytest.mark.gpu
 
@@ -371,27 +371,6 @@ def test_ranged_and_sampled_read_back(fp):
 
 
 # ------------------------------------------------------------------------------------------- the solve where it runs
-
-EPS0 = 8.8541878128e-12
-
-
-def numpy_poisson(rho, L):
-    """phi of the 3-point-Laplacian Poisson problem in double with numpy's FFT: phi_hat = rho_hat / (eps0 K^2),
-    K^2 = sum_axis (2/d sin(pi m/n))^2, mean mode 0 (the definition in oracle/es3d_oracle_impl.h, not its code)."""
-    nz, ny, nx = rho.shape
-    hat = np.fft.rfftn(rho)
-    k2 = 0.0
-    for axis, (n, length, half) in enumerate(((nz, L[2], False), (ny, L[1], False), (nx, L[0], True))):
-        m = np.arange(n // 2 + 1) if half else np.arange(n)
-        term = (2.0 * n / length * np.sin(np.pi * m / n)) ** 2
-        shape = [1, 1, 1]
-        shape[axis] = term.size
-        k2 = k2 + term.reshape(shape)
-    k2[0, 0, 0] = 1.0
-    hat /= EPS0 * k2
-    hat[0, 0, 0] = 0.0
-    return np.fft.irfftn(hat, s=rho.shape, axes=(0, 1, 2))
-
 
 @pytest.mark.parametrize("n,precision", [(256, "fp32"), (256, "fp64"), (512, "fp32")])
 def test_poisson_solve_against_numpy_at_the_sizes_it_runs_at(fp, n, precision):
