@@ -150,6 +150,7 @@ int add_species(fpic_handle* h, double mass, double charge, uint64_t count, int*
     if (!std::isfinite(z) || std::fabs(z - zr) > 1e-6 || zr == 0 || std::fabs(zr) > 255)
         return fail(h, FPIC_ERR_INVALID_ARG, ".charge <- must be a non-zero integer multiple (|Z| <= 255) of spec.particle_charge");
     if (count >= 0xFFFFFFFFull - 4096) return fail(h, FPIC_ERR_INVALID_ARG, ".count <- at most 2^32 particles per species and device");
+    if (count == 0) return fail(h, FPIC_ERR_INVALID_ARG, ".count <- must be at least 1");
     Species s;
     s.mass = mass; s.charge = charge; s.Z = static_cast<int>(zr); s.n = static_cast<size_t>(count);
     st->sp.push_back(s);

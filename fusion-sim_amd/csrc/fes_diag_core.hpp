@@ -64,7 +64,7 @@ struct Ring {
 };
 
 // out = the rows part[0], part[stride], ..., part[(nparts - 1) stride] combined in that order: sums left to right (counts,
-// energies, momenta), speed_max the largest; substep and nspecies are part[0]'s (the parts are one sub-step of one box)
+// energies, momenta), speed_max the largest (NaN if any part's is); substep and nspecies are part[0]'s (the parts are one sub-step of one box)
 inline void combine(const fpic_energy* part, size_t stride, int nparts, fpic_energy* out)
 {
     fpic_energy r = part[0];
@@ -77,7 +77,7 @@ inline void combine(const fpic_energy* part, size_t stride, int nparts, fpic_ene
             r.count[s] += q.count[s];
             r.kinetic[s] += q.kinetic[s];
             for (int a = 0; a < 3; ++a) r.momentum[s][a] += q.momentum[s][a];
-            r.speed_max[s] = std::max(r.speed_max[s], q.speed_max[s]);
+            if (q.speed_max[s] > r.speed_max[s] || q.speed_max[s] != q.speed_max[s]) r.speed_max[s] = q.speed_max[s]; // (NaN kept)
         }
     }
     *out = r;

@@ -3,7 +3,7 @@
 // partials of each species (one workgroup per species, one for the fields) and a last one-thread launch writes the row:
 //   diag_particles_kernel  one launch per species: vx, vy, vz (and x on a decomposed rank, whose dead slots have x < 0) in
 //                          16-byte loads; per lane the count, sum |v|^2 and sum v as EXACT fixed-point integers (Fix, units of
-//                          2^-80 c^2 or c: each term truncated once, the sums then independent of the particles' order — the
+//                          2^-80 c^2 or c: each term floored once, the sums then independent of the particles' order — the
 //                          binning lays a species out in an order its atomics decide, and two twin handles must agree bit
 //                          for bit) and max |v|^2; combined by lane shuffles within the wave and through LDS across its waves
 //   diag_field_kernel      the owned planes of the node E (electrostatic) or of the lattice E and B (full EM; B of the integer
@@ -21,26 +21,50 @@ namespace fes {
 constexpr int kDiagThreads = 256;
 constexpr int kDiagBlocks = 2048;      // partial rows per species: 8 workgroups of 4 waves per CU of the 256
 constexpr int kDiagFieldBlocks = 512;
-// partial row of a species pass, 64-bit words: count | sum |v|^2 (Fix: lo, hi) | sum vx, vy, vz (Fix) | max |v|^2 (double)
-constexpr int kDiagWords = 10;
+// partial row of a species pass, 64-bit words: count | sum |v|^2 (Fix: lo, hi) | sum vx, vy, vz (Fix) | max |v|^2 (double) |
+// the sums that met a term outside the fixed-point range (bit 0: |v|^2, bits 1..3: vx, vy, vz)
+constexpr int kDiagWords = 11;
 constexpr int kDiagQuantities = 6;     // count, sum |v|^2, sum vx, sum vy, sum vz, max |v|^2 (as doubles after the combine)
 
-// Fixed-point sums: value * 2^80, truncated to an integer (floor), in 128-bit two's complement.  A term below 2^15 (|v| < 181 c)
-// times 2^32 particles stays below 2^127; the resolution 2^-80 is 1e-14 of the square of a speed of 1e-5 c.
+// Fixed-point sums: value * 2^80, floored to an integer, in 128-bit two's complement.  A term below 2^15 (|v| < 181 c) times
+// 2^32 particles stays below 2^127; the resolution 2^-80 is 1e-14 of the square of a speed of 1e-5 c.  A term outside that
+// range, or not finite, adds nothing and marks its sum, which the species then reports as NaN (fix_add).
 using Fix = unsigned __int128;
+constexpr double kFixRange = 0x1p15;
+// floor(d 2^80), exactly, for |d| < kFixRange.  y = |d| 2^80 is exact (a power-of-two scale, below 2^95); so are h = floor(y
+// 2^-64) < 2^31 and r = y - h 2^64 in [0, 2^64) (the low bits of y), and the conversion of r truncates: floor(y) = h 2^64 + lo.
+// A negative d floors to -ceil(y), one below -floor(y) when y has a fraction.  (Splitting a negative x = d 2^80 directly as
+// h = -1, r = 2^64 + x instead rounds r to a multiple of 2^11 whenever |x| < 2^64.)
 __device__ __forceinline__ Fix to_fix(double d)
 {
-    const double x = d * 0x1p80;
-    const double h = floor(x * 0x1p-64);
-    const double r = x - h * 0x1p64;                 // exact, in [0, 2^64)
-    return (static_cast<Fix>(static_cast<__int128>(static_cast<long long>(h))) << 64) + static_cast<unsigned long long>(r);
+    const double y = fabs(d) * 0x1p80;
+    const double h = floor(y * 0x1p-64);
+    const double r = y - h * 0x1p64;
+    const unsigned long long lo = static_cast<unsigned long long>(r);
+    const Fix mag = (static_cast<Fix>(static_cast<unsigned long long>(h)) << 64) + lo;
+    if (!(d < 0)) return mag;
+    return ~mag + (static_cast<double>(lo) != r ? 0 : 1);  // -(mag + 1) when y has a fraction, else -mag
 }
+// the double nearest to s 2^-80 (ties to even): the magnitude's top 64 bits, with a sticky bit for any set bit below them,
+// converted in one rounding.  (Converting the two 64-bit words and adding them rounds twice: the low word of a small negative
+// sum, 2^64 - |s|, lands on a multiple of 2^11.)
 __device__ __forceinline__ double from_fix(Fix s)
 {
-    const long long hi = static_cast<long long>(static_cast<unsigned long long>(s >> 64));
-    const unsigned long long lo = static_cast<unsigned long long>(s);
-    return (static_cast<double>(hi) * 0x1p64 + static_cast<double>(lo)) * 0x1p-80;
+    const bool neg = static_cast<__int128>(s) < 0;
+    const Fix m = neg ? ~s + 1 : s;
+    const unsigned long long hi = static_cast<unsigned long long>(m >> 64);
+    double r;
+    if (!hi) {
+        r = static_cast<double>(static_cast<unsigned long long>(m));
+    } else {
+        const int sh = 64 - __clzll(static_cast<long long>(hi));                // bits of hi: m >> sh has its top bit set
+        const unsigned long long top = static_cast<unsigned long long>(m >> sh) | ((m & ((static_cast<Fix>(1) << sh) - 1)) != 0 ? 1ull : 0ull);
+        r = ldexp(static_cast<double>(top), sh);
+    }
+    return (neg ? -r : r) * 0x1p-80;
 }
+// the larger of two maxima, NaN if either is (fmax would drop it)
+__device__ __forceinline__ double max_keep_nan(double a, double b) { return (b > a || b != b) ? b : a; }
 __device__ __forceinline__ Fix shfl_xor_fix(Fix v, int off)
 {
     const unsigned long long lo = __shfl_xor(static_cast<unsigned long long>(v), off, 64);
@@ -49,20 +73,27 @@ __device__ __forceinline__ Fix shfl_xor_fix(Fix v, int off)
 }
 
 struct DiagAcc {
-    unsigned long long n = 0;
+    unsigned long long n = 0, out = 0;  // out: the sums that met a term outside the fixed-point range (bits as kDiagWords)
     Fix v2 = 0, vx = 0, vy = 0, vz = 0;
-    double m2 = 0;
+    double m2 = 0;                      // NaN once a |v|^2 is
 };
+
+// one term into its sum, or — outside the range, NaN and infinities included — its bit into `out`
+__device__ __forceinline__ void fix_add(Fix& sum, unsigned long long& out, double d, int bit)
+{
+    if (fabs(d) < kFixRange) sum += to_fix(d);
+    else out |= 1ull << bit;
+}
 
 __device__ __forceinline__ void diag_add(DiagAcc& a, double x, double y, double z)
 {
     const double v2 = x * x + y * y + z * z;
     a.n += 1;
-    a.v2 += to_fix(v2);
-    a.vx += to_fix(x);
-    a.vy += to_fix(y);
-    a.vz += to_fix(z);
-    a.m2 = fmax(a.m2, v2);
+    fix_add(a.v2, a.out, v2, 0);
+    fix_add(a.vx, a.out, x, 1);
+    fix_add(a.vy, a.out, y, 2);
+    fix_add(a.vz, a.out, z, 3);
+    a.m2 = max_keep_nan(a.m2, v2);
 }
 
 __device__ __forceinline__ void diag_store_acc(const DiagAcc& a, unsigned long long* w)
@@ -74,13 +105,15 @@ __device__ __forceinline__ void diag_store_acc(const DiagAcc& a, unsigned long l
         w[2 + 2 * k] = static_cast<unsigned long long>(f[k] >> 64);
     }
     w[9] = __double_as_longlong(a.m2);
+    w[10] = a.out;
 }
 __device__ __forceinline__ void diag_load_acc(DiagAcc& a, const unsigned long long* w)
 {
     a.n += w[0];
     Fix* f[4] = { &a.v2, &a.vx, &a.vy, &a.vz };
     for (int k = 0; k < 4; ++k) *f[k] += (static_cast<Fix>(w[2 + 2 * k]) << 64) | w[1 + 2 * k];
-    a.m2 = fmax(a.m2, __longlong_as_double(static_cast<long long>(w[9])));
+    a.m2 = max_keep_nan(a.m2, __longlong_as_double(static_cast<long long>(w[9])));
+    a.out |= w[10];
 }
 
 // the workgroup's accumulators combined (integers exactly, the maximum) -> lane 0 of wave 0 holds them on return
@@ -94,7 +127,8 @@ __device__ __forceinline__ void diag_acc_combine(DiagAcc& a)
         a.vx += shfl_xor_fix(a.vx, off);
         a.vy += shfl_xor_fix(a.vy, off);
         a.vz += shfl_xor_fix(a.vz, off);
-        a.m2 = fmax(a.m2, __shfl_xor(a.m2, off, 64));
+        a.m2 = max_keep_nan(a.m2, __shfl_xor(a.m2, off, 64));
+        a.out |= __shfl_xor(a.out, off, 64);
     }
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     if (lane == 0) diag_store_acc(a, lds[wave]);
@@ -228,11 +262,9 @@ __global__ __launch_bounds__(kDiagThreads) void diag_combine_kernel(const unsign
         diag_acc_combine(a);
         if (threadIdx.x == 0) {
             double* o = sums + s * kDiagQuantities;
+            const Fix f[4] = { a.v2, a.vx, a.vy, a.vz };
             o[0] = static_cast<double>(a.n);
-            o[1] = from_fix(a.v2);
-            o[2] = from_fix(a.vx);
-            o[3] = from_fix(a.vy);
-            o[4] = from_fix(a.vz);
+            for (int k = 0; k < 4; ++k) o[1 + k] = (a.out >> k & 1) ? __builtin_nan("") : from_fix(f[k]);
             o[5] = a.m2;
         }
         return;

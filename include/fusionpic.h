@@ -410,6 +410,11 @@ typedef struct fpic_energy {
     double   speed_max[FPIC_ENERGY_SPECIES];    /* max |v| in units of c */
     double   reserved[8];
 } fpic_energy;
+/* The particle sums are exact: every term (|v|^2, vx, vy, vz of a stored velocity, in double) is floored once to a multiple
+ * of 2^-80 (c^2 or c) and the integers are added in 128 bits, so the result does not depend on the particles' order; the
+ * sum is then rounded once to the nearest double.  A velocity that is not finite, or a term of 2^15 or more (|v| >= 181 c),
+ * cannot enter such a sum: the species' kinetic is then NaN, so is each momentum component that met one, and speed_max is
+ * NaN (a |v|^2 was NaN) or +inf.  The other species are unaffected. */
 
 #define FPIC_DIAG_LOCAL  0   /* this handle's particles and the planes it owns */
 #define FPIC_DIAG_GLOBAL 1   /* the whole simulation; with a communicator this is collective (every rank calls it) */

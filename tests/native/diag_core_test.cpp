@@ -116,6 +116,14 @@ static void combine()
     for (int i = 0; i < 4; ++i) { block[i].substep = 3 * (i % 2 + 1); block[i].field_e = i; block[i].count[0] = 1u << i; }
     fesdiag::combine(block.data() + 1, 2, 2, &out);
     CHECK(out.substep == 6 && out.field_e == 4.0 && out.count[0] == 10);
+    // a species with a NaN speed_max on one rank (a non-finite velocity) stays NaN, wherever that rank is; +inf stays +inf
+    for (int at = 0; at < 3; ++at) {
+        std::vector<fpic_energy> r3(rows);
+        r3[at].speed_max[0] = std::nan("");
+        r3[at].speed_max[1] = HUGE_VAL;
+        fesdiag::combine(r3.data(), 1, 3, &out);
+        CHECK(std::isnan(out.speed_max[0]) && out.speed_max[1] == HUGE_VAL);
+    }
 }
 
 int main()
