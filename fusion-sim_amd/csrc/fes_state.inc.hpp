@@ -45,10 +45,12 @@ struct Diag {
     fpic_energy* row_dev = nullptr;    // the row of fpic_energy_now
     void* gather = nullptr;            // the ranks' rows of a collective call
     size_t gather_bytes = 0;
+    unsigned long long* hist = nullptr; // the counters of fpic_histogram (fes_hist.inc.hpp): bins, then `outside`; grows to the largest request
+    size_t hist_words = 0;
 };
 inline void diag_release(Diag& g)
 {
-    for (void* p : { static_cast<void*>(g.ring_dev), static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather })
+    for (void* p : { static_cast<void*>(g.ring_dev), static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist) })
         if (p) (void)hipFree(p);
     g = Diag();
 }

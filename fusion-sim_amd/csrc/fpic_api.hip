@@ -1407,6 +1407,12 @@ int fpic_energy_history(fpic_handle* h, int scope, fpic_energy* rows, uint64_t c
     BOX_ONLY(h, "fpic_energy_history");
     return fes::energy_history(h, scope, rows, capacity, n, dropped);
 }
+int fpic_histogram(fpic_handle* h, const fpic_hist_spec* spec, int scope, uint64_t* counts, uint64_t* outside)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_histogram");
+    return fes::histogram(h, spec, scope, counts, outside);
+}
 int fpic_get_particles_of(fpic_handle* h, int species, void* pos_aos, void* vel_aos, int dtype)
 {
     CHECK_HANDLE(h);

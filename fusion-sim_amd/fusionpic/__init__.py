@@ -12,6 +12,7 @@ synchronously, with spec errors worded ".prop <- ..." (utilities.js:118-127).
 There is no CPU path here.  If libfusionpic.so is missing the import fails; if no
 gfx950 device is present the factory raises.
 """
+import builtins
 import ctypes
 import os
 import sys
@@ -43,7 +44,7 @@ ABI_FUNCTIONS = [
     "fpic_comm_unique_id", "fpic_comm_init", "fpic_comm_destroy", "fpic_comm_info", "fpic_comm_set_overlap",
     "fpic_domain_init", "fpic_domain_set_particles", "fpic_domain_get_particles", "fpic_domain_stats",
     "fpic_group_precalc", "fpic_group_step", "fpic_group_density",
-    "fpic_energy_now", "fpic_energy_record", "fpic_energy_history",
+    "fpic_energy_now", "fpic_energy_record", "fpic_energy_history", "fpic_histogram",
 ]
 
 
@@ -127,6 +128,62 @@ def _energy_sum(rows):
 _lib = None
 
 
+HIST_AXES = {"x": 0, "y": 1, "z": 2, "vx": 3, "vy": 4, "vz": 5, "v2": 6}
+HIST_MAX_BINS = 1 << 22
+
+
+class HistSpec(ctypes.Structure):
+    """mirror of fpic_hist_spec (include/fusionpic.h)"""
+    _fields_ = [
+        ("species", ctypes.c_int32), ("naxes", ctypes.c_int32), ("axis", ctypes.c_int32 * 2), ("bins", ctypes.c_int32 * 2),
+        ("lo", ctypes.c_double * 2), ("hi", ctypes.c_double * 2), ("reserved", ctypes.c_double * 4),
+    ]
+
+
+def _hist_spec(axes, bins, range, species):
+    """(HistSpec, shape, ranges as a float64 [naxes][2] array) of a histogram request.  Only what the structure cannot carry is refused here (an unknown
+    axis name, more than two axes, a bin count that is no 32-bit integer, arguments of the wrong length); the library checks
+    the rest."""
+    names = [axes] if isinstance(axes, str) else list(axes)
+    na = len(names)
+    if na not in (1, 2):
+        raise FusionPicError(-1, ".naxes <- must be 1 or 2")
+    nb = list(bins) if isinstance(bins, (list, tuple, np.ndarray)) else [bins] * na
+    try:
+        rg = np.asarray(range, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise FusionPicError(-1, ".range <- one (lo, hi) per axis")
+    rg = rg.reshape(1, 2) if rg.shape == (2,) and na == 1 else rg
+    if len(nb) != na:
+        raise FusionPicError(-1, ".bins <- one bin count per axis")
+    if rg.shape != (na, 2):
+        raise FusionPicError(-1, ".range <- one (lo, hi) per axis")
+    s = HistSpec()
+    s.species, s.naxes = int(species), na
+    for a in builtins.range(na):
+        if names[a] not in HIST_AXES:
+            raise FusionPicError(-1, ".axis <- must be one of x, y, z, vx, vy, vz, v2")
+        if isinstance(nb[a], bool) or not isinstance(nb[a], (int, np.integer)) or not -2 ** 31 <= int(nb[a]) < 2 ** 31:
+            raise FusionPicError(-1, ".bins <- must be a positive integer")
+        s.axis[a], s.bins[a], s.lo[a], s.hi[a] = HIST_AXES[names[a]], int(nb[a]), rg[a, 0], rg[a, 1]
+    return s, tuple(int(b) for b in nb), rg
+
+
+def _hist_call(sim, s, shape, scope):
+    """fpic_histogram of one handle -> (counts of `shape`, outside)"""
+    n = int(np.prod([max(b, 0) for b in shape], dtype=np.int64))
+    counts = np.zeros(n if 0 < n <= HIST_MAX_BINS else 1, dtype=np.uint64)   # (a refused request writes nothing)
+    outside = ctypes.c_uint64()
+    sim._check(sim._lib.fpic_histogram(sim._h, ctypes.byref(s), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope], counts.ctypes.data,
+                                       ctypes.byref(outside)))
+    return counts.reshape(shape), int(outside.value)
+
+
+def _hist_result(counts, outside, shape, rg):
+    return {"counts": counts, "outside": outside,
+            "edges": [rg[a, 0] + np.arange(shape[a] + 1) * (rg[a, 1] - rg[a, 0]) / shape[a] for a in builtins.range(len(shape))]}
+
+
 def load_library(path=None):
     """dlopen libfusionpic.so.  Fails loudly when the HIP library has not been built."""
     global _lib
@@ -200,6 +257,7 @@ def load_library(path=None):
     lib.fpic_energy_now.argtypes = [vp, ci, ctypes.POINTER(Energy)]
     lib.fpic_energy_record.argtypes = [vp, ci, ctypes.c_uint32]
     lib.fpic_energy_history.argtypes = [vp, ci, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+    lib.fpic_histogram.argtypes = [vp, ctypes.POINTER(HistSpec), ci, vp, ctypes.POINTER(ctypes.c_uint64)]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -456,6 +514,16 @@ class CylindricalParticlePusher:
         self._check(self._lib.fpic_comm_info(self._h, ctypes.byref(r), ctypes.byref(w)))
         return r.value, w.value
 
+    def histogram(self, axes, bins, range, species=0, scope="global"):
+        """Phase-space histogram of one species of a CART3D box, reduced on the device (fpic_histogram; an (r,z) handle is
+        refused).  axes: a name or a pair of names from x y z vx vy vz v2 (stored values: positions as fractions of the box,
+        velocities in units of c); bins: an int or a pair; range: (lo, hi) or a pair of them.  Returns {counts: uint64 array
+        of shape (bins0,) or (bins0, bins1), outside: the live particles in no bin, edges: the bin edges per axis}.  'global'
+        on a rank with a communicator is collective; on a member of an in-process group it is an error (BoxGroup.histogram)."""
+        s, shape, rg = _hist_spec(axes, bins, range, species)
+        counts, outside = _hist_call(self, s, shape, scope)
+        return _hist_result(counts, outside, shape, rg)
+
     def sync(self):
         self._check(self._lib.fpic_sync(self._h))
 
@@ -669,6 +737,8 @@ class ElectrostaticBoxPusher:
                                                   ctypes.byref(n), ctypes.byref(dropped)))
         return rows, int(dropped.value)
 
+    histogram = CylindricalParticlePusher.histogram
+
 
 class BoxGroup:
     """All ranks of a z-slab decomposition as handles of this process on one GPU (fpic_group_*): the in-process
@@ -696,6 +766,15 @@ class BoxGroup:
     def energy(self):
         """the whole box: the members' LOCAL values (each its own particles and planes) combined in rank order"""
         return _energy_dict(_energy_sum([s._energy_row("local") for s in self.sims]))
+
+    def histogram(self, axes, bins, range, species=0):
+        """the whole box: the members' LOCAL histograms (each its own particles) added up"""
+        s, shape, rg = _hist_spec(axes, bins, range, species)
+        parts = [_hist_call(m, s, shape, "local") for m in self.sims]
+        counts = parts[0][0]
+        for c, _ in parts[1:]:
+            counts += c
+        return _hist_result(counts, sum(p[1] for p in parts), shape, rg)
 
 
 def commUniqueId(library=None):

@@ -33,7 +33,7 @@
  * geometry 'cart3d' (+ ny, length_y, solver 'poisson_fft'|'none', macro_weight) selects the self-consistent
  * electrostatic box — an extension with no reference counterpart (include/fusionpic.h): radius, height are
  * then the box lengths along x and z, nr, nz the node counts; same method names, plus addSpecies, addB,
- * readField, energy, recordEnergy, energyHistory.  Multi-GPU (one process per GPU): empic.commUniqueId() on rank 0, simulation.commInit(id,
+ * readField, energy, recordEnergy, energyHistory, histogram.  Multi-GPU (one process per GPU): empic.commUniqueId() on rank 0, simulation.commInit(id,
  * rank, world) on every rank; density() then sums the per-cell sums over the ranks inside the library (RCCL).
  */
 'use strict';
@@ -233,6 +233,20 @@ function makeBox(spec, lib) {
     out.energy = function (scope) { return lib.energy(h, scopeOf(scope)); };
     out.recordEnergy = function (every, capacity) { lib.recordEnergy(h, every, capacity === undefined ? 4096 : capacity); };  // every 0: off
     out.energyHistory = function (scope) { return lib.energyHistory(h, scopeOf(scope)); };  // { rows (oldest first), dropped }
+    // phase-space histogram of one species, reduced on the GPU (fpic_histogram): request = { axes: one or two names from
+    // x y z vx vy vz v2, bins: one count per axis, range: one [lo, hi] per axis, species (default 0) }, over the stored
+    // values (positions as fractions of the box, velocities in units of c)
+    // -> { counts: BigUint64Array, row-major [bins[0]][bins[1]], outside }
+    const HIST_AXES = { x: 0, y: 1, z: 2, vx: 3, vy: 4, vz: 5, v2: 6 };
+    out.histogram = function (request, scope) {
+        if (request === null || typeof request !== 'object') throw new TypeError('.request <- expected { axes, bins, range, species }');
+        const axes = request.axes, bins = request.bins, range = request.range;
+        if (!Array.isArray(axes) || (axes.length !== 1 && axes.length !== 2)) throw new RangeError('.axes <- expected an array of one or two axis names');
+        if (!Array.isArray(bins) || bins.length !== axes.length || !bins.every((b) => Number.isInteger(b) && b >= 1 && b <= 0x7fffffff)) throw new RangeError('.bins <- expected one positive integer per axis');
+        if (!Array.isArray(range) || range.length !== axes.length || !range.every((r) => Array.isArray(r) && r.length === 2 && r.every((x) => typeof x === 'number'))) throw new RangeError('.range <- expected one [lo, hi] per axis');
+        const codes = axes.map((a) => { if (!(a in HIST_AXES)) throw new RangeError('.axis <- must be one of x, y, z, vx, vy, vz, v2'); return HIST_AXES[a]; });
+        return lib.histogram(h, request.species || 0, Int32Array.from(codes), Int32Array.from(bins), Float64Array.from(range.flat()), scopeOf(scope));
+    };
     out.saveCheckpoint = function (path) { lib.saveCheckpoint(h, String(path)); };   // fpic_save_checkpoint: particles of every species + fields
     out.loadCheckpoint = function (path) { lib.loadCheckpoint(h, String(path)); };
     out.sort = function () { lib.sort(h); };

@@ -808,6 +808,47 @@ static napi_value n_energy_history(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* histogram(h, species, axes: Int32Array, bins: Int32Array, ranges: Float64Array (lo, hi per axis), scope)
+ * -> { counts: BigUint64Array of bins[0] (* bins[1]), outside }.  The arrays' lengths are checked here, the request
+ * itself by the library (which is asked before a buffer of the request's size is made). */
+static napi_value n_histogram(napi_env env, napi_callback_info info)
+{
+    napi_value argv[6]; fpic_handle* h; int sp, scope;
+    if (!get_args(env, info, 6, argv, &h) || !get_species(env, argv[1], &sp) || !get_scope(env, argv[5], &scope)) return NULL;
+    napi_typedarray_type ta, tb, tr; void *pa, *pb, *pr; size_t la, lb, lr;
+    if (!get_typed(env, argv[2], &ta, &pa, &la) || !get_typed(env, argv[3], &tb, &pb, &lb) || !get_typed(env, argv[4], &tr, &pr, &lr)) return NULL;
+    if (!pa || !pb || !pr || ta != napi_int32_array || tb != napi_int32_array || tr != napi_float64_array) {
+        napi_throw_type_error(env, NULL, ".axes <- expected Int32Array axes, Int32Array bins and Float64Array ranges");
+        return NULL;
+    }
+    if (la != 1 && la != 2) { napi_throw_range_error(env, NULL, ".naxes <- must be 1 or 2"); return NULL; }
+    if (!check_len(env, "bins", lb, la) || !check_len(env, "range", lr, 2 * la)) return NULL;
+    fpic_hist_spec s;
+    memset(&s, 0, sizeof s);
+    s.species = sp; s.naxes = (int32_t)la;
+    uint64_t total = 1;
+    for (size_t a = 0; a < la; ++a) {
+        s.axis[a] = ((const int32_t*)pa)[a];
+        s.bins[a] = ((const int32_t*)pb)[a];
+        s.lo[a] = ((const double*)pr)[2 * a];
+        s.hi[a] = ((const double*)pr)[2 * a + 1];
+        if (s.bins[a] < 1) { napi_throw_range_error(env, NULL, ".bins <- must be at least 1"); return NULL; }
+        total *= (uint64_t)s.bins[a];
+    }
+    if (total > FPIC_HIST_MAX_BINS) { napi_throw_range_error(env, NULL, ".bins <- more than FPIC_HIST_MAX_BINS (2^22) bins in all"); return NULL; }
+    napi_value buf, arr, out, v;
+    void* data = NULL;
+    NAPI_OK(env, napi_create_arraybuffer(env, (size_t)total * sizeof(uint64_t), &data, &buf));
+    uint64_t outside = 0;
+    if (fpic_histogram(h, &s, scope, (uint64_t*)data, &outside) != FPIC_OK) return throw_fpic(env, h);
+    NAPI_OK(env, napi_create_typedarray(env, napi_biguint64_array, (size_t)total, buf, 0, &arr));
+    NAPI_OK(env, napi_create_object(env, &out));
+    NAPI_OK(env, napi_set_named_property(env, out, "counts", arr));
+    NAPI_OK(env, napi_create_double(env, (double)outside, &v));
+    NAPI_OK(env, napi_set_named_property(env, out, "outside", v));
+    return out;
+}
+
 static napi_value n_build_arch(napi_env env, napi_callback_info info)
 {
     (void)info;
@@ -834,6 +875,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "domainInit", n_domain_init }, { "domainSetParticles", n_domain_set_particles }, { "domainGetParticles", n_domain_get_particles },
         { "domainStats", n_domain_stats },
         { "energy", n_energy }, { "recordEnergy", n_record_energy }, { "energyHistory", n_energy_history },
+        { "histogram", n_histogram },
     };
     for (size_t i = 0; i < sizeof table / sizeof table[0]; ++i) {
         napi_value fn;

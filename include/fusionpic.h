@@ -431,6 +431,45 @@ int fpic_energy_record(fpic_handle* h, int every, uint32_t capacity);
  * is collective: every rank must hold the same number of rows (else FPIC_ERR_STATE on every rank). */
 int fpic_energy_history(fpic_handle* h, int scope, fpic_energy* rows, uint64_t capacity, uint64_t* n, uint64_t* dropped);
 
+/* ---- CART3D phase-space histograms, reduced on the device: the live particles of ONE species binned over one or two axes,
+ * without reading a particle back.  The value q of an axis is a double made from the particle's state in normalised units
+ * as stored (what fpic_get_particles_of / fpic_domain_get_particles return in the handle's own precision):
+ *   FPIC_AXIS_X, _Y, _Z     the stored position, a fraction of the box in [0, 1), converted to double
+ *   FPIC_AXIS_VX, _VY, _VZ  the stored velocity in units of c, converted to double.  Full EM (solver = YEE): the stored
+ *                           velocity is the half-time one of the leap-frog, and it is binned as stored
+ *   FPIC_AXIS_V2            vx*vx + vy*vy + vz*vz in double, added left to right, every operation rounded once
+ * Per axis the caller gives bins >= 1 and finite lo < hi; scale = bins / (hi - lo) is formed once, in double.  A particle
+ *   is INSIDE the axis iff q >= lo && q < hi (a NaN is not inside), and its index there is
+ *   k = min((int64) floor((q - lo) * scale), bins - 1)   (subtraction and product each rounded once, no fused multiply-add;
+ *                                                          the min only catches a product that rounds up to bins).
+ * A particle inside every axis adds 1 to counts[k0] (one axis) or counts[k0 * bins[1] + k1] (two axes, row-major
+ * [bins[0]][bins[1]], the layout of numpy.histogram2d); every other live particle adds 1 to *outside.  So
+ * sum(counts) + *outside = fpic_energy.count[species] always.  The dead slots of a decomposed rank are skipped.  Counts are
+ * integers added with integer atomics: the same state gives the same bits.
+ * Refused (FPIC_ERR_INVALID_ARG): naxes other than 1 or 2, a species the handle does not have, an axis code outside 0..6,
+ * the same axis twice, bins < 1, bins[0] * bins[1] above FPIC_HIST_MAX_BINS, lo / hi not finite or not lo < hi or with a
+ * bins / (hi - lo) that is not finite, a reserved word that is not zero; a handle that is not CART3D.  precalc() is not
+ * needed: the call reads particles only. */
+#define FPIC_AXIS_X  0
+#define FPIC_AXIS_Y  1
+#define FPIC_AXIS_Z  2
+#define FPIC_AXIS_VX 3
+#define FPIC_AXIS_VY 4
+#define FPIC_AXIS_VZ 5
+#define FPIC_AXIS_V2 6
+#define FPIC_HIST_MAX_BINS (1u << 22)   /* 32 MiB of counters */
+typedef struct fpic_hist_spec {
+    int32_t species, naxes;      /* naxes 1 or 2 */
+    int32_t axis[2], bins[2];    /* FPIC_AXIS_X .. FPIC_AXIS_V2 */
+    double  lo[2], hi[2];
+    double  reserved[4];         /* zero */
+} fpic_hist_spec;
+/* counts: bins[0] (* bins[1]) words; outside: one word.  scope as for fpic_energy_now: LOCAL is this handle's own particles;
+ * GLOBAL with a communicator is collective (every rank calls it with the same spec and gets the same sums); GLOBAL on a
+ * member of an in-process group is FPIC_ERR_STATE (the host adds up the members' LOCAL counts).  Synchronous: enqueues on
+ * the handle's stream, copies back, waits. */
+int fpic_histogram(fpic_handle* h, const fpic_hist_spec* spec, int scope, uint64_t* counts, uint64_t* outside);
+
 int fpic_sync(fpic_handle* h);
 int fpic_profile(fpic_handle* h, int enable);
 int fpic_get_stats(fpic_handle* h, fpic_stats* out);
