@@ -21,11 +21,13 @@
 //   fes_domain.inc.hpp      the z-slab decomposition: message lists, both transports, migration, decomposed solves and cycles
 //   fes_diag.inc.hpp        the energy diagnostics: the reductions, the recording ring, the ranks' combination
 //   fes_hist.inc.hpp        the phase-space histograms: the pass of one request, the ranks' sum
+//   fes_mom.inc.hpp         the fluid moment grids: the sweeps of one request, the held planes' places, the ranks' sum
 #include "fes_api.hpp"
 #include "fes_kernels.hpp"
 #include "fes_diag_kernels.hpp"
 #include "fes_diag_core.hpp"
 #include "fes_hist_kernels.hpp"
+#include "fes_mom_kernels.hpp"
 #include "fes_fft.hpp"
 #include "fes_tri.hpp"
 #include "fpic_comm.hpp"
@@ -337,6 +339,7 @@ namespace {
 
 #include "fes_diag.inc.hpp"
 #include "fes_hist.inc.hpp"
+#include "fes_mom.inc.hpp"
 
 int precalc(fpic_handle* h)
 {

@@ -47,10 +47,12 @@ struct Diag {
     size_t gather_bytes = 0;
     unsigned long long* hist = nullptr; // the counters of fpic_histogram (fes_hist.inc.hpp): bins, then `outside`; grows to the largest request
     size_t hist_words = 0;
+    unsigned long long* mom = nullptr;  // the buffer of fpic_moments (fes_mom.inc.hpp): a grid of the held planes per moment, then `rejected`, `spilled`; grows to the largest request
+    size_t mom_words = 0;
 };
 inline void diag_release(Diag& g)
 {
-    for (void* p : { static_cast<void*>(g.ring_dev), static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist) })
+    for (void* p : { static_cast<void*>(g.ring_dev), static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom) })
         if (p) (void)hipFree(p);
     g = Diag();
 }

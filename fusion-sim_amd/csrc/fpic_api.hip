@@ -1413,6 +1413,12 @@ int fpic_histogram(fpic_handle* h, const fpic_hist_spec* spec, int scope, uint64
     BOX_ONLY(h, "fpic_histogram");
     return fes::histogram(h, spec, scope, counts, outside);
 }
+int fpic_moments(fpic_handle* h, const fpic_moments_spec* spec, int scope, int64_t* out, fpic_moments_info* info)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_moments");
+    return fes::moments(h, spec, scope, out, info);
+}
 int fpic_get_particles_of(fpic_handle* h, int species, void* pos_aos, void* vel_aos, int dtype)
 {
     CHECK_HANDLE(h);

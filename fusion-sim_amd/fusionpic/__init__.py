@@ -44,7 +44,7 @@ ABI_FUNCTIONS = [
     "fpic_comm_unique_id", "fpic_comm_init", "fpic_comm_destroy", "fpic_comm_info", "fpic_comm_set_overlap",
     "fpic_domain_init", "fpic_domain_set_particles", "fpic_domain_get_particles", "fpic_domain_stats",
     "fpic_group_precalc", "fpic_group_step", "fpic_group_density",
-    "fpic_energy_now", "fpic_energy_record", "fpic_energy_history", "fpic_histogram",
+    "fpic_energy_now", "fpic_energy_record", "fpic_energy_history", "fpic_histogram", "fpic_moments",
 ]
 
 
@@ -184,6 +184,55 @@ def _hist_result(counts, outside, shape, rg):
             "edges": [rg[a, 0] + np.arange(shape[a] + 1) * (rg[a, 1] - rg[a, 0]) / shape[a] for a in builtins.range(len(shape))]}
 
 
+MOMENT_NAMES = ("N", "FX", "FY", "FZ", "SXX", "SYY", "SZZ", "SXY", "SXZ", "SYZ")   # bit b of a mask is MOMENT_NAMES[b]
+MOMENT_SETS = {"n": 0x001, "order1": 0x00F, "order2": 0x3FF}
+MOM_ONE = 1 << 42          # N of one particle, summed over its eight nodes
+MOM_SCALE = 1 << 32        # the fixed-point scale of every other moment
+SPEED_OF_LIGHT = 2.998e8   # (empic.js:27, as the library)
+ELECTRON_VOLT = 1.602176634e-19
+
+
+class MomentsSpec(ctypes.Structure):
+    """mirror of fpic_moments_spec (include/fusionpic.h)"""
+    _fields_ = [("species", ctypes.c_int32), ("mask", ctypes.c_uint32), ("reserved", ctypes.c_double * 4)]
+
+
+class MomentsInfo(ctypes.Structure):
+    """mirror of fpic_moments_info"""
+    _fields_ = [("rejected", ctypes.c_uint64), ("spilled", ctypes.c_uint64), ("reserved", ctypes.c_uint64 * 2)]
+
+
+def _moments_mask(which):
+    """the mask of "n" | "order1" | "order2" or of an iterable of moment names"""
+    if isinstance(which, str):
+        if which not in MOMENT_SETS:
+            raise FusionPicError(-1, ".which <- must be one of n, order1, order2 or an iterable of moment names")
+        return MOMENT_SETS[which]
+    mask = 0
+    for name in which:
+        if name not in MOMENT_NAMES:
+            raise FusionPicError(-1, ".which <- no such moment: must be among " + " ".join(MOMENT_NAMES))
+        mask |= 1 << MOMENT_NAMES.index(name)
+    return mask
+
+
+def _moments_call(sim, mask, species, scope):
+    """fpic_moments of one handle -> (int64 [popcount(mask)][nz][ny][nr], rejected, spilled)"""
+    s = MomentsSpec()
+    s.species, s.mask = int(species), int(mask) & 0xFFFFFFFF
+    nm = bin(mask & 0x3FF).count("1") if 0 < mask < 1 << 10 else 1   # (a refused request writes nothing)
+    out = np.zeros((nm, sim.nz, sim.ny, sim.nx), dtype=np.int64)
+    info = MomentsInfo()
+    sim._check(sim._lib.fpic_moments(sim._h, ctypes.byref(s), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope], out.ctypes.data, ctypes.byref(info)))
+    return out, int(info.rejected), int(info.spilled)
+
+
+def _moments_result(mask, grids, rejected, spilled):
+    out = {MOMENT_NAMES[b]: grids[k] for k, b in enumerate(b for b in builtins.range(10) if mask >> b & 1)}
+    out["rejected"], out["spilled"] = rejected, spilled
+    return out
+
+
 def load_library(path=None):
     """dlopen libfusionpic.so.  Fails loudly when the HIP library has not been built."""
     global _lib
@@ -258,6 +307,7 @@ def load_library(path=None):
     lib.fpic_energy_record.argtypes = [vp, ci, ctypes.c_uint32]
     lib.fpic_energy_history.argtypes = [vp, ci, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     lib.fpic_histogram.argtypes = [vp, ctypes.POINTER(HistSpec), ci, vp, ctypes.POINTER(ctypes.c_uint64)]
+    lib.fpic_moments.argtypes = [vp, ctypes.POINTER(MomentsSpec), ci, vp, ctypes.POINTER(MomentsInfo)]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -570,6 +620,7 @@ class ElectrostaticBoxPusher:
         self.nodes = self.nx * self.ny * self.nz
         self.counts = [count if count else int(spec["nparticles"]) ** 2]
         self.n = self.counts[0]
+        self.masses = [float(spec["particle_mass"])]
         h = ctypes.c_void_p()
         rc = self._lib.fpic_create(ctypes.byref(s), ctypes.byref(h))
         if rc != 0:
@@ -599,6 +650,7 @@ class ElectrostaticBoxPusher:
         idx = ctypes.c_int()
         self._check(self._lib.fpic_add_species(self._h, float(mass), float(charge), int(count), ctypes.byref(idx)))
         self.counts.append(int(count))
+        self.masses.append(float(mass))
         return idx.value
 
     def addB(self, bx, by, bz):
@@ -739,6 +791,38 @@ class ElectrostaticBoxPusher:
 
     histogram = CylindricalParticlePusher.histogram
 
+    # ---- fluid moment grids (fpic_moments), reduced on the device
+    def moments(self, which="order2", species=0, scope="global"):
+        """Velocity moments of one species on the node grid as exact int64 sums (fpic_moments).  which: "n" (N), "order1"
+        (N FX FY FZ), "order2" (all ten) or an iterable of names from MOMENT_NAMES.  Returns {name: int64 array of shape
+        (nz, ny, nr), rejected, spilled}: N in units of 2^-42 particles, the others in units of 2^-32 of v/c resp. (v/c)^2.
+        'global' on a rank with a communicator is collective; on a member of an in-process group it is an error
+        (BoxGroup.moments)."""
+        mask = _moments_mask(which)
+        return _moments_result(mask, *_moments_call(self, mask, species, scope))
+
+    def fluid(self, species=0, scope="global", moments=None):
+        """Fluid quantities of one species per node, float64 numpy on top of moments("order2") (or of `moments`, a result of
+        it): n (m^-3), flux[3] (m^-2 s^-1), u[3] (m/s, zero where N == 0), Pi[3][3] (momentum flux, Pa), P[3][3] (pressure,
+        Pa), T (eV, zero where N == 0); arrays shaped (..., nz, ny, nr)."""
+        return _fluid(self, moments if moments is not None else self.moments("order2", species, scope), species)
+
+
+def _fluid(sim, m, species):
+    spec = sim.spec
+    dv = (float(spec["radius"]) / sim.nx) * (float(spec["length_y"]) / sim.ny) * (float(spec["height"]) / sim.nz)
+    per = float(spec.get("macro_weight", 1.0)) / dv          # real particles per macro-particle and m^3
+    mass, c = sim.masses[species], SPEED_OF_LIGHT
+    n = m["N"].astype(np.float64) / MOM_ONE * per
+    flux = np.stack([m[k].astype(np.float64) for k in ("FX", "FY", "FZ")]) * (c / MOM_SCALE * per)
+    some = m["N"] > 0
+    u = np.divide(flux, n, out=np.zeros_like(flux), where=some)
+    S = {k: m[k].astype(np.float64) * (mass * c * c / MOM_SCALE * per) for k in ("SXX", "SYY", "SZZ", "SXY", "SXZ", "SYZ")}
+    Pi = np.array([[S["SXX"], S["SXY"], S["SXZ"]], [S["SXY"], S["SYY"], S["SYZ"]], [S["SXZ"], S["SYZ"], S["SZZ"]]])
+    P = Pi - mass * n * u[:, None] * u[None, :]
+    T = np.divide(P[0, 0] + P[1, 1] + P[2, 2], 3 * n, out=np.zeros_like(n), where=some) / ELECTRON_VOLT
+    return {"n": n, "flux": flux, "u": u, "Pi": Pi, "P": P, "T": T}
+
 
 class BoxGroup:
     """All ranks of a z-slab decomposition as handles of this process on one GPU (fpic_group_*): the in-process
@@ -775,6 +859,18 @@ class BoxGroup:
         for c, _ in parts[1:]:
             counts += c
         return _hist_result(counts, sum(p[1] for p in parts), shape, rg)
+
+    def moments(self, which="order2", species=0):
+        """the whole box: the members' LOCAL moment grids (each its own particles, on the planes it holds) added up"""
+        mask = _moments_mask(which)
+        parts = [_moments_call(m, mask, species, "local") for m in self.sims]
+        grids = parts[0][0]
+        for g, _, _ in parts[1:]:
+            grids += g
+        return _moments_result(mask, grids, sum(p[1] for p in parts), sum(p[2] for p in parts))
+
+    def fluid(self, species=0):
+        return _fluid(self.sims[0], self.moments("order2", species), species)
 
 
 def commUniqueId(library=None):

@@ -33,7 +33,7 @@
  * geometry 'cart3d' (+ ny, length_y, solver 'poisson_fft'|'none', macro_weight) selects the self-consistent
  * electrostatic box — an extension with no reference counterpart (include/fusionpic.h): radius, height are
  * then the box lengths along x and z, nr, nz the node counts; same method names, plus addSpecies, addB,
- * readField, energy, recordEnergy, energyHistory, histogram.  Multi-GPU (one process per GPU): empic.commUniqueId() on rank 0, simulation.commInit(id,
+ * readField, energy, recordEnergy, energyHistory, histogram, moments.  Multi-GPU (one process per GPU): empic.commUniqueId() on rank 0, simulation.commInit(id,
  * rank, world) on every rank; density() then sums the per-cell sums over the ranks inside the library (RCCL).
  */
 'use strict';
@@ -246,6 +246,34 @@ function makeBox(spec, lib) {
         if (!Array.isArray(range) || range.length !== axes.length || !range.every((r) => Array.isArray(r) && r.length === 2 && r.every((x) => typeof x === 'number'))) throw new RangeError('.range <- expected one [lo, hi] per axis');
         const codes = axes.map((a) => { if (!(a in HIST_AXES)) throw new RangeError('.axis <- must be one of x, y, z, vx, vy, vz, v2'); return HIST_AXES[a]; });
         return lib.histogram(h, request.species || 0, Int32Array.from(codes), Int32Array.from(bins), Float64Array.from(range.flat()), scopeOf(scope));
+    };
+    // fluid moment grids of one species, reduced on the GPU (fpic_moments): request = { species (default 0), which: 'n' | 'order1' |
+    // 'order2' (default) | an array of names from N FX FY FZ SXX SYY SZZ SXY SXZ SYZ }
+    // -> { NAME: BigInt64Array [nz][ny][nr] per moment asked for (N in units of 2^-42 particles, the others of 2^-32), rejected, spilled }
+    const MOMENT_NAMES = ['N', 'FX', 'FY', 'FZ', 'SXX', 'SYY', 'SZZ', 'SXY', 'SXZ', 'SYZ'];
+    const MOMENT_SETS = { n: 0x001, order1: 0x00F, order2: 0x3FF };
+    out.moments = function (request, scope) {
+        if (request === null || typeof request !== 'object') throw new TypeError('.request <- expected { species, which }');
+        const which = request.which === undefined ? 'order2' : request.which;
+        let mask = 0;
+        if (typeof which === 'string') {
+            if (!(which in MOMENT_SETS)) throw new RangeError('.which <- must be one of n, order1, order2 or an array of moment names');
+            mask = MOMENT_SETS[which];
+        } else if (Array.isArray(which)) {
+            for (const name of which) {
+                const bit = MOMENT_NAMES.indexOf(name);
+                if (bit < 0) throw new RangeError('.which <- no such moment: must be among ' + MOMENT_NAMES.join(' '));
+                mask |= 1 << bit;
+            }
+        } else {
+            throw new TypeError('.which <- must be one of n, order1, order2 or an array of moment names');
+        }
+        if (mask === 0) throw new RangeError('.mask <- no moment asked for');
+        const names = MOMENT_NAMES.filter((_, b) => (mask >> b) & 1);
+        const grids = new BigInt64Array(names.length * nodes);
+        const res = lib.moments(h, request.species || 0, mask, scopeOf(scope), grids);
+        names.forEach((name, k) => { res[name] = grids.subarray(k * nodes, (k + 1) * nodes); });
+        return res;
     };
     out.saveCheckpoint = function (path) { lib.saveCheckpoint(h, String(path)); };   // fpic_save_checkpoint: particles of every species + fields
     out.loadCheckpoint = function (path) { lib.loadCheckpoint(h, String(path)); };

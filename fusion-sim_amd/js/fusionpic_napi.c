@@ -849,6 +849,36 @@ static napi_value n_histogram(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* moments(h, species, mask, scope, out: BigInt64Array of popcount(mask) * nodes) -> { rejected, spilled }; the grids land in
+ * `out` in ascending bit order.  The array's type and length are checked here, the request itself by the library. */
+static napi_value n_moments(napi_env env, napi_callback_info info)
+{
+    napi_value argv[5]; fpic_handle* h; int sp, scope; double mask;
+    if (!get_args(env, info, 5, argv, &h) || !get_species(env, argv[1], &sp) || !get_double(env, argv[2], &mask) || !get_scope(env, argv[3], &scope)) return NULL;
+    if (!(mask >= 1 && mask <= (double)FPIC_MOM_ORDER2) || mask != (double)(uint32_t)mask) {
+        napi_throw_range_error(env, NULL, ".mask <- must be a mask of FPIC_MOM_N .. FPIC_MOM_SYZ (bits 0 .. 9), not zero");
+        return NULL;
+    }
+    napi_typedarray_type t; void* data; size_t len;
+    if (!get_typed(env, argv[4], &t, &data, &len)) return NULL;
+    if (!data || t != napi_bigint64_array) { napi_throw_type_error(env, NULL, ".out <- expected a BigInt64Array"); return NULL; }
+    size_t grids = 0;
+    for (uint32_t m = (uint32_t)mask; m; m &= m - 1) ++grids;
+    if (!check_len(env, "out", len, grids * g_box->nodes)) return NULL;
+    fpic_moments_spec s;
+    memset(&s, 0, sizeof s);
+    s.species = sp; s.mask = (uint32_t)mask;
+    fpic_moments_info mi;
+    if (fpic_moments(h, &s, scope, (int64_t*)data, &mi) != FPIC_OK) return throw_fpic(env, h);
+    napi_value out, v;
+    NAPI_OK(env, napi_create_object(env, &out));
+    NAPI_OK(env, napi_create_double(env, (double)mi.rejected, &v));
+    NAPI_OK(env, napi_set_named_property(env, out, "rejected", v));
+    NAPI_OK(env, napi_create_double(env, (double)mi.spilled, &v));
+    NAPI_OK(env, napi_set_named_property(env, out, "spilled", v));
+    return out;
+}
+
 static napi_value n_build_arch(napi_env env, napi_callback_info info)
 {
     (void)info;
@@ -875,7 +905,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "domainInit", n_domain_init }, { "domainSetParticles", n_domain_set_particles }, { "domainGetParticles", n_domain_get_particles },
         { "domainStats", n_domain_stats },
         { "energy", n_energy }, { "recordEnergy", n_record_energy }, { "energyHistory", n_energy_history },
-        { "histogram", n_histogram },
+        { "histogram", n_histogram }, { "moments", n_moments },
     };
     for (size_t i = 0; i < sizeof table / sizeof table[0]; ++i) {
         napi_value fn;

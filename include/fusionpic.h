@@ -470,6 +470,69 @@ typedef struct fpic_hist_spec {
  * the handle's stream, copies back, waits. */
 int fpic_histogram(fpic_handle* h, const fpic_hist_spec* spec, int scope, uint64_t* counts, uint64_t* outside);
 
+/* ---- CART3D fluid moment grids, reduced on the device: the velocity moments of order 0, 1 and 2 of ONE species on the node
+ * grid, as exact int64 sums, without reading a particle back.  Ten moments, one bit of `mask` each; the particle value m
+ * is a double made from the stored velocity in units of c converted to double (full EM, solver = YEE: the half-time
+ * velocity as stored, as in fpic_histogram):
+ *   bit 0       N             1
+ *   bits 1 2 3  FX FY FZ      vx, vy, vz
+ *   bits 4 5 6  SXX SYY SZZ   vx*vx, vy*vy, vz*vz     (one multiplication in double, rounded once)
+ *   bits 7 8 9  SXY SXZ SYZ   vx*vy, vx*vz, vy*vz     (likewise)
+ * Per live particle (the dead slots of a decomposed rank are skipped): the cell (i, j, k) and the upper weights wx1, wy1,
+ * wz1 (0 .. 16384) are those of the charge deposit, formed from the stored position in the handle's precision; the lower
+ * weight is w0 = 16384 - w1, the eight nodes are (i+a, j+b, k+c), a, b, c in {0, 1}, wrapped periodically.
+ *   REJECTED: a particle with a velocity component that is not finite or has |v| >= 128 adds to NO moment (not to N either)
+ *     and adds 1 to info->rejected.  So every |m| < 2^14 and no integer below overflows.
+ *   N adds wx[a] * wy[b] * wz[c] to node (a, b, c): 2^42 per particle — the charge deposit's integer with Z = 1, so the sum
+ *     over the species of Z_s * N_s equals FPIC_F3_RHO_FIXED bit for bit.
+ *   Every other moment: t = (int64) floor(m * 2^32) (the scaling is exact; one floor, also for a negative m).  t is split
+ *     with remainder axis by axis, z first, then y, then x:  upper = (w1 * t + 8192) >> 14 (an arithmetic, flooring shift),
+ *     lower = t - upper.  t -> (tz[0], tz[1]) by wz1; each tz[c] -> (tzy[c][0], tzy[c][1]) by wy1; each of those -> the
+ *     terms of nodes a = 0, 1 by wx1; index 1 is the upper part.  The eight terms of a particle add up to t exactly:
+ *     summed over the nodes, a moment equals the sum of t over the accepted particles, and N equals 2^42 times their number.
+ * Accumulators are int64 per node and moment, node index i + nr * (j + ny * k), added as two's-complement integer atomics:
+ * the same state gives the same bits whatever the slot order, the binning, the tile shape or the number of ranks.  A node
+ * holds 2^21 unit-weight particles of N before overflow (the bound of rho_fixed with Z = 1); |t| < 2^46 leaves the other
+ * moments at least 2^17 particles of the largest value per node.
+ * out: popcount(mask) grids of nr * ny * nz int64 each, in ascending bit order.
+ * scope as for fpic_histogram.  LOCAL is the contribution of THIS HANDLE'S OWN PARTICLES: on a rank of a decomposition the
+ *   grids are whole-grid-shaped, the planes the rank holds (its slab and the ghost / halo planes) in their places and zero
+ *   elsewhere.  A rank's particles in its ghost planes add to nodes the rank does not own — that is intended: the ranks'
+ *   LOCAL grids are partial sums that add up, as integers, to exactly the grids of one undecomposed handle.  GLOBAL with a
+ *   communicator is collective (every rank calls it with the same spec; the grids and both counters are summed over the
+ *   ranks, every rank gets the same full grids); GLOBAL on a member of an in-process group is FPIC_ERR_STATE (the host adds
+ *   up the members' LOCAL grids).
+ * info->spilled counts the accepted particles that added through global memory instead of their tile's window in LDS (a
+ *   particle that has left its tile since the last binning; every particle of a species that is not binned); it has no
+ *   effect on the sums.
+ * Refused (FPIC_ERR_INVALID_ARG): a null pointer, a species the handle does not have, mask == 0, bits above 9, a reserved
+ * word that is not zero; FPIC_ERR_STATE: a handle that is not CART3D.  precalc() is not needed; the call reads particles and
+ * writes nothing but its own buffer.  Synchronous: enqueues on the handle's stream, copies back, waits. */
+#define FPIC_MOM_N   (1u << 0)
+#define FPIC_MOM_FX  (1u << 1)
+#define FPIC_MOM_FY  (1u << 2)
+#define FPIC_MOM_FZ  (1u << 3)
+#define FPIC_MOM_SXX (1u << 4)
+#define FPIC_MOM_SYY (1u << 5)
+#define FPIC_MOM_SZZ (1u << 6)
+#define FPIC_MOM_SXY (1u << 7)
+#define FPIC_MOM_SXZ (1u << 8)
+#define FPIC_MOM_SYZ (1u << 9)
+#define FPIC_MOM_ORDER0 0x001u
+#define FPIC_MOM_ORDER1 0x00Fu
+#define FPIC_MOM_ORDER2 0x3FFu
+typedef struct fpic_moments_spec {
+    int32_t  species;
+    uint32_t mask;
+    double   reserved[4];        /* zero */
+} fpic_moments_spec;
+typedef struct fpic_moments_info {
+    uint64_t rejected;           /* particles left out by the rule above */
+    uint64_t spilled;            /* particles that added through global memory; no effect on the sums */
+    uint64_t reserved[2];
+} fpic_moments_info;
+int fpic_moments(fpic_handle* h, const fpic_moments_spec* spec, int scope, int64_t* out, fpic_moments_info* info);
+
 int fpic_sync(fpic_handle* h);
 int fpic_profile(fpic_handle* h, int enable);
 int fpic_get_stats(fpic_handle* h, fpic_stats* out);
