@@ -51,17 +51,31 @@ function fieldEnergy() {
     for (let i = 0; i < e.length; i += 4) s += e[i] * e[i] + e[i + 1] * e[i + 1] + e[i + 2] * e[i + 2];
     return 0.5 * eps0 * s * dx * dx * dx;
 }
-// Ex at one node near the crest of the perturbation: its zero crossings give the period
-const probe = 4 * (Math.round(g / 4));
-let last = sim.readField(field)[probe], crossings = [], t = 0;
+// Ex at one node near the crest of the perturbation: its zero crossings give the period.  The electrostatic box records that
+// node as a point series on the device (a point on a node gets the node's record exactly) and drains it once per ten frames:
+// no grid crosses the host per frame.  Full EM watches the lattice field (edge_E), which the series does not read — the
+// series interpolates the node-centred E — so it keeps the read-back per frame.
+const node = Math.round(g / 4), probe = 4 * node;
+const request = { points: [[node * dx, 0, 0]] };
+let last = yee ? sim.readField(field)[probe] : sim.series(request).points[0], crossings = [], t = 0, seen = 0;
+function crossing(ex, at) {
+    if ((ex > 0) !== (last > 0)) crossings.push(at - 2 * dt * Math.abs(ex) / (Math.abs(ex) + Math.abs(last)));
+    last = ex;
+}
+if (!yee) sim.recordSeries(2, 16, request);              // one row per frame (two sub-steps)
 for (let frame = 0; frame < frames; frame++) {
     sim.step();                                             // two sub-steps
     t += 2 * dt;
-    const ex = sim.readField(field)[probe];
-    if ((ex > 0) !== (last > 0)) crossings.push(t - 2 * dt * Math.abs(ex) / (Math.abs(ex) + Math.abs(last)));
-    last = ex;
+    if (yee) {
+        crossing(sim.readField(field)[probe], t);
+    } else if (frame % 10 === 9 || frame === frames - 1) {
+        const h = sim.seriesHistory();
+        if (h.dropped) throw new Error('the series ring overflowed');
+        for (let r = 0; r < h.rows; r++) { seen += 2 * dt; crossing(h.points[8 * r], seen); }
+    }
     if (frame % 10 === 0) console.log('frame %d  t = %s ns  field energy %s J', frame, (t * 1e9).toFixed(4), fieldEnergy().toExponential(4));
 }
+if (!yee) sim.recordSeries(0);
 let measured = NaN;
 if (crossings.length >= 3) measured = Math.PI * (crossings.length - 1) / (crossings[crossings.length - 1] - crossings[0]);
 const expected = wp * Math.cos(k * dx / 2);

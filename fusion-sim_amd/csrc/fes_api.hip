@@ -22,12 +22,14 @@
 //   fes_diag.inc.hpp        the energy diagnostics: the reductions, the recording ring, the ranks' combination
 //   fes_hist.inc.hpp        the phase-space histograms: the pass of one request, the ranks' sum
 //   fes_mom.inc.hpp         the fluid moment grids: the sweeps of one request, the held planes' places, the ranks' sum
+//   fes_series.inc.hpp      the series: rows of field points and tracer particles, now or into a ring, the ranks' selection
 #include "fes_api.hpp"
 #include "fes_kernels.hpp"
 #include "fes_diag_kernels.hpp"
 #include "fes_diag_core.hpp"
 #include "fes_hist_kernels.hpp"
 #include "fes_mom_kernels.hpp"
+#include "fes_series_kernels.hpp"
 #include "fes_fft.hpp"
 #include "fes_tri.hpp"
 #include "fpic_comm.hpp"
@@ -340,6 +342,7 @@ namespace {
 #include "fes_diag.inc.hpp"
 #include "fes_hist.inc.hpp"
 #include "fes_mom.inc.hpp"
+#include "fes_series.inc.hpp"
 
 int precalc(fpic_handle* h)
 {

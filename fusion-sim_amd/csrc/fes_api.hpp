@@ -39,6 +39,10 @@ int energy_history(fpic_handle* h, int scope, fpic_energy* rows, uint64_t capaci
 int histogram(fpic_handle* h, const fpic_hist_spec* spec, int scope, uint64_t* counts, uint64_t* outside);
 // fluid moment grids (fes_mom.inc.hpp)
 int moments(fpic_handle* h, const fpic_moments_spec* spec, int scope, int64_t* out, fpic_moments_info* info);
+// field points and tracer particles as rows (fes_series.inc.hpp)
+int series_now(fpic_handle* h, const fpic_series_spec* spec, int scope, double* points_out, double* tracers_out);
+int series_record(fpic_handle* h, const fpic_series_spec* spec, int every, uint32_t capacity);
+int series_history(fpic_handle* h, int scope, uint64_t* substeps, double* points_out, double* tracers_out, uint64_t capacity, uint64_t* n, uint64_t* dropped);
 uint64_t last_spill(const fpic_handle* h); // out-of-window deposits of the sub-step before last (lagged read-back)
 
 } // namespace fes

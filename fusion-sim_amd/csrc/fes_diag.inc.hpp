@@ -204,15 +204,19 @@ int energy_history(fpic_handle* h, int scope, fpic_energy* rows, uint64_t capaci
     return FPIC_OK;
 }
 
+static int series_after_substep(fpic_handle* h);   // (fes_series.inc.hpp: the series recorder's share of the hook)
+
 // the recording hook, at the end of every sub-step of every path (substeps(), group_run()): counts the sub-step and, every
-// `every`-th one, enqueues the reduction into the ring.  Recording off: nothing is enqueued.
+// `every`-th one, enqueues the reduction into the ring; then the series recorder, which shares the counter and nothing else,
+// takes its turn.  Recording off: nothing is enqueued.
 static int diag_after_substep(fpic_handle* h)
 {
     Diag& g = h->es->diag;
     g.substep++;
-    if (!g.every || g.substep % static_cast<uint64_t>(g.every)) return FPIC_OK;
-    fpic_energy* row = g.ring_dev + g.ring.slot(g.ring.seq);
-    if (int rc = h->prec == FPIC_F32 ? diag_enqueue<float>(h, row) : diag_enqueue<double>(h, row)) return rc;
-    g.ring.seq++;
-    return FPIC_OK;
+    if (g.every && g.substep % static_cast<uint64_t>(g.every) == 0) {
+        fpic_energy* row = g.ring_dev + g.ring.slot(g.ring.seq);
+        if (int rc = h->prec == FPIC_F32 ? diag_enqueue<float>(h, row) : diag_enqueue<double>(h, row)) return rc;
+        g.ring.seq++;
+    }
+    return series_after_substep(h);
 }

@@ -35,6 +35,29 @@ struct Species {
     void* em_args = nullptr;           // EmPushArgs of the last full-EM launch, resident for the kernel's out-of-line paths
 };
 
+// the series diagnostic (fes_series.inc.hpp): a request's copies on the device — one allocation holding the points' normalised
+// coordinates (T [npoints][3]) and, per species that has tracers, the sorted ids, their entries and the bitmap filter
+struct SeriesTable {
+    int species;
+    uint32_t m, log2bits;
+    const uint32_t *sorted, *index, *filter;
+};
+struct SeriesReq {
+    uint32_t npoints = 0, ntracers = 0;
+    void* block = nullptr;
+    size_t bytes = 0;
+    std::vector<SeriesTable> tables;
+    size_t width() const { return static_cast<size_t>(fesser::kEntry) * (static_cast<size_t>(npoints) + ntracers); }   // doubles per row
+};
+// ... and the recorder: a ring of rows of req.width() doubles; the host keeps the sub-step of each slot
+struct Series {
+    int every = 0;
+    fesdiag::Ring ring;
+    double* ring_dev = nullptr;
+    std::vector<uint64_t> ring_substep;
+    SeriesReq req;
+};
+
 // the energy diagnostics (fes_diag.inc.hpp): the sub-step counter of fpic_energy, the recording ring, the reduction's buffers
 struct Diag {
     uint64_t substep = 0;              // sub-steps advanced since create
@@ -49,10 +72,12 @@ struct Diag {
     size_t hist_words = 0;
     unsigned long long* mom = nullptr;  // the buffer of fpic_moments (fes_mom.inc.hpp): a grid of the held planes per moment, then `rejected`, `spilled`; grows to the largest request
     size_t mom_words = 0;
+    Series series;                      // the recorder of fpic_series_record (fes_series.inc.hpp); shares `substep`
 };
 inline void diag_release(Diag& g)
 {
-    for (void* p : { static_cast<void*>(g.ring_dev), static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom) })
+    for (void* p : { static_cast<void*>(g.ring_dev), static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom),
+                    static_cast<void*>(g.series.ring_dev), g.series.req.block })
         if (p) (void)hipFree(p);
     g = Diag();
 }

@@ -1419,6 +1419,25 @@ int fpic_moments(fpic_handle* h, const fpic_moments_spec* spec, int scope, int64
     BOX_ONLY(h, "fpic_moments");
     return fes::moments(h, spec, scope, out, info);
 }
+int fpic_series_now(fpic_handle* h, const fpic_series_spec* spec, int scope, double* points_out, double* tracers_out)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_series_now");
+    return fes::series_now(h, spec, scope, points_out, tracers_out);
+}
+int fpic_series_record(fpic_handle* h, const fpic_series_spec* spec, int every, uint32_t capacity)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_series_record");
+    return fes::series_record(h, spec, every, capacity);
+}
+int fpic_series_history(fpic_handle* h, int scope, uint64_t* substeps, double* points_out, double* tracers_out, uint64_t capacity, uint64_t* n,
+                        uint64_t* dropped)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_series_history");
+    return fes::series_history(h, scope, substeps, points_out, tracers_out, capacity, n, dropped);
+}
 int fpic_get_particles_of(fpic_handle* h, int species, void* pos_aos, void* vel_aos, int dtype)
 {
     CHECK_HANDLE(h);

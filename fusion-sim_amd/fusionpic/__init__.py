@@ -45,6 +45,7 @@ ABI_FUNCTIONS = [
     "fpic_domain_init", "fpic_domain_set_particles", "fpic_domain_get_particles", "fpic_domain_stats",
     "fpic_group_precalc", "fpic_group_step", "fpic_group_density",
     "fpic_energy_now", "fpic_energy_record", "fpic_energy_history", "fpic_histogram", "fpic_moments",
+    "fpic_series_now", "fpic_series_record", "fpic_series_history",
 ]
 
 
@@ -184,6 +185,66 @@ def _hist_result(counts, outside, shape, rg):
             "edges": [rg[a, 0] + np.arange(shape[a] + 1) * (rg[a, 1] - rg[a, 0]) / shape[a] for a in builtins.range(len(shape))]}
 
 
+SERIES_MAX_POINTS = 4096
+SERIES_MAX_TRACERS = 65536
+# the columns of a point row and of a tracer row (fpic_series_*): 8 doubles each
+SERIES_POINT_COLUMNS = ("ex", "ey", "ez", "phi", "bx", "by", "bz", "present")
+SERIES_TRACER_COLUMNS = ("x", "y", "z", "vx", "vy", "vz", "found", "zero")
+
+
+class SeriesSpec(ctypes.Structure):
+    """mirror of fpic_series_spec (include/fusionpic.h)"""
+    _fields_ = [("npoints", ctypes.c_uint32), ("ntracers", ctypes.c_uint32), ("points", ctypes.c_void_p),
+                ("tracer_species", ctypes.c_void_p), ("tracer_id", ctypes.c_void_p), ("reserved", ctypes.c_double * 4)]
+
+
+def _series_spec(points, tracers, species):
+    """(SeriesSpec, the arrays it points to) of a request.  Only what the structure cannot carry is refused here (a shape, an
+    id that is no uint32); every other check is the library's."""
+    s = SeriesSpec()
+    keep = []
+    if points is not None and np.size(points):
+        pts = np.ascontiguousarray(points, dtype=np.float64)
+        if pts.ndim != 2 or pts.shape[1] != 3:
+            raise FusionPicError(-1, ".points <- must be an array of shape (npoints, 3)")
+        if pts.shape[0] >= 1 << 32:
+            raise FusionPicError(-1, ".points <- more than FPIC_SERIES_MAX_POINTS (4096) points")
+        s.npoints, s.points = pts.shape[0], pts.ctypes.data
+        keep.append(pts)
+    if tracers is not None and np.size(tracers):
+        raw = np.asarray(tracers)
+        if raw.ndim != 1 or raw.dtype.kind not in "iu" or (raw.size and (int(raw.min()) < 0 or int(raw.max()) >= 1 << 32)):
+            raise FusionPicError(-1, ".tracers <- must be a one-dimensional array of particle indices (uint32)")
+        if raw.size >= 1 << 32:
+            raise FusionPicError(-1, ".tracers <- more than FPIC_SERIES_MAX_TRACERS (65536) tracers")
+        ids = np.ascontiguousarray(raw, dtype=np.uint32)
+        sp = np.asarray(species)
+        if sp.ndim == 0 and sp.dtype.kind in "iu":
+            sp = np.full(ids.shape, int(sp))
+        if sp.shape != ids.shape or sp.dtype.kind not in "iu":
+            raise FusionPicError(-1, ".species <- must be an int or an array of ints as long as tracers")
+        sp = np.ascontiguousarray(np.clip(sp, -1, (1 << 31) - 1), dtype=np.int32)     # (an unknown species stays unknown)
+        s.ntracers, s.tracer_species, s.tracer_id = ids.shape[0], sp.ctypes.data, ids.ctypes.data
+        keep += [ids, sp]
+    return s, keep
+
+
+def _series_select(parts, flag):
+    """entry by entry, the one of `parts` (arrays [..., 8] of the members of a group) whose column `flag` is set; zeros where
+    none is.  Returns (selection, owner: the member's index per entry, -1 where none).  Two members flagging one entry is an
+    internal error of the library and is reported, not resolved."""
+    stack = np.stack(parts)
+    flags = stack[..., flag] != 0
+    if (flags.sum(axis=0) > 1).any():
+        raise FusionPicError(-5, "internal error: two members of the group report one entry of a series row")
+    out = np.zeros_like(stack[0])
+    owner = np.full(out.shape[:-1], -1, dtype=np.int64)
+    for r in builtins.range(len(parts)):
+        out[flags[r]] = stack[r][flags[r]]
+        owner[flags[r]] = r
+    return out, owner
+
+
 MOMENT_NAMES = ("N", "FX", "FY", "FZ", "SXX", "SYY", "SZZ", "SXY", "SXZ", "SYZ")   # bit b of a mask is MOMENT_NAMES[b]
 MOMENT_SETS = {"n": 0x001, "order1": 0x00F, "order2": 0x3FF}
 MOM_ONE = 1 << 42          # N of one particle, summed over its eight nodes
@@ -308,6 +369,9 @@ def load_library(path=None):
     lib.fpic_energy_history.argtypes = [vp, ci, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     lib.fpic_histogram.argtypes = [vp, ctypes.POINTER(HistSpec), ci, vp, ctypes.POINTER(ctypes.c_uint64)]
     lib.fpic_moments.argtypes = [vp, ctypes.POINTER(MomentsSpec), ci, vp, ctypes.POINTER(MomentsInfo)]
+    lib.fpic_series_now.argtypes = [vp, ctypes.POINTER(SeriesSpec), ci, vp, vp]
+    lib.fpic_series_record.argtypes = [vp, ctypes.POINTER(SeriesSpec), ci, ctypes.c_uint32]
+    lib.fpic_series_history.argtypes = [vp, ci, vp, vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -574,6 +638,41 @@ class CylindricalParticlePusher:
         counts, outside = _hist_call(self, s, shape, scope)
         return _hist_result(counts, outside, shape, rg)
 
+    # ---- series: the field at points and the state of tracer particles as rows (fpic_series_*)
+    def series(self, points=None, tracers=None, species=0, scope="global"):
+        """The rows of the current state of a CART3D box (fpic_series_now; an (r,z) handle is refused).  points: positions in
+        metres, shape (P, 3), wrapped periodically; tracers: particle indices within `species` (an int, or an array as long as
+        tracers).  Returns {points: float64 (P, 8) with the columns SERIES_POINT_COLUMNS, tracers: float64 (M, 8) with
+        SERIES_TRACER_COLUMNS}: the field interpolated with the charge deposit's weights from what readField(F3_E) and
+        readField(F3_B_NODES) hold, and the six stored numbers of each particle.  'global' on a rank with a communicator is
+        collective; on a member of an in-process group it is an error (BoxGroup.series)."""
+        s, keep = _series_spec(points, tracers, species)
+        pts = np.zeros((s.npoints if s.npoints <= SERIES_MAX_POINTS else 0, 8))          # (a refused request writes nothing)
+        trs = np.zeros((s.ntracers if s.ntracers <= SERIES_MAX_TRACERS else 0, 8))
+        self._check(self._lib.fpic_series_now(self._h, ctypes.byref(s), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope],
+                                              pts.ctypes.data, trs.ctypes.data))
+        return {"points": pts, "tracers": trs}
+
+    def recordSeries(self, every, capacity=4096, points=None, tracers=None, species=0):
+        """after every `every`-th sub-step the rows of series() go into a device ring of `capacity` rows on the handle's
+        stream (fpic_series_record; 0: off).  Independent of recordEnergy, with which it shares the sub-step counter."""
+        s, keep = _series_spec(points, tracers, species)
+        self._check(self._lib.fpic_series_record(self._h, ctypes.byref(s) if every else None, int(every), int(capacity)))
+        self._series_shape = (int(s.npoints), int(s.ntracers)) if every else (0, 0)
+
+    def seriesHistory(self, scope="global"):
+        """({substep: uint64 (rows,), points: float64 (rows, P, 8), tracers: float64 (rows, M, 8)}, dropped): the rows
+        recorded since the last call, oldest first, and how many older rows the ring overwrote"""
+        sc = {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope]
+        P, M = getattr(self, "_series_shape", (0, 0))
+        n, dropped = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self._lib.fpic_series_history(self._h, sc, None, None, None, 0, ctypes.byref(n), ctypes.byref(dropped)))
+        rows = n.value
+        out = {"substep": np.zeros(rows, dtype=np.uint64), "points": np.zeros((rows, P, 8)), "tracers": np.zeros((rows, M, 8))}
+        self._check(self._lib.fpic_series_history(self._h, sc, np.zeros(1, dtype=np.uint64).ctypes.data if not rows else out["substep"].ctypes.data,
+                                                  out["points"].ctypes.data, out["tracers"].ctypes.data, rows, ctypes.byref(n), ctypes.byref(dropped)))
+        return out, int(dropped.value)
+
     def sync(self):
         self._check(self._lib.fpic_sync(self._h))
 
@@ -790,6 +889,9 @@ class ElectrostaticBoxPusher:
         return rows, int(dropped.value)
 
     histogram = CylindricalParticlePusher.histogram
+    series = CylindricalParticlePusher.series
+    recordSeries = CylindricalParticlePusher.recordSeries
+    seriesHistory = CylindricalParticlePusher.seriesHistory
 
     # ---- fluid moment grids (fpic_moments), reduced on the device
     def moments(self, which="order2", species=0, scope="global"):
@@ -871,6 +973,32 @@ class BoxGroup:
 
     def fluid(self, species=0):
         return _fluid(self.sims[0], self.moments("order2", species), species)
+
+    def series(self, points=None, tracers=None, species=0):
+        """the whole box: entry by entry the row of the member that reports it (its flag set) among the members' LOCAL rows —
+        the owner of a point's cell plane, the holder of a tracer's live slot.  As series(), plus owner_points / owner_tracers:
+        the member's index per entry (-1: nobody reports it)."""
+        parts = [m.series(points, tracers, species, "local") for m in self.sims]
+        pts, op = _series_select([p["points"] for p in parts], SERIES_POINT_COLUMNS.index("present"))
+        trs, ot = _series_select([p["tracers"] for p in parts], SERIES_TRACER_COLUMNS.index("found"))
+        return {"points": pts, "tracers": trs, "owner_points": op, "owner_tracers": ot}
+
+    def recordSeries(self, every, capacity=4096, points=None, tracers=None, species=0):
+        """every member records its LOCAL rows of the same request"""
+        for m in self.sims:
+            m.recordSeries(every, capacity, points, tracers, species)
+
+    def seriesHistory(self):
+        """the members' LOCAL histories drained and selected as series() does, row by row: ({substep, points, tracers,
+        owner_points, owner_tracers}, dropped)"""
+        parts = [m.seriesHistory("local") for m in self.sims]
+        first, dropped = parts[0]
+        for p, d in parts[1:]:
+            if d != dropped or not np.array_equal(p["substep"], first["substep"]):
+                raise FusionPicError(-5, "the members hold different recorded rows: record with the same settings on every member")
+        pts, op = _series_select([p["points"] for p, _ in parts], SERIES_POINT_COLUMNS.index("present"))
+        trs, ot = _series_select([p["tracers"] for p, _ in parts], SERIES_TRACER_COLUMNS.index("found"))
+        return {"substep": first["substep"], "points": pts, "tracers": trs, "owner_points": op, "owner_tracers": ot}, dropped
 
 
 def commUniqueId(library=None):

@@ -33,7 +33,7 @@
  * geometry 'cart3d' (+ ny, length_y, solver 'poisson_fft'|'none', macro_weight) selects the self-consistent
  * electrostatic box — an extension with no reference counterpart (include/fusionpic.h): radius, height are
  * then the box lengths along x and z, nr, nz the node counts; same method names, plus addSpecies, addB,
- * readField, energy, recordEnergy, energyHistory, histogram, moments.  Multi-GPU (one process per GPU): empic.commUniqueId() on rank 0, simulation.commInit(id,
+ * readField, energy, recordEnergy, energyHistory, histogram, moments, series, recordSeries, seriesHistory.  Multi-GPU (one process per GPU): empic.commUniqueId() on rank 0, simulation.commInit(id,
  * rank, world) on every rank; density() then sums the per-cell sums over the ranks inside the library (RCCL).
  */
 'use strict';
@@ -247,6 +247,32 @@ function makeBox(spec, lib) {
         const codes = axes.map((a) => { if (!(a in HIST_AXES)) throw new RangeError('.axis <- must be one of x, y, z, vx, vy, vz, v2'); return HIST_AXES[a]; });
         return lib.histogram(h, request.species || 0, Int32Array.from(codes), Int32Array.from(bins), Float64Array.from(range.flat()), scopeOf(scope));
     };
+    // series (fpic_series_*): the field at points and the state of tracer particles as rows of 8 doubles, now or recorded into a
+    // device ring.  request = { points: [[x, y, z], ...] in metres (wrapped periodically), tracers: particle indices, species: one
+    // index or one per tracer (default 0) }; either list may be missing, not both.  A point row is Ex Ey Ez phi Bx By Bz present,
+    // a tracer row x y z vx vy vz found 0 (the stored values).
+    const seriesArgs = function (request) {
+        if (request === null || typeof request !== 'object') throw new TypeError('.request <- expected { points, tracers, species }');
+        const points = request.points === undefined || request.points === null ? [] : request.points;
+        const tracers = request.tracers === undefined || request.tracers === null ? [] : Array.from(request.tracers);
+        if (!Array.isArray(points) || !points.every((p) => (Array.isArray(p) || ArrayBuffer.isView(p)) && p.length === 3 && Array.from(p).every((x) => typeof x === 'number')))
+            throw new RangeError('.points <- expected an array of [x, y, z]');
+        if (!tracers.every((t) => Number.isInteger(t) && t >= 0 && t <= 0xffffffff)) throw new RangeError('.tracers <- expected particle indices (uint32)');
+        let species = request.species === undefined ? 0 : request.species;
+        if (typeof species === 'number') species = tracers.map(() => species);
+        else species = Array.from(species);
+        if (species.length !== tracers.length || !species.every((x) => Number.isInteger(x) && Math.abs(x) <= 0x7fffffff)) throw new RangeError('.species <- expected one index, or one per tracer');
+        return [Float64Array.from(points.map((p) => Array.from(p)).flat()), Int32Array.from(species), Uint32Array.from(tracers)];
+    };
+    // -> { points: Float64Array [P][8], tracers: Float64Array [M][8] }
+    out.series = function (request, scope) { return lib.series(h, ...seriesArgs(request), scopeOf(scope)); };
+    // after every `every`-th sub-step the same rows go into a ring of `capacity` rows on the device (every 0: off)
+    out.recordSeries = function (every, capacity, request) {
+        const args = every ? seriesArgs(request) : [null, null, null];
+        lib.recordSeries(h, every, capacity === undefined ? 4096 : capacity, ...args);
+    };
+    // -> { rows, dropped, substep: Float64Array [rows], points: Float64Array [rows][P][8], tracers: Float64Array [rows][M][8] }, oldest first
+    out.seriesHistory = function (scope) { return lib.seriesHistory(h, scopeOf(scope)); };
     // fluid moment grids of one species, reduced on the GPU (fpic_moments): request = { species (default 0), which: 'n' | 'order1' |
     // 'order2' (default) | an array of names from N FX FY FZ SXX SYY SZZ SXY SXZ SYZ }
     // -> { NAME: BigInt64Array [nz][ny][nr] per moment asked for (N in units of 2^-42 particles, the others of 2^-32), rejected, spilled }

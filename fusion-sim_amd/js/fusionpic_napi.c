@@ -40,6 +40,8 @@ typedef struct {
     size_t nodes;
     int nspecies;
     size_t count[MAX_SPECIES];
+    /* the request fpic_series_record armed: how many entries a recorded row has (seriesHistory sizes its arrays by them) */
+    size_t series_points, series_tracers;
 } box_t;
 
 static void box_finalize(napi_env env, void* data, void* hint)
@@ -163,6 +165,7 @@ static napi_value n_create(napi_env env, napi_callback_info info)
     b->nodes = b->cells * (size_t)(s.ny > 0 ? s.ny : 1);
     b->nspecies = 1;
     b->count[0] = b->n;
+    b->series_points = b->series_tracers = 0;
     napi_value ext;
     if (napi_create_external(env, b, box_finalize, NULL, &ext) != napi_ok) {
         box_finalize(env, b, NULL);
@@ -879,6 +882,94 @@ static napi_value n_moments(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* ---- series: the field at points and the state of tracer particles as rows (fpic_series_*).  A request travels as three
+ * typed arrays: points Float64Array of 3 P (metres), species Int32Array and ids Uint32Array of M each; null / undefined is an
+ * empty list.  The arrays' types and lengths are checked here, the request itself by the library. */
+static int get_series_request(napi_env env, napi_value* argv, fpic_series_spec* s)
+{
+    napi_typedarray_type tp, ts, ti; void *pp, *ps, *pi; size_t lp, ls, li;
+    if (!get_typed(env, argv[0], &tp, &pp, &lp) || !get_typed(env, argv[1], &ts, &ps, &ls) || !get_typed(env, argv[2], &ti, &pi, &li)) return 0;
+    if ((pp && tp != napi_float64_array) || (ps && ts != napi_int32_array) || (pi && ti != napi_uint32_array)) {
+        napi_throw_type_error(env, NULL, ".points <- expected Float64Array points, Int32Array species and Uint32Array ids");
+        return 0;
+    }
+    if (lp % 3) { napi_throw_range_error(env, NULL, ".points <- expected three numbers per point"); return 0; }
+    if (!check_len(env, "species", ls, li)) return 0;
+    if (lp / 3 > FPIC_SERIES_MAX_POINTS) { napi_throw_range_error(env, NULL, ".points <- more than FPIC_SERIES_MAX_POINTS (4096) points"); return 0; }
+    if (li > FPIC_SERIES_MAX_TRACERS) { napi_throw_range_error(env, NULL, ".tracers <- more than FPIC_SERIES_MAX_TRACERS (65536) tracers"); return 0; }
+    memset(s, 0, sizeof *s);
+    s->npoints = (uint32_t)(lp / 3); s->ntracers = (uint32_t)li;
+    s->points = lp ? (const double*)pp : NULL;
+    s->tracer_species = li ? (const int32_t*)ps : NULL;
+    s->tracer_id = li ? (const uint32_t*)pi : NULL;
+    return 1;
+}
+
+static napi_value new_f64(napi_env env, size_t n, double** data)
+{
+    napi_value buf, arr;
+    void* p = NULL;
+    NAPI_OK(env, napi_create_arraybuffer(env, n * sizeof(double), &p, &buf));
+    NAPI_OK(env, napi_create_typedarray(env, napi_float64_array, n, buf, 0, &arr));
+    *data = (double*)p;
+    return arr;
+}
+
+/* series(h, points, species, ids, scope) -> { points: Float64Array of 8 P, tracers: Float64Array of 8 M } */
+static napi_value n_series(napi_env env, napi_callback_info info)
+{
+    napi_value argv[5]; fpic_handle* h; int scope; fpic_series_spec s;
+    if (!get_args(env, info, 5, argv, &h) || !get_scope(env, argv[4], &scope) || !get_series_request(env, argv + 1, &s)) return NULL;
+    double *pd = NULL, *td = NULL;
+    napi_value pts = new_f64(env, (size_t)8 * s.npoints, &pd), trs = new_f64(env, (size_t)8 * s.ntracers, &td), out;
+    if (!pts || !trs) return NULL;
+    if (fpic_series_now(h, &s, scope, pd, td) != FPIC_OK) return throw_fpic(env, h);
+    NAPI_OK(env, napi_create_object(env, &out));
+    NAPI_OK(env, napi_set_named_property(env, out, "points", pts));
+    NAPI_OK(env, napi_set_named_property(env, out, "tracers", trs));
+    return out;
+}
+
+/* recordSeries(h, every, capacity, points, species, ids) */
+static napi_value n_record_series(napi_env env, napi_callback_info info)
+{
+    napi_value argv[6]; fpic_handle* h; double every, cap; fpic_series_spec s;
+    if (!get_args(env, info, 6, argv, &h) || !get_double(env, argv[1], &every) || !get_double(env, argv[2], &cap) || !get_series_request(env, argv + 3, &s)) return NULL;
+    if (every < 0 || every > 2147483647.0 || cap < 0 || cap > 4294967295.0) { napi_throw_range_error(env, NULL, ".every <- out of range"); return NULL; }
+    if (fpic_series_record(h, every > 0 ? &s : NULL, (int)every, (uint32_t)cap) != FPIC_OK) return throw_fpic(env, h);
+    g_box->series_points = every > 0 ? s.npoints : 0;
+    g_box->series_tracers = every > 0 ? s.ntracers : 0;
+    return undefined(env);
+}
+
+/* seriesHistory(h, scope) -> { rows, dropped, substep: Float64Array of rows, points: Float64Array [rows][P][8],
+ * tracers: Float64Array [rows][M][8] } (the rows recorded since the last call, oldest first) */
+static napi_value n_series_history(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2]; fpic_handle* h; int scope;
+    if (!get_args(env, info, 2, argv, &h) || !get_scope(env, argv[1], &scope)) return NULL;
+    uint64_t n = 0, dropped = 0;
+    if (fpic_series_history(h, scope, NULL, NULL, NULL, 0, &n, &dropped) != FPIC_OK) return throw_fpic(env, h);
+    double *sd = NULL, *pd = NULL, *td = NULL;
+    napi_value sub = new_f64(env, (size_t)n, &sd), pts = new_f64(env, (size_t)n * 8 * g_box->series_points, &pd),
+               trs = new_f64(env, (size_t)n * 8 * g_box->series_tracers, &td), out, v;
+    if (!sub || !pts || !trs) return NULL;
+    uint64_t* steps = (uint64_t*)calloc((size_t)n + 1, sizeof(uint64_t));
+    if (!steps) { napi_throw_error(env, NULL, "host allocation failed"); return NULL; }
+    if (fpic_series_history(h, scope, steps, pd, td, n, &n, &dropped) != FPIC_OK) { free(steps); return throw_fpic(env, h); }
+    for (uint64_t i = 0; i < n; ++i) sd[i] = (double)steps[i];
+    free(steps);
+    NAPI_OK(env, napi_create_object(env, &out));
+    NAPI_OK(env, napi_create_double(env, (double)n, &v));
+    NAPI_OK(env, napi_set_named_property(env, out, "rows", v));
+    NAPI_OK(env, napi_create_double(env, (double)dropped, &v));
+    NAPI_OK(env, napi_set_named_property(env, out, "dropped", v));
+    NAPI_OK(env, napi_set_named_property(env, out, "substep", sub));
+    NAPI_OK(env, napi_set_named_property(env, out, "points", pts));
+    NAPI_OK(env, napi_set_named_property(env, out, "tracers", trs));
+    return out;
+}
+
 static napi_value n_build_arch(napi_env env, napi_callback_info info)
 {
     (void)info;
@@ -906,6 +997,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "domainStats", n_domain_stats },
         { "energy", n_energy }, { "recordEnergy", n_record_energy }, { "energyHistory", n_energy_history },
         { "histogram", n_histogram }, { "moments", n_moments },
+        { "series", n_series }, { "recordSeries", n_record_series }, { "seriesHistory", n_series_history },
     };
     for (size_t i = 0; i < sizeof table / sizeof table[0]; ++i) {
         napi_value fn;

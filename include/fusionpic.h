@@ -533,6 +533,63 @@ typedef struct fpic_moments_info {
 } fpic_moments_info;
 int fpic_moments(fpic_handle* h, const fpic_moments_spec* spec, int scope, int64_t* out, fpic_moments_info* info);
 
+/* ---- CART3D series: the field at chosen points and the state of chosen particles (tracers) as rows of doubles, taken now
+ * or recorded after every `every`-th sub-step into a device ring, without reading a grid or a species back.  One request
+ * holds two lists, either of which may be empty (not both):
+ *   points[npoints][3]   positions in metres, anywhere: a point outside [0, L) is wrapped periodically
+ *   tracers[ntracers]    pairs (tracer_species[t], tracer_id[t]); the id is the caller's particle index within the species
+ *                        (first + k of fpic_set_particles_range / fpic_get_particles_range; on a decomposed handle the
+ *                        first_id + k of fpic_domain_set_particles, what fpic_domain_get_particles returns as ids)
+ * A POINT ROW is 8 doubles: the four components of the node record FPIC_F3_E (Ex, Ey, Ez and the fourth as stored: phi in the
+ * electrostatic box), the three of FPIC_F3_B_NODES (zeros unless solver = YEE), and `present` (1.0 or 0.0).  The value is
+ * interpolated from exactly the arrays fpic_read_field3 returns for those two grids at that moment (reading them closes
+ * nothing and forms nothing), with the charge deposit's weights:
+ *   1. per axis u = p / L in double, u -= floor(u), u = 0 if that is not < 1; then u is converted to the handle's precision T;
+ *   2. the cell i and the upper weight w1 (0 .. 16384) are the charge deposit's, evaluated in T:
+ *      g = u * n, i = (int) g (i = 0 if that is n), w1 = ((int) ((g - floor(g)) * 32768) + 1) >> 1;  w0 = 16384 - w1;
+ *   3. the eight nodes (i+a, j+b, k+c), a, b, c in {0, 1}, wrapped periodically, e = a + 2 b + 4 c, with the integer weight
+ *      W_e = wx[a] * wy[b] * wz[c] (they add up to 2^42);
+ *   4. per component value = (sum over e of (double) W_e * (double) F_e) * 2^-42: the first product starts the sum, the other
+ *      seven are added in the order e = 1 .. 7, every operation rounded once in double, no fused multiply-add.
+ * A point on a node therefore gets the node's record exactly (one weight is 2^42, the others 0), as long as u * n lands
+ * within 2^-16 of the integer (in float: up to 64 nodes per axis).
+ * A TRACER ROW is 8 doubles: the six stored numbers of the particle — position as a fraction of the box, velocity in units
+ * of c, each converted to double, what fpic_get_particles_range / fpic_domain_get_particles return with dtype f64 —, `found`
+ * (1.0 or 0.0) and a zero.  A handle reports the tracers whose LIVE slot it holds (the dead slots of a decomposed rank never
+ * match).  An entry that is not present / not found is all zeros.
+ * scope: LOCAL is what this handle sees.  On a rank of a z-slab decomposition a point belongs to the rank that owns plane k
+ * of step 2; that rank must hold the plane above its slab too (ghost_planes >= 1; FPIC_ERR_STATE otherwise).  GLOBAL with a
+ * communicator is collective: the ranks' rows are gathered and every rank takes each entry from the rank whose flag is set
+ * (a selection, not a sum; two flags for one entry are FPIC_ERR_STATE).  GLOBAL on a member of an in-process group is
+ * FPIC_ERR_STATE (the host selects among the members' LOCAL rows).
+ * Refused (FPIC_ERR_INVALID_ARG): a null pointer, both lists empty, more than FPIC_SERIES_MAX_POINTS points or
+ * FPIC_SERIES_MAX_TRACERS tracers, a point that is not finite, a species the handle does not have, the same (species, id)
+ * twice, on an undecomposed handle an id that is not below the species' count (a decomposed rank accepts any id: it does not
+ * know the total), a reserved word that is not zero, capacity = 0 with every > 0; FPIC_ERR_STATE: a handle that is not
+ * CART3D, points before fpic_precalc. */
+#define FPIC_SERIES_MAX_POINTS  4096u
+#define FPIC_SERIES_MAX_TRACERS 65536u
+typedef struct fpic_series_spec {
+    uint32_t        npoints, ntracers;
+    const double*   points;          /* [npoints][3], metres */
+    const int32_t*  tracer_species;  /* [ntracers] */
+    const uint32_t* tracer_id;       /* [ntracers] */
+    double          reserved[4];     /* zero */
+} fpic_series_spec;
+/* The rows of the current state: points_out [npoints][8], tracers_out [ntracers][8] (either may be NULL when its list is
+ * empty).  Enqueues on the handle's stream, copies back, waits.  fpic_precalc is needed only if npoints > 0. */
+int fpic_series_now(fpic_handle* h, const fpic_series_spec* spec, int scope, double* points_out, double* tracers_out);
+/* After every `every`-th sub-step (the counter of fpic_energy.substep) the same rows are written into a device ring of
+ * `capacity` rows on the handle's stream: no host synchronisation, no collective.  every = 0 turns recording off and frees
+ * the ring (spec may then be NULL); a new call starts an empty ring.  Independent of fpic_energy_record. */
+int fpic_series_record(fpic_handle* h, const fpic_series_spec* spec, int every, uint32_t capacity);
+/* The rows recorded since the last drain, oldest first: substeps[r], points_out[r][npoints][8], tracers_out[r][ntracers][8]
+ * for r < *n (substeps = NULL: *n receives how many there are, nothing is drained).  capacity: the rows the arrays have room
+ * for.  If the ring wrapped, the newest rows are returned and *dropped counts the others.  GLOBAL with a communicator is
+ * collective: every rank must hold the same number of rows (else FPIC_ERR_STATE on every rank). */
+int fpic_series_history(fpic_handle* h, int scope, uint64_t* substeps, double* points_out, double* tracers_out, uint64_t capacity,
+                        uint64_t* n, uint64_t* dropped);
+
 int fpic_sync(fpic_handle* h);
 int fpic_profile(fpic_handle* h, int enable);
 int fpic_get_stats(fpic_handle* h, fpic_stats* out);
