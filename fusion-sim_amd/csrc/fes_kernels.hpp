@@ -1467,25 +1467,51 @@ __device__ __attribute__((noinline)) void current_segment(const long long (&p1)[
     }
 }
 
-// the move a -> b_in (nearest periodic image) cut at the zigzag relay point (es3d_current)
-__device__ __forceinline__ void current_deposit(const long long (&a)[3], const long long (&b_in)[3], int nx, int ny, int nz, int Z, unsigned long long* Jfix, Held held)
+// the move a_in -> b_in (nearest periodic image) as es3d_current takes it: whole-cell steps on the axes where it skips a cell
+// (|v| > c only), then the rest; each piece cut at the zigzag relay point
+__device__ __forceinline__ void current_deposit(const long long (&a_in)[3], const long long (&b_in)[3], int nx, int ny, int nz, int Z, unsigned long long* Jfix, Held held)
 {
     constexpr long long S = 32768;
     const int n[3] = { nx, ny, nz };
-    long long b[3], ca[3], cb[3], r[3];
+    long long a[3], b[3];
 #pragma unroll
     for (int m = 0; m < 3; ++m) {
         const long long box = static_cast<long long>(n[m]) * S;
-        long long dd = b_in[m] - a[m];
+        long long dd = b_in[m] - a_in[m];
         if (2 * dd > box) dd -= box;
         else if (2 * dd < -box) dd += box;
+        a[m] = a_in[m];
         b[m] = a[m] + dd;
-        ca[m] = floor_div_ll(a[m], S);
-        cb[m] = floor_div_ll(b[m], S);
-        r[m] = (ca[m] == cb[m]) ? (a[m] + b[m]) / 2 : (ca[m] > cb[m] ? ca[m] : cb[m]) * S;
     }
-    current_segment(a, r, ca, nx, ny, nz, Z, Jfix, held);
-    current_segment(r, b, cb, nx, ny, nz, Z, Jfix, held);
+    long long turns = 0; // whole-cell steps: the most cells any axis skips
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+        const long long dc = floor_div_ll(b[m], S) - floor_div_ll(a[m], S);
+        const long long over = (dc < 0 ? -dc : dc) - 1;
+        turns = over > turns ? over : turns;
+    }
+    for (long long turn = 0; turn <= turns; ++turn) {
+        long long q[3], ca[3], cb[3], r[3];
+        bool skips = false;
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {
+            ca[m] = floor_div_ll(a[m], S);
+            const long long dc = floor_div_ll(b[m], S) - ca[m];
+            q[m] = dc >= 2 ? a[m] + S : (dc <= -2 ? a[m] - S : a[m]);
+            skips |= q[m] != a[m];
+        }
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {
+            if (!skips) q[m] = b[m];
+            cb[m] = floor_div_ll(q[m], S);
+            r[m] = (ca[m] == cb[m]) ? (a[m] + q[m]) / 2 : (ca[m] > cb[m] ? ca[m] : cb[m]) * S;
+        }
+        current_segment(a, r, ca, nx, ny, nz, Z, Jfix, held);
+        current_segment(r, q, cb, nx, ny, nz, Z, Jfix, held);
+        if (!skips) break;
+#pragma unroll
+        for (int m = 0; m < 3; ++m) a[m] = q[m];
+    }
 }
 
 template <typename T>
@@ -1751,7 +1777,7 @@ __device__ __forceinline__ void current_cell_fast(int wx, int wy, int wz, int d0
 }
 
 // The rare moves of the tiled kernel, out of line, by value: from (f*) to (t*, nearest image) in single fixed-point
-// units (cell * 2^14 + weight).  es3d_current in doubled coordinates: the relay point, one segment per cell, each into
+// units (cell * 2^14 + weight).  es3d_current in doubled coordinates: whole-cell steps while the move skips a cell, the relay point, one segment per cell, each into
 // the LDS window when its cell lies inside and into global memory otherwise (through g, the resident copy of the
 // arguments: a face crossing is one particle in ten and should not wait for a load; this is none).  Returns the number
 // of segments that went to global memory.
@@ -1760,32 +1786,59 @@ __device__ __attribute__((noinline)) unsigned em_current_rare(int f0, int f1, in
                                                               FPIC_LDS unsigned long long* lJ, const EmPushArgs<T>* g)
 {
     constexpr int S = 32768;
-    const int from[3] = { 2 * f0, 2 * f1, 2 * f2 }, to[3] = { 2 * t0, 2 * t1, 2 * t2 };
-    int ca[3], cb[3], r[3];
-    bool same = true;
-#pragma unroll
-    for (int m = 0; m < 3; ++m) {
-        ca[m] = from[m] >> 15;   // floor division by S (arithmetic shift)
-        cb[m] = to[m] >> 15;
-        same &= ca[m] == cb[m];
-        r[m] = (ca[m] == cb[m]) ? (from[m] + to[m]) / 2 : (ca[m] > cb[m] ? ca[m] : cb[m]) * S;
-    }
+    // doubled coordinates RELATIVE to the cell the move starts in (org): a doubled absolute coordinate leaves 32 bits at
+    // cell 65536, a relative one stays below half a box (n * 2^14); cells below are relative to org too
+    const int org[3] = { f0 >> 14, f1 >> 14, f2 >> 14 };
+    int from[3] = { 2 * (f0 - (org[0] << 14)), 2 * (f1 - (org[1] << 14)), 2 * (f2 - (org[2] << 14)) };
+    const int to[3] = { 2 * (t0 - (org[0] << 14)), 2 * (t1 - (org[1] << 14)), 2 * (t2 - (org[2] << 14)) };
     unsigned spilled = 0;
     auto segment = [&](const int (&p1)[3], const int (&p2)[3], const int (&cell)[3]) {
-        const int s = em_slot<T>(cell[0], cell[1], cell[2], ox, oy, oz, nx, ny, nz);
+        const int s = em_slot<T>(org[0] + cell[0], org[1] + cell[1], org[2] + cell[2], ox, oy, oz, nx, ny, nz);
         if (s >= 0) {
             current_cell<T>(p1, p2, cell, s, Z, lJ);
         } else {
-            const long long q1[3] = { p1[0], p1[1], p1[2] }, q2[3] = { p2[0], p2[1], p2[2] }, cc[3] = { cell[0], cell[1], cell[2] };
+            long long q1[3], q2[3], cc[3];
+#pragma unroll
+            for (int m = 0; m < 3; ++m) {
+                const long long o = static_cast<long long>(org[m]) * S;
+                q1[m] = o + p1[m]; q2[m] = o + p2[m]; cc[m] = static_cast<long long>(org[m]) + cell[m];
+            }
             current_segment(q1, q2, cc, nx, ny, nz, Z, g->Jfix, g->held); // (a face crossing is one particle in ten; this, none)
             ++spilled;
         }
     };
-    if (same) { // one cell (outside the window, or reached by a weight that rounded up to a whole cell): the whole segment at once
-        segment(from, to, ca);
-    } else {
-        segment(from, r, ca);
-        segment(r, to, cb);
+    int turns = 0; // whole-cell steps: the most cells any axis skips
+#pragma unroll
+    for (int m = 0; m < 3; ++m) {
+        const int dc = (to[m] >> 15) - (from[m] >> 15);
+        turns = max(turns, (dc < 0 ? -dc : dc) - 1);
+    }
+    for (int turn = 0; turn <= turns; ++turn) { // (one turn unless the move skips a cell on some axis: then whole-cell steps on those axes first, es3d_current)
+        int q[3], ca[3], cb[3], r[3];
+        bool skips = false, same = true;
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {
+            ca[m] = from[m] >> 15;   // floor division by S (arithmetic shift)
+            const int dc = (to[m] >> 15) - ca[m];
+            q[m] = dc >= 2 ? from[m] + S : (dc <= -2 ? from[m] - S : from[m]);
+            skips |= q[m] != from[m];
+        }
+#pragma unroll
+        for (int m = 0; m < 3; ++m) {
+            if (!skips) q[m] = to[m];
+            cb[m] = q[m] >> 15;
+            same &= ca[m] == cb[m];
+            r[m] = (ca[m] == cb[m]) ? (from[m] + q[m]) / 2 : (ca[m] > cb[m] ? ca[m] : cb[m]) * S;
+        }
+        if (same) { // one cell (outside the window, or reached by a weight that rounded up to a whole cell): the whole segment at once
+            segment(from, q, ca);
+        } else {
+            segment(from, r, ca);
+            segment(r, q, cb);
+        }
+        if (!skips) break;
+#pragma unroll
+        for (int m = 0; m < 3; ++m) from[m] = q[m];
     }
     return spilled;
 }

@@ -94,8 +94,8 @@ double* es3d_k2_table(int n, double d)
  *
  * Coordinates are DOUBLED fixed-point lattice coordinates: H = 2 * (cell * 2^14 + w1), S = 2^15 per cell (the same
  * 14-bit quantised positions the charge deposit uses, doubled so that midpoints stay integers).  The move a -> b
- * (nearest periodic image) is cut at a relay point (zigzag, Umeda et al. 2003) into two segments that each stay
- * inside one cell; per segment and cell the Villasenor-Buneman fluxes through the four dual faces of each direction,
+ * (nearest periodic image; one that skips a cell is taken in whole-cell steps first, see es3d_current) is cut at a
+ * relay point (zigzag, Umeda et al. 2003) into two segments that each stay inside one cell; per segment and cell the Villasenor-Buneman fluxes through the four dual faces of each direction,
  *     Jx(j+b, k+c) += dX * [ 3 * Ay_b * Az_c  +-  dY dZ ],   Ay_0 = 2S - Y1 - Y2,  Ay_1 = Y1 + Y2   (+ for b == c),
  * in units where one particle crossing a whole face carries 12 * S^3 * ... = 96 * 2^42: with the charge grid of
  * es3d_deposit (2^42 per particle) the lattice continuity equation holds EXACTLY in integers,
@@ -132,17 +132,12 @@ static void current_segment(const int64_t p1[3], const int64_t p2[3], const int6
     }
 }
 
-void es3d_current(const int64_t a[3], const int64_t b_in[3], int nx, int ny, int nz, int Z, int64_t* Jfix)
+/* the zigzag of a move whose cell index changes by at most one per axis: cut at the relay point into two segments */
+static void current_zigzag(const int64_t a[3], const int64_t b[3], int nx, int ny, int nz, int Z, int64_t* Jfix)
 {
     const int64_t S = 32768;
-    const int n[3] = { nx, ny, nz };
-    int64_t b[3], ca[3], cb[3], r[3];
+    int64_t ca[3], cb[3], r[3];
     for (int m = 0; m < 3; ++m) {
-        const int64_t box = (int64_t)n[m] * S;
-        int64_t dd = b_in[m] - a[m];
-        if (2 * dd > box) dd -= box;                /* nearest periodic image of the end point */
-        else if (2 * dd < -box) dd += box;
-        b[m] = a[m] + dd;
         ca[m] = floor_div(a[m], S);
         cb[m] = floor_div(b[m], S);
         /* relay point: the midpoint inside one cell, the face between two (both coordinates are even: the midpoint is an integer) */
@@ -150,6 +145,38 @@ void es3d_current(const int64_t a[3], const int64_t b_in[3], int nx, int ny, int
     }
     current_segment(a, r, ca, nx, ny, nz, Z, Jfix);
     current_segment(r, b, cb, nx, ny, nz, Z, Jfix);
+}
+
+void es3d_current(const int64_t a_in[3], const int64_t b_in[3], int nx, int ny, int nz, int Z, int64_t* Jfix)
+{
+    const int64_t S = 32768;
+    const int n[3] = { nx, ny, nz };
+    int64_t a[3], b[3];
+    for (int m = 0; m < 3; ++m) {
+        const int64_t box = (int64_t)n[m] * S;
+        int64_t dd = b_in[m] - a_in[m];
+        if (2 * dd > box) dd -= box;                /* nearest periodic image of the end point */
+        else if (2 * dd < -box) dd += box;
+        a[m] = a_in[m];
+        b[m] = a[m] + dd;
+    }
+    /* A segment is integrated with the weights of ONE cell, and at the relay point the weights of two cells agree only
+     * when the cells share that face.  A move that skips a cell on some axis (possible only for |v| > c below the CFL
+     * limit) therefore first takes whole-cell steps on those axes, each a zigzag of its own, until no axis skips;
+     * continuity holds for every piece, hence for the move. */
+    for (;;) {
+        int64_t w[3];
+        int skips = 0;
+        for (int m = 0; m < 3; ++m) {
+            const int64_t dc = floor_div(b[m], S) - floor_div(a[m], S);
+            w[m] = a[m] + (dc >= 2 ? S : dc <= -2 ? -S : 0);
+            skips |= w[m] != a[m];
+        }
+        if (!skips) break;
+        current_zigzag(a, w, nx, ny, nz, Z, Jfix);
+        for (int m = 0; m < 3; ++m) a[m] = w[m];
+    }
+    current_zigzag(a, b, nx, ny, nz, Z, Jfix);
 }
 
 #ifdef _OPENMP
