@@ -3,7 +3,8 @@ slab-decomposed Poisson solve as a periodic tridiagonal system per (kx, ky) mode
 instead of transposing the spectrum) built for the HOST with g++ and checked against numpy's FFT solve of the same
 system: 1..8 ranks, 2..512 planes per rank, modes from the longest wave of a 512^3 grid (lam = 1.5e-4: the
 ill-conditioned end) to the shortest (lam = 8), float and double storage.  No GPU involved; the kernels that wrap this
-core are held to one handle's transform solve in tests/test_gpu_es3d.py."""
+core are held to one handle's transform solve in tests/test_gpu_es3d.py, and to numpy float64, two closed forms and exact
+eigenmodes on every rank's planes in tests/test_gpu_decomposed_solve.py."""
 import os
 import subprocess
 
