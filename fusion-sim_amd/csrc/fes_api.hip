@@ -23,6 +23,7 @@
 //   fes_hist.inc.hpp        the phase-space histograms: the pass of one request, the ranks' sum
 //   fes_mom.inc.hpp         the fluid moment grids: the sweeps of one request, the held planes' places, the ranks' sum
 //   fes_series.inc.hpp      the series: rows of field points and tracer particles, now or into a ring, the ranks' selection
+//   fes_modes.inc.hpp       the modes: Fourier amplitudes of the node fields at chosen wave vectors, now or into a ring, the ranks' sum
 #include "fes_api.hpp"
 #include "fes_kernels.hpp"
 #include "fes_diag_kernels.hpp"
@@ -30,6 +31,7 @@
 #include "fes_hist_kernels.hpp"
 #include "fes_mom_kernels.hpp"
 #include "fes_series_kernels.hpp"
+#include "fes_modes_kernels.hpp"
 #include "fes_fft.hpp"
 #include "fes_tri.hpp"
 #include "fpic_comm.hpp"
@@ -343,6 +345,7 @@ namespace {
 #include "fes_hist.inc.hpp"
 #include "fes_mom.inc.hpp"
 #include "fes_series.inc.hpp"
+#include "fes_modes.inc.hpp"
 
 int precalc(fpic_handle* h)
 {

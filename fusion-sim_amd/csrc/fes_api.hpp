@@ -43,6 +43,10 @@ int moments(fpic_handle* h, const fpic_moments_spec* spec, int scope, int64_t* o
 int series_now(fpic_handle* h, const fpic_series_spec* spec, int scope, double* points_out, double* tracers_out);
 int series_record(fpic_handle* h, const fpic_series_spec* spec, int every, uint32_t capacity);
 int series_history(fpic_handle* h, int scope, uint64_t* substeps, double* points_out, double* tracers_out, uint64_t capacity, uint64_t* n, uint64_t* dropped);
+// Fourier amplitudes of the node fields at chosen wave vectors (fes_modes.inc.hpp)
+int modes_now(fpic_handle* h, const fpic_modes_spec* spec, int scope, double* out);
+int modes_record(fpic_handle* h, const fpic_modes_spec* spec, int every, uint32_t capacity);
+int modes_history(fpic_handle* h, int scope, uint64_t* substeps, double* out, uint64_t capacity, uint64_t* n, uint64_t* dropped);
 uint64_t last_spill(const fpic_handle* h); // out-of-window deposits of the sub-step before last (lagged read-back)
 
 } // namespace fes

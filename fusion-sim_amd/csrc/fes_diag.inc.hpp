@@ -205,10 +205,11 @@ int energy_history(fpic_handle* h, int scope, fpic_energy* rows, uint64_t capaci
 }
 
 static int series_after_substep(fpic_handle* h);   // (fes_series.inc.hpp: the series recorder's share of the hook)
+static int modes_after_substep(fpic_handle* h);    // (fes_modes.inc.hpp: the modes recorder's)
 
 // the recording hook, at the end of every sub-step of every path (substeps(), group_run()): counts the sub-step and, every
-// `every`-th one, enqueues the reduction into the ring; then the series recorder, which shares the counter and nothing else,
-// takes its turn.  Recording off: nothing is enqueued.
+// `every`-th one, enqueues the reduction into the ring; then the series recorder and the modes recorder, which share the
+// counter and nothing else, take their turns.  Recording off: nothing is enqueued.
 static int diag_after_substep(fpic_handle* h)
 {
     Diag& g = h->es->diag;
@@ -218,5 +219,6 @@ static int diag_after_substep(fpic_handle* h)
         if (int rc = h->prec == FPIC_F32 ? diag_enqueue<float>(h, row) : diag_enqueue<double>(h, row)) return rc;
         g.ring.seq++;
     }
-    return series_after_substep(h);
+    if (int rc = series_after_substep(h)) return rc;
+    return modes_after_substep(h);
 }

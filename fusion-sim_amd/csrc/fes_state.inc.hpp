@@ -58,6 +58,29 @@ struct Series {
     SeriesReq req;
 };
 
+// the modes diagnostic (fes_modes.inc.hpp): a request's copies on the device — one allocation holding the three twiddle tables
+// (complex doubles, nx + ny + nz entries), the reduced wave vectors (int32 [nmodes][3]) and the workgroups' partial rows
+struct ModesReq {
+    uint32_t nmodes = 0, mask = 0;
+    int nq = 0;
+    int place[fesmod::kQuantities] = {};
+    fesmod::Shape shape{};
+    void* block = nullptr;
+    size_t bytes = 0;
+    const double2 *wx = nullptr, *wy = nullptr, *wz = nullptr;
+    const int32_t* modes = nullptr;
+    double2* partial = nullptr;
+    size_t width() const { return static_cast<size_t>(2) * nmodes * nq; }   // doubles per row
+};
+// ... and the recorder: a ring of rows of req.width() doubles; the host keeps the sub-step of each slot
+struct Modes {
+    int every = 0;
+    fesdiag::Ring ring;
+    double* ring_dev = nullptr;
+    std::vector<uint64_t> ring_substep;
+    ModesReq req;
+};
+
 // the energy diagnostics (fes_diag.inc.hpp): the sub-step counter of fpic_energy, the recording ring, the reduction's buffers
 struct Diag {
     uint64_t substep = 0;              // sub-steps advanced since create
@@ -73,11 +96,12 @@ struct Diag {
     unsigned long long* mom = nullptr;  // the buffer of fpic_moments (fes_mom.inc.hpp): a grid of the held planes per moment, then `rejected`, `spilled`; grows to the largest request
     size_t mom_words = 0;
     Series series;                      // the recorder of fpic_series_record (fes_series.inc.hpp); shares `substep`
+    Modes modes;                        // the recorder of fpic_modes_record (fes_modes.inc.hpp); shares `substep`
 };
 inline void diag_release(Diag& g)
 {
     for (void* p : { static_cast<void*>(g.ring_dev), static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom),
-                    static_cast<void*>(g.series.ring_dev), g.series.req.block })
+                    static_cast<void*>(g.series.ring_dev), g.series.req.block, static_cast<void*>(g.modes.ring_dev), g.modes.req.block })
         if (p) (void)hipFree(p);
     g = Diag();
 }

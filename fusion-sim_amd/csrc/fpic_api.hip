@@ -1438,6 +1438,24 @@ int fpic_series_history(fpic_handle* h, int scope, uint64_t* substeps, double* p
     BOX_ONLY(h, "fpic_series_history");
     return fes::series_history(h, scope, substeps, points_out, tracers_out, capacity, n, dropped);
 }
+int fpic_modes_now(fpic_handle* h, const fpic_modes_spec* spec, int scope, double* out)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_modes_now");
+    return fes::modes_now(h, spec, scope, out);
+}
+int fpic_modes_record(fpic_handle* h, const fpic_modes_spec* spec, int every, uint32_t capacity)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_modes_record");
+    return fes::modes_record(h, spec, every, capacity);
+}
+int fpic_modes_history(fpic_handle* h, int scope, uint64_t* substeps, double* out, uint64_t capacity, uint64_t* n, uint64_t* dropped)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_modes_history");
+    return fes::modes_history(h, scope, substeps, out, capacity, n, dropped);
+}
 int fpic_get_particles_of(fpic_handle* h, int species, void* pos_aos, void* vel_aos, int dtype)
 {
     CHECK_HANDLE(h);

@@ -46,6 +46,7 @@ ABI_FUNCTIONS = [
     "fpic_group_precalc", "fpic_group_step", "fpic_group_density",
     "fpic_energy_now", "fpic_energy_record", "fpic_energy_history", "fpic_histogram", "fpic_moments",
     "fpic_series_now", "fpic_series_record", "fpic_series_history",
+    "fpic_modes_now", "fpic_modes_record", "fpic_modes_history",
 ]
 
 
@@ -245,6 +246,50 @@ def _series_select(parts, flag):
     return out, owner
 
 
+MODES_MAX = 256
+MODE_FIELDS = ("ex", "ey", "ez", "phi", "bx", "by", "bz", "rho")   # bit b of a mask is MODE_FIELDS[b]
+
+
+class ModesSpec(ctypes.Structure):
+    """mirror of fpic_modes_spec (include/fusionpic.h)"""
+    _fields_ = [("nmodes", ctypes.c_uint32), ("mask", ctypes.c_uint32), ("modes", ctypes.c_void_p), ("reserved", ctypes.c_double * 4)]
+
+
+def _modes_spec(modes, fields):
+    """(ModesSpec, the selected names in bit order, the array the structure points to) of a request.  Only what the structure
+    cannot carry is refused here (a shape, a component that is no int32, an unknown name); every other check is the library's."""
+    names = [fields] if isinstance(fields, str) else list(fields)
+    mask = 0
+    for f in names:
+        if f not in MODE_FIELDS:
+            raise FusionPicError(-1, ".fields <- must be names from ex, ey, ez, phi, bx, by, bz, rho")
+        mask |= 1 << MODE_FIELDS.index(f)
+    raw = np.asarray(modes if modes is not None else np.zeros((0, 3), dtype=np.int64))
+    if raw.size == 0:
+        raw = np.zeros((0, 3), dtype=np.int64)
+    if raw.ndim != 2 or raw.shape[1] != 3 or raw.dtype.kind not in "iu" or (raw.size and (int(raw.min()) < -2 ** 31 or int(raw.max()) >= 2 ** 31)):
+        raise FusionPicError(-1, ".modes <- must be an array of int32 triples of shape (nmodes, 3)")
+    if raw.shape[0] >= 1 << 32:
+        raise FusionPicError(-1, ".nmodes <- must lie in [1, FPIC_MODES_MAX (256)]")
+    m = np.ascontiguousarray(raw, dtype=np.int32)
+    s = ModesSpec()
+    s.nmodes, s.mask, s.modes = m.shape[0], mask, (m.ctypes.data if m.shape[0] else None)
+    return s, [f for f in MODE_FIELDS if f in names], m
+
+
+def _modes_dict(rows, names):
+    """float64 [..., nmodes, nq, 2] -> {name: complex128 [..., nmodes]}"""
+    return {f: np.ascontiguousarray(rows[..., q, 0] + 1j * rows[..., q, 1]) for q, f in enumerate(names)}
+
+
+def _modes_sum(parts):
+    """the members' rows added in rank order, as the library adds the ranks'"""
+    out = parts[0].copy()
+    for p in parts[1:]:
+        out += p
+    return out
+
+
 MOMENT_NAMES = ("N", "FX", "FY", "FZ", "SXX", "SYY", "SZZ", "SXY", "SXZ", "SYZ")   # bit b of a mask is MOMENT_NAMES[b]
 MOMENT_SETS = {"n": 0x001, "order1": 0x00F, "order2": 0x3FF}
 MOM_ONE = 1 << 42          # N of one particle, summed over its eight nodes
@@ -372,6 +417,9 @@ def load_library(path=None):
     lib.fpic_series_now.argtypes = [vp, ctypes.POINTER(SeriesSpec), ci, vp, vp]
     lib.fpic_series_record.argtypes = [vp, ctypes.POINTER(SeriesSpec), ci, ctypes.c_uint32]
     lib.fpic_series_history.argtypes = [vp, ci, vp, vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+    lib.fpic_modes_now.argtypes = [vp, ctypes.POINTER(ModesSpec), ci, vp]
+    lib.fpic_modes_record.argtypes = [vp, ctypes.POINTER(ModesSpec), ci, ctypes.c_uint32]
+    lib.fpic_modes_history.argtypes = [vp, ci, vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -673,6 +721,48 @@ class CylindricalParticlePusher:
                                                   out["points"].ctypes.data, out["tracers"].ctypes.data, rows, ctypes.byref(n), ctypes.byref(dropped)))
         return out, int(dropped.value)
 
+    # ---- modes: the Fourier amplitudes of the node fields at chosen wave vectors (fpic_modes_*)
+    def _modes_rows(self, modes, fields, scope):
+        s, names, keep = _modes_spec(modes, fields)
+        rows = np.zeros((s.nmodes if s.nmodes <= MODES_MAX else 0, len(names), 2))      # (a refused request writes nothing)
+        spare = np.zeros(2)
+        self._check(self._lib.fpic_modes_now(self._h, ctypes.byref(s), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope],
+                                             rows.ctypes.data if rows.size else spare.ctypes.data))
+        return rows, names
+
+    def modes(self, modes, fields=("ex", "ey", "ez", "phi"), scope="global"):
+        """The complex Fourier amplitudes of the node fields of a CART3D box at the wave vectors `modes` (int triples
+        (mx, my, mz), shape (nmodes, 3); fpic_modes_now; an (r,z) handle is refused): A(m) = (1/N) sum F exp(-2 pi i (mx i /
+        nx + my j / ny + mz k / nz)) over the nodes, of what readField(F3_E) / readField(F3_B_NODES) hold and of
+        readField(F3_RHO_FIXED) in C/m^3, summed in double on the device.  fields: names from MODE_FIELDS.  Returns {name:
+        complex128 (nmodes,)}.  'global' on a rank with a communicator is collective; on a member of an in-process group it
+        is an error (BoxGroup.modes)."""
+        return _modes_dict(*self._modes_rows(modes, fields, scope))
+
+    def recordModes(self, every, capacity=4096, modes=None, fields=("ex", "ey", "ez", "phi")):
+        """after every `every`-th sub-step the row of modes() goes into a device ring of `capacity` rows on the handle's stream
+        (fpic_modes_record; 0: off).  Independent of recordEnergy and recordSeries, with which it shares the sub-step counter."""
+        s, names, keep = _modes_spec(modes, fields)
+        self._check(self._lib.fpic_modes_record(self._h, ctypes.byref(s) if every else None, int(every), int(capacity)))
+        self._modes_shape = (int(s.nmodes), names) if every else (0, [])
+
+    def _modes_history_rows(self, scope):
+        sc = {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope]
+        M, names = getattr(self, "_modes_shape", (0, []))
+        n, dropped = ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self._lib.fpic_modes_history(self._h, sc, None, None, 0, ctypes.byref(n), ctypes.byref(dropped)))
+        rows = n.value
+        sub, out, spare = np.zeros(max(rows, 1), dtype=np.uint64), np.zeros((rows, M, len(names), 2)), np.zeros(2)
+        self._check(self._lib.fpic_modes_history(self._h, sc, sub.ctypes.data, out.ctypes.data if out.size else spare.ctypes.data, rows,
+                                                 ctypes.byref(n), ctypes.byref(dropped)))
+        return sub[:rows], out, names, int(dropped.value)
+
+    def modesHistory(self, scope="global"):
+        """({substep: uint64 (rows,), name: complex128 (rows, nmodes) per recorded field}, dropped): the rows recorded since the
+        last call, oldest first, and how many older rows the ring overwrote"""
+        sub, out, names, dropped = self._modes_history_rows(scope)
+        return dict(_modes_dict(out, names), substep=sub), dropped
+
     def sync(self):
         self._check(self._lib.fpic_sync(self._h))
 
@@ -892,6 +982,11 @@ class ElectrostaticBoxPusher:
     series = CylindricalParticlePusher.series
     recordSeries = CylindricalParticlePusher.recordSeries
     seriesHistory = CylindricalParticlePusher.seriesHistory
+    _modes_rows = CylindricalParticlePusher._modes_rows
+    modes = CylindricalParticlePusher.modes
+    recordModes = CylindricalParticlePusher.recordModes
+    _modes_history_rows = CylindricalParticlePusher._modes_history_rows
+    modesHistory = CylindricalParticlePusher.modesHistory
 
     # ---- fluid moment grids (fpic_moments), reduced on the device
     def moments(self, which="order2", species=0, scope="global"):
@@ -999,6 +1094,34 @@ class BoxGroup:
         pts, op = _series_select([p["points"] for p, _ in parts], SERIES_POINT_COLUMNS.index("present"))
         trs, ot = _series_select([p["tracers"] for p, _ in parts], SERIES_TRACER_COLUMNS.index("found"))
         return {"substep": first["substep"], "points": pts, "tracers": trs, "owner_points": op, "owner_tracers": ot}, dropped
+
+
+    def modes(self, modes, fields=("ex", "ey", "ez", "phi")):
+        """the whole box: the members' LOCAL rows (each the sum over its own planes) added in rank order"""
+        parts = [m._modes_rows(modes, fields, "local") for m in self.sims]
+        return _modes_dict(_modes_sum([p[0] for p in parts]), parts[0][1])
+
+    def recordModes(self, every, capacity=4096, modes=None, fields=("ex", "ey", "ez", "phi")):
+        """every member records its LOCAL rows of the same request"""
+        for m in self.sims:
+            m.recordModes(every, capacity, modes, fields)
+
+    def modesHistory(self):
+        """the members' LOCAL histories drained and added row by row in rank order, as modes() does.  The members' pending
+        row counts are compared first (a query drains nothing), so a mismatch loses no rows."""
+        counts = []
+        for m in self.sims:
+            n, d = ctypes.c_uint64(), ctypes.c_uint64()
+            m._check(m._lib.fpic_modes_history(m._h, DIAG_LOCAL, None, None, 0, ctypes.byref(n), ctypes.byref(d)))
+            counts.append((n.value, d.value))
+        if any(c != counts[0] for c in counts):
+            raise FusionPicError(-5, "the members hold different recorded rows: record with the same settings on every member")
+        parts = [m._modes_history_rows("local") for m in self.sims]
+        sub, _, names, dropped = parts[0]
+        for s2, _, _, d2 in parts[1:]:
+            if d2 != dropped or not np.array_equal(s2, sub):
+                raise FusionPicError(-5, "the members hold different recorded rows: record with the same settings on every member")
+        return dict(_modes_dict(_modes_sum([p[1] for p in parts]), names), substep=sub), dropped
 
 
 def commUniqueId(library=None):

@@ -33,7 +33,7 @@
  * geometry 'cart3d' (+ ny, length_y, solver 'poisson_fft'|'none', macro_weight) selects the self-consistent
  * electrostatic box — an extension with no reference counterpart (include/fusionpic.h): radius, height are
  * then the box lengths along x and z, nr, nz the node counts; same method names, plus addSpecies, addB,
- * readField, energy, recordEnergy, energyHistory, histogram, moments, series, recordSeries, seriesHistory.  Multi-GPU (one process per GPU): empic.commUniqueId() on rank 0, simulation.commInit(id,
+ * readField, energy, recordEnergy, energyHistory, histogram, moments, series, recordSeries, seriesHistory, modes, recordModes, modesHistory.  Multi-GPU (one process per GPU): empic.commUniqueId() on rank 0, simulation.commInit(id,
  * rank, world) on every rank; density() then sums the per-cell sums over the ranks inside the library (RCCL).
  */
 'use strict';
@@ -273,6 +273,35 @@ function makeBox(spec, lib) {
     };
     // -> { rows, dropped, substep: Float64Array [rows], points: Float64Array [rows][P][8], tracers: Float64Array [rows][M][8] }, oldest first
     out.seriesHistory = function (scope) { return lib.seriesHistory(h, scopeOf(scope)); };
+    // modes (fpic_modes_*): the complex Fourier amplitudes A(m) = (1/N) sum F exp(-2 pi i (mx i / nx + my j / ny + mz k / nz)) of the
+    // node fields at chosen wave vectors, summed in double on the GPU, now or recorded into a device ring.  request = { modes:
+    // [[mx, my, mz], ...] (integers within [-n/2, n/2] per axis), fields: names from ex ey ez phi bx by bz rho (default the first
+    // four) } -> { fields: the selected names in the order of the values, values: Float64Array [M][nq][2] of interleaved re, im }
+    const MODE_FIELDS = ['ex', 'ey', 'ez', 'phi', 'bx', 'by', 'bz', 'rho'];
+    let recordedModeFields = [];
+    const modesArgs = function (request) {
+        if (request === null || typeof request !== 'object') throw new TypeError('.request <- expected { modes, fields }');
+        const modes = request.modes === undefined || request.modes === null ? [] : request.modes;
+        if (!Array.isArray(modes) || !modes.every((m) => (Array.isArray(m) || ArrayBuffer.isView(m)) && m.length === 3 && Array.from(m).every((x) => Number.isInteger(x) && Math.abs(x) <= 0x7fffffff)))
+            throw new RangeError('.modes <- expected an array of integer triples [mx, my, mz]');
+        const fields = request.fields === undefined ? MODE_FIELDS.slice(0, 4) : request.fields;
+        if (!Array.isArray(fields) || !fields.every((f) => MODE_FIELDS.includes(f))) throw new RangeError('.fields <- must be names from ex, ey, ez, phi, bx, by, bz, rho');
+        let mask = 0;
+        for (const f of fields) mask |= 1 << MODE_FIELDS.indexOf(f);
+        return [Int32Array.from(modes.map((m) => Array.from(m)).flat()), mask, MODE_FIELDS.filter((f) => fields.includes(f))];
+    };
+    out.modes = function (request, scope) {
+        const [modes, mask, names] = modesArgs(request);
+        return { fields: names, values: lib.modes(h, modes, mask, scopeOf(scope)) };
+    };
+    // after every `every`-th sub-step the same row goes into a ring of `capacity` rows on the device (every 0: off)
+    out.recordModes = function (every, capacity, request) {
+        const [modes, mask, names] = every ? modesArgs(request) : [null, 0, []];
+        lib.recordModes(h, every, capacity === undefined ? 4096 : capacity, modes, mask);
+        recordedModeFields = names;
+    };
+    // -> { rows, dropped, substep: Float64Array [rows], fields, values: Float64Array [rows][M][nq][2] }, oldest first
+    out.modesHistory = function (scope) { return Object.assign(lib.modesHistory(h, scopeOf(scope)), { fields: recordedModeFields }); };
     // fluid moment grids of one species, reduced on the GPU (fpic_moments): request = { species (default 0), which: 'n' | 'order1' |
     // 'order2' (default) | an array of names from N FX FY FZ SXX SYY SZZ SXY SXZ SYZ }
     // -> { NAME: BigInt64Array [nz][ny][nr] per moment asked for (N in units of 2^-42 particles, the others of 2^-32), rejected, spilled }

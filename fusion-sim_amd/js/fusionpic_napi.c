@@ -42,6 +42,8 @@ typedef struct {
     size_t count[MAX_SPECIES];
     /* the request fpic_series_record armed: how many entries a recorded row has (seriesHistory sizes its arrays by them) */
     size_t series_points, series_tracers;
+    /* the request fpic_modes_record armed: the doubles of a recorded row (modesHistory sizes its array by them) */
+    size_t modes_width;
 } box_t;
 
 static void box_finalize(napi_env env, void* data, void* hint)
@@ -166,6 +168,7 @@ static napi_value n_create(napi_env env, napi_callback_info info)
     b->nspecies = 1;
     b->count[0] = b->n;
     b->series_points = b->series_tracers = 0;
+    b->modes_width = 0;
     napi_value ext;
     if (napi_create_external(env, b, box_finalize, NULL, &ext) != napi_ok) {
         box_finalize(env, b, NULL);
@@ -970,6 +973,75 @@ static napi_value n_series_history(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* ---- modes: the Fourier amplitudes of the node fields at chosen wave vectors (fpic_modes_*).  A request travels as an
+ * Int32Array of 3 M wave-vector components and the mask of quantities.  The array's type and length are checked here, the
+ * request itself by the library. */
+static int get_modes_request(napi_env env, napi_value* argv, fpic_modes_spec* s, size_t* width)
+{
+    napi_typedarray_type tm; void* pm; size_t lm; double mask;
+    if (!get_typed(env, argv[0], &tm, &pm, &lm) || !get_double(env, argv[1], &mask)) return 0;
+    if (pm && tm != napi_int32_array) { napi_throw_type_error(env, NULL, ".modes <- expected an Int32Array of wave-vector components"); return 0; }
+    if (lm % 3) { napi_throw_range_error(env, NULL, ".modes <- expected three components per wave vector"); return 0; }
+    if (lm / 3 > FPIC_MODES_MAX) { napi_throw_range_error(env, NULL, ".nmodes <- must lie in [1, FPIC_MODES_MAX (256)]"); return 0; }
+    if (mask < 0 || mask > 4294967295.0 || mask != (double)(uint32_t)mask) { napi_throw_range_error(env, NULL, ".mask <- expected a mask of quantity bits"); return 0; }
+    memset(s, 0, sizeof *s);
+    s->nmodes = (uint32_t)(lm / 3); s->mask = (uint32_t)mask;
+    s->modes = lm ? (const int32_t*)pm : NULL;
+    size_t nq = 0;
+    for (uint32_t b = s->mask & FPIC_MODE_ALL; b; b >>= 1) nq += b & 1u;
+    *width = 2 * (size_t)s->nmodes * nq;
+    return 1;
+}
+
+/* modes(h, modes, mask, scope) -> Float64Array [M][nq][2] (re, im; the quantities in ascending bit order) */
+static napi_value n_modes(napi_env env, napi_callback_info info)
+{
+    napi_value argv[4]; fpic_handle* h; int scope; fpic_modes_spec s; size_t width;
+    if (!get_args(env, info, 4, argv, &h) || !get_scope(env, argv[3], &scope) || !get_modes_request(env, argv + 1, &s, &width)) return NULL;
+    double* d = NULL;
+    napi_value out = new_f64(env, width ? width : 2, &d);      /* (a refused request writes nothing) */
+    if (!out) return NULL;
+    if (fpic_modes_now(h, &s, scope, d) != FPIC_OK) return throw_fpic(env, h);
+    return out;
+}
+
+/* recordModes(h, every, capacity, modes, mask) */
+static napi_value n_record_modes(napi_env env, napi_callback_info info)
+{
+    napi_value argv[5]; fpic_handle* h; double every, cap; fpic_modes_spec s; size_t width;
+    if (!get_args(env, info, 5, argv, &h) || !get_double(env, argv[1], &every) || !get_double(env, argv[2], &cap) || !get_modes_request(env, argv + 3, &s, &width)) return NULL;
+    if (every < 0 || every > 2147483647.0 || cap < 0 || cap > 4294967295.0) { napi_throw_range_error(env, NULL, ".every <- out of range"); return NULL; }
+    if (fpic_modes_record(h, every > 0 ? &s : NULL, (int)every, (uint32_t)cap) != FPIC_OK) return throw_fpic(env, h);
+    g_box->modes_width = every > 0 ? width : 0;
+    return undefined(env);
+}
+
+/* modesHistory(h, scope) -> { rows, dropped, substep: Float64Array of rows, values: Float64Array [rows][M][nq][2] } (the rows
+ * recorded since the last call, oldest first) */
+static napi_value n_modes_history(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2]; fpic_handle* h; int scope;
+    if (!get_args(env, info, 2, argv, &h) || !get_scope(env, argv[1], &scope)) return NULL;
+    uint64_t n = 0, dropped = 0;
+    if (fpic_modes_history(h, scope, NULL, NULL, 0, &n, &dropped) != FPIC_OK) return throw_fpic(env, h);
+    double *sd = NULL, *vd = NULL;
+    napi_value sub = new_f64(env, (size_t)n, &sd), vals = new_f64(env, (size_t)n * g_box->modes_width, &vd), out, v;
+    if (!sub || !vals) return NULL;
+    uint64_t* steps = (uint64_t*)calloc((size_t)n + 1, sizeof(uint64_t));
+    if (!steps) { napi_throw_error(env, NULL, "host allocation failed"); return NULL; }
+    if (fpic_modes_history(h, scope, steps, vd, n, &n, &dropped) != FPIC_OK) { free(steps); return throw_fpic(env, h); }
+    for (uint64_t i = 0; i < n; ++i) sd[i] = (double)steps[i];
+    free(steps);
+    NAPI_OK(env, napi_create_object(env, &out));
+    NAPI_OK(env, napi_create_double(env, (double)n, &v));
+    NAPI_OK(env, napi_set_named_property(env, out, "rows", v));
+    NAPI_OK(env, napi_create_double(env, (double)dropped, &v));
+    NAPI_OK(env, napi_set_named_property(env, out, "dropped", v));
+    NAPI_OK(env, napi_set_named_property(env, out, "substep", sub));
+    NAPI_OK(env, napi_set_named_property(env, out, "values", vals));
+    return out;
+}
+
 static napi_value n_build_arch(napi_env env, napi_callback_info info)
 {
     (void)info;
@@ -998,6 +1070,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "energy", n_energy }, { "recordEnergy", n_record_energy }, { "energyHistory", n_energy_history },
         { "histogram", n_histogram }, { "moments", n_moments },
         { "series", n_series }, { "recordSeries", n_record_series }, { "seriesHistory", n_series_history },
+        { "modes", n_modes }, { "recordModes", n_record_modes }, { "modesHistory", n_modes_history },
     };
     for (size_t i = 0; i < sizeof table / sizeof table[0]; ++i) {
         napi_value fn;

@@ -590,6 +590,72 @@ int fpic_series_record(fpic_handle* h, const fpic_series_spec* spec, int every, 
 int fpic_series_history(fpic_handle* h, int scope, uint64_t* substeps, double* points_out, double* tracers_out, uint64_t capacity,
                         uint64_t* n, uint64_t* dropped);
 
+/* ---- CART3D modes: the complex Fourier amplitudes of the node fields at a chosen list of wave vectors, taken now or
+ * recorded after every `every`-th sub-step into a device ring, without reading a grid back and without a full transform (any
+ * grid shape).  A request names nmodes wave vectors m = (mx, my, mz) as int32 triples and a mask of quantities:
+ *   FPIC_MODE_EX, _EY, _EZ, _PHI   the four components of the node record FPIC_F3_E as stored (the fourth is phi in the
+ *                                  electrostatic box)
+ *   FPIC_MODE_BX, _BY, _BZ         the three components of FPIC_F3_B_NODES (all zero unless solver = YEE, as in a point row)
+ *   FPIC_MODE_RHO                  the integer charge grid FPIC_F3_RHO_FIXED converted to double, times the double
+ *                                  q0 W / (2^42 dV) with which the library forms FPIC_F3_RHO (formed as
+ *                                  particle_charge * macro_weight / (4398046511104.0 * dV), dV = (lx/nx) * (ly/ny) * (lz/nz))
+ * The arrays are read as they are at that moment — nothing is closed and nothing is formed, exactly as a point row of
+ * fpic_series reads them — so the amplitude is the discrete transform of what a point series on every node would return.
+ * For a quantity F on the N = nx ny nz nodes (node index i + nx * (j + ny * k)):
+ *   A(m) = (1/N) * sum_k sum_j sum_i (double) F[k][j][i] * wx[(mx i) mod nx] * wy[(my j) mod ny] * wz[(mz k) mod nz]
+ * The arithmetic is double in fp32 and fp64 states alike (a float converts exactly).  (m i) mod n is integer arithmetic; a
+ * negative m is reduced into [0, n) first.  wa[t] = exp(-2 pi i t / na) comes from three tables of doubles built on the
+ * host with two guaranteed properties: an entry with 4 t divisible by na is exactly (+-1, 0) or (0, +-1), and wa[na - t] is
+ * bit for bit the conjugate of wa[t] (t <= na / 2 is computed, the rest mirrored).  So a field of small integers at modes
+ * whose twiddles all lie in {+-1, +-i} sums exactly, and A(-m) is exactly conj A(m).
+ * The order of the sum is fixed — a function of the grid shape, the planes the handle owns and the request alone.  With p
+ * the smallest power of two >= nmodes and S = 256 / p: the owned rows (k, j), in the order of j + ny * k, are cut into
+ * contiguous shares of ceil(rows / 1024) rows, one per workgroup.  Within a share, for each s < S: per row the terms of
+ * the nodes i = s, s + S, s + 2 S, ... are added in ascending i (product F * wx first, re and im apart), that sum is
+ * multiplied by (wy * wz) of the row, and the rows' products are added in row order; then the S sums are added in the
+ * order s = 0, 1, ...  The workgroups' sums are added in workgroup order within 64 contiguous groups of
+ * ceil(workgroups / 64), the groups' sums in group order, and the total is divided by N.  Every operation is rounded once
+ * (no fused multiply-add).  So the order depends on nmodes through S, and on nothing else of the request: a permuted list
+ * and any sub-mask return the same bits for what they share, a request with another NUMBER of modes returns another
+ * rounding of the same sums.  No floating-point atomics; no dependence on timing: two calls on one state, and two handles
+ * holding the same fields, return the same bits.
+ * out: double [nmodes][nq][2] (re, im), the nq selected quantities in ascending bit order.
+ * scope: LOCAL is the sum over the planes this handle owns (all nz; the slab of a rank of a decomposition), with k the
+ * global plane and N the global node count, so the ranks' LOCAL rows add up to the box.  GLOBAL with a communicator is
+ * collective: the ranks' rows are gathered and added in rank order on every rank (every rank gets the same bits).  GLOBAL on
+ * a member of an in-process group is FPIC_ERR_STATE (the host adds up the members' LOCAL rows in rank order).
+ * Refused (FPIC_ERR_INVALID_ARG): a null pointer, nmodes = 0 or above FPIC_MODES_MAX, a component outside [-na/2, na/2],
+ * the same triple twice, an empty mask or unknown bits, a reserved word that is not zero, capacity = 0 with every > 0;
+ * FPIC_ERR_STATE: a handle that is not CART3D, a call before fpic_precalc, a rank that does not hold its owned planes.
+ * The recorder is not part of a checkpoint (as the series' and the energy's are not): arm it again after a load. */
+#define FPIC_MODES_MAX 256u
+#define FPIC_MODE_EX  (1u << 0)
+#define FPIC_MODE_EY  (1u << 1)
+#define FPIC_MODE_EZ  (1u << 2)
+#define FPIC_MODE_PHI (1u << 3)
+#define FPIC_MODE_BX  (1u << 4)
+#define FPIC_MODE_BY  (1u << 5)
+#define FPIC_MODE_BZ  (1u << 6)
+#define FPIC_MODE_RHO (1u << 7)
+#define FPIC_MODE_ALL 0xFFu
+typedef struct fpic_modes_spec {
+    uint32_t        nmodes, mask;
+    const int32_t*  modes;           /* [nmodes][3] */
+    double          reserved[4];     /* zero */
+} fpic_modes_spec;
+/* The amplitudes of the current state: out [nmodes][nq][2].  Enqueues on the handle's stream, copies back, waits. */
+int fpic_modes_now(fpic_handle* h, const fpic_modes_spec* spec, int scope, double* out);
+/* After every `every`-th sub-step (the counter of fpic_energy.substep) the same row is written into a device ring of
+ * `capacity` rows on the handle's stream: no host synchronisation, no collective.  every = 0 turns recording off and frees
+ * the ring (spec may then be NULL); a new call starts an empty ring; a refused call leaves the running recorder as it was.
+ * Independent of fpic_energy_record and fpic_series_record. */
+int fpic_modes_record(fpic_handle* h, const fpic_modes_spec* spec, int every, uint32_t capacity);
+/* The rows recorded since the last drain, oldest first: substeps[r], out[r][nmodes][nq][2] for r < *n (substeps = NULL: *n
+ * receives how many there are, nothing is drained).  capacity: the rows the arrays have room for.  If the ring wrapped, the
+ * newest rows are returned and *dropped counts the others.  GLOBAL with a communicator is collective: every rank must hold
+ * the same number of rows (else FPIC_ERR_STATE on every rank). */
+int fpic_modes_history(fpic_handle* h, int scope, uint64_t* substeps, double* out, uint64_t capacity, uint64_t* n, uint64_t* dropped);
+
 int fpic_sync(fpic_handle* h);
 int fpic_profile(fpic_handle* h, int enable);
 int fpic_get_stats(fpic_handle* h, fpic_stats* out);
