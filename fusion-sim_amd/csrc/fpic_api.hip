@@ -255,7 +255,9 @@ int launch_push(fpic_handle* h, int nsub)
     t.census_valid = scatter && h->chunk_census_fresh ? 1 : 0; // (the launch before was an in-place fused push over this very work list)
     // TEST SWITCH (tests/test_gpu_parity.py: the count pass and the per-item census must reserve the same ranges): the
     // re-binning launch counts its chunk itself although the launch before left its census
-    if (t.census_valid && std::getenv("FPIC_TEST_COUNT_PASS")) t.census_valid = 0;
+    if (t.census_valid && h->test_count_pass) t.census_valid = 0;
+    t.outbox = static_cast<nat_u32x4*>(h->outbox); t.outbox_state = h->outbox_state;
+    t.outbox_cap = h->outbox ? h->outbox_cap : 0;
     h->sums_fresh = h->census_fresh = false;
     h->chunk_census_fresh = false;
     h->scatter_pending = false;
@@ -263,6 +265,7 @@ int launch_push(fpic_handle* h, int nsub)
     timing_begin(h, KC_PUSH);
     if (fuse) {
         HIP_TRY(h, hipMemsetAsync(h->tile_count, 0, sizeof(uint32_t) * h->ntiles, h->stream));
+        if (scatter && h->outbox_state) HIP_TRY(h, hipMemsetAsync(h->outbox_state, 0, sizeof(unsigned long long), h->stream)); // the cursor
         if constexpr (sizeof(T) == 4) {
             const size_t gcells = sums_cells(h->nr, h->nz);
             if (sums) {
@@ -515,6 +518,11 @@ int create_state(fpic_handle* h)
         if (int rc = dev_alloc(h, reinterpret_cast<void**>(&h->alive[s]), h->n_pad, &h->bytes_particles)) return rc;
         if (int rc = dev_alloc(h, reinterpret_cast<void**>(&h->id[s]), h->n_pad * sizeof(uint32_t), &h->bytes_particles)) return rc;
     }
+    if constexpr (sizeof(T) == 4) { // the re-binning launch's outbox: n/2 records of 2 (counter form) or 3 16-byte planes
+        const size_t planes = h->spec.rng_mode == 1 ? outbox_planes<true>() : outbox_planes<false>();
+        if (int rc = dev_alloc(h, &h->outbox, h->outbox_cap * planes * 16, &h->bytes_particles)) return rc;
+        if (int rc = dev_alloc(h, reinterpret_cast<void**>(&h->outbox_state), 3 * sizeof(unsigned long long), &h->bytes_particles)) return rc;
+    }
     const size_t rgba = h->ncell * 4 * sizeof(T);
     const size_t gcells = sums_cells(h->nr, h->nz);
     struct { void** p; size_t bytes; } grids[] = {
@@ -578,7 +586,7 @@ void release(fpic_handle* h)
     }
     void* bufs[] = { h->E, h->B, h->sink, h->sink_alive, h->inv_cdf_xy, h->entropy, h->coef, h->cell_sums, h->moments,
                      h->norm, h->avg, h->stamp, h->shape_half, h->shape_tenth, h->tile_count, h->tile_start2[0],
-                     h->tile_start2[1], h->tile_cursor, h->coarse_cursor, h->nwork2[0], h->nwork2[1], h->work2[0], h->work2[1], h->spilled, h->chunk_census };
+                     h->tile_start2[1], h->tile_cursor, h->coarse_cursor, h->nwork2[0], h->nwork2[1], h->work2[0], h->work2[1], h->spilled, h->chunk_census, h->outbox, h->outbox_state };
     for (void* b : bufs) if (b) (void)hipFree(b);
     if (h->spilled_host) (void)hipHostFree(h->spilled_host);
     for (hipEvent_t e : h->spill_event) if (e) (void)hipEventDestroy(e);
@@ -863,6 +871,9 @@ int fpic_create(const fpic_spec* spec, fpic_handle** out)
     h->ntx = (h->nr + 1 + kTileSide - 1) / kTileSide;
     h->ntz = (h->nz + 1 + kTileSide - 1) / kTileSide;
     h->ntiles = static_cast<uint32_t>(h->ntx) * h->ntz + 1;
+    h->outbox_cap = h->n / 2;
+    if (const char* v = std::getenv("FPIC_TEST_OUTBOX_RECORDS")) h->outbox_cap = static_cast<size_t>(std::strtoull(v, nullptr, 10));
+    h->test_count_pass = std::getenv("FPIC_TEST_COUNT_PASS") != nullptr;
     int rc = FPIC_OK;
     if (h->n >= 0xFFFFFFFFull - 4096) rc = fail(nullptr, FPIC_ERR_INVALID_ARG, ".nparticles <- at most 2^32 particles per device");
     else if (spec->geometry == FPIC_GEOM_CYL_RZ && h->ntiles > static_cast<uint32_t>(kMaxTiles)) rc = fail(nullptr, FPIC_ERR_INVALID_ARG, ".nr <- grid of %d x %d cells exceeds %d tiles of %d^2 cells", h->nr, h->nz, kMaxTiles, kTileSide);
@@ -1541,6 +1552,12 @@ int fpic_get_stats(fpic_handle* h, fpic_stats* out)
     out->solve_launches = h->solve_launches;
     out->bytes_particle_state = h->bytes_particles;
     out->bytes_grid_state = h->bytes_grid;
+    if (h->outbox_state) {
+        unsigned long long st[3] = {};
+        HIP_TRY(h, hipMemcpy(st, h->outbox_state, sizeof st, hipMemcpyDeviceToHost));
+        out->outbox_items = st[1];
+        out->outbox_full_items = st[2];
+    }
     return FPIC_OK;
 }
 

@@ -82,6 +82,12 @@ struct fpic_handle {
     uint32_t* chunk_census = nullptr;
     bool chunk_census_fresh = false;
     size_t work_cap = 0;
+    // the re-binning launch's outbox (float state; fpic_push.hpp): records of the leavers' final states, n/2 of them, and
+    // its device words [cursor, items delivered through it, items that found no room]
+    void* outbox = nullptr;
+    unsigned long long* outbox_state = nullptr;
+    size_t outbox_cap = 0;             // records (FPIC_TEST_OUTBOX_RECORDS overrides: tests)
+    bool test_count_pass = false;      // FPIC_TEST_COUNT_PASS: the re-binning launch counts its items itself (tests)
     bool binned = false;
     int deposits_since_bin = 0;
     unsigned long long t_substep = 0; // counter-based RNG mode: global index of the next sub-step

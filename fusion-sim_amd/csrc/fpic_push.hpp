@@ -70,6 +70,8 @@ __device__ __forceinline__ void counter_rand(uint32_t id, unsigned long long t, 
     u[3] = static_cast<T>(c3 >> 8) * static_cast<T>(1.0 / 16777216.0);
 }
 
+typedef uint32_t nat_u32x4 __attribute__((ext_vector_type(4)));
+
 // Extra arguments of the tiled form.
 template <typename T>
 struct TileArgs {
@@ -92,6 +94,12 @@ struct TileArgs {
     // z — is skipped: the electrostatic push has done so since round 3)
     uint32_t* chunk_census;
     int census_valid;
+    // SCATTER, float state: the outbox (see push_tiles_kernel).  outbox_state[0] is the cursor in records, zeroed by the
+    // host before the launch; [1] and [2] count the work items that delivered through the outbox and those that had
+    // leavers but no room (statistics)
+    nat_u32x4* outbox;
+    unsigned long long* outbox_state;
+    unsigned long long outbox_cap;     // records
 };
 
 template <typename T>
@@ -141,6 +149,13 @@ constexpr int push_threads() { return CTR ? FPIC_PUSH_THREADS_CTR : FPIC_PUSH_TH
 constexpr int kNbr = 5;                                // tile neighbourhood tracked in LDS when binning
 constexpr int kNbrSlots = kNbr * kNbr + 1;             // + the bin of clipped particles
 constexpr int kOwnSlot = (kNbr / 2) * kNbr + kNbr / 2; // the workgroup's own tile
+// The outbox of the re-binning launch (float state): a leaver's final state travels as one record of PLANES 16-byte
+// pieces — the NF state scalars, the particle's id, one word alive | slot << 8 — through a region of global memory the
+// work item reserves, and is delivered to its bin from LDS in sorted runs once the windows are dead.
+constexpr int kOutboxWords = 4;      // LDS words behind the ranges: leaver counter, reservation (low, high), its length
+constexpr int kOutboxPiece = 2048;   // records sorted in LDS at a time
+template <bool CTR>
+constexpr int outbox_planes() { return ((CTR ? 6 : 10) + 2 + 3) / 4; }
 
 // LDS pointers carry their address space in the type: through a generic pointer the
 // compiler emits flat_load instead of ds_read_b128.  (HIP's float4/double2 classes
@@ -477,26 +492,52 @@ __global__ __launch_bounds__(256) void push_kernel(PushArgs<T> a)
 // launch's census counted, from which the host has laid out dst_tile_start.  The
 // workgroup first counts its chunk per bin, reserves one range per bin, then pushes
 // and stores each final state at range + rank of arrival in the other particle set.
+// With float state the leavers (particles bound for another bin of the neighbourhood than
+// the item's own) take two steps instead: dense records into the item's reservation of the outbox during
+// the push, then, once the LDS windows are dead, back through LDS in sorted runs.
 template <typename T>
 constexpr size_t push_sums_offset() { return (static_cast<size_t>(kPushLds) * kPushLds * (12 * sizeof(T) + 1) + 15) / 16 * 16; }
 template <typename T>
-constexpr size_t push_stage_offset() // end of: coefficient window | sink bytes | double sums | census | ranks | ranges
+constexpr size_t push_stage_offset() // end of: coefficient window | sink bytes | double sums | census | ranks | ranges | outbox words
 {
     return (push_sums_offset<T>() + static_cast<size_t>(kTileLds) * kTileLds * 4 * sizeof(double) +
-            3 * kNbrSlots * sizeof(uint32_t) + 15) / 16 * 16;
+            (3 * kNbrSlots + kOutboxWords) * sizeof(uint32_t) + 15) / 16 * 16;
 }
 template <typename T, bool FUSE, bool SUMS = true>
 constexpr size_t push_tiles_lds_bytes()
 {
-    // coefficient window | sink bytes | double sums window (SUMS) | census | ranks | ranges
+    // coefficient window | sink bytes | double sums window (SUMS) | census | ranks | ranges | outbox words
     return !FUSE ? push_sums_offset<T>()
-                 : SUMS ? push_stage_offset<T>() : push_sums_offset<T>() + 3 * kNbrSlots * sizeof(uint32_t) + 16;
+                 : SUMS ? push_stage_offset<T>() : push_sums_offset<T>() + (3 * kNbrSlots + kOutboxWords) * sizeof(uint32_t) + 16;
 }
+
+// records of one piece: what fits below the census words (planes as words [4 * PLANES][P], u32 place [P], u16 perm [P])
+template <typename T, bool CTR, bool SUMS>
+constexpr int outbox_piece()
+{
+    const size_t room = push_sums_offset<T>() + (SUMS ? static_cast<size_t>(kTileLds) * kTileLds * 4 * sizeof(double) : 0);
+    const size_t fit = room / (outbox_planes<CTR>() * 16 + 6) / 64 * 64;
+    return fit < static_cast<size_t>(kOutboxPiece) ? static_cast<int>(fit) : kOutboxPiece;
+}
+
+// Development probes of the re-binning launch (timing only, wrong results): FPIC_ABL_PUSH & 2 stores no leaver of the
+// 5x5 neighbourhood at all; FPIC_ABL_PUSH & 4 writes the outbox records and never delivers them.
+#if defined(FPIC_ABL_PUSH) && (FPIC_ABL_PUSH & 2)
+constexpr bool kAblNoLeaverStores = true;
+#else
+constexpr bool kAblNoLeaverStores = false;
+#endif
+#if defined(FPIC_ABL_PUSH) && (FPIC_ABL_PUSH & 4)
+constexpr bool kAblNoDelivery = true;
+#else
+constexpr bool kAblNoDelivery = false;
+#endif
 
 template <typename T, bool FUSE, bool SCATTER, bool CTR, bool SUMS = true>
 __global__ __launch_bounds__(push_threads<CTR>()) void push_tiles_kernel(PushArgs<T> a, TileArgs<T> t)
 {
     constexpr int kPushThreads = push_threads<CTR>();
+    constexpr bool OUTBOX = SCATTER && sizeof(T) == 4; // (double keeps the direct path: its launch is not the flagship's)
     static_assert(FUSE || !SCATTER, "the re-binning launch relies on the census of the fused form");
     constexpr int PPT = Vec16<T>::N;
     constexpr int LW = kPushLds;
@@ -508,6 +549,7 @@ __global__ __launch_bounds__(push_threads<CTR>()) void push_tiles_kernel(PushArg
     FPIC_LDS uint32_t* lcensus = (FPIC_LDS uint32_t*)(lsums + (SUMS ? SW * SW * 4 : 0));
     FPIC_LDS uint32_t* lrank = lcensus + kNbrSlots;
     FPIC_LDS uint32_t* lrange = lrank + kNbrSlots;
+    FPIC_LDS uint32_t* lbox = lrange + kNbrSlots;     // [kOutboxWords]
     if (blockIdx.x >= *t.nwork) return;
     const BlockWork w = t.work[blockIdx.x];
     const int ti = static_cast<int>(w.tile % t.ntx), tj = static_cast<int>(w.tile / t.ntx);
@@ -533,7 +575,7 @@ __global__ __launch_bounds__(push_threads<CTR>()) void push_tiles_kernel(PushArg
     if constexpr (FUSE) {
         if constexpr (SUMS)
             for (int k = threadIdx.x; k < SW * SW * 4; k += kPushThreads) lsums[k] = 0.0;
-        if (threadIdx.x < 3 * kNbrSlots) lcensus[threadIdx.x] = 0;
+        if (threadIdx.x < 3 * kNbrSlots + kOutboxWords) lcensus[threadIdx.x] = 0;
     }
     __syncthreads();
     const WindowTables<T> tab{ GlobalTables<T>{ a.coef, a.sink_alive, a.nr }, lcoef, lsink, i0, j0 };
@@ -588,17 +630,50 @@ __global__ __launch_bounds__(push_threads<CTR>()) void push_tiles_kernel(PushArg
         }
         if (own_count) __hip_atomic_fetch_add(lrank + kOwnSlot, own_count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         __syncthreads();
-        if (threadIdx.x < kNbrSlots) {
-            const uint32_t c = lrank[threadIdx.x];
-            uint32_t start = 0;
-            if (c) {
-                const uint32_t bin = nb.bin_of_slot(threadIdx.x);
-                start = t.dst_tile_start[bin] + atomicAdd(t.dst_tile_cursor + bin, c);
+        if (threadIdx.x < 64) { // (one wave: kNbrSlots <= 64)
+            const uint32_t c = threadIdx.x < kNbrSlots ? lrank[threadIdx.x] : 0u;
+            if (threadIdx.x < kNbrSlots) {
+                uint32_t start = 0;
+                if (c) {
+                    const uint32_t bin = nb.bin_of_slot(threadIdx.x);
+                    start = t.dst_tile_start[bin] + atomicAdd(t.dst_tile_cursor + bin, c);
+                }
+                lrange[threadIdx.x] = start;
+                lrank[threadIdx.x] = 0;
             }
-            lrange[threadIdx.x] = start;
-            lrank[threadIdx.x] = 0;
+            if constexpr (OUTBOX) {
+                // the item's leavers: everything the census holds outside the own slot.  ONE region for the whole item,
+                // or none of it: an item that finds no room keeps the direct stores for all its leavers
+                uint32_t L = threadIdx.x == kOwnSlot ? 0u : c;
+#pragma unroll
+                for (int d = 32; d; d >>= 1) L += __shfl_xor(L, d);
+                if (threadIdx.x == 0 && L) {
+                    const unsigned long long o = atomicAdd(t.outbox_state, static_cast<unsigned long long>(L));
+                    const bool fits = o + L <= t.outbox_cap;
+                    if (fits) { lbox[1] = static_cast<uint32_t>(o); lbox[2] = static_cast<uint32_t>(o >> 32); lbox[3] = L; }
+                    atomicAdd(t.outbox_state + (fits ? 1 : 2), 1ull);
+                }
+            }
         }
         __syncthreads();
+        uint32_t box_len = 0;
+        nat_u32x4* box = nullptr;
+        if constexpr (OUTBOX) {
+            box_len = lbox[3];
+            box = t.outbox + ((static_cast<unsigned long long>(lbox[2]) << 32) | lbox[1]) * outbox_planes<CTR>();
+        }
+        // rank of a lane's particle among the wave's that satisfy `in`, on top of ONE LDS atomic per wave: consecutive
+        // lanes get consecutive ranks
+        auto wave_rank = [&](bool in, FPIC_LDS uint32_t* counter) -> uint32_t {
+            const unsigned long long mask = __ballot(in);
+            if (!mask) return 0u;
+            const int lane = static_cast<int>(threadIdx.x & 63);
+            const int leader = __ffsll(static_cast<long long>(mask)) - 1;
+            uint32_t wave_base = 0;
+            if (lane == leader) wave_base = __hip_atomic_fetch_add(counter, static_cast<uint32_t>(__popcll(mask)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+            wave_base = __shfl(wave_base, leader);
+            return wave_base + static_cast<uint32_t>(__popcll(mask & ((1ull << lane) - 1ull)));
+        };
         // Pass B: the push proper; a particle's place is its bin's range + its rank of arrival
         for (size_t g = g_begin + threadIdx.x; g < g_end; g += kPushThreads) {
             const size_t base = g * PPT;
@@ -617,29 +692,41 @@ __global__ __launch_bounds__(push_threads<CTR>()) void push_tiles_kernel(PushArg
                     uint32_t key;
                     const int sl = nb.slot(visible, ic, jc, key);
                     slot_of[k] = sl;
-                    if (sl >= 0 && sl != kOwnSlot) dest[k] = lrange[sl] + __hip_atomic_fetch_add(lrank + sl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    if (sl >= 0 && sl != kOwnSlot) { if (!box_len) dest[k] = lrange[sl] + __hip_atomic_fetch_add(lrank + sl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
                     else if (sl < 0) dest[k] = t.dst_tile_start[key] + atomicAdd(t.dst_tile_cursor + key, 1u); // beyond the 5x5 tiles: rare
                 }
             }
             // stayers: one LDS atomic per wave and k, ranks inside the wave in lane order (consecutive lanes store
-            // to consecutive slots)
+            // to consecutive slots); with an outbox the leavers take their record's index the same way
 #pragma unroll
             for (int k = 0; k < PPT; ++k) {
                 const bool own = k < cnt && slot_of[k] == kOwnSlot;
-                const unsigned long long mask = __ballot(own);
-                if (mask) {
-                    const int lane = static_cast<int>(threadIdx.x & 63);
-                    const int leader = __ffsll(static_cast<long long>(mask)) - 1;
-                    uint32_t wave_base = 0;
-                    if (lane == leader) wave_base = __hip_atomic_fetch_add(lrank + kOwnSlot, static_cast<uint32_t>(__popcll(mask)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-                    wave_base = __shfl(wave_base, leader);
-                    if (own) dest[k] = lrange[kOwnSlot] + wave_base + static_cast<uint32_t>(__popcll(mask & ((1ull << lane) - 1ull)));
+                const uint32_t r = wave_rank(own, lrank + kOwnSlot);
+                if (own) dest[k] = lrange[kOwnSlot] + r;
+                if (box_len) { // (uniform over the workgroup)
+                    const bool leaves = k < cnt && slot_of[k] >= 0 && slot_of[k] != kOwnSlot;
+                    const uint32_t i = wave_rank(leaves, lbox);
+                    if (leaves) dest[k] = i;
                 }
             }
             advance_state<T, CTR>(a, tab, WindowSums<T, SUMS>{ lsums, lcensus, ti0 - kTileHalo, tj0 - kTileHalo, nb, t.cell_sums, t.tile_count, &my_spill, &my_own, a.raster_bits }, cnt, q);
 #pragma unroll
             for (int k = 0; k < PPT; ++k) {
-                if (k < cnt) {
+                const bool leaves = k < cnt && slot_of[k] >= 0 && slot_of[k] != kOwnSlot;
+                if (kAblNoLeaverStores && leaves) continue;
+                if (box_len && leaves) {
+                    // PLANES dense 16-byte stores: plane p of record i at box[p * box_len + i]
+                    const uint32_t i = dest[k];
+                    if (i >= box_len) continue; // (cannot happen while the census counts what pass B sees)
+                    const uint32_t meta = (q[k].alive ? 1u : 0u) | static_cast<uint32_t>(slot_of[k]) << 8;
+                    box[i] = nat_u32x4{ __float_as_uint(q[k].x), __float_as_uint(q[k].y), __float_as_uint(q[k].z), __float_as_uint(q[k].vx) };
+                    if constexpr (CTR) {
+                        box[box_len + i] = nat_u32x4{ __float_as_uint(q[k].vy), __float_as_uint(q[k].vz), pid[k], meta };
+                    } else {
+                        box[box_len + i] = nat_u32x4{ __float_as_uint(q[k].vy), __float_as_uint(q[k].vz), __float_as_uint(q[k].u1), __float_as_uint(q[k].u2) };
+                        box[2 * static_cast<size_t>(box_len) + i] = nat_u32x4{ __float_as_uint(q[k].c1), __float_as_uint(q[k].c2), pid[k], meta };
+                    }
+                } else if (k < cnt) {
                     const size_t d = dest[k];
                     t.dst_slab[0 * a.stride + d] = q[k].x; t.dst_slab[1 * a.stride + d] = q[k].y; t.dst_slab[2 * a.stride + d] = q[k].z;
                     t.dst_slab[3 * a.stride + d] = q[k].vx; t.dst_slab[4 * a.stride + d] = q[k].vy; t.dst_slab[5 * a.stride + d] = q[k].vz;
@@ -683,6 +770,77 @@ __global__ __launch_bounds__(push_threads<CTR>()) void push_tiles_kernel(PushArg
             }
         }
         if (my_spill) atomicAdd(t.spilled, static_cast<unsigned long long>(my_spill));
+    }
+
+    if constexpr (OUTBOX) {
+        // Phase 2: the windows are dead.  The item's records come back in pieces of P, are sorted by slot in LDS (count,
+        // scan, place) and leave column by column: consecutive lanes hold consecutive places of one slot = consecutive
+        // addresses.  lcensus counts the piece per slot, lrank holds the slots' first places in the piece, lrange moves on
+        // by what has been delivered.  Only this workgroup ever touches its reservation.
+        constexpr int PLANES = outbox_planes<CTR>();
+        constexpr int NF = CTR ? 6 : 10;
+        constexpr int P = outbox_piece<T, CTR, SUMS>();
+        static_assert(P >= 64 && P <= 65536, "a piece's places must fit the u16 permutation and the rank's 16 bits");
+        __syncthreads();
+        const uint32_t L = kAblNoDelivery ? 0u : lbox[3];
+        if (L) { // (uniform over the workgroup)
+            const nat_u32x4* box = t.outbox + ((static_cast<unsigned long long>(lbox[2]) << 32) | lbox[1]) * PLANES;
+            FPIC_LDS uint32_t* rec = (FPIC_LDS uint32_t*)push_lds;                 // [4 * PLANES][P]: word w of record r at rec[w * P + r]
+            FPIC_LDS uint32_t* place = rec + 4 * PLANES * P;                       // [P]: destination index of the record at place p
+            FPIC_LDS uint16_t* perm = (FPIC_LDS uint16_t*)(place + P);             // [P]: the record at place p
+            constexpr int META = NF + 1;
+            for (uint32_t p0 = 0; p0 < L; p0 += P) {
+                const uint32_t m = L - p0 < static_cast<uint32_t>(P) ? L - p0 : static_cast<uint32_t>(P);
+                if (threadIdx.x < kNbrSlots) lcensus[threadIdx.x] = 0;
+                __syncthreads();
+                for (uint32_t r = threadIdx.x; r < m; r += kPushThreads) {
+                    uint32_t w[4 * PLANES];
+#pragma unroll
+                    for (int pl = 0; pl < PLANES; ++pl) {
+                        const nat_u32x4 v = box[static_cast<size_t>(pl) * L + p0 + r];
+                        w[4 * pl] = v.x; w[4 * pl + 1] = v.y; w[4 * pl + 2] = v.z; w[4 * pl + 3] = v.w;
+                    }
+                    uint32_t slot = w[META] >> 8;
+                    if (slot >= static_cast<uint32_t>(kNbrSlots)) slot = kNbrSlots - 1; // (keeps a damaged record inside the tables)
+                    const uint32_t rank = __hip_atomic_fetch_add(lcensus + slot, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    w[META] = (w[META] & 0xffu) | slot << 8 | rank << 16;
+#pragma unroll
+                    for (int k = 0; k <= META; ++k) rec[k * P + r] = w[k];
+                }
+                __syncthreads();
+                if (threadIdx.x < 64) { // exclusive scan of the slots' counts by one wave
+                    const uint32_t c = threadIdx.x < kNbrSlots ? lcensus[threadIdx.x] : 0u;
+                    uint32_t incl = c;
+#pragma unroll
+                    for (int d = 1; d < 64; d <<= 1) {
+                        const uint32_t up = __shfl_up(incl, d);
+                        if (static_cast<int>(threadIdx.x) >= d) incl += up;
+                    }
+                    if (threadIdx.x < kNbrSlots) lrank[threadIdx.x] = incl - c;
+                }
+                __syncthreads();
+                for (uint32_t r = threadIdx.x; r < m; r += kPushThreads) {
+                    const uint32_t meta = rec[META * P + r];
+                    const uint32_t slot = (meta >> 8) & 0xffu, rank = meta >> 16;
+                    const uint32_t p = lrank[slot] + rank;
+                    if (p < m) {
+                        perm[p] = static_cast<uint16_t>(r);
+                        place[p] = lrange[slot] + rank;
+                    }
+                }
+                __syncthreads();
+                for (uint32_t p = threadIdx.x; p < m; p += kPushThreads) {
+                    const uint32_t r = perm[p];
+                    const size_t d = place[p];
+#pragma unroll
+                    for (int f = 0; f < NF; ++f) t.dst_slab[f * a.stride + d] = __uint_as_float(rec[f * P + r]);
+                    t.dst_id[d] = rec[NF * P + r];
+                    t.dst_alive[d] = static_cast<uint8_t>(rec[META * P + r] & 0xffu);
+                }
+                __syncthreads();
+                if (threadIdx.x < kNbrSlots) lrange[threadIdx.x] += lcensus[threadIdx.x];
+            }
+        }
     }
 }
 

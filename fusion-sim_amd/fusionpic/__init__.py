@@ -76,7 +76,7 @@ class Stats(ctypes.Structure):
         ("ms_push", ctypes.c_double), ("ms_deposit", ctypes.c_double), ("ms_stamp", ctypes.c_double),
         ("ms_precalc", ctypes.c_double), ("ms_sort", ctypes.c_double), ("bytes_particle_state", ctypes.c_uint64),
         ("bytes_grid_state", ctypes.c_uint64), ("ms_solve", ctypes.c_double), ("solve_launches", ctypes.c_uint64),
-        ("reserved", ctypes.c_double * 6),
+        ("outbox_items", ctypes.c_uint64), ("outbox_full_items", ctypes.c_uint64), ("reserved", ctypes.c_double * 4),
     ]
 
     def as_dict(self):

@@ -207,7 +207,9 @@ typedef struct fpic_stats {
     uint64_t bytes_grid_state;
     double ms_solve;             /* CART3D: sum over field solves (rho conversion, FFTs, k-space, gradient) */
     uint64_t solve_launches;
-    double reserved[6];
+    uint64_t outbox_items;       /* (r,z) re-binning launches: work items whose leavers went through the outbox */
+    uint64_t outbox_full_items;  /* ... and work items that found no room in it and stored their leavers directly */
+    double reserved[4];
 } fpic_stats;
 
 /* Last error text.  h may be NULL after a failed fpic_create. */
