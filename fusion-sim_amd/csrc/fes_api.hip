@@ -19,7 +19,8 @@
 //   fes_host_io.inc.hpp     uploads, downloads, creation of the state
 //   fes_checkpoint.inc.hpp  checkpoint files (box, rank of a decomposition)
 //   fes_domain.inc.hpp      the z-slab decomposition: message lists, both transports, migration, decomposed solves and cycles
-//   fes_diag.inc.hpp        the energy diagnostics: the reductions, the recording ring, the ranks' combination
+//   fes_record.inc.hpp      what the diagnostics share: the scope of a call, the ranks' gather and integer sum, the recorder (ring, hook, drain)
+//   fes_diag.inc.hpp        the energy diagnostics: the reductions, the ranks' combination
 //   fes_hist.inc.hpp        the phase-space histograms: the pass of one request, the ranks' sum
 //   fes_mom.inc.hpp         the fluid moment grids: the sweeps of one request, the held planes' places, the ranks' sum
 //   fes_series.inc.hpp      the series: rows of field points and tracer particles, now or into a ring, the ranks' selection
@@ -341,11 +342,34 @@ namespace {
 
 } // namespace
 
+#include "fes_record.inc.hpp"
 #include "fes_diag.inc.hpp"
 #include "fes_hist.inc.hpp"
 #include "fes_mom.inc.hpp"
 #include "fes_series.inc.hpp"
 #include "fes_modes.inc.hpp"
+
+// the recording hook, at the end of every sub-step of every path (substeps(), group_run()): counts the sub-step, then every
+// recorder that is due — the energy rows, the series, the modes, which share the counter and nothing else — enqueues its row
+// into its ring.  No host synchronisation, no collective; recording off: nothing is enqueued.
+static int diag_after_substep(fpic_handle* h)
+{
+    Diag& g = h->es->diag;
+    g.substep++;
+    const bool f32 = h->prec == FPIC_F32;
+    for (int k = 0; k < kRecorders; ++k) {
+        void* row = rec_due(g.rec[k], g.substep);
+        if (!row) continue;
+        fpic_energy* e = static_cast<fpic_energy*>(row);
+        double* w = static_cast<double*>(row);
+        const int rc = k == kRecEnergy   ? (f32 ? diag_enqueue<float>(h, e) : diag_enqueue<double>(h, e))
+                       : k == kRecSeries ? (f32 ? series_enqueue<float>(h, g.series_req, w) : series_enqueue<double>(h, g.series_req, w))
+                                         : (f32 ? modes_enqueue<float>(h, g.modes_req, w) : modes_enqueue<double>(h, g.modes_req, w));
+        if (rc) return rc;
+        rec_commit(g.rec[k], g.substep);
+    }
+    return FPIC_OK;
+}
 
 int precalc(fpic_handle* h)
 {

@@ -1,13 +1,14 @@
 // fes_diag.inc.hpp: the energy and momentum diagnostics of a CART3D handle (fpic_energy_now, fpic_energy_record,
 // fpic_energy_history) — part of fes_api.hip's translation unit (included there, inside namespace fes).  The definitions are
 // the oracle's field_energy, em_field_energy and kinetic_energy (oracle/es3d_oracle.py); the kernels are fes_diag_kernels.hpp,
-// the host rules (owned planes, ring, combination of the ranks' rows) fes_diag_core.hpp.
+// the host rules (owned planes, combination of the ranks' rows) fes_diag_core.hpp, the recorder and the ranks' gather
+// fes_record.inc.hpp.
 //
 // A reduction is enqueued on the handle's stream: one particle pass per species (kDiagBlocks partial rows each), one pass
 // over the owned planes of the fields, one launch that combines the partials (a workgroup per species and one for the
 // fields) and one that writes the row — to the
-// handle's scratch row (fpic_energy_now) or to the recording ring (after every `every`-th sub-step; no host
-// synchronisation, no collective).  A rank reduces its own particles and its own planes [z0, z0 + nzl), so its LOCAL rows
+// handle's scratch row (fpic_energy_now) or to the recording ring (the hook diag_after_substep of fes_api.hip, after every
+// `every`-th sub-step; no host synchronisation, no collective).  A rank reduces its own particles and its own planes [z0, z0 + nzl), so its LOCAL rows
 // summed over the ranks count every particle and every node once.  GLOBAL on a rank with a communicator gathers the ranks'
 // rows with ONE ncclAllGather and every rank combines them in rank order (fesdiag::combine): every rank gets the same
 // bits, the sums of an in-process group's members in rank order, and speed_max a maximum, which a sum all-reduce cannot give.
@@ -73,46 +74,6 @@ static int diag_enqueue(fpic_handle* h, fpic_energy* out)
     return FPIC_OK;
 }
 
-// whether a call of `scope` is collective: GLOBAL on a rank of a decomposition over more than one handle
-static int diag_scope(fpic_handle* h, int scope, bool& collective)
-{
-    if (scope != FPIC_DIAG_LOCAL && scope != FPIC_DIAG_GLOBAL) return fail(h, FPIC_ERR_INVALID_ARG, ".scope <- must be 0 (local) or 1 (global)");
-    const Domain* d = h->es->dom;
-    collective = scope == FPIC_DIAG_GLOBAL && d && d->world > 1;
-    if (!collective) return FPIC_OK;
-    if (!h->comm)
-        return fail(h, FPIC_ERR_STATE, "GLOBAL on a member of an in-process group: add up the members' LOCAL values (BoxGroup.energy)");
-    if (h->comm->world != d->world || h->comm->rank != d->rank)
-        return fail(h, FPIC_ERR_STATE, "the communicator (rank %d of %d) and the decomposition (rank %d of %d) disagree", h->comm->rank, h->comm->world, d->rank, d->world);
-    return FPIC_OK;
-}
-
-// `bytes` (a multiple of 8) of every rank, in rank order, into `all`: one in-place ncclAllGather on the handle's stream
-static int diag_gather(fpic_handle* h, const void* mine, size_t bytes, std::vector<unsigned char>& all)
-{
-    Diag& g = h->es->diag;
-    const int world = h->comm->world, rank = h->comm->rank;
-    const size_t need = bytes * world;
-    if (g.gather_bytes < need) {
-        if (g.gather) {
-            HIP_TRY(h, hipStreamSynchronize(h->stream));
-            HIP_TRY(h, hipFree(g.gather));
-            h->bytes_grid -= g.gather_bytes;
-            g.gather = nullptr;
-            g.gather_bytes = 0;
-        }
-        if (int rc = dev_alloc(h, &g.gather, need, &h->bytes_grid)) return rc;
-        g.gather_bytes = need;
-    }
-    unsigned char* buf = static_cast<unsigned char*>(g.gather);
-    HIP_TRY(h, hipMemcpyAsync(buf + rank * bytes, mine, bytes, hipMemcpyHostToDevice, h->stream));
-    if (int e = fcomm::check(h, fdyn::rccl().AllGather(buf + rank * bytes, buf, bytes / sizeof(double), ncclDouble, h->comm->nccl, h->stream), "ncclAllGather")) return e;
-    all.resize(need);
-    HIP_TRY(h, hipMemcpyAsync(all.data(), buf, need, hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    return FPIC_OK;
-}
-
 int energy_now(fpic_handle* h, int scope, fpic_energy* out)
 {
     if (!out) return fail(h, FPIC_ERR_INVALID_ARG, ".out <- Non-optional property is undefined!");
@@ -135,90 +96,36 @@ int energy_now(fpic_handle* h, int scope, fpic_energy* out)
     return FPIC_OK;
 }
 
+static_assert(sizeof(fpic_energy) % sizeof(double) == 0, "a recorder's rows are whole 8-byte words");
+
 int energy_record(fpic_handle* h, int every, uint32_t capacity)
 {
-    if (every < 0) return fail(h, FPIC_ERR_INVALID_ARG, ".every <- must be >= 0 (0 turns recording off)");
-    if (every > 0 && capacity < 1) return fail(h, FPIC_ERR_INVALID_ARG, ".capacity <- must be at least 1");
+    if (int rc = rec_check(h, every, capacity)) return rc;
     State* st = h->es;
     if (every > 0 && st->sp.size() > static_cast<size_t>(FPIC_ENERGY_SPECIES))
         return fail(h, FPIC_ERR_STATE, "the energy diagnostics report at most %d species (fpic_energy); this box has %zu", FPIC_ENERGY_SPECIES, st->sp.size());
-    Diag& g = st->diag;
-    if (g.ring_dev) { // (recorded rows still in flight write to it)
-        HIP_TRY(h, hipStreamSynchronize(h->stream));
-        HIP_TRY(h, hipFree(g.ring_dev));
-        h->bytes_grid -= g.ring.cap * sizeof(fpic_energy);
-        g.ring_dev = nullptr;
-    }
-    g.ring = fesdiag::Ring();
-    g.every = 0;
+    Recorder& r = st->diag.rec[kRecEnergy];
+    if (int rc = rec_disarm(h, r, false)) return rc;
     if (!every) return FPIC_OK;
     if (int rc = diag_buffers(h)) return rc;
-    if (int rc = dev_alloc(h, reinterpret_cast<void**>(&g.ring_dev), static_cast<size_t>(capacity) * sizeof(fpic_energy), &h->bytes_grid)) return rc;
-    g.ring.cap = capacity;
-    g.every = every;
-    return FPIC_OK;
+    return rec_arm(h, r, every, capacity, sizeof(fpic_energy));
 }
 
 int energy_history(fpic_handle* h, int scope, fpic_energy* rows, uint64_t capacity, uint64_t* n, uint64_t* dropped)
 {
-    if (!n) return fail(h, FPIC_ERR_INVALID_ARG, ".n <- Non-optional property is undefined!");
-    bool collective = false;
-    if (int rc = diag_scope(h, scope, collective)) return rc;
-    Diag& g = h->es->diag;
-    uint64_t first = 0, cnt = 0, drop = 0;
-    if (g.ring_dev) g.ring.pending(first, cnt, drop);
-    if (!rows) { // a query: nothing is drained
-        *n = cnt;
-        if (dropped) *dropped = drop;
-        return FPIC_OK;
-    }
-    if (capacity < cnt) return fail(h, FPIC_ERR_INVALID_ARG, ".capacity <- %llu rows are pending, room for %llu", static_cast<unsigned long long>(cnt), static_cast<unsigned long long>(capacity));
-    std::vector<fpic_energy> mine(cnt);
-    uint64_t slot[2], len[2];
-    const int nr = g.ring.runs(first, cnt, slot, len);
-    for (int k = 0, at = 0; k < nr; at += static_cast<int>(len[k]), ++k)
-        HIP_TRY(h, hipMemcpyAsync(mine.data() + at, g.ring_dev + slot[k], len[k] * sizeof(fpic_energy), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (collective) {
-        // every rank must drain the same number of rows: agreed first (one small gather), so that a mismatch stops every
-        // rank here instead of leaving some in the gather of the rows
-        const double mine_n[2] = { static_cast<double>(cnt), static_cast<double>(drop) };
+    Recorder& r = h->es->diag.rec[kRecEnergy];
+    Drain d;
+    if (int rc = rec_drain(h, r, scope, !rows, capacity, nullptr, n, dropped, d)) return rc;
+    if (d.query) return FPIC_OK;
+    const fpic_energy* mine = reinterpret_cast<const fpic_energy*>(d.rows.data());
+    if (d.cnt && d.collective) {
         std::vector<unsigned char> all;
-        if (int rc = diag_gather(h, mine_n, sizeof(mine_n), all)) return rc;
-        const double* ns = reinterpret_cast<const double*>(all.data());
-        for (int r = 0; r < h->comm->world; ++r)
-            if (ns[2 * r] != mine_n[0] || ns[2 * r + 1] != mine_n[1])
-                return fail(h, FPIC_ERR_STATE, "the ranks hold different numbers of recorded rows (%llu here, %.0f on rank %d): record with the same settings on every rank",
-                            static_cast<unsigned long long>(cnt), ns[2 * r], r);
-        if (cnt) {
-            if (int rc = diag_gather(h, mine.data(), cnt * sizeof(fpic_energy), all)) return rc;
-            const fpic_energy* parts = reinterpret_cast<const fpic_energy*>(all.data());
-            for (uint64_t i = 0; i < cnt; ++i) fesdiag::combine(parts + i, cnt, h->comm->world, rows + i);
-        }
-    } else if (cnt) {
-        std::memcpy(rows, mine.data(), cnt * sizeof(fpic_energy));
+        if (int rc = diag_gather(h, mine, d.cnt * sizeof(fpic_energy), all)) return rc;
+        const fpic_energy* parts = reinterpret_cast<const fpic_energy*>(all.data());
+        for (uint64_t i = 0; i < d.cnt; ++i) fesdiag::combine(parts + i, d.cnt, h->comm->world, rows + i);
+    } else if (d.cnt) {
+        std::memcpy(rows, mine, d.cnt * sizeof(fpic_energy));
     }
-    g.ring.drained = g.ring.seq;
-    *n = cnt;
-    if (dropped) *dropped = drop;
+    rec_drained(r, d, nullptr, n, dropped);   // (an energy row carries its sub-step)
     return FPIC_OK;
-}
-
-static int series_after_substep(fpic_handle* h);   // (fes_series.inc.hpp: the series recorder's share of the hook)
-static int modes_after_substep(fpic_handle* h);    // (fes_modes.inc.hpp: the modes recorder's)
-
-// the recording hook, at the end of every sub-step of every path (substeps(), group_run()): counts the sub-step and, every
-// `every`-th one, enqueues the reduction into the ring; then the series recorder and the modes recorder, which share the
-// counter and nothing else, take their turns.  Recording off: nothing is enqueued.
-static int diag_after_substep(fpic_handle* h)
-{
-    Diag& g = h->es->diag;
-    g.substep++;
-    if (g.every && g.substep % static_cast<uint64_t>(g.every) == 0) {
-        fpic_energy* row = g.ring_dev + g.ring.slot(g.ring.seq);
-        if (int rc = h->prec == FPIC_F32 ? diag_enqueue<float>(h, row) : diag_enqueue<double>(h, row)) return rc;
-        g.ring.seq++;
-    }
-    if (int rc = series_after_substep(h)) return rc;
-    return modes_after_substep(h);
 }

@@ -1,6 +1,7 @@
 // fes_diag_core.hpp — the host rules of the energy diagnostics (fpic_energy_*; the kernels are fes_diag_kernels.hpp, the
-// orchestration fes_diag.inc.hpp): which planes a handle reduces and where it holds them, the recording ring's indexing and
-// drop count, and the fixed-order combination of several handles' rows.  Plain C++, shared with a host test
+// orchestration fes_diag.inc.hpp) and of what the box diagnostics share (fes_record.inc.hpp): which planes a handle reduces
+// and where it holds them, the recording ring's indexing, drop count, commit and drain, the ranks' agreement on a drain, the
+// ranks' integer sum, and the fixed-order combination of several handles' rows.  Plain C++, shared with a host test
 // (tests/native/diag_core_test.cpp, g++).
 #ifndef FES_DIAG_CORE_HPP
 #define FES_DIAG_CORE_HPP
@@ -61,7 +62,26 @@ struct Ring {
         len_out[1] = n - head;
         return 2;
     }
+    void commit() { ++seq; }                  // the row enqueued into slot(seq) counts from now on
+    void mark_drained() { drained = seq; }    // the rows pending() named have been delivered
 };
+
+// the ranks' agreement before a collective drain: pairs = [world][2], every rank's (pending rows, dropped rows) as doubles in
+// rank order; the first rank whose pair differs from (n, dropped), or -1
+inline int disagreeing_rank(const double* pairs, int world, double n, double dropped)
+{
+    for (int r = 0; r < world; ++r)
+        if (pairs[2 * r] != n || pairs[2 * r + 1] != dropped) return r;
+    return -1;
+}
+
+// out[i] = parts[i] + parts[m + i] + ... + parts[(world - 1) m + i]: `world` parts of m words, added in rank order
+inline void add_words(const uint64_t* parts, size_t m, int world, uint64_t* out)
+{
+    for (size_t i = 0; i < m; ++i) out[i] = 0;
+    for (int r = 0; r < world; ++r)
+        for (size_t i = 0; i < m; ++i) out[i] += parts[static_cast<size_t>(r) * m + i];
+}
 
 // out = the rows part[0], part[stride], ..., part[(nparts - 1) stride] combined in that order: sums left to right (counts,
 // energies, momenta), speed_max the largest (NaN if any part's is); substep and nspecies are part[0]'s (the parts are one sub-step of one box)

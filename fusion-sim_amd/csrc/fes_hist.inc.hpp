@@ -5,10 +5,8 @@
 // A call zeroes the counters (nbins + 1 words: the bins, then `outside`) on the handle's stream, launches one pass over the
 // species' slots, copies the counters back and waits.  The pass keeps a private histogram in LDS when the request has at
 // most kHistLdsBins bins and adds to the global counters directly otherwise.  GLOBAL on a rank with a communicator gathers
-// the ranks' counters in chunks of kHistGatherWords with ncclAllGather (bytes, as diag_gather moves them) and every rank
-// adds them as integers: every rank gets the same sums.
-
-constexpr size_t kHistGatherWords = size_t(1) << 17;   // 1 MiB per rank and chunk
+// the ranks' counters in chunks of kHistGatherWords and every rank adds them as integers (diag_sum_ranks,
+// fes_record.inc.hpp): every rank gets the same sums.
 
 static int hist_buffer(fpic_handle* h, size_t words)
 {
@@ -91,17 +89,10 @@ int histogram(fpic_handle* h, const fpic_hist_spec* spec, int scope, uint64_t* c
         HIP_TRY(h, hipStreamSynchronize(h->stream));
         return FPIC_OK;
     }
-    std::vector<uint64_t> mine(words), sum(words, 0);
-    HIP_TRY(h, hipMemcpyAsync(mine.data(), dev, words * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    std::vector<uint64_t> sum(words);
+    HIP_TRY(h, hipMemcpyAsync(sum.data(), dev, words * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
-    std::vector<unsigned char> all;
-    for (size_t at = 0; at < words; at += kHistGatherWords) {
-        const size_t m = std::min(kHistGatherWords, words - at);
-        if (int rc = diag_gather(h, mine.data() + at, m * sizeof(uint64_t), all)) return rc;
-        const uint64_t* parts = reinterpret_cast<const uint64_t*>(all.data());
-        for (int r = 0; r < h->comm->world; ++r)
-            for (size_t i = 0; i < m; ++i) sum[at + i] += parts[static_cast<size_t>(r) * m + i];
-    }
+    if (int rc = diag_sum_ranks(h, sum.data(), words)) return rc;
     std::memcpy(counts, sum.data(), nbins * sizeof(uint64_t));
     *outside = sum[nbins];
     return FPIC_OK;

@@ -5,8 +5,8 @@
 // A request is checked, its wave vectors reduced and the three twiddle tables built on the host once (modes_upload), and kept
 // on the device in one allocation together with the workgroups' partial rows.  A row is enqueued on the handle's stream: the
 // partial pass over the planes this handle owns, then the combine pass, which writes the row — to a scratch row
-// (fpic_modes_now) or to the recording ring (the hook modes_after_substep, driven by diag_after_substep; no host
-// synchronisation, no collective).  GLOBAL on a rank with a communicator gathers the ranks' rows with diag_gather and every
+// (fpic_modes_now) or to the recording ring (the hook diag_after_substep; no host synchronisation, no collective; the
+// recorder is fes_record.inc.hpp).  GLOBAL on a rank with a communicator gathers the ranks' rows with diag_gather and every
 // rank adds them in rank order (fesmod::add_parts).
 //
 // What the arrays hold on the owned planes when a row is taken (a call, or the hook at the end of a sub-step): E4 / B4n are
@@ -120,15 +120,15 @@ static int modes_enqueue(fpic_handle* h, const ModesReq& q, double* row)
 }
 
 // rows [rows][width] of this handle -> the caller's array, the ranks' rows added in rank order if collective
-static int modes_deliver(fpic_handle* h, const std::vector<double>& mine, size_t count, bool collective, double* out)
+static int modes_deliver(fpic_handle* h, const double* mine, size_t count, bool collective, double* out)
 {
     if (!count) return FPIC_OK;
     if (!collective) {
-        std::memcpy(out, mine.data(), count * sizeof(double));
+        std::memcpy(out, mine, count * sizeof(double));
         return FPIC_OK;
     }
     std::vector<unsigned char> all;
-    if (int rc = diag_gather(h, mine.data(), count * sizeof(double), all)) return rc;
+    if (int rc = diag_gather(h, mine, count * sizeof(double), all)) return rc;
     fesmod::add_parts(reinterpret_cast<const double*>(all.data()), count, h->comm->world, count, out);
     return FPIC_OK;
 }
@@ -142,103 +142,41 @@ int modes_now(fpic_handle* h, const fpic_modes_spec* spec, int scope, double* ou
     const bool f32 = h->prec == FPIC_F32;
     ModesReq q;
     int rc = modes_upload(h, *spec, q);
-    void* row = nullptr;
     std::vector<double> mine;
-    if (rc == FPIC_OK) rc = dev_alloc(h, &row, q.width() * sizeof(double), nullptr);
-    if (rc == FPIC_OK) rc = f32 ? modes_enqueue<float>(h, q, static_cast<double*>(row)) : modes_enqueue<double>(h, q, static_cast<double*>(row));
-    if (rc == FPIC_OK) {
-        mine.resize(q.width());
-        hipError_t e = hipMemcpyAsync(mine.data(), row, mine.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = fail(h, FPIC_ERR_HIP, "modes read-back failed: %s", hipGetErrorString(e));
-    }
-    if (rc == FPIC_OK) rc = modes_deliver(h, mine, mine.size(), collective, out);
-    if (row) (void)hipFree(row);
-    if (int rc2 = modes_free(h, q)) return rc ? rc : rc2;
-    return rc;
+    if (rc == FPIC_OK)
+        rc = rec_row_now(h, q.width() * sizeof(double), "modes",
+                         [&](void* row) { return f32 ? modes_enqueue<float>(h, q, static_cast<double*>(row)) : modes_enqueue<double>(h, q, static_cast<double*>(row)); }, mine);
+    if (rc == FPIC_OK) rc = modes_deliver(h, mine.data(), mine.size(), collective, out);
+    const int rc2 = modes_free(h, q);
+    return rc ? rc : rc2;
 }
 
 int modes_record(fpic_handle* h, const fpic_modes_spec* spec, int every, uint32_t capacity)
 {
-    if (every < 0) return fail(h, FPIC_ERR_INVALID_ARG, ".every <- must be >= 0 (0 turns recording off)");
-    if (every > 0 && capacity < 1) return fail(h, FPIC_ERR_INVALID_ARG, ".capacity <- must be at least 1");
+    if (int rc = rec_check(h, every, capacity)) return rc;
     if (every > 0 && !spec) return fail(h, FPIC_ERR_INVALID_ARG, ".spec <- Non-optional property is undefined!");
     ModesReq q;
     if (every > 0) // (a refused request leaves the recorder as it was)
         if (int rc = modes_upload(h, *spec, q)) return rc;
-    Modes& s = h->es->diag.modes;
-    if (s.ring_dev || s.req.block) HIP_TRY(h, hipStreamSynchronize(h->stream)); // (recorded rows still in flight write to it)
-    if (s.ring_dev) {
-        HIP_TRY(h, hipFree(s.ring_dev));
-        h->bytes_grid -= s.ring.cap * s.req.width() * sizeof(double);
-        s.ring_dev = nullptr;
-    }
-    if (int rc = modes_free(h, s.req)) return rc;
-    s.ring = fesdiag::Ring();
-    s.ring_substep.clear();
-    s.every = 0;
+    Diag& g = h->es->diag;
+    Recorder& r = g.rec[kRecModes];
+    if (int rc = rec_disarm(h, r, g.modes_req.block != nullptr)) return rc;
+    if (int rc = modes_free(h, g.modes_req)) return rc;
     if (!every) return FPIC_OK;
-    s.req = q;
-    if (int rc = dev_alloc(h, reinterpret_cast<void**>(&s.ring_dev), static_cast<size_t>(capacity) * q.width() * sizeof(double), &h->bytes_grid)) {
-        (void)modes_free(h, s.req);
-        return rc;
-    }
-    s.ring.cap = capacity;
-    s.ring_substep.assign(capacity, 0);
-    s.every = every;
-    return FPIC_OK;
+    g.modes_req = q;
+    const int rc = rec_arm(h, r, every, capacity, q.width() * sizeof(double));
+    if (rc) (void)modes_free(h, g.modes_req);
+    return rc;
 }
 
 int modes_history(fpic_handle* h, int scope, uint64_t* substeps, double* out, uint64_t capacity, uint64_t* n, uint64_t* dropped)
 {
-    if (!n) return fail(h, FPIC_ERR_INVALID_ARG, ".n <- Non-optional property is undefined!");
-    bool collective = false;
-    if (int rc = diag_scope(h, scope, collective)) return rc;
-    Modes& s = h->es->diag.modes;
-    uint64_t first = 0, cnt = 0, drop = 0;
-    if (s.ring_dev) s.ring.pending(first, cnt, drop);
-    if (!substeps) { // a query: nothing is drained
-        *n = cnt;
-        if (dropped) *dropped = drop;
-        return FPIC_OK;
-    }
-    if (capacity < cnt) return fail(h, FPIC_ERR_INVALID_ARG, ".capacity <- %llu rows are pending, room for %llu", static_cast<unsigned long long>(cnt), static_cast<unsigned long long>(capacity));
-    if (cnt && !out) return fail(h, FPIC_ERR_INVALID_ARG, ".out <- Non-optional property is undefined!");
-    const size_t W = s.req.width();
-    std::vector<double> mine(cnt * W);
-    uint64_t slot[2], len[2];
-    const int nr = s.ring.runs(first, cnt, slot, len);
-    for (int k = 0, at = 0; k < nr; at += static_cast<int>(len[k]), ++k)
-        HIP_TRY(h, hipMemcpyAsync(mine.data() + at * W, s.ring_dev + slot[k] * W, len[k] * W * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (collective) { // every rank must drain the same rows: agreed first, as fpic_energy_history does
-        const double mine_n[2] = { static_cast<double>(cnt), static_cast<double>(drop) };
-        std::vector<unsigned char> all;
-        if (int rc = diag_gather(h, mine_n, sizeof(mine_n), all)) return rc;
-        const double* ns = reinterpret_cast<const double*>(all.data());
-        for (int r = 0; r < h->comm->world; ++r)
-            if (ns[2 * r] != mine_n[0] || ns[2 * r + 1] != mine_n[1])
-                return fail(h, FPIC_ERR_STATE, "the ranks hold different numbers of recorded rows (%llu here, %.0f on rank %d): record with the same settings on every rank",
-                            static_cast<unsigned long long>(cnt), ns[2 * r], r);
-    }
-    if (int rc = modes_deliver(h, mine, mine.size(), collective, out)) return rc;
-    for (uint64_t i = 0; i < cnt; ++i) substeps[i] = s.ring_substep[s.ring.slot(first + i)];
-    s.ring.drained = s.ring.seq;
-    *n = cnt;
-    if (dropped) *dropped = drop;
-    return FPIC_OK;
-}
-
-// the recording hook (called by diag_after_substep, which has counted the sub-step)
-static int modes_after_substep(fpic_handle* h)
-{
-    Diag& g = h->es->diag;
-    Modes& s = g.modes;
-    if (!s.every || g.substep % static_cast<uint64_t>(s.every)) return FPIC_OK;
-    const uint64_t slot = s.ring.slot(s.ring.seq);
-    double* row = s.ring_dev + slot * s.req.width();
-    if (int rc = h->prec == FPIC_F32 ? modes_enqueue<float>(h, s.req, row) : modes_enqueue<double>(h, s.req, row)) return rc;
-    s.ring_substep[slot] = g.substep;
-    s.ring.seq++;
+    Recorder& r = h->es->diag.rec[kRecModes];
+    Drain d;
+    if (int rc = rec_drain(h, r, scope, !substeps, capacity, out ? nullptr : "out", n, dropped, d)) return rc;
+    if (d.query) return FPIC_OK;
+    if (d.cnt)
+        if (int rc = modes_deliver(h, d.rows.data(), d.rows.size(), d.collective, out)) return rc;
+    rec_drained(r, d, substeps, n, dropped);
     return FPIC_OK;
 }

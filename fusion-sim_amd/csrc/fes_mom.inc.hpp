@@ -9,7 +9,7 @@
 // takes the flat pass, and so do the arrivals of a migration that wait in the tail of a binned species' array for the next
 // re-binning push.  `out` is whole-grid-shaped: a rank that holds its slab's planes only gets them in their places and zero
 // elsewhere.  GLOBAL on a rank with a communicator gathers the ranks' grids and counters in chunks of kHistGatherWords
-// through diag_gather and every rank adds them as integers.
+// and every rank adds them as integers (diag_sum_ranks, fes_record.inc.hpp).
 
 static int mom_buffer(fpic_handle* h, size_t words)
 {
@@ -120,24 +120,10 @@ int moments(fpic_handle* h, const fpic_moments_spec* spec, int scope, int64_t* o
         info->spilled = counters[1];
         return FPIC_OK;
     }
-    // the ranks' grids and counters, chunk by chunk: every rank adds them as integers and gets the same sums
-    std::vector<unsigned char> all;
-    std::vector<uint64_t> sum;
-    uint64_t* grid = reinterpret_cast<uint64_t*>(out);
-    for (size_t at = 0; at < nm * nodes; at += kHistGatherWords) {
-        const size_t m = std::min(kHistGatherWords, nm * nodes - at);
-        if (int rc = diag_gather(h, grid + at, m * sizeof(uint64_t), all)) return rc;
-        const uint64_t* parts = reinterpret_cast<const uint64_t*>(all.data());
-        sum.assign(m, 0);
-        for (int r = 0; r < h->comm->world; ++r)
-            for (size_t i = 0; i < m; ++i) sum[i] += parts[static_cast<size_t>(r) * m + i];
-        std::memcpy(grid + at, sum.data(), m * sizeof(uint64_t));
-    }
-    if (int rc = diag_gather(h, counters, sizeof(counters), all)) return rc;
-    const uint64_t* parts = reinterpret_cast<const uint64_t*>(all.data());
-    for (int r = 0; r < h->comm->world; ++r) {
-        info->rejected += parts[2 * r];
-        info->spilled += parts[2 * r + 1];
-    }
+    // the ranks' grids, chunk by chunk, then their counters: every rank adds them as integers and gets the same sums
+    if (int rc = diag_sum_ranks(h, reinterpret_cast<uint64_t*>(out), nm * nodes)) return rc;
+    if (int rc = diag_sum_ranks(h, counters, 2)) return rc;
+    info->rejected = counters[0];
+    info->spilled = counters[1];
     return FPIC_OK;
 }

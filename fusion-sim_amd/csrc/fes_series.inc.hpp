@@ -6,7 +6,7 @@
 // the device in one allocation.  A row is enqueued on the handle's stream: the row is zeroed, the point pass writes the
 // entries of the points whose cell plane this handle owns, one tracer pass per species that has tracers writes the entries
 // of the tracers whose live slot it holds — to a scratch row (fpic_series_now) or to the recording ring (the hook
-// series_after_substep, driven by diag_after_substep; no host synchronisation, no collective).  GLOBAL on a rank with a
+// diag_after_substep; no host synchronisation, no collective; the recorder is fes_record.inc.hpp).  GLOBAL on a rank with a
 // communicator gathers the ranks' rows in chunks of kSeriesGatherEntries with diag_gather and every rank takes each entry
 // from the rank whose flag is set (fesser::select).
 
@@ -66,8 +66,12 @@ static int series_upload(fpic_handle* h, const fpic_series_spec& spec, SeriesReq
         dev += 2 * m + t.filter.size();
     }
     // (synchronous: the staging vector goes out of scope)
-    HIP_TRY(h, hipMemcpyAsync(block, host.data(), host.size(), hipMemcpyHostToDevice, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    hipError_t e = hipMemcpyAsync(block, host.data(), host.size(), hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    if (e != hipSuccess) {
+        (void)series_free(h, q);
+        return fail(h, FPIC_ERR_HIP, "the upload of a series request failed: %s", hipGetErrorString(e));
+    }
     return FPIC_OK;
 }
 
@@ -130,13 +134,13 @@ static int series_select_ranks(fpic_handle* h, const double* mine, size_t total_
 }
 
 // rows [rows][npoints + ntracers][8] as they lie in a ring row -> the caller's two arrays, selected over the ranks if collective
-static int series_deliver(fpic_handle* h, const SeriesReq& q, const std::vector<double>& mine, size_t rows, bool collective, double* points_out, double* tracers_out)
+static int series_deliver(fpic_handle* h, const SeriesReq& q, const double* mine, size_t rows, bool collective, double* points_out, double* tracers_out)
 {
     const size_t P = q.npoints, M = q.ntracers, E = fesser::kEntry;
     std::vector<double> pts(rows * P * E), trs(rows * M * E);
     for (size_t r = 0; r < rows; ++r) {
-        if (P) std::memcpy(pts.data() + r * P * E, mine.data() + r * (P + M) * E, P * E * sizeof(double));
-        if (M) std::memcpy(trs.data() + r * M * E, mine.data() + (r * (P + M) + P) * E, M * E * sizeof(double));
+        if (P) std::memcpy(pts.data() + r * P * E, mine + r * (P + M) * E, P * E * sizeof(double));
+        if (M) std::memcpy(trs.data() + r * M * E, mine + (r * (P + M) + P) * E, M * E * sizeof(double));
     }
     if (!collective) {
         if (P && rows) std::memcpy(points_out, pts.data(), pts.size() * sizeof(double));
@@ -161,26 +165,18 @@ int series_now(fpic_handle* h, const fpic_series_spec* spec, int scope, double* 
     if (int rc = f32 ? series_prepare<float>(h) : series_prepare<double>(h)) return rc;
     SeriesReq q;
     int rc = f32 ? series_upload<float>(h, *spec, q) : series_upload<double>(h, *spec, q);
-    void* row = nullptr;
     std::vector<double> mine;
-    if (rc == FPIC_OK) rc = dev_alloc(h, &row, q.width() * sizeof(double), nullptr);
-    if (rc == FPIC_OK) rc = f32 ? series_enqueue<float>(h, q, static_cast<double*>(row)) : series_enqueue<double>(h, q, static_cast<double*>(row));
-    if (rc == FPIC_OK) {
-        mine.resize(q.width());
-        hipError_t e = hipMemcpyAsync(mine.data(), row, mine.size() * sizeof(double), hipMemcpyDeviceToHost, h->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
-        if (e != hipSuccess) rc = fail(h, FPIC_ERR_HIP, "series read-back failed: %s", hipGetErrorString(e));
-    }
-    if (rc == FPIC_OK) rc = series_deliver(h, q, mine, 1, collective, points_out, tracers_out);
-    if (row) (void)hipFree(row);
-    if (q.block) { (void)hipFree(q.block); h->bytes_grid -= q.bytes; }
-    return rc;
+    if (rc == FPIC_OK)
+        rc = rec_row_now(h, q.width() * sizeof(double), "series",
+                         [&](void* row) { return f32 ? series_enqueue<float>(h, q, static_cast<double*>(row)) : series_enqueue<double>(h, q, static_cast<double*>(row)); }, mine);
+    if (rc == FPIC_OK) rc = series_deliver(h, q, mine.data(), 1, collective, points_out, tracers_out);
+    const int rc2 = series_free(h, q);
+    return rc ? rc : rc2;
 }
 
 int series_record(fpic_handle* h, const fpic_series_spec* spec, int every, uint32_t capacity)
 {
-    if (every < 0) return fail(h, FPIC_ERR_INVALID_ARG, ".every <- must be >= 0 (0 turns recording off)");
-    if (every > 0 && capacity < 1) return fail(h, FPIC_ERR_INVALID_ARG, ".capacity <- must be at least 1");
+    if (int rc = rec_check(h, every, capacity)) return rc;
     if (every > 0 && !spec) return fail(h, FPIC_ERR_INVALID_ARG, ".spec <- Non-optional property is undefined!");
     const bool f32 = h->prec == FPIC_F32;
     SeriesReq q;
@@ -188,80 +184,27 @@ int series_record(fpic_handle* h, const fpic_series_spec* spec, int every, uint3
         if (int rc = f32 ? series_prepare<float>(h) : series_prepare<double>(h)) return rc;
         if (int rc = f32 ? series_upload<float>(h, *spec, q) : series_upload<double>(h, *spec, q)) return rc;
     }
-    Series& s = h->es->diag.series;
-    if (s.ring_dev || s.req.block) HIP_TRY(h, hipStreamSynchronize(h->stream)); // (recorded rows still in flight write to it)
-    if (s.ring_dev) {
-        HIP_TRY(h, hipFree(s.ring_dev));
-        h->bytes_grid -= s.ring.cap * s.req.width() * sizeof(double);
-        s.ring_dev = nullptr;
-    }
-    if (int rc = series_free(h, s.req)) return rc;
-    s.ring = fesdiag::Ring();
-    s.ring_substep.clear();
-    s.every = 0;
+    Diag& g = h->es->diag;
+    Recorder& r = g.rec[kRecSeries];
+    if (int rc = rec_disarm(h, r, g.series_req.block != nullptr)) return rc;
+    if (int rc = series_free(h, g.series_req)) return rc;
     if (!every) return FPIC_OK;
-    s.req = q;
-    if (int rc = dev_alloc(h, reinterpret_cast<void**>(&s.ring_dev), static_cast<size_t>(capacity) * q.width() * sizeof(double), &h->bytes_grid)) {
-        (void)series_free(h, s.req);
-        return rc;
-    }
-    s.ring.cap = capacity;
-    s.ring_substep.assign(capacity, 0);
-    s.every = every;
-    return FPIC_OK;
+    g.series_req = q;
+    const int rc = rec_arm(h, r, every, capacity, q.width() * sizeof(double));
+    if (rc) (void)series_free(h, g.series_req);
+    return rc;
 }
 
 int series_history(fpic_handle* h, int scope, uint64_t* substeps, double* points_out, double* tracers_out, uint64_t capacity, uint64_t* n, uint64_t* dropped)
 {
-    if (!n) return fail(h, FPIC_ERR_INVALID_ARG, ".n <- Non-optional property is undefined!");
-    bool collective = false;
-    if (int rc = diag_scope(h, scope, collective)) return rc;
-    Series& s = h->es->diag.series;
-    uint64_t first = 0, cnt = 0, drop = 0;
-    if (s.ring_dev) s.ring.pending(first, cnt, drop);
-    if (!substeps) { // a query: nothing is drained
-        *n = cnt;
-        if (dropped) *dropped = drop;
-        return FPIC_OK;
-    }
-    if (capacity < cnt) return fail(h, FPIC_ERR_INVALID_ARG, ".capacity <- %llu rows are pending, room for %llu", static_cast<unsigned long long>(cnt), static_cast<unsigned long long>(capacity));
-    if (cnt && s.req.npoints && !points_out) return fail(h, FPIC_ERR_INVALID_ARG, ".points_out <- Non-optional property is undefined!");
-    if (cnt && s.req.ntracers && !tracers_out) return fail(h, FPIC_ERR_INVALID_ARG, ".tracers_out <- Non-optional property is undefined!");
-    const size_t W = s.req.width();
-    std::vector<double> mine(cnt * W);
-    uint64_t slot[2], len[2];
-    const int nr = s.ring.runs(first, cnt, slot, len);
-    for (int k = 0, at = 0; k < nr; at += static_cast<int>(len[k]), ++k)
-        HIP_TRY(h, hipMemcpyAsync(mine.data() + at * W, s.ring_dev + slot[k] * W, len[k] * W * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
-    if (collective) { // every rank must drain the same rows: agreed first, as fpic_energy_history does
-        const double mine_n[2] = { static_cast<double>(cnt), static_cast<double>(drop) };
-        std::vector<unsigned char> all;
-        if (int rc = diag_gather(h, mine_n, sizeof(mine_n), all)) return rc;
-        const double* ns = reinterpret_cast<const double*>(all.data());
-        for (int r = 0; r < h->comm->world; ++r)
-            if (ns[2 * r] != mine_n[0] || ns[2 * r + 1] != mine_n[1])
-                return fail(h, FPIC_ERR_STATE, "the ranks hold different numbers of recorded rows (%llu here, %.0f on rank %d): record with the same settings on every rank",
-                            static_cast<unsigned long long>(cnt), ns[2 * r], r);
-    }
-    if (int rc = series_deliver(h, s.req, mine, cnt, collective, points_out, tracers_out)) return rc;
-    for (uint64_t i = 0; i < cnt; ++i) substeps[i] = s.ring_substep[s.ring.slot(first + i)];
-    s.ring.drained = s.ring.seq;
-    *n = cnt;
-    if (dropped) *dropped = drop;
-    return FPIC_OK;
-}
-
-// the recording hook (called by diag_after_substep, which has counted the sub-step)
-static int series_after_substep(fpic_handle* h)
-{
     Diag& g = h->es->diag;
-    Series& s = g.series;
-    if (!s.every || g.substep % static_cast<uint64_t>(s.every)) return FPIC_OK;
-    const uint64_t slot = s.ring.slot(s.ring.seq);
-    double* row = s.ring_dev + slot * s.req.width();
-    if (int rc = h->prec == FPIC_F32 ? series_enqueue<float>(h, s.req, row) : series_enqueue<double>(h, s.req, row)) return rc;
-    s.ring_substep[slot] = g.substep;
-    s.ring.seq++;
+    Recorder& r = g.rec[kRecSeries];
+    const char* missing = g.series_req.npoints && !points_out ? "points_out" : g.series_req.ntracers && !tracers_out ? "tracers_out" : nullptr;
+    Drain d;
+    if (int rc = rec_drain(h, r, scope, !substeps, capacity, missing, n, dropped, d)) return rc;
+    if (d.query) return FPIC_OK;
+    if (d.cnt)
+        if (int rc = series_deliver(h, g.series_req, d.rows.data(), d.cnt, d.collective, points_out, tracers_out)) return rc;
+    rec_drained(r, d, substeps, n, dropped);
     return FPIC_OK;
 }

@@ -49,14 +49,6 @@ struct SeriesReq {
     std::vector<SeriesTable> tables;
     size_t width() const { return static_cast<size_t>(fesser::kEntry) * (static_cast<size_t>(npoints) + ntracers); }   // doubles per row
 };
-// ... and the recorder: a ring of rows of req.width() doubles; the host keeps the sub-step of each slot
-struct Series {
-    int every = 0;
-    fesdiag::Ring ring;
-    double* ring_dev = nullptr;
-    std::vector<uint64_t> ring_substep;
-    SeriesReq req;
-};
 
 // the modes diagnostic (fes_modes.inc.hpp): a request's copies on the device — one allocation holding the three twiddle tables
 // (complex doubles, nx + ny + nz entries), the reduced wave vectors (int32 [nmodes][3]) and the workgroups' partial rows
@@ -72,21 +64,25 @@ struct ModesReq {
     double2* partial = nullptr;
     size_t width() const { return static_cast<size_t>(2) * nmodes * nq; }   // doubles per row
 };
-// ... and the recorder: a ring of rows of req.width() doubles; the host keeps the sub-step of each slot
-struct Modes {
-    int every = 0;
-    fesdiag::Ring ring;
-    double* ring_dev = nullptr;
-    std::vector<uint64_t> ring_substep;
-    ModesReq req;
-};
 
-// the energy diagnostics (fes_diag.inc.hpp): the sub-step counter of fpic_energy, the recording ring, the reduction's buffers
+// a recorder (fes_record.inc.hpp): after every `every`-th sub-step a row of row_bytes is enqueued into a device ring; the host
+// keeps the sub-step of each slot.  The energy rows, the series and the modes have one each; what a row holds is its owner's
+struct Recorder {
+    int every = 0;                     // 0: off
+    fesdiag::Ring ring;
+    void* dev = nullptr;               // [ring.cap] rows
+    size_t row_bytes = 0;
+    std::vector<uint64_t> substep;     // [ring.cap]
+};
+enum { kRecEnergy, kRecSeries, kRecModes, kRecorders };
+
+// the diagnostics of a handle: the sub-step counter the recorders share, the recorders and their requests, the buffers of the
+// energy reduction (fes_diag.inc.hpp), of the histograms and of the moments, the ranks' gather
 struct Diag {
     uint64_t substep = 0;              // sub-steps advanced since create
-    int every = 0;                     // record after every `every`-th sub-step; 0: off
-    fesdiag::Ring ring;
-    fpic_energy* ring_dev = nullptr;   // [ring.cap] rows
+    Recorder rec[kRecorders];
+    SeriesReq series_req;              // what rec[kRecSeries] records (fes_series.inc.hpp)
+    ModesReq modes_req;                // what rec[kRecModes] records (fes_modes.inc.hpp)
     double* partial = nullptr;         // partial rows of the species passes and of the field pass
     fpic_energy* row_dev = nullptr;    // the row of fpic_energy_now
     void* gather = nullptr;            // the ranks' rows of a collective call
@@ -95,13 +91,12 @@ struct Diag {
     size_t hist_words = 0;
     unsigned long long* mom = nullptr;  // the buffer of fpic_moments (fes_mom.inc.hpp): a grid of the held planes per moment, then `rejected`, `spilled`; grows to the largest request
     size_t mom_words = 0;
-    Series series;                      // the recorder of fpic_series_record (fes_series.inc.hpp); shares `substep`
-    Modes modes;                        // the recorder of fpic_modes_record (fes_modes.inc.hpp); shares `substep`
 };
 inline void diag_release(Diag& g)
 {
-    for (void* p : { static_cast<void*>(g.ring_dev), static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom),
-                    static_cast<void*>(g.series.ring_dev), g.series.req.block, static_cast<void*>(g.modes.ring_dev), g.modes.req.block })
+    for (Recorder& r : g.rec)
+        if (r.dev) (void)hipFree(r.dev);
+    for (void* p : { g.series_req.block, g.modes_req.block, static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom) })
         if (p) (void)hipFree(p);
     g = Diag();
 }

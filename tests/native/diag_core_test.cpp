@@ -1,5 +1,6 @@
 // Host test of fusion-sim_amd/csrc/fes_diag_core.hpp (the rules of the energy diagnostics): the planes a handle reduces and
-// where it holds them, the recording ring's indexing and drop count, the fixed-order combination of rows.  Built with g++
+// where it holds them, the recording ring's indexing, drop count, commit and drain, the ranks' agreement on a drain, the
+// ranks' integer sum, the fixed-order combination of rows.  Built with g++
 // by tests/test_energy_host.py; prints "ok" and exits 0, or names the first failed check and exits 1.
 #include <cmath>
 #include <cstdio>
@@ -76,6 +77,83 @@ static void ring()
     q.seq = 4;
     q.pending(first, n, dropped);
     CHECK(first == 0 && n == 4 && dropped == 0 && q.runs(first, n, slot, len) == 1 && len[0] == 4);
+    // commit and mark_drained: a recorder's life in a ring of 3 — 13 rows committed one at a time, each into slot(seq)
+    fesdiag::Ring c;
+    c.cap = 3;
+    uint64_t held[3] = { 0, 0, 0 };
+    for (uint64_t row = 1; row <= 13; ++row) {
+        held[c.slot(c.seq)] = row;
+        c.commit();
+        CHECK(c.seq == row && c.drained == 0);
+    }
+    c.pending(first, n, dropped);
+    CHECK(first == 10 && n == 3 && dropped == 10);
+    CHECK(c.runs(first, n, slot, len) == 2 && slot[0] == 1 && len[0] == 2 && slot[1] == 0 && len[1] == 1);
+    for (uint64_t i = 0; i < n; ++i) CHECK(held[c.slot(first + i)] == 11 + i);
+    // a delivery that failed marks nothing: the same rows are pending again; after mark_drained none are
+    c.pending(first, n, dropped);
+    CHECK(first == 10 && n == 3 && dropped == 10);
+    c.mark_drained();
+    c.pending(first, n, dropped);
+    CHECK(n == 0 && dropped == 0 && c.drained == 13);
+    c.commit();
+    c.pending(first, n, dropped);
+    CHECK(first == 13 && n == 1 && dropped == 0 && c.slot(first) == 1);
+}
+
+static void agreement()
+{
+    // world 1: a rank agrees with itself
+    const double one[2] = { 3, 10 };
+    CHECK(fesdiag::disagreeing_rank(one, 1, 3, 10) == -1);
+    CHECK(fesdiag::disagreeing_rank(one, 1, 0, 0) == 0);
+    // world 3, all the same (zero rows too)
+    const double same[6] = { 3, 10, 3, 10, 3, 10 }, none[6] = { 0, 0, 0, 0, 0, 0 };
+    CHECK(fesdiag::disagreeing_rank(same, 3, 3, 10) == -1);
+    CHECK(fesdiag::disagreeing_rank(none, 3, 0, 0) == -1);
+    // a mismatch on the first rank, on the last rank, and the first of two
+    const double first[6] = { 2, 10, 3, 10, 3, 10 }, last[6] = { 3, 10, 3, 10, 4, 10 }, two[6] = { 3, 10, 5, 10, 4, 10 };
+    CHECK(fesdiag::disagreeing_rank(first, 3, 3, 10) == 0);
+    CHECK(fesdiag::disagreeing_rank(last, 3, 3, 10) == 2);
+    CHECK(fesdiag::disagreeing_rank(two, 3, 3, 10) == 1);
+    // the same number of rows, another number dropped
+    const double drop[6] = { 3, 10, 3, 9, 3, 10 };
+    CHECK(fesdiag::disagreeing_rank(drop, 3, 3, 10) == 1);
+    CHECK(fesdiag::disagreeing_rank(drop, 3, 3, 9) == 0);
+}
+
+static void word_sum()
+{
+    // three parts of four words: plain sums, a carry past 2^32, the top of the 64-bit range
+    const uint64_t big = 0xFFFFFFFFull;
+    const uint64_t parts[12] = { 1, big, 0, 1ull << 63,   2, 1, 0, (1ull << 63) - 1,   3, big, 0, 0 };
+    uint64_t out[4] = { 99, 99, 99, 99 };   // (overwritten, not added to)
+    fesdiag::add_words(parts, 4, 3, out);
+    CHECK(out[0] == 6 && out[1] == 2 * big + 1 && out[1] == 0x1FFFFFFFFull && out[2] == 0 && out[3] == ~0ull);
+    // one part: a copy
+    fesdiag::add_words(parts, 4, 1, out);
+    CHECK(out[0] == 1 && out[1] == big && out[2] == 0 && out[3] == 1ull << 63);
+    // in chunks of 4 words with a final short chunk, as the ranks' gather delivers them: chunk c of rank r is [r][m] of
+    // that chunk's block.  10 words of 3 ranks -> chunks of 4, 4, 2
+    const size_t n = 10, chunk = 4;
+    const int world = 3;
+    std::vector<uint64_t> mine[3], want(n, 0), got(n, 7);
+    for (int r = 0; r < world; ++r)
+        for (size_t i = 0; i < n; ++i) {
+            mine[r].push_back((big - 1) * (r + 1) + 1000 * i + r);
+            want[i] += mine[r].back();
+        }
+    size_t chunks = 0;
+    for (size_t at = 0; at < n; at += chunk, ++chunks) {
+        const size_t m = std::min(chunk, n - at);
+        std::vector<uint64_t> block;
+        for (int r = 0; r < world; ++r) block.insert(block.end(), mine[r].begin() + at, mine[r].begin() + at + m);
+        fesdiag::add_words(block.data(), m, world, got.data() + at);
+    }
+    CHECK(chunks == 3 && got == want && want[9] > (1ull << 32));
+    // no words: nothing is touched
+    fesdiag::add_words(parts, 0, 3, out);
+    CHECK(out[0] == 1);
 }
 
 static void combine()
@@ -130,6 +208,8 @@ int main()
 {
     owned_planes();
     ring();
+    agreement();
+    word_sum();
     combine();
     if (failures) return 1;
     std::printf("ok\n");
