@@ -22,6 +22,7 @@
 //   fes_record.inc.hpp      what the diagnostics share: the scope of a call, the ranks' gather and integer sum, the recorder (ring, hook, drain)
 //   fes_diag.inc.hpp        the energy diagnostics: the reductions, the ranks' combination
 //   fes_hist.inc.hpp        the phase-space histograms: the pass of one request, the ranks' sum
+//   fes_select.inc.hpp      the particle selection: the filter-and-compact pass of one request, the ranks' merge
 //   fes_mom.inc.hpp         the fluid moment grids: the sweeps of one request, the held planes' places, the ranks' sum
 //   fes_series.inc.hpp      the series: rows of field points and tracer particles, now or into a ring, the ranks' selection
 //   fes_modes.inc.hpp       the modes: Fourier amplitudes of the node fields at chosen wave vectors, now or into a ring, the ranks' sum
@@ -30,6 +31,7 @@
 #include "fes_diag_kernels.hpp"
 #include "fes_diag_core.hpp"
 #include "fes_hist_kernels.hpp"
+#include "fes_select_kernels.hpp"
 #include "fes_mom_kernels.hpp"
 #include "fes_series_kernels.hpp"
 #include "fes_modes_kernels.hpp"
@@ -345,6 +347,7 @@ namespace {
 #include "fes_record.inc.hpp"
 #include "fes_diag.inc.hpp"
 #include "fes_hist.inc.hpp"
+#include "fes_select.inc.hpp"
 #include "fes_mom.inc.hpp"
 #include "fes_series.inc.hpp"
 #include "fes_modes.inc.hpp"

@@ -91,12 +91,14 @@ struct Diag {
     size_t hist_words = 0;
     unsigned long long* mom = nullptr;  // the buffer of fpic_moments (fes_mom.inc.hpp): a grid of the held planes per moment, then `rejected`, `spilled`; grows to the largest request
     size_t mom_words = 0;
+    void* sel = nullptr;                // the buffer of fpic_select (fes_select.inc.hpp): the cursor, then out_id[rows], out_state[6][rows]; grows to the largest request
+    size_t sel_bytes = 0;
 };
 inline void diag_release(Diag& g)
 {
     for (Recorder& r : g.rec)
         if (r.dev) (void)hipFree(r.dev);
-    for (void* p : { g.series_req.block, g.modes_req.block, static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom) })
+    for (void* p : { g.series_req.block, g.modes_req.block, static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom), g.sel })
         if (p) (void)hipFree(p);
     g = Diag();
 }

@@ -1467,6 +1467,12 @@ int fpic_modes_history(fpic_handle* h, int scope, uint64_t* substeps, double* ou
     BOX_ONLY(h, "fpic_modes_history");
     return fes::modes_history(h, scope, substeps, out, capacity, n, dropped);
 }
+int fpic_select(fpic_handle* h, const fpic_select_spec* spec, int scope, uint64_t capacity, uint32_t* ids, void* pos_aos, void* vel_aos, int dtype, uint64_t* matched)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_select");
+    return fes::select(h, spec, scope, capacity, ids, pos_aos, vel_aos, dtype, matched);
+}
 int fpic_get_particles_of(fpic_handle* h, int species, void* pos_aos, void* vel_aos, int dtype)
 {
     CHECK_HANDLE(h);

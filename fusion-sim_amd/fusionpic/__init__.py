@@ -47,6 +47,7 @@ ABI_FUNCTIONS = [
     "fpic_energy_now", "fpic_energy_record", "fpic_energy_history", "fpic_histogram", "fpic_moments",
     "fpic_series_now", "fpic_series_record", "fpic_series_history",
     "fpic_modes_now", "fpic_modes_record", "fpic_modes_history",
+    "fpic_select",
 ]
 
 
@@ -184,6 +185,80 @@ def _hist_call(sim, s, shape, scope):
 def _hist_result(counts, outside, shape, rg):
     return {"counts": counts, "outside": outside,
             "edges": [rg[a, 0] + np.arange(shape[a] + 1) * (rg[a, 1] - rg[a, 0]) / shape[a] for a in builtins.range(len(shape))]}
+
+
+SELECT_MAX_TERMS = 7
+SELECT_MAX_ROWS = 1 << 24
+
+
+class SelectSpec(ctypes.Structure):
+    """mirror of fpic_select_spec (include/fusionpic.h)"""
+    _fields_ = [
+        ("species", ctypes.c_int32), ("nterms", ctypes.c_int32), ("axis", ctypes.c_int32 * 8), ("lo", ctypes.c_double * 8),
+        ("hi", ctypes.c_double * 8), ("id_mod", ctypes.c_uint32), ("id_rem", ctypes.c_uint32), ("reserved", ctypes.c_double * 4),
+    ]
+
+
+def _select_spec(where, species, every):
+    """SelectSpec of a selection request.  where: {axis name: (lo, hi)}, None for the infinite side; every: (mod, rem) or
+    None.  Only what the structure cannot carry is refused here (an unknown axis name, a bound that is no number, an
+    `every` that is no pair of uint32); the library checks the rest."""
+    s = SelectSpec()
+    s.species = int(species)
+    terms = list((where or {}).items())
+    if len(terms) > 8:
+        raise FusionPicError(-1, ".nterms <- must be 0 .. 7")
+    s.nterms = len(terms)
+    for t, (name, bounds) in enumerate(terms):
+        if name not in HIST_AXES:
+            raise FusionPicError(-1, ".axis <- must be one of x, y, z, vx, vy, vz, v2")
+        try:
+            lo, hi = bounds
+            lo = -np.inf if lo is None else float(lo)
+            hi = np.inf if hi is None else float(hi)
+        except (TypeError, ValueError):
+            raise FusionPicError(-1, ".range <- one (lo, hi) per axis, None for the infinite side")
+        s.axis[t], s.lo[t], s.hi[t] = HIST_AXES[name], lo, hi
+    if every is not None:
+        try:
+            mod, rem = every
+            ok = all(isinstance(k, (int, np.integer)) and not isinstance(k, bool) and 0 <= int(k) < 1 << 32 for k in (mod, rem))
+        except (TypeError, ValueError):
+            ok = False
+        if not ok:
+            raise FusionPicError(-1, ".every <- must be a pair (mod, rem) of unsigned 32-bit integers")
+        s.id_mod, s.id_rem = int(mod), int(rem)
+    return s
+
+
+def _select_call(sim, s, capacity, scope, dtype):
+    """fpic_select of one handle -> {ids, position, velocity, matched}.  capacity None: the count query first, then a call
+    with room for exactly that many rows; a given capacity that is too small leaves the three arrays None."""
+    sc = {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope]
+    code = sim.precision if dtype is None else (F32 if np.dtype(dtype) == np.float32 else F64)
+    matched = ctypes.c_uint64()
+    if capacity is None:
+        sim._check(sim._lib.fpic_select(sim._h, ctypes.byref(s), sc, 0, None, None, None, code, ctypes.byref(matched)))
+        capacity = matched.value
+    capacity = int(capacity)
+    if capacity < 0 or capacity >= 1 << 64:
+        raise FusionPicError(-1, ".capacity <- must be an unsigned 64-bit integer")
+    rows = capacity if capacity <= SELECT_MAX_ROWS else 1     # (a refused request writes nothing)
+    ids = np.zeros(rows, dtype=np.uint32)
+    pos, vel = np.zeros((rows, 3), dtype=_np_dtype(code)), np.zeros((rows, 3), dtype=_np_dtype(code))
+    ptr = lambda a: a.ctypes.data if capacity else None       # (capacity 0: the count query)
+    sim._check(sim._lib.fpic_select(sim._h, ctypes.byref(s), sc, capacity, ptr(ids), ptr(pos), ptr(vel), code, ctypes.byref(matched)))
+    m = int(matched.value)
+    if m > capacity:
+        return {"ids": None, "position": None, "velocity": None, "matched": m}
+    return {"ids": ids[:m].copy(), "position": pos[:m].copy(), "velocity": vel[:m].copy(), "matched": m}
+
+
+def _select_count(sim, s, scope):
+    matched = ctypes.c_uint64()
+    sim._check(sim._lib.fpic_select(sim._h, ctypes.byref(s), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope], 0, None, None, None,
+                                    sim.precision, ctypes.byref(matched)))
+    return int(matched.value)
 
 
 SERIES_MAX_POINTS = 4096
@@ -420,6 +495,7 @@ def load_library(path=None):
     lib.fpic_modes_now.argtypes = [vp, ctypes.POINTER(ModesSpec), ci, vp]
     lib.fpic_modes_record.argtypes = [vp, ctypes.POINTER(ModesSpec), ci, ctypes.c_uint32]
     lib.fpic_modes_history.argtypes = [vp, ci, vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+    lib.fpic_select.argtypes = [vp, ctypes.POINTER(SelectSpec), ci, ctypes.c_uint64, vp, vp, vp, ci, ctypes.POINTER(ctypes.c_uint64)]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -685,6 +761,22 @@ class CylindricalParticlePusher:
         s, shape, rg = _hist_spec(axes, bins, range, species)
         counts, outside = _hist_call(self, s, shape, scope)
         return _hist_result(counts, outside, shape, rg)
+
+    # ---- selection: the particles in a window of phase space, filtered and compacted on the device (fpic_select)
+    def select(self, where=None, species=0, every=None, capacity=None, scope="global", dtype=None):
+        """The live particles of one species of a CART3D box that lie in a window of phase space (fpic_select; an (r,z)
+        handle is refused).  where: {axis: (lo, hi)} with names from x y z vx vy vz v2 (stored values: positions as fractions
+        of the box, velocities in units of c), each a half-open interval lo <= q < hi, None for the infinite side; an empty
+        or absent `where` takes every live particle.  every: (mod, rem) keeps only ids with id % mod == rem — the same
+        particles at every time.  capacity None asks for the count first and then fetches; a given capacity that is too
+        small returns None arrays.  Returns {ids: uint32 (matched,), position, velocity: (matched, 3), matched}, in ascending
+        id.  'global' on a rank with a communicator is collective; on a member of an in-process group it is an error
+        (BoxGroup.select)."""
+        return _select_call(self, _select_spec(where, species, every), capacity, scope, dtype)
+
+    def count(self, where=None, species=0, every=None, scope="global"):
+        """how many particles select() would return (the count query of fpic_select: nothing is delivered)"""
+        return _select_count(self, _select_spec(where, species, every), scope)
 
     # ---- series: the field at points and the state of tracer particles as rows (fpic_series_*)
     def series(self, points=None, tracers=None, species=0, scope="global"):
@@ -979,6 +1071,8 @@ class ElectrostaticBoxPusher:
         return rows, int(dropped.value)
 
     histogram = CylindricalParticlePusher.histogram
+    select = CylindricalParticlePusher.select
+    count = CylindricalParticlePusher.count
     series = CylindricalParticlePusher.series
     recordSeries = CylindricalParticlePusher.recordSeries
     seriesHistory = CylindricalParticlePusher.seriesHistory
@@ -1056,6 +1150,25 @@ class BoxGroup:
         for c, _ in parts[1:]:
             counts += c
         return _hist_result(counts, sum(p[1] for p in parts), shape, rg)
+
+    def count(self, where=None, species=0, every=None):
+        """the whole box: the members' LOCAL counts (each its own particles) added up"""
+        s = _select_spec(where, species, every)
+        return sum(_select_count(m, s, "local") for m in self.sims)
+
+    def select(self, where=None, species=0, every=None, capacity=None, dtype=None):
+        """the whole box: the members' LOCAL rows (each its own particles) merged in ascending id.  As select(), plus
+        matched_members: the members' own counts."""
+        s = _select_spec(where, species, every)
+        counts = [_select_count(m, s, "local") for m in self.sims]
+        total = sum(counts)
+        if capacity is not None and total > int(capacity):
+            return {"ids": None, "position": None, "velocity": None, "matched": total, "matched_members": counts}
+        parts = [_select_call(m, s, c, "local", dtype) for m, c in zip(self.sims, counts)]
+        ids = np.concatenate([p["ids"] for p in parts])
+        order = np.argsort(ids, kind="stable")
+        return {"ids": ids[order], "position": np.concatenate([p["position"] for p in parts])[order],
+                "velocity": np.concatenate([p["velocity"] for p in parts])[order], "matched": total, "matched_members": counts}
 
     def moments(self, which="order2", species=0):
         """the whole box: the members' LOCAL moment grids (each its own particles, on the planes it holds) added up"""

@@ -247,6 +247,31 @@ function makeBox(spec, lib) {
         const codes = axes.map((a) => { if (!(a in HIST_AXES)) throw new RangeError('.axis <- must be one of x, y, z, vx, vy, vz, v2'); return HIST_AXES[a]; });
         return lib.histogram(h, request.species || 0, Int32Array.from(codes), Int32Array.from(bins), Float64Array.from(range.flat()), scopeOf(scope));
     };
+    // selection (fpic_select): the live particles of one species in a window of phase space, filtered and compacted on the GPU.
+    // request = { species (default 0), where: { axis: [lo, hi], ... } with names from x y z vx vy vz v2 over the stored values,
+    // null for the infinite side (lo <= q < hi), every: [mod, rem] keeps ids with id % mod === rem, capacity: rows to make room
+    // for (default: ask for the count first; 0: the count alone), dtype: 'fp32' | 'fp64' (default the handle's) }
+    // -> { ids: Uint32Array, position, velocity: [matched][3], matched } in ascending id; the arrays are null when matched
+    // exceeds a given capacity
+    out.select = function (request, scope) {
+        if (request === null || typeof request !== 'object') throw new TypeError('.request <- expected { species, where, every, capacity }');
+        const where = request.where === undefined || request.where === null ? {} : request.where;
+        if (typeof where !== 'object' || Array.isArray(where)) throw new TypeError('.where <- expected { axis: [lo, hi], ... }');
+        const codes = [], ranges = [];
+        for (const [name, r] of Object.entries(where)) {
+            if (!(name in HIST_AXES)) throw new RangeError('.axis <- must be one of x, y, z, vx, vy, vz, v2');
+            if (!Array.isArray(r) || r.length !== 2 || !r.every((x) => x === null || x === undefined || typeof x === 'number')) throw new RangeError('.range <- expected one [lo, hi] per axis, null for the infinite side');
+            codes.push(HIST_AXES[name]);
+            ranges.push(r[0] === null || r[0] === undefined ? -Infinity : r[0], r[1] === null || r[1] === undefined ? Infinity : r[1]);
+        }
+        const every = request.every === undefined || request.every === null ? [0, 0] : request.every;
+        if (!Array.isArray(every) || every.length !== 2 || !every.every((k) => Number.isInteger(k) && k >= 0 && k <= 0xffffffff)) throw new RangeError('.every <- expected [mod, rem] of unsigned 32-bit integers');
+        const capacity = request.capacity === undefined || request.capacity === null ? -1 : request.capacity;
+        if (!Number.isInteger(capacity) || capacity < -1) throw new RangeError('.capacity <- expected a non-negative integer');
+        if (request.dtype !== undefined && request.dtype !== 'fp32' && request.dtype !== 'fp64') throw new RangeError(".dtype <- must be 'fp32' or 'fp64'");
+        const f64 = request.dtype === undefined ? fp64 : request.dtype === 'fp64';
+        return lib.select(h, request.species || 0, Int32Array.from(codes), Float64Array.from(ranges), every[0], every[1], capacity, f64 ? 1 : 0, scopeOf(scope));
+    };
     // series (fpic_series_*): the field at points and the state of tracer particles as rows of 8 doubles, now or recorded into a
     // device ring.  request = { points: [[x, y, z], ...] in metres (wrapped periodically), tracers: particle indices, species: one
     // index or one per tracer (default 0) }; either list may be missing, not both.  A point row is Ex Ey Ez phi Bx By Bz present,

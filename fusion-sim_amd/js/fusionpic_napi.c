@@ -855,6 +855,73 @@ static napi_value n_histogram(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* select(h, species, axes: Int32Array, ranges: Float64Array (lo, hi per term), idMod, idRem, capacity, dtype (0: Float32Array,
+ * 1: Float64Array), scope) -> { ids: Uint32Array, position, velocity, matched }.  capacity < 0: the count query first, then a
+ * call with room for exactly that many rows; capacity 0: the count query alone.  The three arrays are null when `matched`
+ * exceeds a given capacity.  The arrays' lengths are checked here, the request itself by the library. */
+static napi_value n_select(napi_env env, napi_callback_info info)
+{
+    napi_value argv[9]; fpic_handle* h; int sp, scope; double mod, rem, cap, dt;
+    if (!get_args(env, info, 9, argv, &h) || !get_species(env, argv[1], &sp) || !get_double(env, argv[4], &mod) || !get_double(env, argv[5], &rem) ||
+        !get_double(env, argv[6], &cap) || !get_double(env, argv[7], &dt) || !get_scope(env, argv[8], &scope)) return NULL;
+    napi_typedarray_type ta, tr; void *pa, *pr; size_t la, lr;
+    if (!get_typed(env, argv[2], &ta, &pa, &la) || !get_typed(env, argv[3], &tr, &pr, &lr)) return NULL;
+    if ((la && (!pa || !pr)) || ta != napi_int32_array || tr != napi_float64_array) {
+        napi_throw_type_error(env, NULL, ".where <- expected Int32Array axes and Float64Array ranges");
+        return NULL;
+    }
+    if (la > FPIC_SELECT_MAX_TERMS) { napi_throw_range_error(env, NULL, ".nterms <- must be 0 .. 7"); return NULL; }
+    if (!check_len(env, "range", lr, 2 * la)) return NULL;
+    if (!(mod >= 0 && mod <= 4294967295.0 && rem >= 0 && rem <= 4294967295.0) || mod != (double)(uint32_t)mod || rem != (double)(uint32_t)rem) {
+        napi_throw_range_error(env, NULL, ".every <- expected [mod, rem] of unsigned 32-bit integers");
+        return NULL;
+    }
+    if (!(cap >= -1 && cap <= (double)FPIC_SELECT_MAX_ROWS) || cap != (double)(int64_t)cap) {
+        napi_throw_range_error(env, NULL, ".capacity <- more than FPIC_SELECT_MAX_ROWS (2^24) rows, or not an integer");
+        return NULL;
+    }
+    if (dt != 0 && dt != 1) { napi_throw_range_error(env, NULL, ".dtype <- must be 0 (f32) or 1 (f64)"); return NULL; }
+    fpic_select_spec s;
+    memset(&s, 0, sizeof s);
+    s.species = sp; s.nterms = (int32_t)la;
+    for (size_t t = 0; t < la; ++t) {
+        s.axis[t] = ((const int32_t*)pa)[t];
+        s.lo[t] = ((const double*)pr)[2 * t];
+        s.hi[t] = ((const double*)pr)[2 * t + 1];
+    }
+    s.id_mod = (uint32_t)mod; s.id_rem = (uint32_t)rem;
+    const int dtype = dt == 0 ? FPIC_F32 : FPIC_F64;
+    uint64_t matched = 0, capacity = cap < 0 ? 0 : (uint64_t)cap;
+    if (cap < 0) {
+        if (fpic_select(h, &s, scope, 0, NULL, NULL, NULL, dtype, &matched) != FPIC_OK) return throw_fpic(env, h);
+        if (matched > FPIC_SELECT_MAX_ROWS) { napi_throw_range_error(env, NULL, ".capacity <- more than FPIC_SELECT_MAX_ROWS (2^24) rows match: narrow the request"); return NULL; }
+        capacity = matched;
+    }
+    const size_t rows = (size_t)capacity, word = dtype == FPIC_F32 ? sizeof(float) : sizeof(double);
+    napi_value bi, bp, bv, out, v, ids, pos, vel;
+    void *di = NULL, *dp = NULL, *dv = NULL;
+    NAPI_OK(env, napi_create_arraybuffer(env, rows * sizeof(uint32_t), &di, &bi));
+    NAPI_OK(env, napi_create_arraybuffer(env, 3 * rows * word, &dp, &bp));
+    NAPI_OK(env, napi_create_arraybuffer(env, 3 * rows * word, &dv, &bv));
+    if (fpic_select(h, &s, scope, capacity, rows ? (uint32_t*)di : NULL, rows ? dp : NULL, rows ? dv : NULL, dtype, &matched) != FPIC_OK) return throw_fpic(env, h);
+    NAPI_OK(env, napi_create_object(env, &out));
+    if (matched <= capacity) {
+        const napi_typedarray_type real = dtype == FPIC_F32 ? napi_float32_array : napi_float64_array;
+        NAPI_OK(env, napi_create_typedarray(env, napi_uint32_array, (size_t)matched, bi, 0, &ids));
+        NAPI_OK(env, napi_create_typedarray(env, real, 3 * (size_t)matched, bp, 0, &pos));
+        NAPI_OK(env, napi_create_typedarray(env, real, 3 * (size_t)matched, bv, 0, &vel));
+    } else {
+        NAPI_OK(env, napi_get_null(env, &ids));
+        pos = vel = ids;
+    }
+    NAPI_OK(env, napi_set_named_property(env, out, "ids", ids));
+    NAPI_OK(env, napi_set_named_property(env, out, "position", pos));
+    NAPI_OK(env, napi_set_named_property(env, out, "velocity", vel));
+    NAPI_OK(env, napi_create_double(env, (double)matched, &v));
+    NAPI_OK(env, napi_set_named_property(env, out, "matched", v));
+    return out;
+}
+
 /* moments(h, species, mask, scope, out: BigInt64Array of popcount(mask) * nodes) -> { rejected, spilled }; the grids land in
  * `out` in ascending bit order.  The array's type and length are checked here, the request itself by the library. */
 static napi_value n_moments(napi_env env, napi_callback_info info)
@@ -1068,7 +1135,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "domainInit", n_domain_init }, { "domainSetParticles", n_domain_set_particles }, { "domainGetParticles", n_domain_get_particles },
         { "domainStats", n_domain_stats },
         { "energy", n_energy }, { "recordEnergy", n_record_energy }, { "energyHistory", n_energy_history },
-        { "histogram", n_histogram }, { "moments", n_moments },
+        { "histogram", n_histogram }, { "select", n_select }, { "moments", n_moments },
         { "series", n_series }, { "recordSeries", n_record_series }, { "seriesHistory", n_series_history },
         { "modes", n_modes }, { "recordModes", n_record_modes }, { "modesHistory", n_modes_history },
     };

@@ -658,6 +658,45 @@ int fpic_modes_record(fpic_handle* h, const fpic_modes_spec* spec, int every, ui
  * the same number of rows (else FPIC_ERR_STATE on every rank). */
 int fpic_modes_history(fpic_handle* h, int scope, uint64_t* substeps, double* out, uint64_t capacity, uint64_t* n, uint64_t* dropped);
 
+/* ---- CART3D particle selection, filtered and compacted on the device: the live particles of ONE species that lie in a
+ * window of phase space (and, optionally, whose id falls in a residue class) handed to the caller as ids, positions and
+ * velocities, without reading the species back.  A request holds nterms (0 .. FPIC_SELECT_MAX_TERMS) terms, each an axis
+ * code with a half-open interval [lo, hi):
+ *   the value q of an axis is exactly fpic_histogram's: FPIC_AXIS_X .. _VZ the stored number converted to double (positions
+ *   as fractions of the box in [0, 1), velocities in units of c; full EM: the stored half-time velocity as it is),
+ *   FPIC_AXIS_V2 vx*vx + vy*vy + vz*vz in double, added left to right, every operation rounded once.
+ * A live particle MATCHES a term iff q >= lo && q < hi, compared in double (a NaN matches nothing).  Unlike the histogram's
+ * bounds, lo may be -inf and hi may be +inf; a NaN bound, or a pair that is not lo < hi, is refused.  A particle is SELECTED
+ * iff it is live, matches every term and passes the id rule: id_mod 0 or 1 passes every id, otherwise only ids with
+ * id % id_mod == id_rem.  The dead slots of a decomposed rank are never selected.  nterms = 0 selects every live particle
+ * (subject to the id rule).  A window across the periodic boundary is two calls.
+ * The id is the one the tracer series uses: the caller's particle index on an undecomposed handle (first + k of
+ * fpic_set_particles_range), the global id on a decomposed rank (first_id + k of fpic_domain_set_particles).
+ * Outputs: *matched is always the number of selected particles.  If matched <= capacity, rows [0, matched) of ids,
+ * pos_aos ([row][3]) and vel_aos ([row][3]) are written IN ASCENDING ID — the same state gives the same bytes —, the values
+ * being the stored ones cast to `dtype` with a C cast; bytes past `matched` rows are untouched; any of the three pointers
+ * may be NULL.  If matched > capacity nothing is written to the arrays and the call still returns FPIC_OK: capacity = 0
+ * with all pointers NULL is the count query (the two-call idiom of fpic_series_history).
+ * scope: LOCAL is this handle's particles.  GLOBAL with a communicator is collective (every rank calls it with the same
+ * request and capacity): matched is the sum over the ranks, and if it fits every rank receives the same rows, merged in
+ * ascending id.  GLOBAL on a member of an in-process group is FPIC_ERR_STATE (the host merges the members' LOCAL rows).
+ * Refused (FPIC_ERR_INVALID_ARG): a null spec or matched, nterms outside 0 .. 7, an axis code outside 0 .. 6, the same axis
+ * twice, a NaN bound or not lo < hi, id_rem >= id_mod when id_mod > 1, a reserved word that is not zero, entries past
+ * nterms that are not zero, a species the handle does not have, capacity above FPIC_SELECT_MAX_ROWS, capacity > 0 with all
+ * three pointers NULL, a dtype that is neither F32 nor F64; FPIC_ERR_STATE: a handle that is not CART3D.  precalc() is not needed: the call
+ * reads particles and writes nothing but its own buffer.  Synchronous: enqueues on the handle's stream, copies back, waits. */
+#define FPIC_SELECT_MAX_TERMS 7
+#define FPIC_SELECT_MAX_ROWS  (1u << 24)
+typedef struct fpic_select_spec {
+    int32_t  species, nterms;   /* nterms 0..7; 0: every live particle (subject to the id rule) */
+    int32_t  axis[8];           /* FPIC_AXIS_X .. FPIC_AXIS_V2, each code at most once; zero past nterms */
+    double   lo[8], hi[8];
+    uint32_t id_mod, id_rem;    /* id_mod 0 or 1: every id; otherwise only ids with id % id_mod == id_rem */
+    double   reserved[4];       /* zero */
+} fpic_select_spec;
+int fpic_select(fpic_handle* h, const fpic_select_spec* spec, int scope, uint64_t capacity,
+                uint32_t* ids, void* pos_aos, void* vel_aos, int dtype, uint64_t* matched);
+
 int fpic_sync(fpic_handle* h);
 int fpic_profile(fpic_handle* h, int enable);
 int fpic_get_stats(fpic_handle* h, fpic_stats* out);
