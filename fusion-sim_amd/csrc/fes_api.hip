@@ -23,6 +23,7 @@
 //   fes_diag.inc.hpp        the energy diagnostics: the reductions, the ranks' combination
 //   fes_hist.inc.hpp        the phase-space histograms: the pass of one request, the ranks' sum
 //   fes_select.inc.hpp      the particle selection: the filter-and-compact pass of one request, the ranks' merge
+//   fes_load.inc.hpp        the particle loader: a population generated on the device, a rank keeping the particles of its planes
 //   fes_mom.inc.hpp         the fluid moment grids: the sweeps of one request, the held planes' places, the ranks' sum
 //   fes_series.inc.hpp      the series: rows of field points and tracer particles, now or into a ring, the ranks' selection
 //   fes_modes.inc.hpp       the modes: Fourier amplitudes of the node fields at chosen wave vectors, now or into a ring, the ranks' sum
@@ -32,6 +33,7 @@
 #include "fes_diag_core.hpp"
 #include "fes_hist_kernels.hpp"
 #include "fes_select_kernels.hpp"
+#include "fes_load_kernels.hpp"
 #include "fes_mom_kernels.hpp"
 #include "fes_series_kernels.hpp"
 #include "fes_modes_kernels.hpp"
@@ -348,6 +350,7 @@ namespace {
 #include "fes_diag.inc.hpp"
 #include "fes_hist.inc.hpp"
 #include "fes_select.inc.hpp"
+#include "fes_load.inc.hpp"
 #include "fes_mom.inc.hpp"
 #include "fes_series.inc.hpp"
 #include "fes_modes.inc.hpp"

@@ -39,6 +39,8 @@ int energy_history(fpic_handle* h, int scope, fpic_energy* rows, uint64_t capaci
 int histogram(fpic_handle* h, const fpic_hist_spec* spec, int scope, uint64_t* counts, uint64_t* outside);
 // particle selection (fes_select.inc.hpp)
 int select(fpic_handle* h, const fpic_select_spec* spec, int scope, uint64_t capacity, uint32_t* ids, void* pos_aos, void* vel_aos, int dtype, uint64_t* matched);
+// particle loader (fes_load.inc.hpp)
+int load(fpic_handle* h, const fpic_load_spec* spec, uint64_t* loaded);
 // fluid moment grids (fes_mom.inc.hpp)
 int moments(fpic_handle* h, const fpic_moments_spec* spec, int scope, int64_t* out, fpic_moments_info* info);
 // field points and tracer particles as rows (fes_series.inc.hpp)

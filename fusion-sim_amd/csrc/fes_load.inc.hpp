@@ -1,0 +1,118 @@
+// fes_load.inc.hpp: the particle loader of a CART3D handle (fpic_load) — part of fes_api.hip's translation unit (included
+// there after fes_select.inc.hpp, inside namespace fes).  The rule and the checks of a request are fes_load_core.hpp, the
+// passes fes_load_kernels.hpp.
+//
+// An undecomposed handle: one launch of load_slots_kernel over the slots that can hold the range (the range itself while
+// the species is in the caller's order, every slot once it has been binned), then what set_particles sets after an upload.
+// A rank of a decomposition: the counting pass of load_keep_kernel over the indices, the scan of the chunks' counts, the
+// total copied back and held against the capacity — nothing has been touched until here —, then the writing pass and the
+// state domain_set_particles leaves: slot order = ascending id, the ids beside the particles.
+
+template <typename T, bool POS, bool VEL>
+static void load_slots_launch(fpic_handle* h, const LoadArgs<T>& a)
+{
+    const size_t groups = (a.s1 + 3) / 4 - a.s0 / 4;
+    const unsigned grid = static_cast<unsigned>(std::min<size_t>(kLoadBlocks, (groups + kLoadThreads - 1) / kLoadThreads));
+    load_slots_kernel<T, POS, VEL><<<grid, kLoadThreads, 0, h->stream>>>(a);
+}
+
+template <typename T>
+static int load_slots(fpic_handle* h, Species& s, const fesload::Rule& r, uint64_t* loaded)
+{
+    *loaded = r.count;
+    if (!r.count) return FPIC_OK;
+    LoadArgs<T> a{};
+    a.slab = static_cast<T*>(s.slab[s.cur]);
+    a.id = s.ids_identity ? nullptr : s.id[s.cur];
+    a.n_pad = s.n_pad;
+    a.s0 = s.ids_identity ? static_cast<size_t>(r.first) : 0;
+    a.s1 = s.ids_identity ? static_cast<size_t>(r.first + r.count) : s.n;
+    a.r = r;
+    const bool pos = r.flags & FPIC_LOAD_POS, vel = r.flags & FPIC_LOAD_VEL;
+    if (pos && vel) load_slots_launch<T, true, true>(h, a);
+    else if (pos) load_slots_launch<T, true, false>(h, a);
+    else load_slots_launch<T, false, true>(h, a);
+    HIP_TRY(h, hipGetLastError());
+    if (pos) {   // (what set_particles sets after an upload of positions)
+        s.binned = false;
+        s.census_fresh = s.rebin_pending = s.chunk_census_fresh = false;
+        if (h->es->solver != FPIC_SOLVER_NONE) h->es->fields_ready = false;
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return FPIC_OK;
+}
+
+template <typename T>
+static int load_keep(fpic_handle* h, Species& s, const fesload::Rule& r, uint64_t* loaded)
+{
+    State* st = h->es;
+    const Domain& d = *st->dom;
+    const bool append = r.flags & FPIC_LOAD_APPEND;
+    if (append && s.rebin_pending)
+        return fail(h, FPIC_ERR_STATE, ".flags <- FPIC_LOAD_APPEND while a migration rides on the next push: append before the first step or after fpic_sort");
+    const size_t base = append ? s.n : 0;
+    *loaded = 0;
+    size_t kept = 0;
+    if (r.count) {
+        const size_t nchunks = static_cast<size_t>((r.count + kLoadChunk - 1) / kLoadChunk);
+        // the chunks' counts, then 8 bytes for the total (the selection's buffer: grows to the largest request)
+        const size_t total_at = (nchunks * sizeof(uint32_t) + 15) / 16 * 16;
+        if (int rc = select_buffer(h, total_at + 16)) return rc;
+        unsigned char* dev = static_cast<unsigned char*>(st->diag.sel);
+        KeepArgs<T> a{};
+        a.slab = static_cast<T*>(s.slab[s.cur]);
+        a.id = s.id[s.cur];
+        a.n_pad = s.n_pad;
+        a.base = base;
+        a.limit = s.cap;
+        a.chunk = reinterpret_cast<uint32_t*>(dev);
+        a.nchunks = nchunks;
+        a.nz = st->nz; a.z0 = d.z0; a.nzl = d.nzl;
+        a.r = r;
+        unsigned long long* total = reinterpret_cast<unsigned long long*>(dev + total_at);
+        const unsigned grid = static_cast<unsigned>(std::min<size_t>(kLoadBlocks, nchunks));
+        load_keep_kernel<T, false><<<grid, kLoadThreads, 0, h->stream>>>(a);
+        load_scan_kernel<<<1, 1024, 0, h->stream>>>(a.chunk, nchunks, total);
+        HIP_TRY(h, hipGetLastError());
+        unsigned long long got = 0;
+        HIP_TRY(h, hipMemcpyAsync(&got, total, sizeof(got), hipMemcpyDeviceToHost, h->stream));
+        HIP_TRY(h, hipStreamSynchronize(h->stream));
+        if (got > s.cap - std::min(base, s.cap) || base > s.cap)
+            return fail(h, FPIC_ERR_INVALID_ARG, ".count <- rank %d would hold %llu particles of species %d, its capacity is %zu; nothing was changed", d.rank,
+                        static_cast<unsigned long long>(base + got), static_cast<int>(&s - st->sp.data()), s.cap);
+        kept = static_cast<size_t>(got);
+        if (kept) load_keep_kernel<T, true><<<grid, kLoadThreads, 0, h->stream>>>(a);
+        HIP_TRY(h, hipGetLastError());
+    }
+    // the state domain_set_particles leaves: the live set holds the particles in slot order with their ids, the other set's
+    // ids are the slot numbers (the next binning writes both anew)
+    s.n = base + kept;
+    if (s.n) iota3_kernel<<<blocks_for(s.n), 256, 0, h->stream>>>(s.id[s.cur ^ 1], s.n, 0u);
+    HIP_TRY(h, hipGetLastError());
+    s.ids_identity = !append && r.first == 0 && kept == r.count;   // (everything kept from id 0 on: slot = id)
+    s.binned = false;
+    s.census_fresh = s.rebin_pending = s.chunk_census_fresh = false;
+    if (st->solver != FPIC_SOLVER_NONE) st->fields_ready = false;
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    *loaded = kept;
+    return FPIC_OK;
+}
+
+int load(fpic_handle* h, const fpic_load_spec* spec, uint64_t* loaded)
+{
+    if (!spec) return fail(h, FPIC_ERR_INVALID_ARG, ".spec <- Non-optional property is undefined!");
+    State* st = h->es;
+    const bool decomposed = st->dom != nullptr;
+    const double L[3] = { st->lx, st->ly, st->lz };
+    const int nsp = static_cast<int>(st->sp.size());
+    const uint64_t have = decomposed || spec->species < 0 || spec->species >= nsp ? ~0ull : st->sp[spec->species].n;
+    if (const char* why = fesload::check(*spec, nsp, have, L, decomposed)) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    Species& s = st->sp[spec->species];
+    const fesload::Rule r = fesload::rule_of(*spec, have, L);
+    uint64_t done = 0;
+    int rc;
+    if (decomposed) rc = h->prec == FPIC_F32 ? load_keep<float>(h, s, r, &done) : load_keep<double>(h, s, r, &done);
+    else rc = h->prec == FPIC_F32 ? load_slots<float>(h, s, r, &done) : load_slots<double>(h, s, r, &done);
+    if (rc == FPIC_OK && loaded) *loaded = done;
+    return rc;
+}

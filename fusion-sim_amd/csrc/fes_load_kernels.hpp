@@ -1,0 +1,191 @@
+// fes_load_kernels.hpp — the passes of the particle loader of a CART3D handle (fpic_load; host side fes_load.inc.hpp, the rule
+// fes_load_core.hpp).
+//   load_slots_kernel<T, POS, VEL>  an undecomposed handle.  A streaming pass in the launch shape of hist_kernel and
+//       select_kernel (fixed grid, grid-stride) over groups of FOUR slots: a lane takes the four particle indices from
+//       id[slot] (one 16-byte load) or, while the species is in the caller's order, the slot numbers; generates the state of
+//       each index inside [first, first + count); and stores it into the slots.  A group whose four slots are all loaded
+//       is stored with 16-byte stores (one per array in float, two in double); a group at the edge of the range, the tail
+//       of 1-3 slots and a group of a permuted species that holds other particles take scalar stores of the loaded slots
+//       only: every other particle keeps its bits.  Identity order: only the groups of [first, first + count) are visited.
+//   load_keep_kernel<T, WRITE>      a rank of a decomposition, over the INDICES [first, first + count) in chunks of
+//       kLoadChunk (one index per lane, one chunk per workgroup and turn).  WRITE = false generates the position only and
+//       counts per chunk the particles whose cell plane (axis() of the stored z: cells3_kernel, the migration) lies in the
+//       rank's planes [z0, z0 + nzl); load_scan_kernel turns the counts into exclusive offsets and the total; WRITE = true
+//       regenerates, and a kept particle goes to slot base + offset[chunk] + (kept lanes below it): consecutive slots in
+//       ascending index, the id beside it.
+// No LDS beyond a few words, no atomics, no scratch.
+#pragma once
+
+#include "fes_hist_kernels.hpp"
+#include "fes_load_core.hpp"
+
+namespace fes {
+
+constexpr int kLoadThreads = 256;
+constexpr int kLoadBlocks = 2048;       // 8 workgroups of 4 waves per CU of the 256, as kHistBlocks
+constexpr int kLoadChunk = kLoadThreads;   // indices per chunk of load_keep_kernel: one per lane
+
+template <typename T>
+struct LoadArgs {
+    T* slab;                  // x, y, z, vx, vy, vz: six arrays of n_pad
+    const uint32_t* id;       // n_pad words; nullptr: slot = index
+    size_t n_pad;             // a multiple of 1024: a group of four slots stays inside the arrays
+    size_t s0, s1;            // the slots [s0, s1) the pass visits
+    fesload::Rule r;
+};
+
+// the state of index i as the handle stores it
+template <typename T, bool POS, bool VEL>
+__device__ __forceinline__ void load_state(const fesload::Rule& r, uint32_t i, T (&out)[6])
+{
+    double p[3] = {}, theta = 0;
+    if (POS || r.waved) fesload::base_of(r, i, p, theta);
+    if constexpr (VEL) {
+        double v[3];
+        fesload::velocity_of(r, i, theta, v);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) out[3 + a] = static_cast<T>(v[a]);
+    }
+    if constexpr (POS) {
+        fesload::displace(r, theta, p);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) out[a] = wrap01(static_cast<T>(p[a]));
+    }
+}
+
+template <typename T, bool POS, bool VEL>
+__global__ __launch_bounds__(kLoadThreads) void load_slots_kernel(LoadArgs<T> g)
+{
+    const size_t g0 = g.s0 / 4, g1 = (g.s1 + 3) / 4, stride = static_cast<size_t>(gridDim.x) * kLoadThreads;
+    const uint64_t first = g.r.first, count = g.r.count;
+    for (size_t v = g0 + static_cast<size_t>(blockIdx.x) * kLoadThreads + threadIdx.x; v < g1; v += stride) {
+        const size_t base = 4 * v;                        // (base + 3 < n_pad: s1 <= n <= n_pad, both multiples of 4 apart)
+        uint32_t idx[4];
+        if (g.id) {
+            const uint4 q = *reinterpret_cast<const uint4*>(g.id + base);
+            idx[0] = q.x; idx[1] = q.y; idx[2] = q.z; idx[3] = q.w;
+        } else {
+#pragma unroll
+            for (int l = 0; l < 4; ++l) idx[l] = static_cast<uint32_t>(base + l);
+        }
+        uint32_t in = 0;
+#pragma unroll
+        for (int l = 0; l < 4; ++l)
+            in |= (base + l >= g.s0 && base + l < g.s1 && static_cast<uint64_t>(idx[l]) - first < count) ? 1u << l : 0u;   // (idx < first wraps far beyond count)
+        if (!in) continue;
+        T st[4][6];
+#pragma unroll
+        for (int l = 0; l < 4; ++l) load_state<T, POS, VEL>(g.r, idx[l], st[l]);
+        constexpr int C0 = POS ? 0 : 3, C1 = VEL ? 6 : 3;
+        if (in == 0xFu) {
+#pragma unroll
+            for (int c = C0; c < C1; ++c) {
+                T* dst = g.slab + c * g.n_pad + base;
+                if constexpr (sizeof(T) == 4) {
+                    *reinterpret_cast<float4*>(dst) = make_float4(st[0][c], st[1][c], st[2][c], st[3][c]);
+                } else {
+                    *reinterpret_cast<double2*>(dst) = make_double2(st[0][c], st[1][c]);
+                    *reinterpret_cast<double2*>(dst + 2) = make_double2(st[2][c], st[3][c]);
+                }
+            }
+        } else {
+#pragma unroll
+            for (int l = 0; l < 4; ++l)
+                if (in >> l & 1u) {
+#pragma unroll
+                    for (int c = C0; c < C1; ++c) g.slab[c * g.n_pad + base + l] = st[l][c];
+                }
+        }
+    }
+}
+
+template <typename T>
+struct KeepArgs {
+    T* slab;                  // WRITE: the rank's arrays
+    uint32_t* id;
+    size_t n_pad;
+    size_t base, limit;       // WRITE: the kept particles go to slots [base, limit)
+    uint32_t* chunk;          // [nchunks]: the kept particles per chunk (WRITE = false), their exclusive offsets (WRITE = true)
+    size_t nchunks;
+    int nz, z0, nzl;          // the rank owns the cell planes [z0, z0 + nzl)
+    fesload::Rule r;
+};
+
+template <typename T, bool WRITE>
+__global__ __launch_bounds__(kLoadThreads) void load_keep_kernel(KeepArgs<T> g)
+{
+    __shared__ uint32_t wave_kept[kLoadThreads / 64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (size_t c = blockIdx.x; c < g.nchunks; c += gridDim.x) {
+        const uint64_t k = static_cast<uint64_t>(c) * kLoadChunk + threadIdx.x;
+        const uint32_t i = static_cast<uint32_t>(g.r.first + k);
+        T st[3] = {};
+        double theta = 0;
+        bool keep = false;
+        if (k < g.r.count) {
+            double p[3];
+            fesload::base_of(g.r, i, p, theta);
+            fesload::displace(g.r, theta, p);
+#pragma unroll
+            for (int a = 0; a < 3; ++a) st[a] = wrap01(static_cast<T>(p[a]));   // (load_state's arithmetic)
+            int plane, w1;
+            axis(st[2], g.nz, plane, w1);
+            keep = static_cast<unsigned>(plane - g.z0) < static_cast<unsigned>(g.nzl);
+        }
+        const unsigned long long b = __ballot(keep);
+        if (lane == 0) wave_kept[wave] = __popcll(b);
+        __syncthreads();
+        if constexpr (!WRITE) {
+            if (threadIdx.x == 0) {
+                uint32_t s = 0;
+                for (int w = 0; w < kLoadThreads / 64; ++w) s += wave_kept[w];
+                g.chunk[c] = s;
+            }
+        } else if (keep) {
+            size_t slot = g.base + g.chunk[c] + __builtin_amdgcn_mbcnt_hi(static_cast<uint32_t>(b >> 32), __builtin_amdgcn_mbcnt_lo(static_cast<uint32_t>(b), 0u));
+            for (int w = 0; w < wave; ++w) slot += wave_kept[w];
+            if (slot < g.limit) {   // (the host has checked the total against the capacity; the passes count alike)
+                double v[3];
+                fesload::velocity_of(g.r, i, theta, v);
+#pragma unroll
+                for (int a = 0; a < 3; ++a) {
+                    g.slab[a * g.n_pad + slot] = st[a];
+                    g.slab[(3 + a) * g.n_pad + slot] = static_cast<T>(v[a]);
+                }
+                g.id[slot] = i;
+            }
+        }
+        __syncthreads();   // (wave_kept is rewritten by the next chunk)
+    }
+}
+
+// counts[0 .. n) -> their exclusive prefix sums in place, the total in *total: one workgroup, 1024 entries per turn
+__global__ __launch_bounds__(1024) void load_scan_kernel(uint32_t* __restrict__ counts, size_t n, unsigned long long* __restrict__ total)
+{
+    __shared__ unsigned long long wave_sum[16];
+    __shared__ unsigned long long carry;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (threadIdx.x == 0) carry = 0;
+    __syncthreads();
+    for (size_t at = 0; at < n; at += 1024) {
+        const size_t k = at + threadIdx.x;
+        const uint32_t mine = k < n ? counts[k] : 0u;
+        unsigned long long inc = mine;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const unsigned long long up = __shfl_up(inc, off, 64);
+            if (lane >= off) inc += up;
+        }
+        if (lane == 63) wave_sum[wave] = inc;
+        __syncthreads();
+        unsigned long long before = carry;
+        for (int w = 0; w < wave; ++w) before += wave_sum[w];
+        if (k < n) counts[k] = static_cast<uint32_t>(before + inc - mine);   // (below the capacity the host checks, or unused)
+        __syncthreads();
+        if (threadIdx.x == 1023) carry = before + inc;
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) *total = carry;
+}
+
+} // namespace fes

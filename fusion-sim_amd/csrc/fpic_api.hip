@@ -1473,6 +1473,12 @@ int fpic_select(fpic_handle* h, const fpic_select_spec* spec, int scope, uint64_
     BOX_ONLY(h, "fpic_select");
     return fes::select(h, spec, scope, capacity, ids, pos_aos, vel_aos, dtype, matched);
 }
+int fpic_load(fpic_handle* h, const fpic_load_spec* spec, uint64_t* loaded)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_load");
+    return fes::load(h, spec, loaded);
+}
 int fpic_get_particles_of(fpic_handle* h, int species, void* pos_aos, void* vel_aos, int dtype)
 {
     CHECK_HANDLE(h);

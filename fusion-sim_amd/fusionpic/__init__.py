@@ -47,7 +47,7 @@ ABI_FUNCTIONS = [
     "fpic_energy_now", "fpic_energy_record", "fpic_energy_history", "fpic_histogram", "fpic_moments",
     "fpic_series_now", "fpic_series_record", "fpic_series_history",
     "fpic_modes_now", "fpic_modes_record", "fpic_modes_history",
-    "fpic_select",
+    "fpic_select", "fpic_load",
 ]
 
 
@@ -259,6 +259,74 @@ def _select_count(sim, s, scope):
     sim._check(sim._lib.fpic_select(sim._h, ctypes.byref(s), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope], 0, None, None, None,
                                     sim.precision, ctypes.byref(matched)))
     return int(matched.value)
+
+
+LOAD_RANDOM, LOAD_POS, LOAD_VEL, LOAD_LATTICE, LOAD_PAIRED, LOAD_APPEND = 0, 1, 2, 4, 8, 16
+LOAD_SEED = 0x5EEDF051
+
+
+class LoadSpec(ctypes.Structure):
+    """mirror of fpic_load_spec (include/fusionpic.h)"""
+    _fields_ = [
+        ("species", ctypes.c_int32), ("flags", ctypes.c_uint32), ("first", ctypes.c_uint64), ("count", ctypes.c_uint64),
+        ("seed", ctypes.c_uint64), ("stream", ctypes.c_uint32), ("reserved", ctypes.c_uint32),
+        ("lo", ctypes.c_double * 3), ("hi", ctypes.c_double * 3), ("drift", ctypes.c_double * 3), ("vth", ctypes.c_double * 3),
+        ("mode", ctypes.c_int32 * 3), ("reserved2", ctypes.c_int32),
+        ("xamp", ctypes.c_double * 3), ("xphase", ctypes.c_double), ("vamp", ctypes.c_double * 3), ("vphase", ctypes.c_double),
+    ]
+
+
+def _load_spec(box, species=0, first=0, count=None, seed=LOAD_SEED, stream=0, lo=None, hi=None, drift=0, vth=0, mode=None, xamp=0, xphase=0,
+               vamp=0, vphase=0, lattice=False, paired=False, position=True, velocity=True, append=False):
+    """LoadSpec of a loader request.  box: the three lengths in metres (hi = None: the whole box); scalars broadcast to three
+    components.  Only what the structure cannot carry is refused here (a value that is no number, a vector that has not three
+    components, an integer outside its field); the library checks the rest."""
+    s = LoadSpec()
+
+    def whole(name, v, bits, signed=False):
+        lo_, hi_ = (-(1 << bits - 1), 1 << bits - 1) if signed else (0, 1 << bits)
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo_ <= int(v) < hi_:
+            raise FusionPicError(-1, ".%s <- must be %s %d-bit integer" % (name, "a signed" if signed else "an unsigned", bits))
+        return int(v)
+
+    def three(name, v, kind=float):
+        try:
+            if np.ndim(v) == 0:
+                v = [v, v, v]
+            if len(v) != 3:
+                raise ValueError
+            if kind is float:
+                return [float(x) for x in v]
+            return [whole(name, x, 32, signed=True) for x in v]
+        except (TypeError, ValueError):
+            raise FusionPicError(-1, ".%s <- must be a number or three of them" % name)
+
+    def real(name, v):
+        try:
+            return float(v)
+        except (TypeError, ValueError):
+            raise FusionPicError(-1, ".%s <- must be a number" % name)
+
+    s.species = whole("species", species, 32, signed=True)
+    s.first = whole("first", first, 64)
+    s.count = (1 << 64) - 1 if count is None else whole("count", count, 64)
+    s.seed = whole("seed", seed, 64)
+    s.stream = whole("stream", stream, 32)
+    s.flags = ((LOAD_POS if position else 0) | (LOAD_VEL if velocity else 0) | (LOAD_LATTICE if lattice else 0) |
+               (LOAD_PAIRED if paired else 0) | (LOAD_APPEND if append else 0))
+    s.lo[:] = three("lo", 0.0 if lo is None else lo)
+    s.hi[:] = [float(x) for x in box] if hi is None else three("hi", hi)
+    s.drift[:], s.vth[:] = three("drift", drift), three("vth", vth)
+    s.mode[:] = three("mode", 0 if mode is None else mode, kind=int)
+    s.xamp[:], s.vamp[:] = three("xamp", xamp), three("vamp", vamp)
+    s.xphase, s.vphase = real("xphase", xphase), real("vphase", vphase)
+    return s
+
+
+def _load_call(sim, s):
+    loaded = ctypes.c_uint64()
+    sim._check(sim._lib.fpic_load(sim._h, ctypes.byref(s), ctypes.byref(loaded)))
+    return int(loaded.value)
 
 
 SERIES_MAX_POINTS = 4096
@@ -496,6 +564,7 @@ def load_library(path=None):
     lib.fpic_modes_record.argtypes = [vp, ctypes.POINTER(ModesSpec), ci, ctypes.c_uint32]
     lib.fpic_modes_history.argtypes = [vp, ci, vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     lib.fpic_select.argtypes = [vp, ctypes.POINTER(SelectSpec), ci, ctypes.c_uint64, vp, vp, vp, ci, ctypes.POINTER(ctypes.c_uint64)]
+    lib.fpic_load.argtypes = [vp, ctypes.POINTER(LoadSpec), ctypes.POINTER(ctypes.c_uint64)]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -777,6 +846,24 @@ class CylindricalParticlePusher:
     def count(self, where=None, species=0, every=None, scope="global"):
         """how many particles select() would return (the count query of fpic_select: nothing is delivered)"""
         return _select_count(self, _select_spec(where, species, every), scope)
+
+    # ---- the loader: a population generated on the device (fpic_load)
+    def _box_lengths(self):
+        return [float(self.spec.get(k, 1.0)) for k in ("radius", "length_y", "height")]
+
+    def load(self, species=0, first=0, count=None, seed=LOAD_SEED, stream=0, lo=None, hi=None, drift=0, vth=0, mode=None, xamp=0, xphase=0,
+             vamp=0, vphase=0, lattice=False, paired=False, position=True, velocity=True, append=False):
+        """Particles [first, first + count) of one species of a CART3D box generated on the device (fpic_load; an (r,z)
+        handle is refused): uniform in the sub-box [lo, hi) (metres; random, or a Kronecker lattice with lattice=True), a
+        drifting Maxwellian (drift, vth in units of c; paired=True makes the thermal parts of particles 2k and 2k + 1 exact
+        negatives), and a sinusoidal perturbation of the integer mode vector `mode`: a displacement xamp (metres) and a
+        velocity vamp (c) times sinpi(2 (theta + phase)), phases in turns.  Scalars broadcast to three components.  The
+        state of a particle depends on the request and its index alone — not on the precision, the decomposition or the
+        time of the call; two species loaded with one seed and stream coincide.  position / velocity choose what is
+        written.  On a rank of a decomposition the rank keeps the particles of its planes (count is needed; append=True
+        adds to what it holds).  Returns the number of particles written (kept)."""
+        return _load_call(self, _load_spec(self._box_lengths(), species, first, count, seed, stream, lo, hi, drift, vth, mode, xamp, xphase,
+                                           vamp, vphase, lattice, paired, position, velocity, append))
 
     # ---- series: the field at points and the state of tracer particles as rows (fpic_series_*)
     def series(self, points=None, tracers=None, species=0, scope="global"):
@@ -1072,6 +1159,8 @@ class ElectrostaticBoxPusher:
 
     histogram = CylindricalParticlePusher.histogram
     select = CylindricalParticlePusher.select
+    _box_lengths = CylindricalParticlePusher._box_lengths
+    load = CylindricalParticlePusher.load
     count = CylindricalParticlePusher.count
     series = CylindricalParticlePusher.series
     recordSeries = CylindricalParticlePusher.recordSeries
@@ -1150,6 +1239,11 @@ class BoxGroup:
         for c, _ in parts[1:]:
             counts += c
         return _hist_result(counts, sum(p[1] for p in parts), shape, rg)
+
+    def load(self, *args, **request):
+        """load() of every member with the same request: each generates the indices [first, first + count) and keeps the
+        particles of its planes (count is needed: a rank does not know the whole population).  Returns the members' counts."""
+        return [m.load(*args, **request) for m in self.sims]
 
     def count(self, where=None, species=0, every=None):
         """the whole box: the members' LOCAL counts (each its own particles) added up"""

@@ -272,6 +272,43 @@ function makeBox(spec, lib) {
         const f64 = request.dtype === undefined ? fp64 : request.dtype === 'fp64';
         return lib.select(h, request.species || 0, Int32Array.from(codes), Float64Array.from(ranges), every[0], every[1], capacity, f64 ? 1 : 0, scopeOf(scope));
     };
+    // the loader (fpic_load): particles [first, first + count) of one species generated on the GPU.  request = { species, first,
+    // count (default: to the end), seed (an integer up to 2^53 or a BigInt up to 2^64), stream, lo, hi (metres; default the whole
+    // box), drift, vth (units of c), mode (three integers), xamp (metres), xphase, vamp (c), vphase (turns), lattice, paired,
+    // position, velocity (default true), append }; a number where three are expected is taken for all three -> the particles
+    // written (kept, on a rank of a decomposition)
+    out.load = function (request) {
+        if (request === null || typeof request !== 'object') throw new TypeError('.request <- expected { species, first, count, seed, ... }');
+        const three = function (name, v, dflt) {
+            if (v === undefined || v === null) v = dflt;
+            if (typeof v === 'number') v = [v, v, v];
+            if (!(Array.isArray(v) || ArrayBuffer.isView(v)) || v.length !== 3 || !Array.from(v).every((x) => typeof x === 'number')) throw new RangeError('.' + name + ' <- expected a number or three of them');
+            return Array.from(v);
+        };
+        const whole = function (name, v, dflt, least, most) {
+            if (v === undefined || v === null) v = dflt;
+            if (!Number.isInteger(v) || v < least || v > most) throw new RangeError('.' + name + ' <- expected an integer within its field');
+            return v;
+        };
+        const real = function (name, v) {
+            if (v === undefined || v === null) v = 0;
+            if (typeof v !== 'number') throw new RangeError('.' + name + ' <- expected a number');
+            return v;
+        };
+        let seed = request.seed === undefined || request.seed === null ? 0x5EEDF051 : request.seed;
+        if (typeof seed === 'number') {
+            if (!Number.isInteger(seed) || seed < 0 || seed > Number.MAX_SAFE_INTEGER) throw new RangeError('.seed <- expected an integer up to 2^53, or a BigInt up to 2^64');
+            seed = BigInt(seed);
+        }
+        if (typeof seed !== 'bigint' || seed < 0n || seed >= (1n << 64n)) throw new RangeError('.seed <- expected an integer up to 2^53, or a BigInt up to 2^64');
+        const flags = (request.position === false ? 0 : 1) | (request.velocity === false ? 0 : 2) | (request.lattice ? 4 : 0) | (request.paired ? 8 : 0) | (request.append ? 16 : 0);
+        const mode = three('mode', request.mode, 0).map((m) => whole('mode', m, 0, -0x80000000, 0x7fffffff));
+        const words = [whole('first', request.first, 0, 0, Number.MAX_SAFE_INTEGER), whole('count', request.count, -1, -1, Number.MAX_SAFE_INTEGER),
+            Number(seed & 0xffffffffn), Number(seed >> 32n), whole('stream', request.stream, 0, 0, 0xffffffff), flags].concat(mode);
+        const reals = [].concat(three('lo', request.lo, 0), three('hi', request.hi, [spec.radius, spec.length_y, spec.height]), three('drift', request.drift, 0),
+            three('vth', request.vth, 0), three('xamp', request.xamp, 0), [real('xphase', request.xphase)], three('vamp', request.vamp, 0), [real('vphase', request.vphase)]);
+        return lib.load(h, whole('species', request.species, 0, 0, 0x7fffffff), Float64Array.from(words), Float64Array.from(reals));
+    };
     // series (fpic_series_*): the field at points and the state of tracer particles as rows of 8 doubles, now or recorded into a
     // device ring.  request = { points: [[x, y, z], ...] in metres (wrapped periodically), tracers: particle indices, species: one
     // index or one per tracer (default 0) }; either list may be missing, not both.  A point row is Ex Ey Ez phi Bx By Bz present,

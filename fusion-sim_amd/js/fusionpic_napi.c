@@ -855,6 +855,51 @@ static napi_value n_histogram(napi_env env, napi_callback_info info)
     return out;
 }
 
+/* load(h, species, words: Float64Array [first, count (-1: to the end), seed low word, seed high word, stream, flags, mode x, y, z],
+ * reals: Float64Array [lo 3, hi 3, drift 3, vth 3, xamp 3, xphase, vamp 3, vphase]) -> the particles written (kept on a rank of a
+ * decomposition).  The arrays' lengths and the words' ranges are checked here, the request itself by the library. */
+static napi_value n_load(napi_env env, napi_callback_info info)
+{
+    napi_value argv[4]; fpic_handle* h; int sp;
+    if (!get_args(env, info, 4, argv, &h) || !get_species(env, argv[1], &sp)) return NULL;
+    napi_typedarray_type tw, tr; void *pw, *pr; size_t lw, lr;
+    if (!get_typed(env, argv[2], &tw, &pw, &lw) || !get_typed(env, argv[3], &tr, &pr, &lr)) return NULL;
+    if (!pw || !pr || tw != napi_float64_array || tr != napi_float64_array) {
+        napi_throw_type_error(env, NULL, ".request <- expected two Float64Arrays");
+        return NULL;
+    }
+    if (!check_len(env, "words", lw, 9) || !check_len(env, "reals", lr, 20)) return NULL;
+    const double* w = (const double*)pw;
+    const double* r = (const double*)pr;
+    const double most[9] = { 18446744073709549568.0, 18446744073709549568.0, 4294967295.0, 4294967295.0, 4294967295.0, 4294967295.0, 2147483647.0, 2147483647.0, 2147483647.0 };
+    for (int k = 0; k < 9; ++k) {
+        const double least = k == 1 ? -1.0 : (k >= 6 ? -2147483648.0 : 0.0);
+        const double mag = w[k] < 0 ? -w[k] : w[k];
+        if (!(w[k] >= least && w[k] <= most[k]) || mag != (double)(uint64_t)mag) {
+            napi_throw_range_error(env, NULL, ".request <- first, count, seed, stream and mode must be integers within their fields");
+            return NULL;
+        }
+    }
+    fpic_load_spec s;
+    memset(&s, 0, sizeof s);
+    s.species = sp;
+    s.first = (uint64_t)w[0];
+    s.count = w[1] < 0 ? ~(uint64_t)0 : (uint64_t)w[1];
+    s.seed = (uint64_t)(uint32_t)w[2] | (uint64_t)(uint32_t)w[3] << 32;
+    s.stream = (uint32_t)w[4];
+    s.flags = (uint32_t)w[5];
+    for (int a = 0; a < 3; ++a) {
+        s.mode[a] = (int32_t)w[6 + a];
+        s.lo[a] = r[a]; s.hi[a] = r[3 + a]; s.drift[a] = r[6 + a]; s.vth[a] = r[9 + a]; s.xamp[a] = r[12 + a]; s.vamp[a] = r[16 + a];
+    }
+    s.xphase = r[15]; s.vphase = r[19];
+    uint64_t loaded = 0;
+    if (fpic_load(h, &s, &loaded) != FPIC_OK) return throw_fpic(env, h);
+    napi_value v;
+    NAPI_OK(env, napi_create_double(env, (double)loaded, &v));
+    return v;
+}
+
 /* select(h, species, axes: Int32Array, ranges: Float64Array (lo, hi per term), idMod, idRem, capacity, dtype (0: Float32Array,
  * 1: Float64Array), scope) -> { ids: Uint32Array, position, velocity, matched }.  capacity < 0: the count query first, then a
  * call with room for exactly that many rows; capacity 0: the count query alone.  The three arrays are null when `matched`
@@ -1135,7 +1180,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "domainInit", n_domain_init }, { "domainSetParticles", n_domain_set_particles }, { "domainGetParticles", n_domain_get_particles },
         { "domainStats", n_domain_stats },
         { "energy", n_energy }, { "recordEnergy", n_record_energy }, { "energyHistory", n_energy_history },
-        { "histogram", n_histogram }, { "select", n_select }, { "moments", n_moments },
+        { "histogram", n_histogram }, { "select", n_select }, { "load", n_load }, { "moments", n_moments },
         { "series", n_series }, { "recordSeries", n_record_series }, { "seriesHistory", n_series_history },
         { "modes", n_modes }, { "recordModes", n_record_modes }, { "modesHistory", n_modes_history },
     };

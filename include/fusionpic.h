@@ -697,6 +697,59 @@ typedef struct fpic_select_spec {
 int fpic_select(fpic_handle* h, const fpic_select_spec* spec, int scope, uint64_t capacity,
                 uint32_t* ids, void* pos_aos, void* vel_aos, int dtype, uint64_t* matched);
 
+/* ---- CART3D particle loader: a population generated on the device, without host arrays.  The state of particle i (the
+ * caller's index = the id the box carries) depends on the request and on i alone — not on the slot, the rank of a
+ * decomposition, the precision of the handle or the time of the call.  All arithmetic is double, every operation rounded
+ * once; an fp32 handle stores the float rounding of the same double result.
+ *   words      W(b) = Philox4x32-10(counter (i, stream, b, 0x10AD), key (seed lo, seed hi)); b = 0 positions, b = 1
+ *              velocities; the lattice shifts are the block with counter (0, stream, 2, 0x10AD).  Two species loaded with the
+ *              same seed and stream get identical states; different streams are independent.
+ *   fractions  default (FPIC_LOAD_RANDOM)  f_a = W(0)[a] 2^-32
+ *              FPIC_LOAD_LATTICE           f_a = ((i mult_a + shift_a) mod 2^32) 2^-32, mult = 3518319155, 2882110345,
+ *                                          2360945575 (a Kronecker lattice), shift_a = word a of the shift block
+ *   position   in box fractions: p_a = lo[a]/L_a + f_a (hi[a] - lo[a])/L_a (one multiply, one add); the phase in turns
+ *              theta = (mode[0] p_x + mode[1] p_y) + mode[2] p_z; p_a += xamp[a]/L_a sinpi(2 (theta + xphase)); stored as
+ *              the upload stores it (cast to the handle's precision, wrapped into [0, 1)).
+ *   velocity   in units of c: Box-Muller on W(1) = (w0, w1, w2, w3): u1 = (w0 + 0.5) 2^-32, u2 = w1 2^-32,
+ *              n0 = sqrt(-2 ln u1) cospi(2 u2), n1 = sqrt(-2 ln u1) sinpi(2 u2),
+ *              n2 = sqrt(-2 ln((w2 + 0.5) 2^-32)) cospi(2 w3 2^-32) (|n| <= 6.76);
+ *              v_a = drift[a] + vth[a] n_a + vamp[a] sinpi(2 (theta + vphase)), theta from the undisplaced p.
+ *   FPIC_LOAD_PAIRED  the velocity block is taken at i & ~1 and the thermal term of odd i is negated: with zero drift and
+ *              vamp the thermal momentum of an even-aligned, even-length range is exactly zero.
+ * An undecomposed handle: particles [first, first + count) of the species (count = ~0: to the end) are written where they
+ * are now — before the first binning or in the middle of a run —, every other particle keeps its bits; FPIC_LOAD_POS /
+ * FPIC_LOAD_VEL choose the arrays written (at least one).  *loaded = count.
+ * A rank of a decomposition (after fpic_domain_init): the indices [first, first + count) are global ids; the rank generates
+ * them all and KEEPS those whose cell plane floor(z nz) it owns, in ascending id, so the ranks of a world hold between them
+ * exactly the particles one handle would, bit for bit.  Both arrays are required and count must be given.  The call
+ * replaces the rank's population of the species (as fpic_domain_set_particles); with FPIC_LOAD_APPEND the kept particles
+ * follow those the rank holds (several ranges, e.g. two beams; before the first step or after fpic_sort).  If the kept
+ * particles exceed the species' capacity on this rank the call returns FPIC_ERR_INVALID_ARG and changes nothing.
+ * *loaded = the particles kept.  Not collective.
+ * After a load that wrote positions the fields are stale, as after fpic_set_particles_range: fpic_precalc comes next.
+ * Refused (FPIC_ERR_INVALID_ARG): a null spec, a species the handle does not have, a range outside the species, neither POS
+ * nor VEL, unknown flag bits, a reserved word that is not zero, a value that is not finite, vth < 0, not
+ * 0 <= lo < hi <= L, |mode[a]| > 2^15; FPIC_ERR_STATE: a handle that is not CART3D.  Synchronous. */
+#define FPIC_LOAD_RANDOM  0u   /* positions from the random words (the default) */
+#define FPIC_LOAD_POS     1u
+#define FPIC_LOAD_VEL     2u
+#define FPIC_LOAD_LATTICE 4u   /* positions from the Kronecker lattice */
+#define FPIC_LOAD_PAIRED  8u
+#define FPIC_LOAD_APPEND  16u
+typedef struct fpic_load_spec {
+    int32_t  species;
+    uint32_t flags;
+    uint64_t first, count;      /* count = ~0: to the end of the species (an undecomposed handle) */
+    uint64_t seed;
+    uint32_t stream, reserved;  /* reserved: zero */
+    double   lo[3], hi[3];      /* the sub-box in metres, 0 <= lo < hi <= L */
+    double   drift[3], vth[3];  /* units of c */
+    int32_t  mode[3], reserved2;
+    double   xamp[3], xphase;   /* metres; turns */
+    double   vamp[3], vphase;   /* units of c; turns */
+} fpic_load_spec;
+int fpic_load(fpic_handle* h, const fpic_load_spec* spec, uint64_t* loaded);
+
 int fpic_sync(fpic_handle* h);
 int fpic_profile(fpic_handle* h, int enable);
 int fpic_get_stats(fpic_handle* h, fpic_stats* out);
