@@ -41,6 +41,11 @@ int histogram(fpic_handle* h, const fpic_hist_spec* spec, int scope, uint64_t* c
 int select(fpic_handle* h, const fpic_select_spec* spec, int scope, uint64_t capacity, uint32_t* ids, void* pos_aos, void* vel_aos, int dtype, uint64_t* matched);
 // particle loader (fes_load.inc.hpp)
 int load(fpic_handle* h, const fpic_load_spec* spec, uint64_t* loaded);
+// Monte Carlo collisions with a prescribed background (fes_collide.inc.hpp)
+int collide(fpic_handle* h, const fpic_collide_spec* spec, fpic_collide_result* out);
+int collide_register(fpic_handle* h, const fpic_collide_spec* spec, int every, int* index);
+int collide_stats(fpic_handle* h, int index, int scope, fpic_collide_result* out);
+int collide_clear(fpic_handle* h);
 // fluid moment grids (fes_mom.inc.hpp)
 int moments(fpic_handle* h, const fpic_moments_spec* spec, int scope, int64_t* out, fpic_moments_info* info);
 // field points and tracer particles as rows (fes_series.inc.hpp)

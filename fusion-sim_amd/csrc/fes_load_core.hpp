@@ -119,15 +119,21 @@ FES_HIST_HD void displace(const Rule& r, double theta, double (&p)[3])
     }
 }
 
-FES_HIST_HD void normals_of(const Rule& r, uint32_t i, double (&n)[3])
+// three normals from four words: the Box-Muller step (shared with the collision operator, fes_collide_core.hpp)
+FES_HIST_HD void normals_from(const uint32_t (&w)[4], double (&n)[3])
 {
-    uint32_t w[4];
-    philox(r.flags & FPIC_LOAD_PAIRED ? i & ~1u : i, r.stream, 1u, kTag, r.seed_lo, r.seed_hi, w);
     const double u1 = (static_cast<double>(w[0]) + 0.5) * kTwoM32, u3 = (static_cast<double>(w[2]) + 0.5) * kTwoM32;
     const double r1 = sqrt(-2.0 * log(u1)), r3 = sqrt(-2.0 * log(u3));
     n[0] = r1 * cospi_(2.0 * fraction_of(w[1]));
     n[1] = r1 * sinpi_(2.0 * fraction_of(w[1]));
     n[2] = r3 * cospi_(2.0 * fraction_of(w[3]));
+}
+
+FES_HIST_HD void normals_of(const Rule& r, uint32_t i, double (&n)[3])
+{
+    uint32_t w[4];
+    philox(r.flags & FPIC_LOAD_PAIRED ? i & ~1u : i, r.stream, 1u, kTag, r.seed_lo, r.seed_hi, w);
+    normals_from(w, n);
 }
 
 FES_HIST_HD void velocity_of(const Rule& r, uint32_t i, double theta, double (&v)[3])

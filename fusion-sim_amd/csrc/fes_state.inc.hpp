@@ -76,6 +76,13 @@ struct Recorder {
 };
 enum { kRecEnergy, kRecSeries, kRecModes, kRecorders };
 
+// a registered collision operator (fes_collide.inc.hpp): the request, its period in sub-steps, the applications so far
+struct CollideOp {
+    fpic_collide_spec spec;
+    int every;
+    uint64_t applications;
+};
+
 // the diagnostics of a handle: the sub-step counter the recorders share, the recorders and their requests, the buffers of the
 // energy reduction (fes_diag.inc.hpp), of the histograms and of the moments, the ranks' gather
 struct Diag {
@@ -93,12 +100,14 @@ struct Diag {
     size_t mom_words = 0;
     void* sel = nullptr;                // the buffer of fpic_select (fes_select.inc.hpp): the cursor, then out_id[rows], out_state[6][rows]; grows to the largest request
     size_t sel_bytes = 0;
+    unsigned long long* coll = nullptr; // the counts of fpic_collide (fes_collide.inc.hpp): four words per registered operator, four for a call
+    std::vector<CollideOp> coll_ops;    // the registered operators, in registration order
 };
 inline void diag_release(Diag& g)
 {
     for (Recorder& r : g.rec)
         if (r.dev) (void)hipFree(r.dev);
-    for (void* p : { g.series_req.block, g.modes_req.block, static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom), g.sel })
+    for (void* p : { g.series_req.block, g.modes_req.block, static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom), g.sel, static_cast<void*>(g.coll) })
         if (p) (void)hipFree(p);
     g = Diag();
 }

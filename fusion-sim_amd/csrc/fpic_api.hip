@@ -1479,6 +1479,30 @@ int fpic_load(fpic_handle* h, const fpic_load_spec* spec, uint64_t* loaded)
     BOX_ONLY(h, "fpic_load");
     return fes::load(h, spec, loaded);
 }
+int fpic_collide(fpic_handle* h, const fpic_collide_spec* spec, fpic_collide_result* out)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_collide");
+    return fes::collide(h, spec, out);
+}
+int fpic_collide_register(fpic_handle* h, const fpic_collide_spec* spec, int every, int* index)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_collide_register");
+    return fes::collide_register(h, spec, every, index);
+}
+int fpic_collide_stats(fpic_handle* h, int index, int scope, fpic_collide_result* out)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_collide_stats");
+    return fes::collide_stats(h, index, scope, out);
+}
+int fpic_collide_clear(fpic_handle* h)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_collide_clear");
+    return fes::collide_clear(h);
+}
 int fpic_get_particles_of(fpic_handle* h, int species, void* pos_aos, void* vel_aos, int dtype)
 {
     CHECK_HANDLE(h);

@@ -47,7 +47,7 @@ ABI_FUNCTIONS = [
     "fpic_energy_now", "fpic_energy_record", "fpic_energy_history", "fpic_histogram", "fpic_moments",
     "fpic_series_now", "fpic_series_record", "fpic_series_history",
     "fpic_modes_now", "fpic_modes_record", "fpic_modes_history",
-    "fpic_select", "fpic_load",
+    "fpic_select", "fpic_load", "fpic_collide", "fpic_collide_register", "fpic_collide_stats", "fpic_collide_clear",
 ]
 
 
@@ -329,6 +329,84 @@ def _load_call(sim, s):
     return int(loaded.value)
 
 
+COLLIDE_EXCHANGE, COLLIDE_ELASTIC, COLLIDE_RELAX = 0, 1, 2
+COLLIDE_MAX_OPS = 8
+COLLIDE_SEED = 0xC0111DE5
+COLLIDE_KINDS = {"exchange": COLLIDE_EXCHANGE, "elastic": COLLIDE_ELASTIC, "relax": COLLIDE_RELAX}
+
+
+class CollideSpec(ctypes.Structure):
+    """mirror of fpic_collide_spec (include/fusionpic.h)"""
+    _fields_ = [
+        ("species", ctypes.c_int32), ("kind", ctypes.c_int32), ("seed", ctypes.c_uint64), ("stream", ctypes.c_uint32), ("epoch", ctypes.c_uint32),
+        ("nu_tau", ctypes.c_double), ("sigma_tau", ctypes.c_double), ("g_max", ctypes.c_double),
+        ("drift", ctypes.c_double * 3), ("vth", ctypes.c_double * 3), ("mass_ratio", ctypes.c_double), ("reserved", ctypes.c_double * 4),
+    ]
+
+
+class CollideResult(ctypes.Structure):
+    """mirror of fpic_collide_result"""
+    _fields_ = [("applications", ctypes.c_uint64), ("candidates", ctypes.c_uint64), ("collided", ctypes.c_uint64), ("clipped", ctypes.c_uint64)]
+
+
+def _collide_spec(dt, kind, species=0, nu=None, sigma_n=None, tau=None, nu_tau=None, sigma_tau=None, g_max=0, drift=0, vth=0, mass_ratio=None,
+                  seed=COLLIDE_SEED, stream=0, epoch=0):
+    """CollideSpec of a collision request.  kind: a code or one of "exchange", "elastic", "relax".  The rates are given either
+    as the physical triple — nu (1/s), sigma_n (density times cross-section, 1/m) and tau (s; None: dt, the caller's default) —
+    or as the dimensionless pair nu_tau, sigma_tau (per unit of g in c); a rate left out is zero.  mass_ratio None: +inf (a
+    fixed target) for "elastic", 0 otherwise.  Only what the structure cannot carry, or a mix of the two forms, is refused
+    here; the library checks the rest."""
+    s = CollideSpec()
+
+    def whole(name, v, bits, signed=False):
+        lo_, hi_ = (-(1 << bits - 1), 1 << bits - 1) if signed else (0, 1 << bits)
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo_ <= int(v) < hi_:
+            raise FusionPicError(-1, ".%s <- must be %s %d-bit integer" % (name, "a signed" if signed else "an unsigned", bits))
+        return int(v)
+
+    def three(name, v):
+        try:
+            if np.ndim(v) == 0:
+                v = [v, v, v]
+            if len(v) != 3:
+                raise ValueError
+            return [float(x) for x in v]
+        except (TypeError, ValueError):
+            raise FusionPicError(-1, ".%s <- must be a number or three of them" % name)
+
+    def real(name, v):
+        try:
+            return float(v)
+        except (TypeError, ValueError):
+            raise FusionPicError(-1, ".%s <- must be a number" % name)
+
+    if isinstance(kind, str):
+        if kind not in COLLIDE_KINDS:
+            raise FusionPicError(-1, ".kind <- must be one of %s" % ", ".join(sorted(COLLIDE_KINDS)))
+        kind = COLLIDE_KINDS[kind]
+    s.kind = whole("kind", kind, 32, signed=True)
+    s.species = whole("species", species, 32, signed=True)
+    s.seed, s.stream, s.epoch = whole("seed", seed, 64), whole("stream", stream, 32), whole("epoch", epoch, 32)
+    physical, pair = nu is not None or sigma_n is not None or tau is not None, nu_tau is not None or sigma_tau is not None
+    if physical and pair:
+        raise FusionPicError(-1, ".nu_tau <- give either nu, sigma_n, tau or nu_tau, sigma_tau, not both")
+    if physical:
+        t = real("tau", dt if tau is None else tau)
+        s.nu_tau = real("nu", 0.0 if nu is None else nu) * t
+        s.sigma_tau = real("sigma_n", 0.0 if sigma_n is None else sigma_n) * SPEED_OF_LIGHT * t
+    else:
+        s.nu_tau = real("nu_tau", 0.0 if nu_tau is None else nu_tau)
+        s.sigma_tau = real("sigma_tau", 0.0 if sigma_tau is None else sigma_tau)
+    s.g_max = real("g_max", g_max)
+    s.drift[:], s.vth[:] = three("drift", drift), three("vth", vth)
+    s.mass_ratio = (float("inf") if s.kind == COLLIDE_ELASTIC else 0.0) if mass_ratio is None else real("mass_ratio", mass_ratio)
+    return s
+
+
+def _collide_counts(r):
+    return {"applications": int(r.applications), "candidates": int(r.candidates), "collided": int(r.collided), "clipped": int(r.clipped)}
+
+
 SERIES_MAX_POINTS = 4096
 SERIES_MAX_TRACERS = 65536
 # the columns of a point row and of a tracer row (fpic_series_*): 8 doubles each
@@ -565,6 +643,10 @@ def load_library(path=None):
     lib.fpic_modes_history.argtypes = [vp, ci, vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     lib.fpic_select.argtypes = [vp, ctypes.POINTER(SelectSpec), ci, ctypes.c_uint64, vp, vp, vp, ci, ctypes.POINTER(ctypes.c_uint64)]
     lib.fpic_load.argtypes = [vp, ctypes.POINTER(LoadSpec), ctypes.POINTER(ctypes.c_uint64)]
+    lib.fpic_collide.argtypes = [vp, ctypes.POINTER(CollideSpec), ctypes.POINTER(CollideResult)]
+    lib.fpic_collide_register.argtypes = [vp, ctypes.POINTER(CollideSpec), ci, ctypes.POINTER(ctypes.c_int)]
+    lib.fpic_collide_stats.argtypes = [vp, ci, ci, ctypes.POINTER(CollideResult)]
+    lib.fpic_collide_clear.argtypes = [vp]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -865,6 +947,45 @@ class CylindricalParticlePusher:
         return _load_call(self, _load_spec(self._box_lengths(), species, first, count, seed, stream, lo, hi, drift, vth, mode, xamp, xphase,
                                            vamp, vphase, lattice, paired, position, velocity, append))
 
+    # ---- Monte Carlo collisions with a prescribed background (fpic_collide*)
+    def collide(self, kind, **request):
+        """One application, now, of a collision operator to the stored velocities of one species of a CART3D box
+        (fpic_collide; an (r,z) handle is refused).  kind: "exchange" (charge exchange: the velocity becomes the partner's),
+        "elastic" (isotropic scattering in the centre-of-mass frame, mass_ratio = m_background / m_species) or "relax" (the
+        exact Ornstein-Uhlenbeck step of the Lenard-Bernstein operator: a thermostat).  The background is a drifting
+        Maxwellian (drift, vth in units of c; scalars broadcast).  Rates: nu (1/s), sigma_n (density times cross-section,
+        1/m) and tau (s, default the sub-step dt), or the dimensionless nu_tau and sigma_tau; with sigma_tau > 0 give g_max,
+        the bound of the relative speed (c) of the null-collision method.  seed, stream, epoch: the counter of the random
+        words — particle i of a request and epoch always draws the same.  Returns {applications, candidates, collided,
+        clipped}."""
+        s = _collide_spec(float(self.spec["dt"]), kind, **request)
+        out = CollideResult()
+        self._check(self._lib.fpic_collide(self._h, ctypes.byref(s), ctypes.byref(out)))
+        return _collide_counts(out)
+
+    def collideEvery(self, every, kind=None, **request):
+        """Registers a collision operator (see collide) to run at the end of every `every`-th sub-step, with epoch = the
+        sub-step number + `epoch`; tau defaults to every * dt.  Returns the operator's index (fpic_collide_register)."""
+        if kind is None:
+            raise FusionPicError(-1, ".kind <- Non-optional property is undefined!")
+        if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or not -(1 << 31) <= int(every) < 1 << 31:
+            raise FusionPicError(-1, ".every <- must be a signed 32-bit integer")
+        s = _collide_spec(int(every) * float(self.spec["dt"]), kind, **request)
+        index = ctypes.c_int(-1)
+        self._check(self._lib.fpic_collide_register(self._h, ctypes.byref(s), int(every), ctypes.byref(index)))
+        return index.value
+
+    def collisionStats(self, index, scope="global"):
+        """the totals of a registered operator since its registration (fpic_collide_stats); 'global' on a rank with a
+        communicator sums the ranks' counts (collective)"""
+        out = CollideResult()
+        self._check(self._lib.fpic_collide_stats(self._h, int(index), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope], ctypes.byref(out)))
+        return _collide_counts(out)
+
+    def clearCollisions(self):
+        """drops every registered collision operator (fpic_collide_clear)"""
+        self._check(self._lib.fpic_collide_clear(self._h))
+
     # ---- series: the field at points and the state of tracer particles as rows (fpic_series_*)
     def series(self, points=None, tracers=None, species=0, scope="global"):
         """The rows of the current state of a CART3D box (fpic_series_now; an (r,z) handle is refused).  points: positions in
@@ -1161,6 +1282,10 @@ class ElectrostaticBoxPusher:
     select = CylindricalParticlePusher.select
     _box_lengths = CylindricalParticlePusher._box_lengths
     load = CylindricalParticlePusher.load
+    collide = CylindricalParticlePusher.collide
+    collideEvery = CylindricalParticlePusher.collideEvery
+    collisionStats = CylindricalParticlePusher.collisionStats
+    clearCollisions = CylindricalParticlePusher.clearCollisions
     count = CylindricalParticlePusher.count
     series = CylindricalParticlePusher.series
     recordSeries = CylindricalParticlePusher.recordSeries
@@ -1204,6 +1329,12 @@ def _fluid(sim, m, species):
     return {"n": n, "flux": flux, "u": u, "Pi": Pi, "P": P, "T": T}
 
 
+def _collide_sum(parts):
+    out = {k: sum(p[k] for p in parts) for k in ("candidates", "collided", "clipped")}
+    out["applications"] = parts[0]["applications"]
+    return out
+
+
 class BoxGroup:
     """All ranks of a z-slab decomposition as handles of this process on one GPU (fpic_group_*): the in-process
     stand-in for the RCCL exchange."""
@@ -1244,6 +1375,22 @@ class BoxGroup:
         """load() of every member with the same request: each generates the indices [first, first + count) and keeps the
         particles of its planes (count is needed: a rank does not know the whole population).  Returns the members' counts."""
         return [m.load(*args, **request) for m in self.sims]
+
+    def collide(self, kind, **request):
+        """collide() of every member with the same request; the members' counts added up (applications: the first member's)"""
+        return _collide_sum([m.collide(kind, **request) for m in self.sims])
+
+    def collideEvery(self, every, kind=None, **request):
+        """collideEvery() of every member with the same request; the index (the same on every member)"""
+        return [m.collideEvery(every, kind, **request) for m in self.sims][0]
+
+    def collisionStats(self, index):
+        """the whole box: the members' LOCAL totals added up (applications: the first member's)"""
+        return _collide_sum([m.collisionStats(index, "local") for m in self.sims])
+
+    def clearCollisions(self):
+        for m in self.sims:
+            m.clearCollisions()
 
     def count(self, where=None, species=0, every=None):
         """the whole box: the members' LOCAL counts (each its own particles) added up"""

@@ -309,6 +309,74 @@ function makeBox(spec, lib) {
             three('vth', request.vth, 0), three('xamp', request.xamp, 0), [real('xphase', request.xphase)], three('vamp', request.vamp, 0), [real('vphase', request.vphase)]);
         return lib.load(h, whole('species', request.species, 0, 0, 0x7fffffff), Float64Array.from(words), Float64Array.from(reals));
     };
+    // Monte Carlo collisions with a prescribed drifting Maxwellian (fpic_collide*).  request = { kind: 'exchange' | 'elastic' |
+    // 'relax', species, either nu (1/s), sigmaN (density times cross-section, 1/m), tau (s; default the sub-step dt, every * dt
+    // for collideEvery) or the dimensionless nuTau, sigmaTau; gMax (c), drift, vth (c; a number is taken for all three),
+    // massRatio (default Infinity for 'elastic'), seed (an integer up to 2^53 or a BigInt up to 2^64), stream, epoch }
+    // collide -> { applications, candidates, collided, clipped }; collideEvery(every, request) -> the operator's index;
+    // collisionStats(index, scope) -> its totals since registration; clearCollisions() drops every operator
+    const COLLIDE_KINDS = { exchange: 0, elastic: 1, relax: 2 };
+    const collideArgs = function (request, tauDefault) {
+        if (request === null || typeof request !== 'object') throw new TypeError('.request <- expected { kind, species, nu, sigmaN, tau, ... }');
+        const three = function (name, v) {
+            if (v === undefined || v === null) v = 0;
+            if (typeof v === 'number') v = [v, v, v];
+            if (!(Array.isArray(v) || ArrayBuffer.isView(v)) || v.length !== 3 || !Array.from(v).every((x) => typeof x === 'number')) throw new RangeError('.' + name + ' <- expected a number or three of them');
+            return Array.from(v);
+        };
+        const whole = function (name, v, dflt, least, most) {
+            if (v === undefined || v === null) v = dflt;
+            if (!Number.isInteger(v) || v < least || v > most) throw new RangeError('.' + name + ' <- expected an integer within its field');
+            return v;
+        };
+        const real = function (name, v, dflt) {
+            if (v === undefined || v === null) v = dflt;
+            if (typeof v !== 'number') throw new RangeError('.' + name + ' <- expected a number');
+            return v;
+        };
+        const given = (v) => v !== undefined && v !== null;
+        let kind = request.kind;
+        if (typeof kind === 'string') {
+            if (!(kind in COLLIDE_KINDS)) throw new RangeError(".kind <- must be one of 'exchange', 'elastic', 'relax'");
+            kind = COLLIDE_KINDS[kind];
+        }
+        kind = whole('kind', kind, undefined, -0x80000000, 0x7fffffff);
+        let seed = given(request.seed) ? request.seed : 0xC0111DE5;
+        if (typeof seed === 'number') {
+            if (!Number.isInteger(seed) || seed < 0 || seed > Number.MAX_SAFE_INTEGER) throw new RangeError('.seed <- expected an integer up to 2^53, or a BigInt up to 2^64');
+            seed = BigInt(seed);
+        }
+        if (typeof seed !== 'bigint' || seed < 0n || seed >= (1n << 64n)) throw new RangeError('.seed <- expected an integer up to 2^53, or a BigInt up to 2^64');
+        const physical = given(request.nu) || given(request.sigmaN) || given(request.tau), pair = given(request.nuTau) || given(request.sigmaTau);
+        if (physical && pair) throw new RangeError('.nuTau <- give either nu, sigmaN, tau or nuTau, sigmaTau, not both');
+        let nuTau, sigmaTau;
+        if (physical) {
+            const tau = real('tau', request.tau, tauDefault);
+            nuTau = real('nu', request.nu, 0) * tau;
+            sigmaTau = real('sigmaN', request.sigmaN, 0) * 2.998e8 * tau;
+        } else {
+            nuTau = real('nuTau', request.nuTau, 0);
+            sigmaTau = real('sigmaTau', request.sigmaTau, 0);
+        }
+        const words = [kind, Number(seed & 0xffffffffn), Number(seed >> 32n), whole('stream', request.stream, 0, 0, 0xffffffff), whole('epoch', request.epoch, 0, 0, 0xffffffff)];
+        const reals = [nuTau, sigmaTau, real('gMax', request.gMax, 0)].concat(three('drift', request.drift), three('vth', request.vth),
+            [real('massRatio', request.massRatio, kind === 1 ? Infinity : 0)]);
+        return [whole('species', request.species, 0, 0, 0x7fffffff), Float64Array.from(words), Float64Array.from(reals)];
+    };
+    out.collide = function (request) {
+        const a = collideArgs(request, spec.dt);
+        return lib.collide(h, a[0], a[1], a[2]);
+    };
+    out.collideEvery = function (every, request) {
+        if (!Number.isInteger(every) || every < -0x80000000 || every > 0x7fffffff) throw new RangeError('.every <- expected a 32-bit integer');
+        const a = collideArgs(request, every * spec.dt);
+        return lib.collideEvery(h, a[0], a[1], a[2], every);
+    };
+    out.collisionStats = function (index, scope) {
+        if (!Number.isInteger(index) || index < -0x80000000 || index > 0x7fffffff) throw new RangeError('.index <- expected a 32-bit integer');
+        return lib.collisionStats(h, index, scopeOf(scope));
+    };
+    out.clearCollisions = function () { lib.clearCollisions(h); };
     // series (fpic_series_*): the field at points and the state of tracer particles as rows of 8 doubles, now or recorded into a
     // device ring.  request = { points: [[x, y, z], ...] in metres (wrapped periodically), tracers: particle indices, species: one
     // index or one per tracer (default 0) }; either list may be missing, not both.  A point row is Ex Ey Ez phi Bx By Bz present,

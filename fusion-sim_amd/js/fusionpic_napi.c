@@ -900,6 +900,100 @@ static napi_value n_load(napi_env env, napi_callback_info info)
     return v;
 }
 
+/* the request of collide / collideEvery: words: Float64Array [kind, seed low word, seed high word, stream, epoch], reals:
+ * Float64Array [nu_tau, sigma_tau, g_max, drift 3, vth 3, mass_ratio].  The arrays' lengths and the words' ranges are checked
+ * here, the request itself by the library. */
+static int get_collide_spec(napi_env env, int sp, napi_value words, napi_value reals, fpic_collide_spec* s)
+{
+    napi_typedarray_type tw, tr; void *pw, *pr; size_t lw, lr;
+    if (!get_typed(env, words, &tw, &pw, &lw) || !get_typed(env, reals, &tr, &pr, &lr)) return 0;
+    if (!pw || !pr || tw != napi_float64_array || tr != napi_float64_array) {
+        napi_throw_type_error(env, NULL, ".request <- expected two Float64Arrays");
+        return 0;
+    }
+    if (!check_len(env, "words", lw, 5) || !check_len(env, "reals", lr, 10)) return 0;
+    const double* w = (const double*)pw;
+    const double* r = (const double*)pr;
+    for (int k = 0; k < 5; ++k) {
+        const double least = k == 0 ? -2147483648.0 : 0.0, most = k == 0 ? 2147483647.0 : 4294967295.0;
+        const double mag = w[k] < 0 ? -w[k] : w[k];
+        if (!(w[k] >= least && w[k] <= most) || mag != (double)(uint64_t)mag) {
+            napi_throw_range_error(env, NULL, ".request <- kind, seed, stream and epoch must be integers within their fields");
+            return 0;
+        }
+    }
+    memset(s, 0, sizeof *s);
+    s->species = sp;
+    s->kind = (int32_t)w[0];
+    s->seed = (uint64_t)(uint32_t)w[1] | (uint64_t)(uint32_t)w[2] << 32;
+    s->stream = (uint32_t)w[3];
+    s->epoch = (uint32_t)w[4];
+    s->nu_tau = r[0]; s->sigma_tau = r[1]; s->g_max = r[2];
+    for (int a = 0; a < 3; ++a) { s->drift[a] = r[3 + a]; s->vth[a] = r[6 + a]; }
+    s->mass_ratio = r[9];
+    return 1;
+}
+
+static napi_value collide_object(napi_env env, const fpic_collide_result* c)
+{
+    napi_value o, v;
+    const char* names[4] = { "applications", "candidates", "collided", "clipped" };
+    const uint64_t vals[4] = { c->applications, c->candidates, c->collided, c->clipped };
+    NAPI_OK(env, napi_create_object(env, &o));
+    for (int k = 0; k < 4; ++k) {
+        NAPI_OK(env, napi_create_double(env, (double)vals[k], &v));
+        NAPI_OK(env, napi_set_named_property(env, o, names[k], v));
+    }
+    return o;
+}
+
+/* collide(h, species, words, reals) -> { applications, candidates, collided, clipped } */
+static napi_value n_collide(napi_env env, napi_callback_info info)
+{
+    napi_value argv[4]; fpic_handle* h; int sp;
+    fpic_collide_spec s;
+    if (!get_args(env, info, 4, argv, &h) || !get_species(env, argv[1], &sp) || !get_collide_spec(env, sp, argv[2], argv[3], &s)) return NULL;
+    fpic_collide_result c;
+    memset(&c, 0, sizeof c);
+    if (fpic_collide(h, &s, &c) != FPIC_OK) return throw_fpic(env, h);
+    return collide_object(env, &c);
+}
+
+/* collideEvery(h, species, words, reals, every) -> the operator's index */
+static napi_value n_collide_every(napi_env env, napi_callback_info info)
+{
+    napi_value argv[5]; fpic_handle* h; int sp; double every;
+    fpic_collide_spec s;
+    if (!get_args(env, info, 5, argv, &h) || !get_species(env, argv[1], &sp) || !get_collide_spec(env, sp, argv[2], argv[3], &s) || !get_double(env, argv[4], &every)) return NULL;
+    if (!(every >= -2147483648.0 && every <= 2147483647.0) || every != (double)(int)every) { napi_throw_range_error(env, NULL, ".every <- must be a 32-bit integer"); return NULL; }
+    int index = -1;
+    if (fpic_collide_register(h, &s, (int)every, &index) != FPIC_OK) return throw_fpic(env, h);
+    napi_value v;
+    NAPI_OK(env, napi_create_int32(env, index, &v));
+    return v;
+}
+
+/* collisionStats(h, index, scope) -> { applications, candidates, collided, clipped } */
+static napi_value n_collision_stats(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3]; fpic_handle* h; double index; int scope;
+    if (!get_args(env, info, 3, argv, &h) || !get_double(env, argv[1], &index) || !get_scope(env, argv[2], &scope)) return NULL;
+    if (!(index >= -2147483648.0 && index <= 2147483647.0) || index != (double)(int)index) { napi_throw_range_error(env, NULL, ".index <- must be a 32-bit integer"); return NULL; }
+    fpic_collide_result c;
+    memset(&c, 0, sizeof c);
+    if (fpic_collide_stats(h, (int)index, scope, &c) != FPIC_OK) return throw_fpic(env, h);
+    return collide_object(env, &c);
+}
+
+/* clearCollisions(h) */
+static napi_value n_clear_collisions(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1]; fpic_handle* h;
+    if (!get_args(env, info, 1, argv, &h)) return NULL;
+    if (fpic_collide_clear(h) != FPIC_OK) return throw_fpic(env, h);
+    return undefined(env);
+}
+
 /* select(h, species, axes: Int32Array, ranges: Float64Array (lo, hi per term), idMod, idRem, capacity, dtype (0: Float32Array,
  * 1: Float64Array), scope) -> { ids: Uint32Array, position, velocity, matched }.  capacity < 0: the count query first, then a
  * call with room for exactly that many rows; capacity 0: the count query alone.  The three arrays are null when `matched`
@@ -1180,7 +1274,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "domainInit", n_domain_init }, { "domainSetParticles", n_domain_set_particles }, { "domainGetParticles", n_domain_get_particles },
         { "domainStats", n_domain_stats },
         { "energy", n_energy }, { "recordEnergy", n_record_energy }, { "energyHistory", n_energy_history },
-        { "histogram", n_histogram }, { "select", n_select }, { "load", n_load }, { "moments", n_moments },
+        { "histogram", n_histogram }, { "select", n_select }, { "load", n_load }, { "collide", n_collide }, { "collideEvery", n_collide_every }, { "collisionStats", n_collision_stats }, { "clearCollisions", n_clear_collisions }, { "moments", n_moments },
         { "series", n_series }, { "recordSeries", n_record_series }, { "seriesHistory", n_series_history },
         { "modes", n_modes }, { "recordModes", n_record_modes }, { "modesHistory", n_modes_history },
     };

@@ -750,6 +750,68 @@ typedef struct fpic_load_spec {
 } fpic_load_spec;
 int fpic_load(fpic_handle* h, const fpic_load_spec* spec, uint64_t* loaded);
 
+/* ---- CART3D Monte Carlo collisions with a prescribed background: a drifting Maxwellian (drift, vth per axis, units of c)
+ * that is not another species; the momentum and energy the species loses go to that reservoir.  The operator acts on the
+ * stored velocities of one species (under full EM the half-time velocity, as fpic_histogram reads it), as a call or
+ * registered to run after every k-th sub-step.  What happens to particle i (the id the box carries) depends on the request,
+ * the epoch, i and its stored velocity alone — not on the slot, the binning or the rank; with sigma_tau = 0 WHO collides
+ * does not depend on the precision of the handle either.  All arithmetic is double, every operation rounded once; a stored
+ * velocity is converted to double and the result cast back to the handle's precision.
+ *   words      W(b) = Philox4x32-10(counter (i, epoch, stream, 0xC0110 + b), key (seed lo, seed hi)), the loader's
+ *              generator.  W(0) = (w0, w1, w2, w3): candidate, acceptance, two direction words; W(1): the partner's
+ *              three normals n, by the loader's Box-Muller formulas on the four words.
+ *   numbers    x_max = nu_tau + sigma_tau g_max; P_max = -expm1(-x_max); K = (uint64) ldexp(P_max, 32) (x_max = +inf:
+ *              K = 2^32); M = mass_ratio / (1 + mass_ratio) (+inf: M = 1); RELAX: decay = exp(-nu_tau),
+ *              sv[a] = sqrt(-expm1(-2 nu_tau)) vth[a].
+ *   candidate  (EXCHANGE, ELASTIC) a live particle with (uint64) w0 < K — an integer comparison.
+ *   partner    vb[a] = drift[a] + vth[a] n[a]; d[a] = v[a] - vb[a]; g = sqrt((d0 d0 + d1 d1) + d2 d2).
+ *   acceptance sigma_tau == 0: every candidate collides.  Otherwise (null-collision method) x = nu_tau + sigma_tau
+ *              min(g, g_max), u = (w1 + 0.5) 2^-32, and the candidate collides iff u x_max < x; a candidate with g > g_max
+ *              is also counted as `clipped`: the caller's bound was too low.
+ *   EXCHANGE   (charge exchange, Krook) v' = vb.
+ *   ELASTIC    (isotropic in the centre-of-mass frame) c = 1 - 2 (w2 + 0.5) 2^-32, s = sqrt(1 - c c), phi = w3 2^-32,
+ *              nhat = (s cospi(2 phi), s sinpi(2 phi), c); per component t = g nhat[a], r = d[a] - t, q = M r,
+ *              v'[a] = v[a] - q.
+ *   RELAX      (the exact Ornstein-Uhlenbeck step of the Lenard-Bernstein operator) no candidates: every live particle is
+ *              updated and counted as `collided`; r = v[a] - drift[a], p = decay r, k = sv[a] n[a], q = p + k,
+ *              v'[a] = drift[a] + q.
+ * A particle that does not collide keeps its bits; positions are never written, so the fields stay valid and fpic_precalc
+ * is not needed.  A dead slot of a rank of a decomposition is never a candidate and never counted.
+ * fpic_collide applies the request now (synchronous) and returns its counts (applications = 1; with K = 0 nothing can
+ * collide: all four are zero and nothing runs).  fpic_collide_register makes it run at the end of every sub-step whose
+ * number (counted since create) is a multiple of `every`, in registration order, before the recorders take their rows —
+ * a row recorded after that sub-step sees the collided state — with epoch (uint32)(sub-step + spec.epoch): a resumed run
+ * passes the sub-steps already done.  At most FPIC_COLLIDE_MAX_OPS operators; *index names the operator.  Nothing is
+ * synchronised: the counts accumulate on the device and fpic_collide_stats reads the totals since registration (scope as
+ * for the diagnostics: GLOBAL with a communicator sums candidates, collided and clipped over the ranks; applications is the
+ * same on every rank and is not summed).  fpic_collide_clear drops every registered operator.  Registrations are not part of
+ * a checkpoint.
+ * Refused (FPIC_ERR_INVALID_ARG): a null spec, an unknown kind, a species the handle does not have, a NaN anywhere, a
+ * negative rate, sigma_tau not finite, vth < 0 or not finite, a drift that is not finite, g_max not (> 0 and finite) with
+ * sigma_tau > 0 or not 0 without, nu_tau = +inf with sigma_tau > 0, mass_ratio given for a kind other than ELASTIC or <= 0
+ * for ELASTIC, RELAX with sigma_tau != 0, nu_tau == 0 or nu_tau = +inf, a reserved word that is not zero, every < 1, a
+ * ninth registration, an index outside the registered operators; FPIC_ERR_STATE: a handle that is not CART3D. */
+#define FPIC_COLLIDE_EXCHANGE 0
+#define FPIC_COLLIDE_ELASTIC  1
+#define FPIC_COLLIDE_RELAX    2
+#define FPIC_COLLIDE_MAX_OPS  8
+typedef struct fpic_collide_spec {
+    int32_t  species, kind;        /* FPIC_COLLIDE_EXCHANGE 0, _ELASTIC 1, _RELAX 2 */
+    uint64_t seed;
+    uint32_t stream, epoch;
+    double   nu_tau;               /* nu tau >= 0, +inf allowed (not for RELAX) */
+    double   sigma_tau;            /* n sigma c tau >= 0, finite; per unit of g */
+    double   g_max;                /* > 0 and finite when sigma_tau > 0, else 0 */
+    double   drift[3], vth[3];     /* the background, units of c; vth >= 0 */
+    double   mass_ratio;           /* m_background / m_species > 0, +inf allowed; ELASTIC only, else 0 */
+    double   reserved[4];          /* zero */
+} fpic_collide_spec;
+typedef struct fpic_collide_result { uint64_t applications, candidates, collided, clipped; } fpic_collide_result;
+int fpic_collide(fpic_handle* h, const fpic_collide_spec* spec, fpic_collide_result* out);
+int fpic_collide_register(fpic_handle* h, const fpic_collide_spec* spec, int every, int* index);
+int fpic_collide_stats(fpic_handle* h, int index, int scope, fpic_collide_result* out);
+int fpic_collide_clear(fpic_handle* h);
+
 int fpic_sync(fpic_handle* h);
 int fpic_profile(fpic_handle* h, int enable);
 int fpic_get_stats(fpic_handle* h, fpic_stats* out);
