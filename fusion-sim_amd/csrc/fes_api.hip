@@ -25,6 +25,7 @@
 //   fes_select.inc.hpp      the particle selection: the filter-and-compact pass of one request, the ranks' merge
 //   fes_load.inc.hpp        the particle loader: a population generated on the device, a rank keeping the particles of its planes
 //   fes_collide.inc.hpp     Monte Carlo collisions with a prescribed background, now or registered to run after sub-steps
+//   fes_pair.inc.hpp        binary Coulomb collisions between the species (Takizuka-Abe): the cell index of a request, the pairing pass
 //   fes_mom.inc.hpp         the fluid moment grids: the sweeps of one request, the held planes' places, the ranks' sum
 //   fes_series.inc.hpp      the series: rows of field points and tracer particles, now or into a ring, the ranks' selection
 //   fes_modes.inc.hpp       the modes: Fourier amplitudes of the node fields at chosen wave vectors, now or into a ring, the ranks' sum
@@ -36,6 +37,7 @@
 #include "fes_select_kernels.hpp"
 #include "fes_load_kernels.hpp"
 #include "fes_collide_kernels.hpp"
+#include "fes_pair_kernels.hpp"
 #include "fes_mom_kernels.hpp"
 #include "fes_series_kernels.hpp"
 #include "fes_modes_kernels.hpp"
@@ -354,12 +356,14 @@ namespace {
 #include "fes_select.inc.hpp"
 #include "fes_load.inc.hpp"
 #include "fes_collide.inc.hpp"
+#include "fes_pair.inc.hpp"
 #include "fes_mom.inc.hpp"
 #include "fes_series.inc.hpp"
 #include "fes_modes.inc.hpp"
 
 // the recording hook, at the end of every sub-step of every path (substeps(), group_run()): counts the sub-step, applies the
-// registered collision operators that are due (fes_collide.inc.hpp: the rows below see the collided state), then every
+// registered collision operators that are due (fes_collide.inc.hpp against the background, then fes_pair.inc.hpp between the
+// species: the rows below see the collided state), then every
 // recorder that is due — the energy rows, the series, the modes, which share the counter and nothing else — enqueues its row
 // into its ring.  No host synchronisation, no collective; recording off: nothing is enqueued.
 static int diag_after_substep(fpic_handle* h)
@@ -368,6 +372,8 @@ static int diag_after_substep(fpic_handle* h)
     g.substep++;
     if (!g.coll_ops.empty())
         if (int rc = collide_after_substep(h, g.substep)) return rc;
+    if (!g.pair_ops.empty())
+        if (int rc = pair_after_substep(h, g.substep)) return rc;
     const bool f32 = h->prec == FPIC_F32;
     for (int k = 0; k < kRecorders; ++k) {
         void* row = rec_due(g.rec[k], g.substep);

@@ -46,6 +46,11 @@ int collide(fpic_handle* h, const fpic_collide_spec* spec, fpic_collide_result* 
 int collide_register(fpic_handle* h, const fpic_collide_spec* spec, int every, int* index);
 int collide_stats(fpic_handle* h, int index, int scope, fpic_collide_result* out);
 int collide_clear(fpic_handle* h);
+// binary Coulomb collisions between the species of the box (fes_pair.inc.hpp)
+int pair(fpic_handle* h, const fpic_pair_spec* spec, fpic_pair_result* out);
+int pair_register(fpic_handle* h, const fpic_pair_spec* spec, int every, int* index);
+int pair_stats(fpic_handle* h, int index, int scope, fpic_pair_result* out);
+int pair_clear(fpic_handle* h);
 // fluid moment grids (fes_mom.inc.hpp)
 int moments(fpic_handle* h, const fpic_moments_spec* spec, int scope, int64_t* out, fpic_moments_info* info);
 // field points and tracer particles as rows (fes_series.inc.hpp)

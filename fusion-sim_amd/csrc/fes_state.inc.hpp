@@ -83,6 +83,13 @@ struct CollideOp {
     uint64_t applications;
 };
 
+// a registered binary collision operator (fes_pair.inc.hpp): the request, its period in sub-steps, the applications so far
+struct PairOp {
+    fpic_pair_spec spec;
+    int every;
+    uint64_t applications;
+};
+
 // the diagnostics of a handle: the sub-step counter the recorders share, the recorders and their requests, the buffers of the
 // energy reduction (fes_diag.inc.hpp), of the histograms and of the moments, the ranks' gather
 struct Diag {
@@ -102,12 +109,21 @@ struct Diag {
     size_t sel_bytes = 0;
     unsigned long long* coll = nullptr; // the counts of fpic_collide (fes_collide.inc.hpp): four words per registered operator, four for a call
     std::vector<CollideOp> coll_ops;    // the registered operators, in registration order
+    unsigned long long* pair = nullptr; // the counts of fpic_pair (fes_pair.inc.hpp): eight words per registered operator, eight for a call
+    std::vector<PairOp> pair_ops;       // the registered operators, in registration order
+    // the cell index of fpic_pair, one per side (species_a, species_b): pair_seg[s] = 4 + cells words (zeros, then per cell
+    // the count -> the exclusive offset -> the end of the cell's segment), pair_index[s] = the slots by cell; both grow to
+    // the largest request
+    uint32_t* pair_seg[2] = {};
+    uint32_t* pair_index[2] = {};
+    size_t pair_seg_words[2] = {}, pair_index_words[2] = {};
 };
 inline void diag_release(Diag& g)
 {
     for (Recorder& r : g.rec)
         if (r.dev) (void)hipFree(r.dev);
-    for (void* p : { g.series_req.block, g.modes_req.block, static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom), g.sel, static_cast<void*>(g.coll) })
+    for (void* p : { g.series_req.block, g.modes_req.block, static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom), g.sel, static_cast<void*>(g.coll), static_cast<void*>(g.pair),
+                     static_cast<void*>(g.pair_seg[0]), static_cast<void*>(g.pair_seg[1]), static_cast<void*>(g.pair_index[0]), static_cast<void*>(g.pair_index[1]) })
         if (p) (void)hipFree(p);
     g = Diag();
 }

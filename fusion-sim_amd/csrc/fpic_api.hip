@@ -1503,6 +1503,30 @@ int fpic_collide_clear(fpic_handle* h)
     BOX_ONLY(h, "fpic_collide_clear");
     return fes::collide_clear(h);
 }
+int fpic_pair(fpic_handle* h, const fpic_pair_spec* spec, fpic_pair_result* out)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_pair");
+    return fes::pair(h, spec, out);
+}
+int fpic_pair_register(fpic_handle* h, const fpic_pair_spec* spec, int every, int* index)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_pair_register");
+    return fes::pair_register(h, spec, every, index);
+}
+int fpic_pair_stats(fpic_handle* h, int index, int scope, fpic_pair_result* out)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_pair_stats");
+    return fes::pair_stats(h, index, scope, out);
+}
+int fpic_pair_clear(fpic_handle* h)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_pair_clear");
+    return fes::pair_clear(h);
+}
 int fpic_get_particles_of(fpic_handle* h, int species, void* pos_aos, void* vel_aos, int dtype)
 {
     CHECK_HANDLE(h);

@@ -48,6 +48,7 @@ ABI_FUNCTIONS = [
     "fpic_series_now", "fpic_series_record", "fpic_series_history",
     "fpic_modes_now", "fpic_modes_record", "fpic_modes_history",
     "fpic_select", "fpic_load", "fpic_collide", "fpic_collide_register", "fpic_collide_stats", "fpic_collide_clear",
+    "fpic_pair", "fpic_pair_register", "fpic_pair_stats", "fpic_pair_clear",
 ]
 
 
@@ -407,6 +408,61 @@ def _collide_counts(r):
     return {"applications": int(r.applications), "candidates": int(r.candidates), "collided": int(r.collided), "clipped": int(r.clipped)}
 
 
+PAIR_MAX_OPS = 8
+PAIR_CELL_MAX = 2048
+PAIR_SEED = 0x7A1C12ABE
+
+
+class PairSpec(ctypes.Structure):
+    """mirror of fpic_pair_spec (include/fusionpic.h)"""
+    _fields_ = [
+        ("species_a", ctypes.c_int32), ("species_b", ctypes.c_int32), ("seed", ctypes.c_uint64), ("stream", ctypes.c_uint32), ("epoch", ctypes.c_uint32),
+        ("log_lambda", ctypes.c_double), ("tau", ctypes.c_double), ("reserved", ctypes.c_double * 4),
+    ]
+
+
+class PairResult(ctypes.Structure):
+    """mirror of fpic_pair_result"""
+    _fields_ = [("applications", ctypes.c_uint64), ("pairs", ctypes.c_uint64), ("strong", ctypes.c_uint64), ("cells", ctypes.c_uint64),
+                ("overfull_cells", ctypes.c_uint64), ("overfull_particles", ctypes.c_uint64)]
+
+
+def _pair_spec(tau_default, a=0, b=None, log_lambda=None, tau=None, seed=PAIR_SEED, stream=0, epoch=0):
+    """PairSpec of a binary collision request: species a with species b (None: a with itself), the Coulomb logarithm, the
+    time tau (s) one application stands for (None: tau_default).  Only what the structure cannot carry is refused here; the
+    library checks the rest."""
+    s = PairSpec()
+
+    def whole(name, v, bits, signed=False):
+        lo_, hi_ = (-(1 << bits - 1), 1 << bits - 1) if signed else (0, 1 << bits)
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo_ <= int(v) < hi_:
+            raise FusionPicError(-1, ".%s <- must be %s %d-bit integer" % (name, "a signed" if signed else "an unsigned", bits))
+        return int(v)
+
+    def real(name, v):
+        if v is None:
+            raise FusionPicError(-1, ".%s <- Non-optional property is undefined!" % name)
+        try:
+            return float(v)
+        except (TypeError, ValueError):
+            raise FusionPicError(-1, ".%s <- must be a number" % name)
+
+    s.species_a = whole("species_a", a, 32, signed=True)
+    s.species_b = s.species_a if b is None else whole("species_b", b, 32, signed=True)
+    s.seed, s.stream, s.epoch = whole("seed", seed, 64), whole("stream", stream, 32), whole("epoch", epoch, 32)
+    s.log_lambda = real("log_lambda", log_lambda)
+    s.tau = real("tau", tau_default if tau is None else tau)
+    return s
+
+
+_PAIR_DECOMPOSED = ("%s needs an undecomposed handle: between two migrations the particles of a cell can sit on two ranks (in the "
+                    "ghost planes), so a rank cannot pair a cell alone")
+
+
+def _pair_counts(r):
+    return {k: int(getattr(r, k)) for k in ("applications", "pairs", "strong", "cells", "overfull_cells", "overfull_particles")}
+
+
 SERIES_MAX_POINTS = 4096
 SERIES_MAX_TRACERS = 65536
 # the columns of a point row and of a tracer row (fpic_series_*): 8 doubles each
@@ -647,6 +703,10 @@ def load_library(path=None):
     lib.fpic_collide_register.argtypes = [vp, ctypes.POINTER(CollideSpec), ci, ctypes.POINTER(ctypes.c_int)]
     lib.fpic_collide_stats.argtypes = [vp, ci, ci, ctypes.POINTER(CollideResult)]
     lib.fpic_collide_clear.argtypes = [vp]
+    lib.fpic_pair.argtypes = [vp, ctypes.POINTER(PairSpec), ctypes.POINTER(PairResult)]
+    lib.fpic_pair_register.argtypes = [vp, ctypes.POINTER(PairSpec), ci, ctypes.POINTER(ctypes.c_int)]
+    lib.fpic_pair_stats.argtypes = [vp, ci, ci, ctypes.POINTER(PairResult)]
+    lib.fpic_pair_clear.argtypes = [vp]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -986,6 +1046,42 @@ class CylindricalParticlePusher:
         """drops every registered collision operator (fpic_collide_clear)"""
         self._check(self._lib.fpic_collide_clear(self._h))
 
+    # ---- binary Coulomb collisions between the species of the box (fpic_pair*)
+    def collidePair(self, a=0, b=None, **request):
+        """One application, now, of the Takizuka-Abe binary Coulomb collision operator between species a and species b of a
+        CART3D box (b None or b == a: like-particle collisions; fpic_pair; an (r,z) handle and a decomposed handle are
+        refused).  The particles of every grid cell are paired at random and every pair is scattered by a small random
+        angle; momentum and energy of a pair are conserved.  log_lambda: the Coulomb logarithm; tau (s, default the sub-step
+        dt): the time the application stands for; seed, stream, epoch: the counter of the random words.  Returns
+        {applications, pairs, strong, cells, overfull_cells, overfull_particles}: strong counts the pairs whose variance
+        exceeded 1 (tau too long for small-angle theory), overfull_* the cells above PAIR_CELL_MAX particles of a species,
+        which are not collided."""
+        s = _pair_spec(float(self.spec["dt"]), a, b, **request)
+        out = PairResult()
+        self._check(self._lib.fpic_pair(self._h, ctypes.byref(s), ctypes.byref(out)))
+        return _pair_counts(out)
+
+    def collidePairEvery(self, every, a=0, b=None, **request):
+        """Registers a binary collision operator (see collidePair) to run at the end of every `every`-th sub-step, after the
+        operators of collideEvery and before the recorders, with epoch = the sub-step number + `epoch`; tau defaults to
+        every * dt.  Returns the operator's index (fpic_pair_register)."""
+        if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or not -(1 << 31) <= int(every) < 1 << 31:
+            raise FusionPicError(-1, ".every <- must be a signed 32-bit integer")
+        s = _pair_spec(int(every) * float(self.spec["dt"]), a, b, **request)
+        index = ctypes.c_int(-1)
+        self._check(self._lib.fpic_pair_register(self._h, ctypes.byref(s), int(every), ctypes.byref(index)))
+        return index.value
+
+    def pairStats(self, index, scope="global"):
+        """the totals of a registered binary collision operator since its registration (fpic_pair_stats)"""
+        out = PairResult()
+        self._check(self._lib.fpic_pair_stats(self._h, int(index), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope], ctypes.byref(out)))
+        return _pair_counts(out)
+
+    def clearPairs(self):
+        """drops every registered binary collision operator (fpic_pair_clear); those of collideEvery stay"""
+        self._check(self._lib.fpic_pair_clear(self._h))
+
     # ---- series: the field at points and the state of tracer particles as rows (fpic_series_*)
     def series(self, points=None, tracers=None, species=0, scope="global"):
         """The rows of the current state of a CART3D box (fpic_series_now; an (r,z) handle is refused).  points: positions in
@@ -1286,6 +1382,10 @@ class ElectrostaticBoxPusher:
     collideEvery = CylindricalParticlePusher.collideEvery
     collisionStats = CylindricalParticlePusher.collisionStats
     clearCollisions = CylindricalParticlePusher.clearCollisions
+    collidePair = CylindricalParticlePusher.collidePair
+    collidePairEvery = CylindricalParticlePusher.collidePairEvery
+    pairStats = CylindricalParticlePusher.pairStats
+    clearPairs = CylindricalParticlePusher.clearPairs
     count = CylindricalParticlePusher.count
     series = CylindricalParticlePusher.series
     recordSeries = CylindricalParticlePusher.recordSeries
@@ -1391,6 +1491,23 @@ class BoxGroup:
     def clearCollisions(self):
         for m in self.sims:
             m.clearCollisions()
+
+    def collidePair(self, a=0, b=None, **request):
+        """refused (FPIC_ERR_STATE), as by every member: between two migrations the particles of a cell can sit on two
+        ranks, in the ghost planes, so a rank cannot pair a cell alone"""
+        raise FusionPicError(-5, _PAIR_DECOMPOSED % "collidePair")
+
+    def collidePairEvery(self, every, a=0, b=None, **request):
+        """refused, see collidePair"""
+        raise FusionPicError(-5, _PAIR_DECOMPOSED % "collidePairEvery")
+
+    def pairStats(self, index):
+        """refused, see collidePair"""
+        raise FusionPicError(-5, _PAIR_DECOMPOSED % "pairStats")
+
+    def clearPairs(self):
+        """refused, see collidePair"""
+        raise FusionPicError(-5, _PAIR_DECOMPOSED % "clearPairs")
 
     def count(self, where=None, species=0, every=None):
         """the whole box: the members' LOCAL counts (each its own particles) added up"""

@@ -377,6 +377,49 @@ function makeBox(spec, lib) {
         return lib.collisionStats(h, index, scopeOf(scope));
     };
     out.clearCollisions = function () { lib.clearCollisions(h); };
+    // binary Coulomb collisions between the species of the box (Takizuka-Abe; fpic_pair*).  request = { a, b (default a: like
+    // particles), logLambda, tau (s; default the sub-step dt, every * dt for collidePairEvery), seed (an integer up to 2^53 or a
+    // BigInt up to 2^64), stream, epoch }.  collidePair -> { applications, pairs, strong, cells, overfullCells,
+    // overfullParticles }; collidePairEvery(every, request) -> the operator's index; pairStats(index, scope) -> its totals
+    // since registration; clearPairs() drops every pair operator (those of collideEvery stay)
+    const pairArgs = function (request, tauDefault) {
+        if (request === null || typeof request !== 'object') throw new TypeError('.request <- expected { a, b, logLambda, tau, ... }');
+        const whole = function (name, v, dflt, least, most) {
+            if (v === undefined || v === null) v = dflt;
+            if (!Number.isInteger(v) || v < least || v > most) throw new RangeError('.' + name + ' <- expected an integer within its field');
+            return v;
+        };
+        const real = function (name, v, dflt) {
+            if (v === undefined || v === null) v = dflt;
+            if (typeof v !== 'number') throw new RangeError('.' + name + ' <- expected a number');
+            return v;
+        };
+        const given = (v) => v !== undefined && v !== null;
+        let seed = given(request.seed) ? request.seed : 0x7A1C12ABE;
+        if (typeof seed === 'number') {
+            if (!Number.isInteger(seed) || seed < 0 || seed > Number.MAX_SAFE_INTEGER) throw new RangeError('.seed <- expected an integer up to 2^53, or a BigInt up to 2^64');
+            seed = BigInt(seed);
+        }
+        if (typeof seed !== 'bigint' || seed < 0n || seed >= (1n << 64n)) throw new RangeError('.seed <- expected an integer up to 2^53, or a BigInt up to 2^64');
+        const a = whole('a', request.a, 0, -0x80000000, 0x7fffffff);
+        const words = [a, whole('b', request.b, a, -0x80000000, 0x7fffffff), Number(seed & 0xffffffffn), Number(seed >> 32n),
+            whole('stream', request.stream, 0, 0, 0xffffffff), whole('epoch', request.epoch, 0, 0, 0xffffffff)];
+        return [Float64Array.from(words), Float64Array.from([real('logLambda', request.logLambda, undefined), real('tau', request.tau, tauDefault)])];
+    };
+    out.collidePair = function (request) {
+        const a = pairArgs(request, spec.dt);
+        return lib.collidePair(h, a[0], a[1]);
+    };
+    out.collidePairEvery = function (every, request) {
+        if (!Number.isInteger(every) || every < -0x80000000 || every > 0x7fffffff) throw new RangeError('.every <- expected a 32-bit integer');
+        const a = pairArgs(request, every * spec.dt);
+        return lib.collidePairEvery(h, a[0], a[1], every);
+    };
+    out.pairStats = function (index, scope) {
+        if (!Number.isInteger(index) || index < -0x80000000 || index > 0x7fffffff) throw new RangeError('.index <- expected a 32-bit integer');
+        return lib.pairStats(h, index, scopeOf(scope));
+    };
+    out.clearPairs = function () { lib.clearPairs(h); };
     // series (fpic_series_*): the field at points and the state of tracer particles as rows of 8 doubles, now or recorded into a
     // device ring.  request = { points: [[x, y, z], ...] in metres (wrapped periodically), tracers: particle indices, species: one
     // index or one per tracer (default 0) }; either list may be missing, not both.  A point row is Ex Ey Ez phi Bx By Bz present,

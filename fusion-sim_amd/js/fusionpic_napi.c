@@ -994,6 +994,99 @@ static napi_value n_clear_collisions(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* the request of collidePair / collidePairEvery: words: Float64Array [species_a, species_b, seed low word, seed high word,
+ * stream, epoch], reals: Float64Array [log_lambda, tau].  The arrays' lengths and the words' ranges are checked here, the
+ * request itself by the library. */
+static int get_pair_spec(napi_env env, napi_value words, napi_value reals, fpic_pair_spec* s)
+{
+    napi_typedarray_type tw, tr; void *pw, *pr; size_t lw, lr;
+    if (!get_typed(env, words, &tw, &pw, &lw) || !get_typed(env, reals, &tr, &pr, &lr)) return 0;
+    if (!pw || !pr || tw != napi_float64_array || tr != napi_float64_array) {
+        napi_throw_type_error(env, NULL, ".request <- expected two Float64Arrays");
+        return 0;
+    }
+    if (!check_len(env, "words", lw, 6) || !check_len(env, "reals", lr, 2)) return 0;
+    const double* w = (const double*)pw;
+    const double* r = (const double*)pr;
+    for (int k = 0; k < 6; ++k) {
+        const double least = k < 2 ? -2147483648.0 : 0.0, most = k < 2 ? 2147483647.0 : 4294967295.0;
+        const double mag = w[k] < 0 ? -w[k] : w[k];
+        if (!(w[k] >= least && w[k] <= most) || mag != (double)(uint64_t)mag) {
+            napi_throw_range_error(env, NULL, ".request <- a, b, seed, stream and epoch must be integers within their fields");
+            return 0;
+        }
+    }
+    memset(s, 0, sizeof *s);
+    s->species_a = (int32_t)w[0];
+    s->species_b = (int32_t)w[1];
+    s->seed = (uint64_t)(uint32_t)w[2] | (uint64_t)(uint32_t)w[3] << 32;
+    s->stream = (uint32_t)w[4];
+    s->epoch = (uint32_t)w[5];
+    s->log_lambda = r[0];
+    s->tau = r[1];
+    return 1;
+}
+
+static napi_value pair_object(napi_env env, const fpic_pair_result* c)
+{
+    napi_value o, v;
+    const char* names[6] = { "applications", "pairs", "strong", "cells", "overfullCells", "overfullParticles" };
+    const uint64_t vals[6] = { c->applications, c->pairs, c->strong, c->cells, c->overfull_cells, c->overfull_particles };
+    NAPI_OK(env, napi_create_object(env, &o));
+    for (int k = 0; k < 6; ++k) {
+        NAPI_OK(env, napi_create_double(env, (double)vals[k], &v));
+        NAPI_OK(env, napi_set_named_property(env, o, names[k], v));
+    }
+    return o;
+}
+
+/* collidePair(h, words, reals) -> { applications, pairs, strong, cells, overfullCells, overfullParticles } */
+static napi_value n_collide_pair(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3]; fpic_handle* h;
+    fpic_pair_spec s;
+    if (!get_args(env, info, 3, argv, &h) || !get_pair_spec(env, argv[1], argv[2], &s)) return NULL;
+    fpic_pair_result c;
+    memset(&c, 0, sizeof c);
+    if (fpic_pair(h, &s, &c) != FPIC_OK) return throw_fpic(env, h);
+    return pair_object(env, &c);
+}
+
+/* collidePairEvery(h, words, reals, every) -> the operator's index */
+static napi_value n_collide_pair_every(napi_env env, napi_callback_info info)
+{
+    napi_value argv[4]; fpic_handle* h; double every;
+    fpic_pair_spec s;
+    if (!get_args(env, info, 4, argv, &h) || !get_pair_spec(env, argv[1], argv[2], &s) || !get_double(env, argv[3], &every)) return NULL;
+    if (!(every >= -2147483648.0 && every <= 2147483647.0) || every != (double)(int)every) { napi_throw_range_error(env, NULL, ".every <- must be a 32-bit integer"); return NULL; }
+    int index = -1;
+    if (fpic_pair_register(h, &s, (int)every, &index) != FPIC_OK) return throw_fpic(env, h);
+    napi_value v;
+    NAPI_OK(env, napi_create_int32(env, index, &v));
+    return v;
+}
+
+/* pairStats(h, index, scope) -> the totals of a registered operator */
+static napi_value n_pair_stats(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3]; fpic_handle* h; double index; int scope;
+    if (!get_args(env, info, 3, argv, &h) || !get_double(env, argv[1], &index) || !get_scope(env, argv[2], &scope)) return NULL;
+    if (!(index >= -2147483648.0 && index <= 2147483647.0) || index != (double)(int)index) { napi_throw_range_error(env, NULL, ".index <- must be a 32-bit integer"); return NULL; }
+    fpic_pair_result c;
+    memset(&c, 0, sizeof c);
+    if (fpic_pair_stats(h, (int)index, scope, &c) != FPIC_OK) return throw_fpic(env, h);
+    return pair_object(env, &c);
+}
+
+/* clearPairs(h) */
+static napi_value n_clear_pairs(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1]; fpic_handle* h;
+    if (!get_args(env, info, 1, argv, &h)) return NULL;
+    if (fpic_pair_clear(h) != FPIC_OK) return throw_fpic(env, h);
+    return undefined(env);
+}
+
 /* select(h, species, axes: Int32Array, ranges: Float64Array (lo, hi per term), idMod, idRem, capacity, dtype (0: Float32Array,
  * 1: Float64Array), scope) -> { ids: Uint32Array, position, velocity, matched }.  capacity < 0: the count query first, then a
  * call with room for exactly that many rows; capacity 0: the count query alone.  The three arrays are null when `matched`
@@ -1274,7 +1367,8 @@ static napi_value init(napi_env env, napi_value exports)
         { "domainInit", n_domain_init }, { "domainSetParticles", n_domain_set_particles }, { "domainGetParticles", n_domain_get_particles },
         { "domainStats", n_domain_stats },
         { "energy", n_energy }, { "recordEnergy", n_record_energy }, { "energyHistory", n_energy_history },
-        { "histogram", n_histogram }, { "select", n_select }, { "load", n_load }, { "collide", n_collide }, { "collideEvery", n_collide_every }, { "collisionStats", n_collision_stats }, { "clearCollisions", n_clear_collisions }, { "moments", n_moments },
+        { "histogram", n_histogram }, { "select", n_select }, { "load", n_load }, { "collide", n_collide }, { "collideEvery", n_collide_every }, { "collisionStats", n_collision_stats }, { "clearCollisions", n_clear_collisions },
+        { "collidePair", n_collide_pair }, { "collidePairEvery", n_collide_pair_every }, { "pairStats", n_pair_stats }, { "clearPairs", n_clear_pairs }, { "moments", n_moments },
         { "series", n_series }, { "recordSeries", n_record_series }, { "seriesHistory", n_series_history },
         { "modes", n_modes }, { "recordModes", n_record_modes }, { "modesHistory", n_modes_history },
     };

@@ -812,6 +812,70 @@ int fpic_collide_register(fpic_handle* h, const fpic_collide_spec* spec, int eve
 int fpic_collide_stats(fpic_handle* h, int index, int scope, fpic_collide_result* out);
 int fpic_collide_clear(fpic_handle* h);
 
+/* ---- CART3D binary Coulomb collisions between the species of the box (Takizuka & Abe 1977): species_a with species_b,
+ * species_a == species_b for like-particle collisions.  The particles of a grid cell are paired at random and every pair is
+ * scattered by a small random angle; the operator acts on the stored velocities (under full EM the half-time velocity), as
+ * a call or registered to run after every k-th sub-step.  The result depends on the request, the epoch, the particles'
+ * ids, their cells and their stored velocities alone — not on the slots, the binning or the order the kernels visit
+ * anything in.  All arithmetic is double, every operation rounded once; a stored velocity is converted to double, and
+ * AFTER EVERY PAIR both velocities are cast back to the handle's precision: a particle's next pair starts from the cast
+ * value.  Velocities are in units of c.
+ *   cell       the charge deposit's cell (i, j, k) of the stored position, evaluated in the handle's precision as the
+ *              deposit and fpic_moments do.
+ *   words      P(b) = Philox4x32-10(counter (id, epoch, stream, 0xC0120 + b), key (seed lo, seed hi)), the loader's
+ *              generator.
+ *   order      the particles of one species in a cell are sorted ascending by (P(0)[0] of their own id, id).
+ *   numbers    m_ab = m_a m_b / (m_a + m_b); kappa = (q_a q_b)^2 log_lambda tau W / (8 pi eps0^2 m_ab^2 c^3 dV), dV the
+ *              cell volume as in the charge density's scale, W the macro weight, eps0 and c the constants of the box
+ *              (8.8541878128e-12, 2.998e8); the mass factors m_ab / m_a and m_ab / m_b.
+ *   unlike     Nm >= Nf the two counts in the cell, `many` the species with more particles (a tie: species_a).  Nf = 0:
+ *              nothing.  many[j] pairs with few[j mod Nf]; a few particle takes its partners in ascending j; the owner of a
+ *              pair is the many particle; N_L = Nf.
+ *   like       N particles s[0 .. N).  N < 2: nothing.  N even: the pairs (s[2t], s[2t+1]), the owner the first member,
+ *              N_L = N.  N odd: (s0,s1), (s1,s2), (s2,s0) in that order, each owner the first member, with N_L = N / 2
+ *              (a double: half the variance), then the pairs (s[3+2t], s[4+2t]) with N_L = N.
+ *   one pair   (owner o, partner p) u = v_o - v_p; up = sqrt(ux ux + uy uy); g = sqrt((ux ux + uy uy) + uz uz).  g == 0: the
+ *              pair is unchanged and not counted.  var = (kappa N_L) / ((g g) g); var > 1 is also counted as `strong` (tau is
+ *              too long for small-angle theory; the pair is still collided).  delta = sqrt(var) n0, n0 the first normal of
+ *              the loader's Box-Muller formulas on P(1) of o.  d2 = delta delta; sinT = (2 delta) / (1 + d2);
+ *              omc = (2 d2) / (1 + d2); phi = P(0)[1] of o 2^-32; cs = cospi(2 phi), sn = sinpi(2 phi).  With up > 0,
+ *              ex = ux / up, ey = uy / up:
+ *                  dux = ((((ex uz) sinT) cs) - (((ey g) sinT) sn)) - ux omc
+ *                  duy = ((((ey uz) sinT) cs) + (((ex g) sinT) sn)) - uy omc
+ *                  duz = (-((up sinT) cs)) - uz omc
+ *              with up == 0: du = ((g sinT) cs, (g sinT) sn, -(g omc)).
+ *              v_o' = v_o + (m_ab / m_o) du; v_p' = v_p - (m_ab / m_p) du.
+ * A cell holding more than FPIC_PAIR_CELL_MAX particles of either species is not collided: it is counted in overfull_cells
+ * and its particles (both species) in overfull_particles, and every one of them keeps its bits.  Positions are never
+ * written: the fields stay valid, the bin tables and the census stay as they are, fpic_precalc is not needed.
+ * fpic_pair applies the request now (synchronous) and returns its counts: applications = 1, pairs (the pairs with g != 0),
+ * strong, cells (the cells that had a pair to collide), overfull_cells, overfull_particles.  fpic_pair_register makes it
+ * run at the end of every sub-step whose number (counted since create) is a multiple of `every`, after the operators of
+ * fpic_collide_register and before the recorders take their rows, in registration order, with epoch
+ * (uint32)(sub-step + spec.epoch).  At most FPIC_PAIR_MAX_OPS operators; *index names the operator.  Nothing is
+ * synchronised: the counts accumulate on the device and fpic_pair_stats reads the totals since registration.
+ * fpic_pair_clear drops every registered pair operator (those of fpic_collide_register stay).  Registrations are not part
+ * of a checkpoint.
+ * Refused (FPIC_ERR_INVALID_ARG): a null spec, a species the handle does not have, a NaN anywhere, log_lambda or tau not
+ * (> 0 and finite), a reserved word that is not zero, every < 1, a ninth registration, an index outside the registered
+ * operators; FPIC_ERR_STATE: a handle that is not CART3D, and a handle with a domain decomposition (between two migrations
+ * the particles of a cell can sit on two ranks, in the ghost planes: a rank cannot pair a cell alone). */
+#define FPIC_PAIR_MAX_OPS  8
+#define FPIC_PAIR_CELL_MAX 2048
+typedef struct fpic_pair_spec {
+    int32_t  species_a, species_b;
+    uint64_t seed;
+    uint32_t stream, epoch;
+    double   log_lambda;           /* the Coulomb logarithm, > 0 and finite */
+    double   tau;                  /* s: the time one application stands for, > 0 and finite */
+    double   reserved[4];          /* zero */
+} fpic_pair_spec;
+typedef struct fpic_pair_result { uint64_t applications, pairs, strong, cells, overfull_cells, overfull_particles; } fpic_pair_result;
+int fpic_pair(fpic_handle* h, const fpic_pair_spec* spec, fpic_pair_result* out);
+int fpic_pair_register(fpic_handle* h, const fpic_pair_spec* spec, int every, int* index);
+int fpic_pair_stats(fpic_handle* h, int index, int scope, fpic_pair_result* out);
+int fpic_pair_clear(fpic_handle* h);
+
 int fpic_sync(fpic_handle* h);
 int fpic_profile(fpic_handle* h, int enable);
 int fpic_get_stats(fpic_handle* h, fpic_stats* out);

@@ -1,0 +1,446 @@
+"""The binary Coulomb collision operator (fpic_pair*) on the GPU against the numpy restatement of its rule
+(tests/pair_reference.py, proved on the CPU by tests/test_pair_reference.py) on the scenes of tests/pair_scene.py: who changed
+and every count exactly, the values, independence of the slots, conservation, overfull cells, the registered form against a
+manual loop, the refusals and the JavaScript host.
+
+The bound of the values (fp64).  The rule's rounded functions are the loader's — the first Box-Muller normal and cospi / sinpi
+of the device's maths library, measured against 50-digit values at 2.29 float64 ulps (tests/test_gpu_load.py).  Four times
+that bounds the kernel, and the reference's own deviation (REF_ULPS) is added because the comparison is with the reference:
+ULPS = 4 x 2.29 + 4.  test_pair_reference.value_bound propagates that many ulps through the rule and adds one rounding per
+operation.  A particle that took part in several pairs (a chain of the unlike pairing, the triple of an odd cell) gets the
+sum of its pairs' bounds times AMPLIFICATION = 0.16: on these scenes the double reference moves by 0.038 of that sum when its
+rounded functions are replaced by correctly rounded ones (tests/test_pair_reference.py), and 4 x 0.038 = 0.16 (a sum of
+worst-case bounds overstates a chain, whose errors do not all line up).
+In fp32 a single-stage particle is bit-equal to the reference cast to float; of the chains and triples at most a share of
+1e-3 may differ (a condition: the reference against its 50-digit twin differs in none of the 3978 particles of the scenes).
+Met on an MI355X (fp64, largest |dv| / bound): like species 0.26 single-stage, 0.41 triples; unlike species 0.33 / 0.62
+(electrons), 0.52 / 0.13 (protons); the overfull scene 0.29.  fp32: no stored value that is not bit-equal to the reference."""
+import hashlib
+import json
+import os
+import re
+import shutil
+import subprocess
+
+import numpy as np
+import pytest
+
+import pair_reference as ref
+import pair_scene as scene
+from helpers import ROOT
+from test_gpu_histogram import PRECISIONS, box_spec, em_dt
+from test_pair_reference import AMPLIFICATION, FP32_SHARE, REF_ULPS, value_bound
+
+pytestmark = pytest.mark.gpu
+
+KERNEL_ULPS_MEASURED = 2.29    # the loader's device functions (tests/test_gpu_load.py)
+ULPS = 4 * KERNEL_ULPS_MEASURED + REF_ULPS
+DTYPE = {"fp32": np.float32, "fp64": np.float64}
+SEEDS = dict(seed=0xC0FFEE0123456789, stream=5, epoch=3)
+C = ref.C
+
+
+@pytest.fixture(scope="module")
+def fp():
+    import fusionpic
+    fusionpic.load_library()
+    return fusionpic
+
+
+def cell_max():
+    """kPairCellMax of the kernel header"""
+    text = open(os.path.join(ROOT, "fusion-sim_amd", "csrc", "fes_pair_kernels.hpp")).read()
+    return int(re.search(r"constexpr\s+int\s+kPairCellMax\s*=\s*(\d+)\s*;", text).group(1))
+
+
+def bits(a, b):
+    return a.dtype == b.dtype and a.shape == b.shape and a.tobytes() == b.tobytes()
+
+
+def box(fp, precision, n, W, dt=5e-12, solver="none", ions=0, **kw):
+    spec = box_spec(scene.SHAPE, scene.L, n, dt, solver=solver, macro_weight=W, particle_mass=scene.ME, particle_charge=scene.QE, **kw)
+    sim = fp.makeCylindricalParticlePusher(spec, precision=precision)
+    if ions:
+        assert sim.addSpecies(scene.MP, -scene.QE, ions) == 1
+    return sim
+
+
+def like_box(fp, precision, **kw):
+    s = scene.like_scene()
+    sim = box(fp, precision, len(s["pos"]), s["W"], **kw)
+    sim.set(position=s["pos"], velocity=s["vel"])
+    return sim
+
+
+def unlike_box(fp, precision, **kw):
+    s = scene.unlike_scene()
+    sim = box(fp, precision, len(s["pos_a"]), s["W"], ions=len(s["pos_b"]), **kw)
+    sim.set(position=s["pos_a"], velocity=s["vel_a"])
+    sim.set(position=s["pos_b"], velocity=s["vel_b"], species=1)
+    return sim
+
+
+def request(like, W, tau=scene.TAU, **seeds):
+    mb, qb = (scene.ME, scene.QE) if like else (scene.MP, -scene.QE)
+    return ref.request(scene.LOG_LAMBDA, tau, scene.ME, scene.QE, mb, qb, W, scene.DV, like=like, **dict(SEEDS, **seeds))
+
+
+_want = {}
+
+
+def wanted(like, precision):
+    """the reference's result on the scene, computed once per (scene, precision)"""
+    key = (like, precision)
+    if key not in _want:
+        if like:
+            s = scene.like_scene()
+            out = ref.apply(request(True, s["W"]), scene.cell_index(s["pos"]), np.arange(len(s["pos"])), s["vel"].astype(DTYPE[precision]))
+        else:
+            s = scene.unlike_scene()
+            out = ref.apply(request(False, s["W"]), scene.cell_index(s["pos_a"]), np.arange(len(s["pos_a"])), s["vel_a"].astype(DTYPE[precision]),
+                            scene.cell_index(s["pos_b"]), np.arange(len(s["pos_b"])), s["vel_b"].astype(DTYPE[precision]))
+        _want[key] = out
+    return _want[key]
+
+
+def counts_of(out, applications=1):
+    return dict(applications=applications, **{k: int(out[k]) for k in ("pairs", "strong", "cells", "overfull_cells", "overfull_particles")})
+
+
+def check_values(precision, got, before, out, side):
+    """who changed exactly, and the values within the bound of the module's docstring"""
+    want = out["v" + side]
+    changed, expected = (got != before).any(axis=1), (want != before).any(axis=1)
+    assert np.array_equal(changed, expected), (precision, side)
+    assert bits(got[~changed], before[~changed])
+    stages = out["stages_" + side]
+    assert np.array_equal(stages > 0, expected)                      # (on these scenes every counted pair moves both members)
+    if precision == "fp64":
+        bound = value_bound(out, ULPS, side, AMPLIFICATION)
+        share = np.abs(got - want) / np.maximum(bound, np.finfo(np.float64).tiny)
+        print("%s species %s: largest |dv| / bound: single-stage %.3f, chains and triples %.3f" %
+              (precision, side, share[stages == 1].max() if (stages == 1).any() else 0, share[stages > 1].max() if (stages > 1).any() else 0))
+        assert np.all(np.abs(got - want) <= bound)
+    else:
+        differs = (got != want).any(axis=1)
+        print("%s species %s: %d of %d particles are not bit-equal to the reference (%d of them single-stage)" %
+              (precision, side, differs.sum(), len(differs), (differs & (stages == 1)).sum()))
+        assert not (differs & (stages <= 1)).any()
+        assert differs.sum() <= FP32_SHARE * len(differs)
+    return changed
+
+
+# ---- 1. who changed and every count exactly; the values
+def test_like_species_cells(fp):
+    sets = {}
+    for precision in PRECISIONS:
+        out = wanted(True, precision)
+        assert out["cells"] == sum(1 for n in scene.LIKE_COUNTS if n >= 2) and out["strong"] > 0 and out["overfull_cells"] == 0
+        assert out["pairs"] == sum(n // 2 + (2 if n % 2 and n > 1 else 0) for n in scene.LIKE_COUNTS)
+        sim = like_box(fp, precision)
+        before = sim.getParticles()
+        got = sim.collidePair(0, log_lambda=scene.LOG_LAMBDA, tau=scene.TAU, **SEEDS)
+        after = sim.getParticles()
+        sim.destroy()
+        print("like species %s: %s" % (precision, got))
+        assert got == counts_of(out)
+        assert bits(after["position"], before["position"])
+        sets[precision] = check_values(precision, after["velocity"], before["velocity"], out, "a")
+    assert np.array_equal(sets["fp32"], sets["fp64"])
+
+
+def test_unlike_species_cells(fp):
+    sets = {}
+    for precision in PRECISIONS:
+        out = wanted(False, precision)
+        assert out["cells"] == sum(1 for a, b in scene.UNLIKE_COUNTS if min(a, b) > 0) and out["overfull_cells"] == 0
+        assert out["pairs"] == sum(max(a, b) for a, b in scene.UNLIKE_COUNTS if min(a, b) > 0)
+        assert out["stages_b"].max() > 10 and out["stages_a"].max() > 10    # each species is the `few` one of a long chain somewhere
+        sim = unlike_box(fp, precision)
+        before = [sim.getParticles(species=k) for k in range(2)]
+        got = sim.collidePair(0, 1, log_lambda=scene.LOG_LAMBDA, tau=scene.TAU, **SEEDS)
+        after = [sim.getParticles(species=k) for k in range(2)]
+        # the same request with the species exchanged: a tie now goes to the protons, so only the counts must agree
+        swapped = sim.collidePair(1, 0, log_lambda=scene.LOG_LAMBDA, tau=scene.TAU, **dict(SEEDS, epoch=4))
+        sim.destroy()
+        print("unlike species %s: %s" % (precision, got))
+        assert got == counts_of(out)
+        assert (swapped["pairs"], swapped["cells"]) == (got["pairs"], got["cells"])
+        sets[precision] = []
+        for k, side in enumerate("ab"):
+            assert bits(after[k]["position"], before[k]["position"])
+            sets[precision].append(check_values(precision, after[k]["velocity"], before[k]["velocity"], out, side))
+    for k in range(2):
+        assert np.array_equal(sets["fp32"][k], sets["fp64"][k])
+
+
+# ---- 2. independence of the slots: no tolerance
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_slot_independence(fp, precision):
+    kw = dict(log_lambda=scene.LOG_LAMBDA, tau=scene.TAU, **SEEDS)
+    # a: sorted into tiles, then pushed for some sub-steps with no field and a time step at which a thermal electron crosses
+    # half a cell per sub-step: particles leave their cells and their tiles (the planes 7 | 8) and sit in the slots of tiles
+    # they have left, which is what the pass's own cell index is for; then collided
+    a = unlike_box(fp, precision, dt=2e-7)
+    a.precalc()
+    a.sort()
+    a.substeps(3)
+    start = [a.getParticles(species=k) for k in range(2)]
+    s = scene.unlike_scene()
+    metres = [p["position"] * DTYPE[precision](scene.L[0]) for p in start]          # (read back as fractions of the box; times 16: exact)
+    moved = scene.cell_index(metres[0].astype(np.float64)) != scene.cell_index(s["pos_a"])
+    tile = lambda pos: (np.floor(np.asarray(pos, dtype=np.float64)).astype(np.int64) >> 3)
+    left_tile = (tile(metres[0]) != tile(s["pos_a"])).any(axis=1)
+    assert moved.mean() > 0.3 and left_tile.sum() > 10
+    counts_a = [a.collidePair(0, 1, **kw), a.collidePair(0, **dict(kw, epoch=9)), a.collidePair(1, **dict(kw, epoch=10))]
+    end_a = [a.getParticles(species=k) for k in range(2)]
+    a.destroy()
+    # b: the same particles uploaded in the caller's order (slot = id) into a fresh handle
+    b = box(fp, precision, len(s["pos_a"]), s["W"], ions=len(s["pos_b"]), dt=2e-7)
+    for k in range(2):
+        b.set(position=metres[k], velocity=start[k]["velocity"], species=k)
+    counts_b = [b.collidePair(0, 1, **kw), b.collidePair(0, **dict(kw, epoch=9)), b.collidePair(1, **dict(kw, epoch=10))]
+    end_b = [b.getParticles(species=k) for k in range(2)]
+    # the same epoch once more on what is now another state: other bytes; and another epoch on a copy of the start: another pairing
+    b.destroy()
+    assert counts_a == counts_b and counts_a[0]["pairs"] > 0 and counts_a[1]["pairs"] > 0 and counts_a[2]["pairs"] > 0
+    for k in range(2):
+        assert bits(end_a[k]["velocity"], end_b[k]["velocity"]) and bits(end_a[k]["position"], end_b[k]["position"])
+        assert (end_a[k]["velocity"] != start[k]["velocity"]).any()
+    c = box(fp, precision, len(s["pos_a"]), s["W"], ions=len(s["pos_b"]), dt=2e-7)
+    for k in range(2):
+        c.set(position=metres[k], velocity=start[k]["velocity"], species=k)
+    c.collidePair(0, 1, **dict(kw, epoch=77))
+    assert not bits(c.getParticles()["velocity"], end_b[0]["velocity"])
+    c.destroy()
+
+
+# ---- 3. conservation on the device
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_momentum_and_energy_are_conserved(fp, precision):
+    """energy() before and after: the total momentum and the total kinetic energy of the two species.  A pair conserves both
+    in exact arithmetic; what is lost is the cast of both members to the stored type after every pair, half an ulp of the
+    component each (the double roundings of the rule are below that even in fp64: 8 of them).  So per component
+    |dP| <= pairs 2 x 4.5 eps_T max |m v| W c, and |dE| <= pairs 2 x 4.5 eps_T 3 max |m v v| W c^2, plus the reduction's own
+    rounding, N 2^-53 of the sums of magnitudes (max |m v| and max |m v v| over both species)."""
+    s = scene.unlike_scene()
+    sim = unlike_box(fp, precision)
+    e0 = sim.energy()
+    got = [sim.collidePair(0, 1, log_lambda=scene.LOG_LAMBDA, tau=scene.TAU, **SEEDS), sim.collidePair(0, log_lambda=scene.LOG_LAMBDA, tau=scene.TAU, **SEEDS),
+           sim.collidePair(1, log_lambda=scene.LOG_LAMBDA, tau=scene.TAU, **SEEDS)]
+    e1 = sim.energy()
+    after = [sim.getParticles(species=k) for k in range(2)]
+    sim.destroy()
+    pairs = sum(g["pairs"] for g in got)
+    assert pairs > 500
+    eps = float(np.finfo(DTYPE[precision]).eps)
+    vmax = [1.5 * float(np.abs(a["velocity"]).max()) for a in after]     # (1.5: a chain's intermediate values)
+    n = len(s["pos_a"]) + len(s["pos_b"])
+    mv = max(scene.ME * vmax[0], scene.MP * vmax[1])
+    mvv = max(scene.ME * vmax[0] ** 2, scene.MP * vmax[1] ** 2)
+    p_bound = pairs * 9 * eps * mv * s["W"] * C + n * 2.0 ** -53 * n * mv * s["W"] * C
+    e_bound = pairs * 27 * eps * mvv * s["W"] * C * C + n * 2.0 ** -53 * n * mvv * s["W"] * C * C
+    dp = np.abs(e1["momentum"].sum(axis=0) - e0["momentum"].sum(axis=0))
+    de = abs(e1["kinetic"].sum() - e0["kinetic"].sum())
+    print("%s: |dP| / bound %s, |dE| / bound %.3g" % (precision, dp / p_bound, de / e_bound))
+    assert np.all(dp <= p_bound) and de <= e_bound
+    assert all((a["velocity"] != v.astype(DTYPE[precision])).any(axis=1).mean() > 0.9 for a, v in zip(after, (s["vel_a"], s["vel_b"])))
+
+
+# ---- 4. overfull cells
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_an_overfull_cell_is_reported_and_left_alone(fp, precision):
+    cap = cell_max()
+    assert cap >= 2048 and cap == fp.PAIR_CELL_MAX
+    cells = [(8, 8, 7), (9, 8, 7), (7, 8, 7), (15, 15, 15)]
+    counts = [cap + 1, cap, 10, 7]
+    pos, vel = scene.populate(counts, 41, 0.01, cells)
+    W = scene.weight(cap, 0.01)
+    sim = box(fp, precision, len(pos), W)
+    sim.set(position=pos, velocity=vel)
+    before = sim.getParticles()
+    got = sim.collidePair(0, log_lambda=scene.LOG_LAMBDA, tau=scene.TAU, **SEEDS)
+    after = sim.getParticles()
+    sim.destroy()
+    out = ref.apply(request(True, W), scene.cell_index(pos), np.arange(len(pos)), vel.astype(DTYPE[precision]), cell_max=cap)
+    assert got == counts_of(out) and got["overfull_cells"] == 1 and got["overfull_particles"] == cap + 1 and got["cells"] == 3
+    inside = scene.cell_index(pos) == scene.cell_index(np.array([[8.5, 8.5, 7.5]]))[0]
+    assert inside.sum() == cap + 1 and bits(after["velocity"][inside], before["velocity"][inside])
+    check_values(precision, after["velocity"], before["velocity"], out, "a")
+    assert (after["velocity"][~inside] != before["velocity"][~inside]).any(axis=1).sum() == len(pos) - cap - 1
+
+
+# ---- 5. the registered form equals the manual loop
+@pytest.mark.parametrize("solver", ["none", "yee"])
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_registered_equals_manual(fp, precision, solver):
+    dt = em_dt(scene.SHAPE, scene.L) if solver == "yee" else 5e-12
+    a, b = (unlike_box(fp, precision, dt=dt, solver=solver) for _ in range(2))
+    n = len(scene.unlike_scene()["pos_a"])
+    for s in (a, b):
+        s.precalc()
+    ops = [(1, (0, 1), dict(log_lambda=10.0, seed=51, stream=1)), (2, (0, None), dict(log_lambda=12.0, seed=52, stream=2, epoch=100))]
+    # a background operator registered AFTER the pair operators still runs before them (documented order)
+    relax = dict(nu_tau=0.2, seed=53, drift=0.0, vth=0.01)
+    assert [a.collidePairEvery(every, *sp, **kw) for every, sp, kw in ops] == [0, 1]
+    assert a.collideEvery(1, "relax", **relax) == 0
+    a.step(2)
+    sums = [dict(applications=0, pairs=0, strong=0, cells=0, overfull_cells=0, overfull_particles=0) for _ in ops]
+    for k in range(1, 5):
+        b.substeps(1)
+        b.collide("relax", epoch=k, **relax)
+        for (every, sp, kw), total in zip(ops, sums):
+            if k % every == 0:
+                for key, v in b.collidePair(*sp, tau=every * dt, **dict(kw, epoch=k + kw.get("epoch", 0))).items():
+                    total[key] += v
+    for k in range(2):
+        pa, pb = a.getParticles(species=k), b.getParticles(species=k)
+        assert bits(pa["velocity"], pb["velocity"]) and bits(pa["position"], pb["position"])
+    stats = [a.pairStats(i) for i in range(2)]
+    assert stats == sums and [s["applications"] for s in stats] == [4, 2] and all(s["pairs"] > 0 for s in stats)
+    assert a.pairStats(0, "local") == stats[0]
+    # clearPairs leaves the background registration alone
+    a.clearPairs()
+    with pytest.raises(fp.FusionPicError, match=r"\.index <- "):
+        a.pairStats(0)
+    assert a.collisionStats(0)["applications"] == 4
+    a.substeps(1)
+    b.substeps(1)
+    b.collide("relax", epoch=5, **relax)
+    assert a.collisionStats(0) == dict(applications=5, candidates=0, collided=5 * n, clipped=0)
+    assert bits(a.getParticles()["velocity"], b.getParticles()["velocity"])
+    # a new registration starts from zero
+    assert a.collidePairEvery(1, 0, log_lambda=10.0) == 0
+    a.substeps(1)
+    assert a.pairStats(0)["applications"] == 1 and a.pairStats(0)["pairs"] > 0
+    a.destroy()
+    b.destroy()
+
+
+# ---- 6. refusals; the next valid call succeeds
+def test_refusals(fp):
+    from helpers import make_spec
+    rz = fp.makeCylindricalParticlePusher(make_spec(16, 16, 8))
+    for call in (lambda: rz.collidePair(0, log_lambda=10.0), lambda: rz.collidePairEvery(1, 0, log_lambda=10.0), lambda: rz.pairStats(0), rz.clearPairs):
+        with pytest.raises(fp.FusionPicError, match="needs a CART3D handle") as e:
+            call()
+        assert e.value.code == -5
+    rz.destroy()
+    sim = like_box(fp, "fp32")
+    nan, inf = float("nan"), float("inf")
+    cases = [
+        (dict(a=1), ".species_a <- no such species"), (dict(a=-1), ".species_a <- no such species"), (dict(b=1), ".species_b <- no such species"),
+        (dict(b=-2), ".species_b <- no such species"), (dict(log_lambda=nan), ".log_lambda <- must not be NaN"), (dict(tau=nan), ".tau <- must not be NaN"),
+        (dict(log_lambda=0.0), ".log_lambda <- must be positive and finite"), (dict(log_lambda=-1.0), ".log_lambda <- must be positive and finite"),
+        (dict(log_lambda=inf), ".log_lambda <- must be positive and finite"), (dict(tau=0.0), ".tau <- must be positive and finite"),
+        (dict(tau=-1e-9), ".tau <- must be positive and finite"), (dict(tau=inf), ".tau <- must be positive and finite"),
+    ]
+    before = sim.getParticles()
+    for kw, message in cases:
+        kw = dict(dict(log_lambda=10.0), **kw)
+        for call in (lambda: sim.collidePair(**kw), lambda: sim.collidePairEvery(1, **kw)):
+            with pytest.raises(fp.FusionPicError) as e:
+                call()
+            assert message in str(e.value) and e.value.code == -1, (kw, str(e.value))
+    lib = sim._lib
+    s = fp._pair_spec(5e-12, log_lambda=10.0)
+    s.reserved[2] = 1.0
+    assert lib.fpic_pair(sim._h, s, None) == -1 and b".reserved <- must be zero" in lib.fpic_last_error(sim._h)
+    assert lib.fpic_pair(sim._h, None, None) == -1 and b".spec <- Non-optional property is undefined!" in lib.fpic_last_error(sim._h)
+    assert lib.fpic_pair_register(sim._h, None, 1, None) == -1 and b".spec <- Non-optional property is undefined!" in lib.fpic_last_error(sim._h)
+    assert lib.fpic_pair_stats(sim._h, 0, 0, None) == -1 and b".out <- Non-optional property is undefined!" in lib.fpic_last_error(sim._h)
+    for every in (0, -1):
+        with pytest.raises(fp.FusionPicError, match=r"\.every <- must be at least 1"):
+            sim.collidePairEvery(every, log_lambda=10.0, tau=scene.TAU)
+    for index in (0, -1):
+        with pytest.raises(fp.FusionPicError, match=r"\.index <- no such registered operator"):
+            sim.pairStats(index)
+    assert bits(sim.getParticles()["velocity"], before["velocity"])                  # nothing refused has touched a particle
+    assert [sim.collidePairEvery(1000 + k, log_lambda=10.0) for k in range(fp.PAIR_MAX_OPS)] == list(range(fp.PAIR_MAX_OPS))
+    with pytest.raises(fp.FusionPicError, match=r"\.spec <- FPIC_PAIR_MAX_OPS \(8\) operators are registered already"):
+        sim.collidePairEvery(1, log_lambda=10.0)
+    with pytest.raises(fp.FusionPicError, match=r"\.index <- no such registered operator"):
+        sim.pairStats(fp.PAIR_MAX_OPS)
+    with pytest.raises(fp.FusionPicError, match=r"\.scope <- "):
+        sim._check(lib.fpic_pair_stats(sim._h, 0, 7, fp.PairResult()))
+    sim.clearPairs()
+    assert lib.fpic_pair(sim._h, fp._pair_spec(5e-12, log_lambda=10.0, tau=scene.TAU), None) == 0     # `out` is optional
+    assert sim.collidePair(0, log_lambda=10.0, tau=scene.TAU)["pairs"] > 0
+    sim.destroy()
+
+
+def test_a_decomposition_is_refused(fp):
+    """between two migrations the particles of a cell can sit on two ranks: all four calls say so, on a member and on the group"""
+    sims = []
+    for r in range(2):
+        s = box(fp, "fp32", 1000, 1.0)
+        s.domainInit(r, 2, ghost_planes=2, migrate_every=2, distributed_solve=0)
+        sims.append(s)
+    g = fp.BoxGroup(sims)
+    for owner in (sims[0], g):
+        for call in (lambda: owner.collidePair(0, log_lambda=10.0), lambda: owner.collidePairEvery(1, 0, log_lambda=10.0), lambda: owner.pairStats(0), owner.clearPairs):
+            with pytest.raises(fp.FusionPicError, match="cannot pair a cell alone") as e:
+                call()
+            assert e.value.code == -5 and "needs an undecomposed handle" in str(e.value)
+    for s in sims:
+        s.destroy()
+
+
+# ---- 7. the JavaScript host
+def test_pair_through_the_javascript_host(fp, tmp_path):
+    node = shutil.which("node")
+    if node is None:
+        pytest.skip("node is not installed on this box")
+    n = 4000
+    W = scene.weight(1, 0.02)
+    spec = box_spec(scene.SHAPE, scene.L, n, 5e-12, solver="none", macro_weight=W, particle_mass=scene.ME, particle_charge=scene.QE)
+    population = dict(seed=123456789, stream=3, drift=[0.0, 0.01, 0.0], vth=0.02)
+    now = dict(a=0, logLambda=10.0, tau=1e-9, seed=99, stream=4, epoch=7)
+    every = dict(logLambda=12.0, seed=5)
+    (tmp_path / "in.json").write_text(json.dumps(dict(spec=spec, population=population, now=now, every=every)))
+    script = r"""
+const fs = require('fs');
+const crypto = require('crypto');
+const empic = require(process.argv[1]);
+const inp = JSON.parse(fs.readFileSync(process.argv[2]));
+const sim = empic.makeCylindricalParticlePusher(inp.spec);
+sim.load(inp.population);
+sim.precalc();
+const first = sim.collidePair(inp.now);
+const index = sim.collidePairEvery(2, inp.every);
+sim.step(2);
+const stats = sim.pairStats(index);
+const local = sim.pairStats(index, 'local');
+const r = sim.select({});
+const sha = (a) => crypto.createHash('sha256').update(Buffer.from(a.buffer, a.byteOffset, a.byteLength)).digest('hex');
+const errors = [];
+const tries = [() => sim.collidePair({}), () => sim.collidePair({logLambda: 'x'}), () => sim.collidePair(7), () => sim.collidePair({logLambda: 10, a: 3}),
+  () => sim.collidePair({logLambda: 10, b: 1}), () => sim.collidePair({logLambda: 10, seed: -1}), () => sim.collidePair({logLambda: -1}),
+  () => sim.collidePair({logLambda: 10, tau: 0}), () => sim.collidePair({logLambda: 10, a: 0.5}),
+  () => sim.collidePairEvery(0, {logLambda: 10}), () => sim.collidePairEvery(1.5, {logLambda: 10}), () => sim.pairStats(4)];
+for (const t of tries) { try { t(); errors.push(null); } catch (err) { errors.push(String(err.message)); } }
+sim.clearPairs();
+let cleared = null;
+try { sim.pairStats(0); } catch (err) { cleared = String(err.message); }
+console.log(JSON.stringify({first: first, index: index, stats: stats, local: local, ids: sha(r.ids), position: sha(r.position), velocity: sha(r.velocity), errors: errors, cleared: cleared}));
+sim.destroy();
+"""
+    shim = os.path.join(ROOT, "fusion-sim_amd", "js", "empic_native.js")
+    raw = subprocess.check_output([node, "-e", script, shim, str(tmp_path / "in.json")], timeout=300)
+    out = json.loads(raw.decode().strip().splitlines()[-1])
+    sim = fp.makeCylindricalParticlePusher(spec)
+    sim.load(**population)
+    sim.precalc()
+    first = sim.collidePair(0, log_lambda=10.0, tau=1e-9, seed=99, stream=4, epoch=7)
+    index = sim.collidePairEvery(2, log_lambda=12.0, seed=5)
+    sim.step(2)
+    stats = sim.pairStats(index)
+    want = sim.select()
+    sim.destroy()
+    sha = lambda a: hashlib.sha256(a.tobytes()).hexdigest()
+    camel = lambda d: {{"overfull_cells": "overfullCells", "overfull_particles": "overfullParticles"}.get(k, k): v for k, v in d.items()}
+    assert out["first"] == camel(first) and first["pairs"] > 0 and first["cells"] > 0
+    assert out["index"] == index == 0 and out["stats"] == camel(stats) == out["local"] and stats["applications"] == 2 and stats["pairs"] > 0
+    assert (out["ids"], out["position"], out["velocity"]) == (sha(want["ids"]), sha(want["position"]), sha(want["velocity"]))
+    assert all(err is not None and " <- " in err for err in out["errors"]), out["errors"]
+    assert out["cleared"] is not None and ".index <- " in out["cleared"]
