@@ -781,7 +781,9 @@ int fpic_load(fpic_handle* h, const fpic_load_spec* spec, uint64_t* loaded);
  * collide: all four are zero and nothing runs).  fpic_collide_register makes it run at the end of every sub-step whose
  * number (counted since create) is a multiple of `every`, in registration order, before the recorders take their rows —
  * a row recorded after that sub-step sees the collided state — with epoch (uint32)(sub-step + spec.epoch): a resumed run
- * passes the sub-steps already done.  At most FPIC_COLLIDE_MAX_OPS operators; *index names the operator.  Nothing is
+ * passes the sub-steps already done.  The count is the handle's own: on a resumed handle the phase of `every` starts again,
+ * so a run cut at a sub-step that is not a common multiple of the registered periods cannot be reproduced by its resumption
+ * (cut at one, it continues bit for bit: tests/test_gpu_sequences.py).  At most FPIC_COLLIDE_MAX_OPS operators; *index names the operator.  Nothing is
  * synchronised: the counts accumulate on the device and fpic_collide_stats reads the totals since registration (scope as
  * for the diagnostics: GLOBAL with a communicator sums candidates, collided and clipped over the ranks; applications is the
  * same on every rank and is not summed).  fpic_collide_clear drops every registered operator.  Registrations are not part of
@@ -852,7 +854,9 @@ int fpic_collide_clear(fpic_handle* h);
  * strong, cells (the cells that had a pair to collide), overfull_cells, overfull_particles.  fpic_pair_register makes it
  * run at the end of every sub-step whose number (counted since create) is a multiple of `every`, after the operators of
  * fpic_collide_register and before the recorders take their rows, in registration order, with epoch
- * (uint32)(sub-step + spec.epoch).  At most FPIC_PAIR_MAX_OPS operators; *index names the operator.  Nothing is
+ * (uint32)(sub-step + spec.epoch).  The count is the handle's own: on a resumed handle the phase of `every` starts again, so
+ * a resume point must be a common multiple of the registered periods, and the resumed registration passes the sub-steps
+ * already done in spec.epoch.  At most FPIC_PAIR_MAX_OPS operators; *index names the operator.  Nothing is
  * synchronised: the counts accumulate on the device and fpic_pair_stats reads the totals since registration.
  * fpic_pair_clear drops every registered pair operator (those of fpic_collide_register stay).  Registrations are not part
  * of a checkpoint.
