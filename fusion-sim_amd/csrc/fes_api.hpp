@@ -51,6 +51,12 @@ int pair(fpic_handle* h, const fpic_pair_spec* spec, fpic_pair_result* out);
 int pair_register(fpic_handle* h, const fpic_pair_spec* spec, int every, int* index);
 int pair_stats(fpic_handle* h, int index, int scope, fpic_pair_result* out);
 int pair_clear(fpic_handle* h);
+// fusion yield tallies between the species of the box (fes_fusion.inc.hpp)
+int fusion(fpic_handle* h, const fpic_fusion_spec* spec, fpic_fusion_result* out, int64_t* grid);
+int fusion_register(fpic_handle* h, const fpic_fusion_spec* spec, int every, int* index);
+int fusion_stats(fpic_handle* h, int index, int scope, fpic_fusion_result* out);
+int fusion_grid(fpic_handle* h, int index, int64_t* grid, int reset);
+int fusion_clear(fpic_handle* h);
 // fluid moment grids (fes_mom.inc.hpp)
 int moments(fpic_handle* h, const fpic_moments_spec* spec, int scope, int64_t* out, fpic_moments_info* info);
 // field points and tracer particles as rows (fes_series.inc.hpp)

@@ -1,0 +1,221 @@
+// fes_fusion.inc.hpp: the fusion yield tally of a CART3D handle (fpic_fusion, fpic_fusion_register, fpic_fusion_stats,
+// fpic_fusion_grid, fpic_fusion_clear) — part of fes_api.hip's translation unit (included there after fes_pair.inc.hpp, inside
+// namespace fes).  The rule and the checks of a request are fes_fusion_core.hpp, the pass fes_fusion_kernels.hpp.
+//
+// One application: per species of the request fpic_pair's cell index (pair_index<T>, into the Diag's index buffers,
+// unchanged), then the tally pass — all enqueued on the handle's stream, nothing read back.  The count words, the tables and
+// the cell grids belong to the handle's Diag and are released with it: slot k < FPIC_FUSION_MAX_OPS serves the k-th
+// registered operator, slot FPIC_FUSION_MAX_OPS the call.  A table is uploaded at the call or at the registration (which
+// waits for the copy: the caller's table need not outlive it); the hook never allocates and never waits.
+// A handle with a Domain is refused as fpic_pair refuses it.
+
+constexpr int kFusionWords = 8;                     // per slot: pairs, below, above, cells, overfull_cells, overfull_particles, yield_hi, yield_lo
+constexpr int kFusionNow = FPIC_FUSION_MAX_OPS;     // the slot of fpic_fusion
+
+static int fusion_slot(fpic_handle* h, int slot)
+{
+    State* st = h->es;
+    Diag& g = st->diag;
+    void* p = nullptr;
+    if (!g.fusion) {
+        const size_t bytes = static_cast<size_t>(FPIC_FUSION_MAX_OPS + 1) * kFusionWords * sizeof(unsigned long long);
+        if (int rc = dev_alloc(h, &p, bytes, &h->bytes_grid)) return rc;
+        g.fusion = static_cast<unsigned long long*>(p);
+        HIP_TRY(h, hipMemsetAsync(g.fusion, 0, bytes, h->stream));
+    }
+    if (!g.fusion_table) {
+        if (int rc = dev_alloc(h, &p, static_cast<size_t>(FPIC_FUSION_MAX_OPS + 1) * FPIC_FUSION_TABLE_MAX * sizeof(double), &h->bytes_grid)) return rc;
+        g.fusion_table = static_cast<double*>(p);
+    }
+    if (!g.fusion_grid[slot]) {
+        if (int rc = dev_alloc(h, &p, pair_cells(st) * sizeof(unsigned long long), &h->bytes_grid)) return rc;
+        g.fusion_grid[slot] = static_cast<unsigned long long*>(p);
+    }
+    return FPIC_OK;
+}
+
+// the slot starts from zero with the request's table, in stream order; returns after the table has been copied
+static int fusion_begin(fpic_handle* h, int slot, const fpic_fusion_spec& spec)
+{
+    State* st = h->es;
+    Diag& g = st->diag;
+    if (int rc = fusion_slot(h, slot)) return rc;
+    HIP_TRY(h, hipMemsetAsync(g.fusion + slot * kFusionWords, 0, kFusionWords * sizeof(unsigned long long), h->stream));
+    HIP_TRY(h, hipMemsetAsync(g.fusion_grid[slot], 0, pair_cells(st) * sizeof(unsigned long long), h->stream));
+    HIP_TRY(h, hipMemcpyAsync(g.fusion_table + static_cast<size_t>(slot) * FPIC_FUSION_TABLE_MAX, spec.sigma, static_cast<size_t>(spec.n) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return FPIC_OK;
+}
+
+// the index buffers of the request's species, as fpic_pair sizes them
+static int fusion_buffers(fpic_handle* h, const fpic_fusion_spec& spec, bool may_grow)
+{
+    fpic_pair_spec p{};
+    p.species_a = spec.species_a;
+    p.species_b = spec.species_b;
+    return pair_buffers(h, p, may_grow);
+}
+
+// one application of the rule r into `slot`: enqueued, nothing waited for
+template <typename T>
+static int fusion_enqueue(fpic_handle* h, const fpic_fusion_spec& spec, const fesfusion::Rule& r, int slot, bool may_grow)
+{
+    State* st = h->es;
+    Diag& g = st->diag;
+    if (int rc = fusion_buffers(h, spec, may_grow)) return rc;
+    const Species& sa = st->sp[spec.species_a];
+    const Species& sb = st->sp[spec.species_b];
+    const bool like = spec.species_a == spec.species_b;
+    if (!sa.n || !sb.n || !(r.s_max > 0)) return FPIC_OK;   // (nothing can react: nothing is launched)
+    if (int rc = pair_index<T>(h, sa, 0)) return rc;
+    if (!like)
+        if (int rc = pair_index<T>(h, sb, 1)) return rc;
+    FusionArgs<T> a{};
+    a.slab_a = static_cast<const T*>(sa.slab[sa.cur]);
+    a.slab_b = static_cast<const T*>(sb.slab[sb.cur]);
+    a.id_a = sa.ids_identity ? nullptr : sa.id[sa.cur];
+    a.id_b = sb.ids_identity ? nullptr : sb.id[sb.cur];
+    a.n_pad_a = sa.n_pad;
+    a.n_pad_b = sb.n_pad;
+    a.seg_a = g.pair_seg[0] + kPairSegLead - 1;
+    a.seg_b = g.pair_seg[like ? 0 : 1] + kPairSegLead - 1;
+    a.index_a = g.pair_index[0];
+    a.index_b = g.pair_index[like ? 0 : 1];
+    a.ncells = static_cast<uint32_t>(pair_cells(st));
+    a.rank_max = (pair_forms() & 2) ? static_cast<uint32_t>(kPairRankMax) : ~0u;
+    a.counts = g.fusion + slot * kFusionWords;
+    a.grid = g.fusion_grid[slot];
+    a.table = g.fusion_table + static_cast<size_t>(slot) * FPIC_FUSION_TABLE_MAX;
+    a.r = r;
+    const size_t nchunks = (pair_cells(st) + kPairChunk - 1) / kPairChunk;
+    const unsigned grid = static_cast<unsigned>(std::min<size_t>(kPairCollideBlocks, nchunks));
+    // (kFusionLdsBytes is below the 64 KiB a launch may ask for without an attribute: the header asserts it)
+    if (like) fusion_tally_kernel<T, true><<<grid, kPairThreads, kFusionLdsBytes, h->stream>>>(a);
+    else fusion_tally_kernel<T, false><<<grid, kPairThreads, kFusionLdsBytes, h->stream>>>(a);
+    HIP_TRY(h, hipGetLastError());
+    return FPIC_OK;
+}
+
+static int fusion_apply(fpic_handle* h, const fpic_fusion_spec& spec, const fesfusion::Rule& r, int slot, bool may_grow)
+{
+    return h->prec == FPIC_F32 ? fusion_enqueue<float>(h, spec, r, slot, may_grow) : fusion_enqueue<double>(h, spec, r, slot, may_grow);
+}
+
+static double fusion_dv(const State* st) { return (st->lx / st->nx) * (st->ly / st->ny) * (st->lz / st->nz); }
+
+static int fusion_check(fpic_handle* h, const fpic_fusion_spec* spec)
+{
+    State* st = h->es;
+    if (const char* why = fesfusion::check(spec, static_cast<int>(st->sp.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    if (const char* why = fesfusion::check_bound(*spec, st->W, fusion_dv(st))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    return FPIC_OK;
+}
+
+static void fusion_result(fpic_fusion_result* out, uint64_t applications, const uint64_t* got, int e)
+{
+    *out = fpic_fusion_result{};
+    out->applications = applications;
+    out->pairs = got[0];
+    out->below = got[1];
+    out->above = got[2];
+    out->cells = got[3];
+    out->overfull_cells = got[4];
+    out->overfull_particles = got[5];
+    uint64_t hi, lo;
+    fesfusion::join(got[6], got[7], hi, lo);
+    out->yield_hi = hi;
+    out->yield_lo = lo;
+    out->unit_exponent = e;
+}
+
+int fusion(fpic_handle* h, const fpic_fusion_spec* spec, fpic_fusion_result* out, int64_t* grid)
+{
+    State* st = h->es;
+    Diag& g = st->diag;
+    if (int rc = pair_refuse_decomposed(h, "fpic_fusion")) return rc;
+    if (int rc = fusion_check(h, spec)) return rc;
+    if (out) *out = fpic_fusion_result{};
+    if (int rc = fusion_begin(h, kFusionNow, *spec)) return rc;
+    const fesfusion::Rule r = fesfusion::rule_of(*spec, spec->epoch, st->W, fusion_dv(st));
+    if (int rc = fusion_apply(h, *spec, r, kFusionNow, true)) return rc;
+    uint64_t got[kFusionWords] = {};
+    HIP_TRY(h, hipMemcpyAsync(got, g.fusion + kFusionNow * kFusionWords, sizeof(got), hipMemcpyDeviceToHost, h->stream));
+    if (grid) HIP_TRY(h, hipMemcpyAsync(grid, g.fusion_grid[kFusionNow], pair_cells(st) * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (out) fusion_result(out, 1, got, r.e);
+    return FPIC_OK;
+}
+
+int fusion_register(fpic_handle* h, const fpic_fusion_spec* spec, int every, int* index)
+{
+    State* st = h->es;
+    Diag& g = st->diag;
+    if (int rc = pair_refuse_decomposed(h, "fpic_fusion_register")) return rc;
+    if (int rc = fusion_check(h, spec)) return rc;
+    if (const char* why = fesfusion::check_register(every, static_cast<int>(g.fusion_ops.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    if (int rc = fusion_buffers(h, *spec, true)) return rc;   // (sized now: the hook finds them in place and never grows them)
+    const int at = static_cast<int>(g.fusion_ops.size());
+    if (int rc = fusion_begin(h, at, *spec)) return rc;
+    FusionOp op{ *spec, every, 0, fesfusion::rule_of(*spec, spec->epoch, st->W, fusion_dv(st)) };
+    op.spec.sigma = nullptr;        // (the table is on the device; the caller's need not outlive this call)
+    g.fusion_ops.push_back(op);
+    if (index) *index = at;
+    return FPIC_OK;
+}
+
+int fusion_stats(fpic_handle* h, int index, int scope, fpic_fusion_result* out)
+{
+    Diag& g = h->es->diag;
+    if (int rc = pair_refuse_decomposed(h, "fpic_fusion_stats")) return rc;
+    if (!out) return fail(h, FPIC_ERR_INVALID_ARG, ".out <- Non-optional property is undefined!");
+    if (const char* why = fesfusion::check_index(index, static_cast<int>(g.fusion_ops.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    bool collective = false;
+    if (int rc = diag_scope(h, scope, collective)) return rc;
+    uint64_t got[kFusionWords] = {};
+    HIP_TRY(h, hipMemcpyAsync(got, g.fusion + index * kFusionWords, sizeof(got), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (collective)
+        if (int rc = diag_sum_ranks(h, got, kFusionWords)) return rc;
+    fusion_result(out, g.fusion_ops[index].applications, got, g.fusion_ops[index].rule.e);
+    return FPIC_OK;
+}
+
+int fusion_grid(fpic_handle* h, int index, int64_t* grid, int reset)
+{
+    State* st = h->es;
+    Diag& g = st->diag;
+    if (int rc = pair_refuse_decomposed(h, "fpic_fusion_grid")) return rc;
+    if (const char* why = fesfusion::check_index(index, static_cast<int>(g.fusion_ops.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    if (!grid && !reset) return fail(h, FPIC_ERR_INVALID_ARG, ".grid <- Non-optional property is undefined!");
+    const size_t bytes = pair_cells(st) * sizeof(int64_t);
+    if (grid) HIP_TRY(h, hipMemcpyAsync(grid, g.fusion_grid[index], bytes, hipMemcpyDeviceToHost, h->stream));
+    if (reset) {   // (behind the copy, in stream order)
+        HIP_TRY(h, hipMemsetAsync(g.fusion_grid[index], 0, bytes, h->stream));
+        HIP_TRY(h, hipMemsetAsync(g.fusion + index * kFusionWords, 0, kFusionWords * sizeof(unsigned long long), h->stream));
+        g.fusion_ops[index].applications = 0;
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return FPIC_OK;
+}
+
+int fusion_clear(fpic_handle* h)
+{
+    if (int rc = pair_refuse_decomposed(h, "fpic_fusion_clear")) return rc;
+    h->es->diag.fusion_ops.clear();   // (applications in flight keep their slots; a later registration zeroes its own in stream order)
+    return FPIC_OK;
+}
+
+// the hook's part (diag_after_substep, after the pair operators): every registered tally that is due, in registration order
+static int fusion_after_substep(fpic_handle* h, uint64_t substep)
+{
+    Diag& g = h->es->diag;
+    for (size_t k = 0; k < g.fusion_ops.size(); ++k) {
+        FusionOp& op = g.fusion_ops[k];
+        if (substep % static_cast<uint64_t>(op.every)) continue;
+        op.applications++;
+        fesfusion::Rule r = op.rule;
+        r.epoch = static_cast<uint32_t>(substep + op.spec.epoch);
+        if (int rc = fusion_apply(h, op.spec, r, static_cast<int>(k), false)) return rc;
+    }
+    return FPIC_OK;
+}

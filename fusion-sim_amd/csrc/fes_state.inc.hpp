@@ -90,6 +90,15 @@ struct PairOp {
     uint64_t applications;
 };
 
+// a registered fusion yield tally (fes_fusion.inc.hpp): the request (its table pointer is not kept: the table is on the
+// device), its period in sub-steps, the applications since registration or the last reset, the kernel's form of the request
+struct FusionOp {
+    fpic_fusion_spec spec;
+    int every;
+    uint64_t applications;
+    fesfusion::Rule rule;
+};
+
 // the diagnostics of a handle: the sub-step counter the recorders share, the recorders and their requests, the buffers of the
 // energy reduction (fes_diag.inc.hpp), of the histograms and of the moments, the ranks' gather
 struct Diag {
@@ -117,13 +126,22 @@ struct Diag {
     uint32_t* pair_seg[2] = {};
     uint32_t* pair_index[2] = {};
     size_t pair_seg_words[2] = {}, pair_index_words[2] = {};
+    // fpic_fusion (fes_fusion.inc.hpp), per registered operator and one more for a call: eight count words, a table of
+    // FPIC_FUSION_TABLE_MAX doubles, and the cell grid (nx ny nz int64, allocated when the operator is first used)
+    unsigned long long* fusion = nullptr;
+    double* fusion_table = nullptr;
+    unsigned long long* fusion_grid[FPIC_FUSION_MAX_OPS + 1] = {};
+    std::vector<FusionOp> fusion_ops;   // the registered tallies, in registration order
 };
 inline void diag_release(Diag& g)
 {
     for (Recorder& r : g.rec)
         if (r.dev) (void)hipFree(r.dev);
     for (void* p : { g.series_req.block, g.modes_req.block, static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom), g.sel, static_cast<void*>(g.coll), static_cast<void*>(g.pair),
-                     static_cast<void*>(g.pair_seg[0]), static_cast<void*>(g.pair_seg[1]), static_cast<void*>(g.pair_index[0]), static_cast<void*>(g.pair_index[1]) })
+                     static_cast<void*>(g.pair_seg[0]), static_cast<void*>(g.pair_seg[1]), static_cast<void*>(g.pair_index[0]), static_cast<void*>(g.pair_index[1]),
+                     static_cast<void*>(g.fusion), static_cast<void*>(g.fusion_table) })
+        if (p) (void)hipFree(p);
+    for (unsigned long long* p : g.fusion_grid)
         if (p) (void)hipFree(p);
     g = Diag();
 }

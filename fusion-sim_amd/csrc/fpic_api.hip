@@ -1527,6 +1527,36 @@ int fpic_pair_clear(fpic_handle* h)
     BOX_ONLY(h, "fpic_pair_clear");
     return fes::pair_clear(h);
 }
+int fpic_fusion(fpic_handle* h, const fpic_fusion_spec* spec, fpic_fusion_result* out, int64_t* grid)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_fusion");
+    return fes::fusion(h, spec, out, grid);
+}
+int fpic_fusion_register(fpic_handle* h, const fpic_fusion_spec* spec, int every, int* index)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_fusion_register");
+    return fes::fusion_register(h, spec, every, index);
+}
+int fpic_fusion_stats(fpic_handle* h, int index, int scope, fpic_fusion_result* out)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_fusion_stats");
+    return fes::fusion_stats(h, index, scope, out);
+}
+int fpic_fusion_grid(fpic_handle* h, int index, int64_t* grid, int reset)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_fusion_grid");
+    return fes::fusion_grid(h, index, grid, reset);
+}
+int fpic_fusion_clear(fpic_handle* h)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_fusion_clear");
+    return fes::fusion_clear(h);
+}
 int fpic_get_particles_of(fpic_handle* h, int species, void* pos_aos, void* vel_aos, int dtype)
 {
     CHECK_HANDLE(h);

@@ -49,6 +49,7 @@ ABI_FUNCTIONS = [
     "fpic_modes_now", "fpic_modes_record", "fpic_modes_history",
     "fpic_select", "fpic_load", "fpic_collide", "fpic_collide_register", "fpic_collide_stats", "fpic_collide_clear",
     "fpic_pair", "fpic_pair_register", "fpic_pair_stats", "fpic_pair_clear",
+    "fpic_fusion", "fpic_fusion_register", "fpic_fusion_stats", "fpic_fusion_grid", "fpic_fusion_clear",
 ]
 
 
@@ -463,6 +464,109 @@ def _pair_counts(r):
     return {k: int(getattr(r, k)) for k in ("applications", "pairs", "strong", "cells", "overfull_cells", "overfull_particles")}
 
 
+FUSION_MAX_OPS = 4
+FUSION_TABLE_MAX = 4096
+FUSION_SEED = 0xF0510D7
+FUSION_C = 2.998e8
+
+
+class FusionSpec(ctypes.Structure):
+    """mirror of fpic_fusion_spec (include/fusionpic.h)"""
+    _fields_ = [
+        ("species_a", ctypes.c_int32), ("species_b", ctypes.c_int32), ("seed", ctypes.c_uint64), ("stream", ctypes.c_uint32), ("epoch", ctypes.c_uint32),
+        ("tau", ctypes.c_double), ("g_lo", ctypes.c_double), ("g_hi", ctypes.c_double), ("n", ctypes.c_int32), ("reserved_i", ctypes.c_int32),
+        ("sigma", ctypes.POINTER(ctypes.c_double)), ("reserved", ctypes.c_double * 4),
+    ]
+
+
+class FusionResult(ctypes.Structure):
+    """mirror of fpic_fusion_result"""
+    _fields_ = [("applications", ctypes.c_uint64), ("pairs", ctypes.c_uint64), ("below", ctypes.c_uint64), ("above", ctypes.c_uint64), ("cells", ctypes.c_uint64),
+                ("overfull_cells", ctypes.c_uint64), ("overfull_particles", ctypes.c_uint64), ("yield_hi", ctypes.c_uint64), ("yield_lo", ctypes.c_uint64),
+                ("unit_exponent", ctypes.c_int32), ("reserved", ctypes.c_int32)]
+
+
+def _fusion_spec(tau_default, a=0, b=None, sigma=None, g_lo=None, g_hi=None, tau=None, seed=FUSION_SEED, stream=0, epoch=0):
+    """FusionSpec of a yield tally: species a with species b (None: a with itself), the table sigma (m^2) at relative speeds
+    uniform from g_lo to g_hi (units of c), the time tau (s) one application stands for (None: tau_default).  Only what the
+    structure cannot carry is refused here; the library checks the rest.  The spec keeps the table alive (spec._table)."""
+    s = FusionSpec()
+
+    def whole(name, v, bits, signed=False):
+        lo_, hi_ = (-(1 << bits - 1), 1 << bits - 1) if signed else (0, 1 << bits)
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo_ <= int(v) < hi_:
+            raise FusionPicError(-1, ".%s <- must be %s %d-bit integer" % (name, "a signed" if signed else "an unsigned", bits))
+        return int(v)
+
+    def real(name, v):
+        if v is None:
+            raise FusionPicError(-1, ".%s <- Non-optional property is undefined!" % name)
+        try:
+            return float(v)
+        except (TypeError, ValueError):
+            raise FusionPicError(-1, ".%s <- must be a number" % name)
+
+    s.species_a = whole("species_a", a, 32, signed=True)
+    s.species_b = s.species_a if b is None else whole("species_b", b, 32, signed=True)
+    s.seed, s.stream, s.epoch = whole("seed", seed, 64), whole("stream", stream, 32), whole("epoch", epoch, 32)
+    s.tau = real("tau", tau_default if tau is None else tau)
+    s.g_lo, s.g_hi = real("g_lo", g_lo), real("g_hi", g_hi)
+    if sigma is None:
+        raise FusionPicError(-1, ".sigma <- Non-optional property is undefined!")
+    try:
+        table = np.ascontiguousarray(sigma, dtype=np.float64)
+    except (TypeError, ValueError):
+        raise FusionPicError(-1, ".sigma <- must be a sequence of numbers")
+    if table.ndim != 1:
+        raise FusionPicError(-1, ".sigma <- must be a sequence of numbers")
+    if not 2 <= len(table) <= FUSION_TABLE_MAX:
+        raise FusionPicError(-1, ".n <- must be 2 .. FPIC_FUSION_TABLE_MAX (4096)")
+    s.n = len(table)
+    s._table = table
+    s.sigma = table.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+    return s
+
+
+def _fusion_counts(r):
+    """the counts of a fpic_fusion_result, the exact total as a Python integer (units of 2**unit_exponent reactions) and as a float"""
+    out = {k: int(getattr(r, k)) for k in ("applications", "pairs", "below", "above", "cells", "overfull_cells", "overfull_particles", "yield_hi", "yield_lo",
+                                           "unit_exponent")}
+    out["reactions_exact"] = (out["yield_hi"] << 32) + out["yield_lo"]
+    out["reactions"] = float(np.ldexp(float(out["reactions_exact"]), out["unit_exponent"])) if out["reactions_exact"] < 1 << 1000 else float("inf")
+    return out
+
+
+def sigma_table(sigma_of_keV, mass_a, mass_b, e_lo_keV, e_hi_keV, n=FUSION_TABLE_MAX):
+    """Samples a cross-section onto the table of fusionYield: returns (S, g_lo, g_hi).  sigma_of_keV: a callable that takes
+    an array of centre-of-mass energies in keV and returns the cross-section in m^2; mass_a, mass_b: the reactants' masses in
+    kg; the table covers e_lo_keV .. e_hi_keV in n points UNIFORM IN THE RELATIVE SPEED g (units of c) with the
+    non-relativistic E = m_ab (g c)^2 / 2, m_ab the reduced mass and c = 2.998e8, the box's.  Negative or non-finite values
+    of the callable are refused.
+    The library ships no nuclear data: a wrong constant in a shipped table is worse than none.  Fits of the D-T, D-D and
+    D-3He cross-sections are published by H.-S. Bosch and G. M. Hale, Nuclear Fusion 32 (1992) 611 (valid 0.5 - 550 keV for
+    D-T), and, older, by B. H. Duane in BNWL-1685 (1972), reproduced in the NRL Plasma Formulary; evaluated data are in the
+    ENDF/B libraries."""
+    keV = 1.602176634e-16
+    mass_a, mass_b, e_lo_keV, e_hi_keV = float(mass_a), float(mass_b), float(e_lo_keV), float(e_hi_keV)
+    if not (mass_a > 0 and mass_b > 0 and np.isfinite(mass_a + mass_b)):
+        raise FusionPicError(-1, ".mass <- must be positive and finite")
+    if not (0 <= e_lo_keV < e_hi_keV and np.isfinite(e_hi_keV)):
+        raise FusionPicError(-1, ".e_lo_keV <- must be 0 <= e_lo_keV < e_hi_keV, finite")
+    if isinstance(n, bool) or not isinstance(n, (int, np.integer)) or not 2 <= int(n) <= FUSION_TABLE_MAX:
+        raise FusionPicError(-1, ".n <- must be 2 .. FPIC_FUSION_TABLE_MAX (4096)")
+    mab = mass_a * mass_b / (mass_a + mass_b)
+    g_lo, g_hi = (float(np.sqrt(2.0 * e * keV / mab)) / FUSION_C for e in (e_lo_keV, e_hi_keV))
+    g = g_lo + np.arange(int(n), dtype=np.float64) * ((g_hi - g_lo) / (int(n) - 1))
+    energy = 0.5 * mab * (g * FUSION_C) ** 2 / keV
+    with np.errstate(all="ignore"):
+        S = np.array(sigma_of_keV(energy), dtype=np.float64)
+    if S.shape != g.shape:
+        raise FusionPicError(-1, ".sigma_of_keV <- must return one value per energy")
+    if not np.all(np.isfinite(S) & (S >= 0)):
+        raise FusionPicError(-1, ".sigma_of_keV <- every value must be finite and not negative")
+    return S, g_lo, g_hi
+
+
 SERIES_MAX_POINTS = 4096
 SERIES_MAX_TRACERS = 65536
 # the columns of a point row and of a tracer row (fpic_series_*): 8 doubles each
@@ -707,6 +811,11 @@ def load_library(path=None):
     lib.fpic_pair_register.argtypes = [vp, ctypes.POINTER(PairSpec), ci, ctypes.POINTER(ctypes.c_int)]
     lib.fpic_pair_stats.argtypes = [vp, ci, ci, ctypes.POINTER(PairResult)]
     lib.fpic_pair_clear.argtypes = [vp]
+    lib.fpic_fusion.argtypes = [vp, ctypes.POINTER(FusionSpec), ctypes.POINTER(FusionResult), ctypes.POINTER(ctypes.c_int64)]
+    lib.fpic_fusion_register.argtypes = [vp, ctypes.POINTER(FusionSpec), ci, ctypes.POINTER(ctypes.c_int)]
+    lib.fpic_fusion_stats.argtypes = [vp, ci, ci, ctypes.POINTER(FusionResult)]
+    lib.fpic_fusion_grid.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_int64), ci]
+    lib.fpic_fusion_clear.argtypes = [vp]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -1082,6 +1191,59 @@ class CylindricalParticlePusher:
         """drops every registered binary collision operator (fpic_pair_clear); those of collideEvery stay"""
         self._check(self._lib.fpic_pair_clear(self._h))
 
+    # ---- fusion yield tallies between the species of the box (fpic_fusion*)
+    def _fusion_cells(self):
+        return (int(self.spec["nz"]), int(self.spec.get("ny", 1)), int(self.spec["nr"]))
+
+    def fusionYield(self, a=0, b=None, grid=False, **request):
+        """The number of binary reactions between species a and species b of a CART3D box (b None or b == a: a species with
+        itself) in the time tau, from a tabulated cross-section (fpic_fusion; an (r,z) handle and a decomposed handle are
+        refused).  A tally, not a sink: no particle is changed.  sigma: the table (m^2, 2 .. 4096 entries, see sigma_table) at
+        relative speeds uniform from g_lo to g_hi (units of c); tau (s, default the sub-step dt); seed, stream, epoch: the
+        counter of the random pairing.  Returns {applications, pairs, below, above, cells, overfull_cells,
+        overfull_particles, yield_hi, yield_lo, unit_exponent, reactions_exact, reactions}: pairs were inside the table,
+        below and above outside it; reactions_exact is the exact total as a Python integer in units of 2**unit_exponent
+        reactions, reactions the same as a float.  grid=True adds "grid": the (nz, ny, nx) int64 cell tallies in the same
+        unit."""
+        s = _fusion_spec(float(self.spec["dt"]), a, b, **request)
+        out = FusionResult()
+        cells = np.zeros(self._fusion_cells(), dtype=np.int64) if grid else None
+        ptr = cells.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)) if grid else None
+        self._check(self._lib.fpic_fusion(self._h, ctypes.byref(s), ctypes.byref(out), ptr))
+        got = _fusion_counts(out)
+        if grid:
+            got["grid"] = cells
+        return got
+
+    def fusionYieldEvery(self, every, a=0, b=None, **request):
+        """Registers a yield tally (see fusionYield) to run at the end of every `every`-th sub-step, after the operators of
+        collidePairEvery and before the recorders, with epoch = the sub-step number + `epoch`; tau defaults to every * dt.
+        The table is copied.  Returns the operator's index (fpic_fusion_register); at most FUSION_MAX_OPS."""
+        if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or not -(1 << 31) <= int(every) < 1 << 31:
+            raise FusionPicError(-1, ".every <- must be a signed 32-bit integer")
+        s = _fusion_spec(int(every) * float(self.spec["dt"]), a, b, **request)
+        index = ctypes.c_int(-1)
+        self._check(self._lib.fpic_fusion_register(self._h, ctypes.byref(s), int(every), ctypes.byref(index)))
+        return index.value
+
+    def fusionStats(self, index, scope="global"):
+        """the totals of a registered yield tally since its registration or its last reset (fpic_fusion_stats)"""
+        out = FusionResult()
+        self._check(self._lib.fpic_fusion_stats(self._h, int(index), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope], ctypes.byref(out)))
+        return _fusion_counts(out)
+
+    def fusionGrid(self, index, reset=False):
+        """the (nz, ny, nx) int64 cell tallies of a registered yield tally, in units of 2**unit_exponent reactions
+        (fpic_fusion_grid); reset=True zeroes the grid, the totals and `applications` behind the copy.  A cell's word is
+        exact for at least 4096 applications between two resets; nothing detects an overflow beyond that."""
+        cells = np.zeros(self._fusion_cells(), dtype=np.int64)
+        self._check(self._lib.fpic_fusion_grid(self._h, int(index), cells.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), 1 if reset else 0))
+        return cells
+
+    def clearFusion(self):
+        """drops every registered yield tally (fpic_fusion_clear)"""
+        self._check(self._lib.fpic_fusion_clear(self._h))
+
     # ---- series: the field at points and the state of tracer particles as rows (fpic_series_*)
     def series(self, points=None, tracers=None, species=0, scope="global"):
         """The rows of the current state of a CART3D box (fpic_series_now; an (r,z) handle is refused).  points: positions in
@@ -1386,6 +1548,12 @@ class ElectrostaticBoxPusher:
     collidePairEvery = CylindricalParticlePusher.collidePairEvery
     pairStats = CylindricalParticlePusher.pairStats
     clearPairs = CylindricalParticlePusher.clearPairs
+    _fusion_cells = CylindricalParticlePusher._fusion_cells
+    fusionYield = CylindricalParticlePusher.fusionYield
+    fusionYieldEvery = CylindricalParticlePusher.fusionYieldEvery
+    fusionStats = CylindricalParticlePusher.fusionStats
+    fusionGrid = CylindricalParticlePusher.fusionGrid
+    clearFusion = CylindricalParticlePusher.clearFusion
     count = CylindricalParticlePusher.count
     series = CylindricalParticlePusher.series
     recordSeries = CylindricalParticlePusher.recordSeries
@@ -1508,6 +1676,26 @@ class BoxGroup:
     def clearPairs(self):
         """refused, see collidePair"""
         raise FusionPicError(-5, _PAIR_DECOMPOSED % "clearPairs")
+
+    def fusionYield(self, a=0, b=None, grid=False, **request):
+        """refused (FPIC_ERR_STATE), as by every member and as collidePair: a rank cannot pair a cell alone"""
+        raise FusionPicError(-5, _PAIR_DECOMPOSED % "fusionYield")
+
+    def fusionYieldEvery(self, every, a=0, b=None, **request):
+        """refused, see fusionYield"""
+        raise FusionPicError(-5, _PAIR_DECOMPOSED % "fusionYieldEvery")
+
+    def fusionStats(self, index):
+        """refused, see fusionYield"""
+        raise FusionPicError(-5, _PAIR_DECOMPOSED % "fusionStats")
+
+    def fusionGrid(self, index, reset=False):
+        """refused, see fusionYield"""
+        raise FusionPicError(-5, _PAIR_DECOMPOSED % "fusionGrid")
+
+    def clearFusion(self):
+        """refused, see fusionYield"""
+        raise FusionPicError(-5, _PAIR_DECOMPOSED % "clearFusion")
 
     def count(self, where=None, species=0, every=None):
         """the whole box: the members' LOCAL counts (each its own particles) added up"""

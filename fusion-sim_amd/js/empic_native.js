@@ -420,6 +420,77 @@ function makeBox(spec, lib) {
         return lib.pairStats(h, index, scopeOf(scope));
     };
     out.clearPairs = function () { lib.clearPairs(h); };
+    // fusion yield tallies between the species of the box (fpic_fusion*): a tally, not a sink — no particle changes.
+    // request = { a, b (default a: a species with itself), sigma: the table (an array or Float64Array of 2 .. 4096
+    // cross-sections in m^2) at relative speeds uniform from gLo to gHi (units of c), tau (s; default the sub-step dt, every * dt
+    // for fusionYieldEvery), seed (an integer up to 2^53 or a BigInt up to 2^64), stream, epoch, grid (fusionYield: true adds the
+    // cell tallies) }.  fusionYield -> { applications, pairs, below, above, cells, overfullCells, overfullParticles, yieldHi,
+    // yieldLo, unitExponent, reactionsExact (a BigInt in units of 2^unitExponent reactions), reactions (a number), grid (a
+    // BigInt64Array of nz*ny*nx cells, x fastest, in the same unit) }; fusionYieldEvery(every, request) -> the operator's index;
+    // fusionStats(index, scope) -> its totals since registration or the last reset; fusionGrid(index, reset) -> its cell
+    // tallies, reset = true zeroes grid, totals and applications behind the copy; clearFusion() drops every tally
+    const fusionArgs = function (request, tauDefault) {
+        if (request === null || typeof request !== 'object') throw new TypeError('.request <- expected { a, b, sigma, gLo, gHi, tau, ... }');
+        const whole = function (name, v, dflt, least, most) {
+            if (v === undefined || v === null) v = dflt;
+            if (!Number.isInteger(v) || v < least || v > most) throw new RangeError('.' + name + ' <- expected an integer within its field');
+            return v;
+        };
+        const real = function (name, v, dflt) {
+            if (v === undefined || v === null) v = dflt;
+            if (typeof v !== 'number') throw new RangeError('.' + name + ' <- expected a number');
+            return v;
+        };
+        const given = (v) => v !== undefined && v !== null;
+        let seed = given(request.seed) ? request.seed : 0xF0510D7;
+        if (typeof seed === 'number') {
+            if (!Number.isInteger(seed) || seed < 0 || seed > Number.MAX_SAFE_INTEGER) throw new RangeError('.seed <- expected an integer up to 2^53, or a BigInt up to 2^64');
+            seed = BigInt(seed);
+        }
+        if (typeof seed !== 'bigint' || seed < 0n || seed >= (1n << 64n)) throw new RangeError('.seed <- expected an integer up to 2^53, or a BigInt up to 2^64');
+        let sigma = request.sigma;
+        if (Array.isArray(sigma)) {
+            if (!sigma.every((x) => typeof x === 'number')) throw new TypeError('.sigma <- expected an array of numbers or a Float64Array');
+            sigma = Float64Array.from(sigma);
+        }
+        if (!(sigma instanceof Float64Array)) throw new TypeError('.sigma <- expected an array of numbers or a Float64Array');
+        const a = whole('a', request.a, 0, -0x80000000, 0x7fffffff);
+        const words = [a, whole('b', request.b, a, -0x80000000, 0x7fffffff), Number(seed & 0xffffffffn), Number(seed >> 32n),
+            whole('stream', request.stream, 0, 0, 0xffffffff), whole('epoch', request.epoch, 0, 0, 0xffffffff)];
+        return [Float64Array.from(words), Float64Array.from([real('tau', request.tau, tauDefault), real('gLo', request.gLo, undefined), real('gHi', request.gHi, undefined)]), sigma];
+    };
+    const fusionCounts = function (r) {
+        const exact = (BigInt(r.yieldTop) << 64n) + (BigInt(r.yieldMid) << 32n) + BigInt(r.yieldLo);
+        r.yieldHi = r.yieldTop * 4294967296 + r.yieldMid;      // (exact below 2^53)
+        delete r.yieldTop;
+        delete r.yieldMid;
+        r.reactionsExact = exact;
+        r.reactions = Number(exact) * Math.pow(2, r.unitExponent);
+        return r;
+    };
+    out.fusionYield = function (request) {
+        const a = fusionArgs(request, spec.dt);
+        const grid = request.grid ? new BigInt64Array(nodes) : null;
+        const r = fusionCounts(lib.fusionYield(h, a[0], a[1], a[2], grid));
+        if (grid) r.grid = grid;
+        return r;
+    };
+    out.fusionYieldEvery = function (every, request) {
+        if (!Number.isInteger(every) || every < -0x80000000 || every > 0x7fffffff) throw new RangeError('.every <- expected a 32-bit integer');
+        const a = fusionArgs(request, every * spec.dt);
+        return lib.fusionYieldEvery(h, a[0], a[1], a[2], every);
+    };
+    out.fusionStats = function (index, scope) {
+        if (!Number.isInteger(index) || index < -0x80000000 || index > 0x7fffffff) throw new RangeError('.index <- expected a 32-bit integer');
+        return fusionCounts(lib.fusionStats(h, index, scopeOf(scope)));
+    };
+    out.fusionGrid = function (index, reset) {
+        if (!Number.isInteger(index) || index < -0x80000000 || index > 0x7fffffff) throw new RangeError('.index <- expected a 32-bit integer');
+        const grid = new BigInt64Array(nodes);
+        lib.fusionGrid(h, index, grid, reset ? 1 : 0);
+        return grid;
+    };
+    out.clearFusion = function () { lib.clearFusion(h); };
     // series (fpic_series_*): the field at points and the state of tracer particles as rows of 8 doubles, now or recorded into a
     // device ring.  request = { points: [[x, y, z], ...] in metres (wrapped periodically), tracers: particle indices, species: one
     // index or one per tracer (default 0) }; either list may be missing, not both.  A point row is Ex Ey Ez phi Bx By Bz present,

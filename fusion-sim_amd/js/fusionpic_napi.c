@@ -1087,6 +1087,137 @@ static napi_value n_clear_pairs(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* the request of fusionYield / fusionYieldEvery: words: Float64Array [species_a, species_b, seed low word, seed high word,
+ * stream, epoch], reals: Float64Array [tau, g_lo, g_hi], sigma: Float64Array of 2 .. FPIC_FUSION_TABLE_MAX cross-sections
+ * (the request points into it: it lives as long as the call).  The arrays' types and lengths and the words' ranges are
+ * checked here, the request itself by the library. */
+static int get_fusion_spec(napi_env env, napi_value words, napi_value reals, napi_value sigma, fpic_fusion_spec* s)
+{
+    napi_typedarray_type tw, tr, ts; void *pw, *pr, *ps; size_t lw, lr, ls;
+    if (!get_typed(env, words, &tw, &pw, &lw) || !get_typed(env, reals, &tr, &pr, &lr) || !get_typed(env, sigma, &ts, &ps, &ls)) return 0;
+    if (!pw || !pr || tw != napi_float64_array || tr != napi_float64_array) {
+        napi_throw_type_error(env, NULL, ".request <- expected two Float64Arrays");
+        return 0;
+    }
+    if (!ps || ts != napi_float64_array) {
+        napi_throw_type_error(env, NULL, ".sigma <- expected a Float64Array");
+        return 0;
+    }
+    if (!check_len(env, "words", lw, 6) || !check_len(env, "reals", lr, 3)) return 0;
+    if (ls < 2 || ls > FPIC_FUSION_TABLE_MAX) {
+        napi_throw_range_error(env, NULL, ".n <- must be 2 .. FPIC_FUSION_TABLE_MAX (4096)");
+        return 0;
+    }
+    const double* w = (const double*)pw;
+    const double* r = (const double*)pr;
+    for (int k = 0; k < 6; ++k) {
+        const double least = k < 2 ? -2147483648.0 : 0.0, most = k < 2 ? 2147483647.0 : 4294967295.0;
+        const double mag = w[k] < 0 ? -w[k] : w[k];
+        if (!(w[k] >= least && w[k] <= most) || mag != (double)(uint64_t)mag) {
+            napi_throw_range_error(env, NULL, ".request <- a, b, seed, stream and epoch must be integers within their fields");
+            return 0;
+        }
+    }
+    memset(s, 0, sizeof *s);
+    s->species_a = (int32_t)w[0];
+    s->species_b = (int32_t)w[1];
+    s->seed = (uint64_t)(uint32_t)w[2] | (uint64_t)(uint32_t)w[3] << 32;
+    s->stream = (uint32_t)w[4];
+    s->epoch = (uint32_t)w[5];
+    s->tau = r[0];
+    s->g_lo = r[1];
+    s->g_hi = r[2];
+    s->n = (int32_t)ls;
+    s->sigma = (const double*)ps;
+    return 1;
+}
+
+/* a BigInt64Array of the box's cells, or null / undefined (*data = NULL) */
+static int get_fusion_grid(napi_env env, napi_value v, int64_t** data)
+{
+    napi_typedarray_type t; void* p; size_t len;
+    *data = NULL;
+    if (!get_typed(env, v, &t, &p, &len)) return 0;
+    if (!p && !len) return 1;
+    if (!p || t != napi_bigint64_array) { napi_throw_type_error(env, NULL, ".grid <- expected a BigInt64Array"); return 0; }
+    if (!check_len(env, "grid", len, g_box->nodes)) return 0;
+    *data = (int64_t*)p;
+    return 1;
+}
+
+/* the counts; the total yield_hi 2^32 + yield_lo travels as three exact numbers (yieldTop = yield_hi >> 32, yieldMid = its low
+ * word, yieldLo), which the shim joins into a BigInt */
+static napi_value fusion_object(napi_env env, const fpic_fusion_result* c)
+{
+    napi_value o, v;
+    const char* names[11] = { "applications", "pairs", "below", "above", "cells", "overfullCells", "overfullParticles", "yieldTop", "yieldMid", "yieldLo", "unitExponent" };
+    const double vals[11] = { (double)c->applications, (double)c->pairs, (double)c->below, (double)c->above, (double)c->cells, (double)c->overfull_cells,
+                              (double)c->overfull_particles, (double)(c->yield_hi >> 32), (double)(c->yield_hi & 0xFFFFFFFFull), (double)c->yield_lo, (double)c->unit_exponent };
+    NAPI_OK(env, napi_create_object(env, &o));
+    for (int k = 0; k < 11; ++k) {
+        NAPI_OK(env, napi_create_double(env, vals[k], &v));
+        NAPI_OK(env, napi_set_named_property(env, o, names[k], v));
+    }
+    return o;
+}
+
+/* fusionYield(h, words, reals, sigma, grid: BigInt64Array of the cells or null) -> the counts */
+static napi_value n_fusion_yield(napi_env env, napi_callback_info info)
+{
+    napi_value argv[5]; fpic_handle* h; int64_t* grid;
+    fpic_fusion_spec s;
+    if (!get_args(env, info, 5, argv, &h) || !get_fusion_spec(env, argv[1], argv[2], argv[3], &s) || !get_fusion_grid(env, argv[4], &grid)) return NULL;
+    fpic_fusion_result c;
+    memset(&c, 0, sizeof c);
+    if (fpic_fusion(h, &s, &c, grid) != FPIC_OK) return throw_fpic(env, h);
+    return fusion_object(env, &c);
+}
+
+/* fusionYieldEvery(h, words, reals, sigma, every) -> the operator's index */
+static napi_value n_fusion_yield_every(napi_env env, napi_callback_info info)
+{
+    napi_value argv[5]; fpic_handle* h; double every;
+    fpic_fusion_spec s;
+    if (!get_args(env, info, 5, argv, &h) || !get_fusion_spec(env, argv[1], argv[2], argv[3], &s) || !get_double(env, argv[4], &every)) return NULL;
+    if (!(every >= -2147483648.0 && every <= 2147483647.0) || every != (double)(int)every) { napi_throw_range_error(env, NULL, ".every <- must be a 32-bit integer"); return NULL; }
+    int index = -1;
+    if (fpic_fusion_register(h, &s, (int)every, &index) != FPIC_OK) return throw_fpic(env, h);
+    napi_value v;
+    NAPI_OK(env, napi_create_int32(env, index, &v));
+    return v;
+}
+
+/* fusionStats(h, index, scope) -> the totals of a registered tally */
+static napi_value n_fusion_stats(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3]; fpic_handle* h; double index; int scope;
+    if (!get_args(env, info, 3, argv, &h) || !get_double(env, argv[1], &index) || !get_scope(env, argv[2], &scope)) return NULL;
+    if (!(index >= -2147483648.0 && index <= 2147483647.0) || index != (double)(int)index) { napi_throw_range_error(env, NULL, ".index <- must be a 32-bit integer"); return NULL; }
+    fpic_fusion_result c;
+    memset(&c, 0, sizeof c);
+    if (fpic_fusion_stats(h, (int)index, scope, &c) != FPIC_OK) return throw_fpic(env, h);
+    return fusion_object(env, &c);
+}
+
+/* fusionGrid(h, index, grid: BigInt64Array of the cells or null, reset: 0 or 1) */
+static napi_value n_fusion_grid(napi_env env, napi_callback_info info)
+{
+    napi_value argv[4]; fpic_handle* h; double index, reset; int64_t* grid;
+    if (!get_args(env, info, 4, argv, &h) || !get_double(env, argv[1], &index) || !get_fusion_grid(env, argv[2], &grid) || !get_double(env, argv[3], &reset)) return NULL;
+    if (!(index >= -2147483648.0 && index <= 2147483647.0) || index != (double)(int)index) { napi_throw_range_error(env, NULL, ".index <- must be a 32-bit integer"); return NULL; }
+    if (fpic_fusion_grid(h, (int)index, grid, reset != 0) != FPIC_OK) return throw_fpic(env, h);
+    return undefined(env);
+}
+
+/* clearFusion(h) */
+static napi_value n_clear_fusion(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1]; fpic_handle* h;
+    if (!get_args(env, info, 1, argv, &h)) return NULL;
+    if (fpic_fusion_clear(h) != FPIC_OK) return throw_fpic(env, h);
+    return undefined(env);
+}
+
 /* select(h, species, axes: Int32Array, ranges: Float64Array (lo, hi per term), idMod, idRem, capacity, dtype (0: Float32Array,
  * 1: Float64Array), scope) -> { ids: Uint32Array, position, velocity, matched }.  capacity < 0: the count query first, then a
  * call with room for exactly that many rows; capacity 0: the count query alone.  The three arrays are null when `matched`
@@ -1368,7 +1499,9 @@ static napi_value init(napi_env env, napi_value exports)
         { "domainStats", n_domain_stats },
         { "energy", n_energy }, { "recordEnergy", n_record_energy }, { "energyHistory", n_energy_history },
         { "histogram", n_histogram }, { "select", n_select }, { "load", n_load }, { "collide", n_collide }, { "collideEvery", n_collide_every }, { "collisionStats", n_collision_stats }, { "clearCollisions", n_clear_collisions },
-        { "collidePair", n_collide_pair }, { "collidePairEvery", n_collide_pair_every }, { "pairStats", n_pair_stats }, { "clearPairs", n_clear_pairs }, { "moments", n_moments },
+        { "collidePair", n_collide_pair }, { "collidePairEvery", n_collide_pair_every }, { "pairStats", n_pair_stats }, { "clearPairs", n_clear_pairs },
+        { "fusionYield", n_fusion_yield }, { "fusionYieldEvery", n_fusion_yield_every }, { "fusionStats", n_fusion_stats }, { "fusionGrid", n_fusion_grid }, { "clearFusion", n_clear_fusion },
+        { "moments", n_moments },
         { "series", n_series }, { "recordSeries", n_record_series }, { "seriesHistory", n_series_history },
         { "modes", n_modes }, { "recordModes", n_record_modes }, { "modesHistory", n_modes_history },
     };

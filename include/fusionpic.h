@@ -880,6 +880,74 @@ int fpic_pair_register(fpic_handle* h, const fpic_pair_spec* spec, int every, in
 int fpic_pair_stats(fpic_handle* h, int index, int scope, fpic_pair_result* out);
 int fpic_pair_clear(fpic_handle* h);
 
+/* ---- CART3D fusion yield tally: the number of binary reactions between species_a and species_b of the box (species_a ==
+ * species_b: a species with itself, D-D) in the time tau, per grid cell and in total, from a tabulated cross-section.  It is a
+ * TALLY, NOT A SINK: it reads the stored velocities and writes nothing to any particle; reactants are not consumed and no
+ * products are made.  The result depends on the request, the epoch, the particles' ids, their cells and their stored
+ * velocities alone — not on the slots, the binning or the order the kernels visit anything in.  All arithmetic is double,
+ * every operation one of + - x / sqrt and rounded once; the sums are integers, so they are exact.  Velocities are in units
+ * of c.
+ *   cell, order, pairs   exactly those of fpic_pair above (the deposit's cell; ascending by (key, id); unlike species
+ *              many[j] with few[j mod Nf], N_L = Nf, Nm pairs; like species the pairs (s[2t], s[2t+1]) with N_L = N, an odd
+ *              cell's leading triple (s0,s1), (s1,s2), (s2,s0) with N_L = N / 2), but the key is
+ *              Philox4x32-10(counter (id, epoch, stream, 0xF0510), key (seed lo, seed hi))[0]: a tag of its own, so a tally
+ *              never correlates with a Coulomb operator on the same seed.
+ *   one pair   u = v_o - v_p; g = sqrt((ux ux + uy uy) + uz uz).
+ *   the table  n values sigma[k] (m^2, 2 <= n <= FPIC_FUSION_TABLE_MAX, each finite and >= 0) at relative speeds uniform in
+ *              g: g_k = g_lo + k dg, dg = (g_hi - g_lo) / (n - 1), 0 <= g_lo < g_hi finite.  g < g_lo is counted `below`,
+ *              g >= g_hi is counted `above`; both contribute nothing.  Otherwise t = (g - g_lo) inv_dg with
+ *              inv_dg = (n - 1) / (g_hi - g_lo), k = min(floor(t), n - 2), sigma = sigma[k] + (t - k) (sigma[k+1] - sigma[k]),
+ *              held to max sigma (a guard of the last rounding).  With E = m_ab (g c)^2 / 2, 4096 points over 1 keV .. 1 MeV
+ *              (a speed ratio of 32) resolve the low end to better than 1 %.
+ *   yield      y = ((((W W) N_L) tau) / dV) (sigma (g c)) real reactions, W the macro weight, dV the cell volume, c =
+ *              2.998e8.  Unlike species: the pairs of a cell add to W^2 Na Nb <sigma v> tau / dV; like species: the pair
+ *              weights add to N^2 / 2.
+ *   fixed point   y_bound = ((((W W) 2048) tau) / dV) (max sigma (g_hi c)); unit_exponent e = the smallest integer with
+ *              y_bound < 2^(e + 40) (not below -1000); a pair adds q = (int64) floor(y 2^-e) < 2^40 to its cell's word of
+ *              the grid and to the total.  The grid is nz x ny x nx int64, x fastest, in units of 2^e reactions; the total
+ *              is yield_hi 2^32 + yield_lo in the same unit (yield_lo < 2^32).  A cell receives fewer than 2^51 per
+ *              application, so a registered operator's grid is exact for at least 4096 applications between two drains
+ *              (fpic_fusion_grid with reset); nothing detects an overflow beyond that.
+ * A cell holding more than FPIC_PAIR_CELL_MAX particles of either species is skipped: it is counted in overfull_cells and its
+ * particles (both species) in overfull_particles.  A table whose entries are all zero launches nothing; every count but
+ * `applications` is zero and unit_exponent is 0.
+ * fpic_fusion tallies now (synchronous) and returns the counts — applications = 1, pairs (those inside the table), below,
+ * above, cells (the cells that had a pair), overfull_cells, overfull_particles, yield_hi, yield_lo, unit_exponent — and, if
+ * `grid` is not NULL, the nz*ny*nx cell words.  fpic_fusion_register copies the table and makes the tally run at the end of
+ * every sub-step whose number (counted since create) is a multiple of `every`, after the operators of fpic_pair_register
+ * (it sees the collided velocities) and before the recorders, in registration order, with epoch
+ * (uint32)(sub-step + spec.epoch); its grid and totals accumulate on the device with no host synchronisation.  At most
+ * FPIC_FUSION_MAX_OPS operators; *index names the operator.  fpic_fusion_stats reads the totals since registration (or since
+ * the last reset), fpic_fusion_grid copies the operator's grid (grid may be NULL with reset != 0) and, with reset != 0,
+ * zeroes the grid, the totals and `applications` behind the copy in stream order.  fpic_fusion_clear drops every registered
+ * tally.  Registrations are not part of a checkpoint.
+ * Refused (FPIC_ERR_INVALID_ARG): a null spec, a species the handle does not have, a reserved word that is not zero, tau
+ * not (> 0 and finite), n outside 2 .. 4096, a null table, g_lo < 0 or not finite, g_hi <= g_lo or not finite, a table entry
+ * that is negative or not finite, a yield bound that is not finite, every < 1, a fifth registration, an index outside the
+ * registered operators, fpic_fusion_grid with neither a grid nor reset; FPIC_ERR_STATE: a handle that is not CART3D, and a
+ * handle with a domain decomposition (as fpic_pair: a rank cannot pair a cell alone). */
+#define FPIC_FUSION_MAX_OPS   4
+#define FPIC_FUSION_TABLE_MAX 4096
+typedef struct fpic_fusion_spec {
+    int32_t  species_a, species_b;
+    uint64_t seed;
+    uint32_t stream, epoch;
+    double   tau;                  /* s: the time one application stands for, > 0 and finite */
+    double   g_lo, g_hi;           /* units of c: the table's first and last relative speed */
+    int32_t  n, reserved_i;        /* table entries; zero */
+    const double* sigma;           /* n cross-sections, m^2 */
+    double   reserved[4];          /* zero */
+} fpic_fusion_spec;
+typedef struct fpic_fusion_result {
+    uint64_t applications, pairs, below, above, cells, overfull_cells, overfull_particles, yield_hi, yield_lo;
+    int32_t  unit_exponent, reserved;
+} fpic_fusion_result;
+int fpic_fusion(fpic_handle* h, const fpic_fusion_spec* spec, fpic_fusion_result* out, int64_t* grid);
+int fpic_fusion_register(fpic_handle* h, const fpic_fusion_spec* spec, int every, int* index);
+int fpic_fusion_stats(fpic_handle* h, int index, int scope, fpic_fusion_result* out);
+int fpic_fusion_grid(fpic_handle* h, int index, int64_t* grid, int reset);
+int fpic_fusion_clear(fpic_handle* h);
+
 int fpic_sync(fpic_handle* h);
 int fpic_profile(fpic_handle* h, int enable);
 int fpic_get_stats(fpic_handle* h, fpic_stats* out);
