@@ -27,6 +27,7 @@
 //   fes_collide.inc.hpp     Monte Carlo collisions with a prescribed background, now or registered to run after sub-steps
 //   fes_pair.inc.hpp        binary Coulomb collisions between the species (Takizuka-Abe): the cell index of a request, the pairing pass
 //   fes_fusion.inc.hpp      fusion yield tallies between the species: fes_pair's cell index, the tally pass, the cell grids
+//   fes_fusion_spectrum.inc.hpp   fusion product spectra: the tally's pairs and yields binned over an energy axis
 //   fes_mom.inc.hpp         the fluid moment grids: the sweeps of one request, the held planes' places, the ranks' sum
 //   fes_series.inc.hpp      the series: rows of field points and tracer particles, now or into a ring, the ranks' selection
 //   fes_modes.inc.hpp       the modes: Fourier amplitudes of the node fields at chosen wave vectors, now or into a ring, the ranks' sum
@@ -40,6 +41,7 @@
 #include "fes_collide_kernels.hpp"
 #include "fes_pair_kernels.hpp"
 #include "fes_fusion_kernels.hpp"
+#include "fes_fusion_spectrum_kernels.hpp"
 #include "fes_mom_kernels.hpp"
 #include "fes_series_kernels.hpp"
 #include "fes_modes_kernels.hpp"
@@ -360,6 +362,7 @@ namespace {
 #include "fes_collide.inc.hpp"
 #include "fes_pair.inc.hpp"
 #include "fes_fusion.inc.hpp"
+#include "fes_fusion_spectrum.inc.hpp"
 #include "fes_mom.inc.hpp"
 #include "fes_series.inc.hpp"
 #include "fes_modes.inc.hpp"
@@ -367,7 +370,7 @@ namespace {
 // the recording hook, at the end of every sub-step of every path (substeps(), group_run()): counts the sub-step, applies the
 // registered collision operators that are due (fes_collide.inc.hpp against the background, then fes_pair.inc.hpp between the
 // species: the rows below see the collided state), then the fusion yield tallies that are due (fes_fusion.inc.hpp: they read
-// the collided velocities and write no particle), then every
+// the collided velocities and write no particle) and the fusion product spectra (fes_fusion_spectrum.inc.hpp), then every
 // recorder that is due — the energy rows, the series, the modes, which share the counter and nothing else — enqueues its row
 // into its ring.  No host synchronisation, no collective; recording off: nothing is enqueued.
 static int diag_after_substep(fpic_handle* h)
@@ -380,6 +383,8 @@ static int diag_after_substep(fpic_handle* h)
         if (int rc = pair_after_substep(h, g.substep)) return rc;
     if (!g.fusion_ops.empty())
         if (int rc = fusion_after_substep(h, g.substep)) return rc;
+    if (!g.fspec_ops.empty())
+        if (int rc = fspec_after_substep(h, g.substep)) return rc;
     const bool f32 = h->prec == FPIC_F32;
     for (int k = 0; k < kRecorders; ++k) {
         void* row = rec_due(g.rec[k], g.substep);

@@ -57,6 +57,11 @@ int fusion_register(fpic_handle* h, const fpic_fusion_spec* spec, int every, int
 int fusion_stats(fpic_handle* h, int index, int scope, fpic_fusion_result* out);
 int fusion_grid(fpic_handle* h, int index, int64_t* grid, int reset);
 int fusion_clear(fpic_handle* h);
+// fusion product spectra (fes_fusion_spectrum.inc.hpp)
+int fusion_spectrum(fpic_handle* h, const fpic_fusion_spectrum_spec* spec, fpic_fusion_result* out, uint64_t* words);
+int fusion_spectrum_register(fpic_handle* h, const fpic_fusion_spectrum_spec* spec, int every, int* index);
+int fusion_spectrum_read(fpic_handle* h, int index, fpic_fusion_result* out, uint64_t* words, int reset);
+int fusion_spectrum_clear(fpic_handle* h);
 // fluid moment grids (fes_mom.inc.hpp)
 int moments(fpic_handle* h, const fpic_moments_spec* spec, int scope, int64_t* out, fpic_moments_info* info);
 // field points and tracer particles as rows (fes_series.inc.hpp)

@@ -99,6 +99,15 @@ struct FusionOp {
     fesfusion::Rule rule;
 };
 
+// a registered fusion product spectrum (fes_fusion_spectrum.inc.hpp): as FusionOp, with the kernel's form of the axis
+struct FspecOp {
+    fpic_fusion_spectrum_spec spec;
+    int every;
+    uint64_t applications;
+    fesfusion::Rule rule;
+    fesfspec::Rule axis;
+};
+
 // the diagnostics of a handle: the sub-step counter the recorders share, the recorders and their requests, the buffers of the
 // energy reduction (fes_diag.inc.hpp), of the histograms and of the moments, the ranks' gather
 struct Diag {
@@ -132,6 +141,12 @@ struct Diag {
     double* fusion_table = nullptr;
     unsigned long long* fusion_grid[FPIC_FUSION_MAX_OPS + 1] = {};
     std::vector<FusionOp> fusion_ops;   // the registered tallies, in registration order
+    // fpic_fusion_spectrum (fes_fusion_spectrum.inc.hpp), per registered operator and one more for a call: eight count words, a
+    // table of FPIC_FUSION_TABLE_MAX doubles and (FPIC_FUSION_SPECTRUM_BINS_MAX + 2) x 2 words of the histogram
+    unsigned long long* fspec = nullptr;
+    double* fspec_table = nullptr;
+    unsigned long long* fspec_words = nullptr;
+    std::vector<FspecOp> fspec_ops;     // the registered spectra, in registration order
 };
 inline void diag_release(Diag& g)
 {
@@ -139,7 +154,8 @@ inline void diag_release(Diag& g)
         if (r.dev) (void)hipFree(r.dev);
     for (void* p : { g.series_req.block, g.modes_req.block, static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom), g.sel, static_cast<void*>(g.coll), static_cast<void*>(g.pair),
                      static_cast<void*>(g.pair_seg[0]), static_cast<void*>(g.pair_seg[1]), static_cast<void*>(g.pair_index[0]), static_cast<void*>(g.pair_index[1]),
-                     static_cast<void*>(g.fusion), static_cast<void*>(g.fusion_table) })
+                     static_cast<void*>(g.fusion), static_cast<void*>(g.fusion_table),
+                     static_cast<void*>(g.fspec), static_cast<void*>(g.fspec_table), static_cast<void*>(g.fspec_words) })
         if (p) (void)hipFree(p);
     for (unsigned long long* p : g.fusion_grid)
         if (p) (void)hipFree(p);

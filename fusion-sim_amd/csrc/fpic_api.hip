@@ -1557,6 +1557,30 @@ int fpic_fusion_clear(fpic_handle* h)
     BOX_ONLY(h, "fpic_fusion_clear");
     return fes::fusion_clear(h);
 }
+int fpic_fusion_spectrum(fpic_handle* h, const fpic_fusion_spectrum_spec* spec, fpic_fusion_result* out, uint64_t* words)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_fusion_spectrum");
+    return fes::fusion_spectrum(h, spec, out, words);
+}
+int fpic_fusion_spectrum_register(fpic_handle* h, const fpic_fusion_spectrum_spec* spec, int every, int* index)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_fusion_spectrum_register");
+    return fes::fusion_spectrum_register(h, spec, every, index);
+}
+int fpic_fusion_spectrum_read(fpic_handle* h, int index, fpic_fusion_result* out, uint64_t* words, int reset)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_fusion_spectrum_read");
+    return fes::fusion_spectrum_read(h, index, out, words, reset);
+}
+int fpic_fusion_spectrum_clear(fpic_handle* h)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_fusion_spectrum_clear");
+    return fes::fusion_spectrum_clear(h);
+}
 int fpic_get_particles_of(fpic_handle* h, int species, void* pos_aos, void* vel_aos, int dtype)
 {
     CHECK_HANDLE(h);

@@ -50,6 +50,7 @@ ABI_FUNCTIONS = [
     "fpic_select", "fpic_load", "fpic_collide", "fpic_collide_register", "fpic_collide_stats", "fpic_collide_clear",
     "fpic_pair", "fpic_pair_register", "fpic_pair_stats", "fpic_pair_clear",
     "fpic_fusion", "fpic_fusion_register", "fpic_fusion_stats", "fpic_fusion_grid", "fpic_fusion_clear",
+    "fpic_fusion_spectrum", "fpic_fusion_spectrum_register", "fpic_fusion_spectrum_read", "fpic_fusion_spectrum_clear",
 ]
 
 
@@ -567,6 +568,70 @@ def sigma_table(sigma_of_keV, mass_a, mass_b, e_lo_keV, e_hi_keV, n=FUSION_TABLE
     return S, g_lo, g_hi
 
 
+FUSION_SPECTRUM_MAX_OPS = 4
+FUSION_SPECTRUM_BINS_MAX = 256
+FSPEC_CM, FSPEC_PRODUCT = 0, 1
+FSPEC_AXES = {"cm": FSPEC_CM, "product": FSPEC_PRODUCT}
+KEV = 1.602176634e-16            # one keV in joules: the unit of a spectrum's axis is the joule
+
+
+class FusionSpectrumSpec(ctypes.Structure):
+    """mirror of fpic_fusion_spectrum_spec (include/fusionpic.h)"""
+    _fields_ = [
+        ("tally", FusionSpec), ("axis", ctypes.c_int32), ("bins", ctypes.c_int32), ("lo", ctypes.c_double), ("hi", ctypes.c_double), ("q_value", ctypes.c_double),
+        ("product_mass", ctypes.c_double), ("other_mass", ctypes.c_double), ("los", ctypes.c_double * 3), ("reserved", ctypes.c_double * 4),
+    ]
+
+
+def _fusion_spectrum_spec(tau_default, a=0, b=None, axis="product", bins=None, lo=None, hi=None, q_value=0.0, product_mass=0.0, other_mass=0.0, los=None, **request):
+    """FusionSpectrumSpec of a product spectrum: the tally's request (see _fusion_spec), the axis ("product": the laboratory
+    energy of the product of mass product_mass, the other product having other_mass; "cm": the reacting centre-of-mass
+    energy), `bins` bins over [lo, hi) joules, the reaction's q_value (J), the line of sight los (None or zeros: isotropic
+    emission).  Only what the structure cannot carry is refused here; the library checks the rest.  The spec keeps the table
+    alive (spec._table)."""
+    s = FusionSpectrumSpec()
+    tally = _fusion_spec(tau_default, a, b, **request)
+    s._table = tally._table
+    s.tally = tally
+    if not isinstance(axis, str) or axis not in FSPEC_AXES:
+        raise FusionPicError(-1, ".axis <- must be one of cm, product")
+    s.axis = FSPEC_AXES[axis]
+    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not -(1 << 31) <= int(bins) < 1 << 31:
+        raise FusionPicError(-1, ".bins <- must be a signed 32-bit integer")
+    s.bins = int(bins)
+
+    def real(name, v):
+        if v is None:
+            raise FusionPicError(-1, ".%s <- Non-optional property is undefined!" % name)
+        try:
+            return float(v)
+        except (TypeError, ValueError):
+            raise FusionPicError(-1, ".%s <- must be a number" % name)
+
+    s.lo, s.hi, s.q_value = real("lo", lo), real("hi", hi), real("q_value", q_value)
+    s.product_mass, s.other_mass = real("product_mass", product_mass), real("other_mass", other_mass)
+    if los is not None:
+        try:
+            v = [float(x) for x in los]
+        except (TypeError, ValueError):
+            raise FusionPicError(-1, ".los <- must be three numbers")
+        if len(v) != 3:
+            raise FusionPicError(-1, ".los <- must be three numbers")
+        s.los[0], s.los[1], s.los[2] = v
+    return s
+
+
+def _fusion_spectrum_result(r, words, lo, hi):
+    """the counts of _fusion_counts, the edges, the exact entries as Python integers and the bins as floats (reactions)"""
+    got = _fusion_counts(r)
+    exact = [(int(words[k, 0]) << 32) + int(words[k, 1]) for k in range(len(words))]
+    nbins = len(exact) - 2
+    got["edges"] = lo + (hi - lo) * np.arange(nbins + 1, dtype=np.float64) / nbins
+    got["bins"], got["under"], got["over"] = exact[:nbins], exact[nbins], exact[nbins + 1]
+    got["yield"] = np.array([float(np.ldexp(float(x), got["unit_exponent"])) for x in exact[:nbins]], dtype=np.float64)
+    return got
+
+
 SERIES_MAX_POINTS = 4096
 SERIES_MAX_TRACERS = 65536
 # the columns of a point row and of a tracer row (fpic_series_*): 8 doubles each
@@ -816,6 +881,10 @@ def load_library(path=None):
     lib.fpic_fusion_stats.argtypes = [vp, ci, ci, ctypes.POINTER(FusionResult)]
     lib.fpic_fusion_grid.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_int64), ci]
     lib.fpic_fusion_clear.argtypes = [vp]
+    lib.fpic_fusion_spectrum.argtypes = [vp, ctypes.POINTER(FusionSpectrumSpec), ctypes.POINTER(FusionResult), ctypes.POINTER(ctypes.c_uint64)]
+    lib.fpic_fusion_spectrum_register.argtypes = [vp, ctypes.POINTER(FusionSpectrumSpec), ci, ctypes.POINTER(ctypes.c_int)]
+    lib.fpic_fusion_spectrum_read.argtypes = [vp, ci, ctypes.POINTER(FusionResult), ctypes.POINTER(ctypes.c_uint64), ci]
+    lib.fpic_fusion_spectrum_clear.argtypes = [vp]
     if path == LIB_PATH:
         _lib = lib
     return lib
@@ -1244,6 +1313,52 @@ class CylindricalParticlePusher:
         """drops every registered yield tally (fpic_fusion_clear)"""
         self._check(self._lib.fpic_fusion_clear(self._h))
 
+    # ---- fusion product spectra (fpic_fusion_spectrum*)
+    def fusionSpectrum(self, a=0, b=None, **request):
+        """The yield of fusionYield(a, b, sigma=, g_lo=, g_hi=, tau=, seed=, stream=, epoch=) distributed over an energy axis
+        (fpic_fusion_spectrum; an (r,z) handle and a decomposed handle are refused).  axis="product": the laboratory energy
+        of the product of mass product_mass (kg; the other product has other_mass) of a reaction that releases q_value (J),
+        emitted isotropically (los None) or along the line of sight los; axis="cm": the reacting centre-of-mass energy.
+        bins (1 .. 256) bins over [lo, hi) joules (KEV is one keV).  A tally: no particle is changed.  Returns the counts of
+        fusionYield for the same request (reactions_exact counts every pair inside the table) and edges (bins + 1 floats, J),
+        bins (exact Python integers in units of 2**unit_exponent reactions), under, over (likewise: the yield below lo and at
+        or above hi) and yield (the bins as floats, reactions).  sum(bins) + under + over == reactions_exact."""
+        s = _fusion_spectrum_spec(float(self.spec["dt"]), a, b, **request)
+        out = FusionResult()
+        words = np.zeros((max(s.bins, 0) + 2, 2), dtype=np.uint64)
+        self._check(self._lib.fpic_fusion_spectrum(self._h, ctypes.byref(s), ctypes.byref(out), words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64))))
+        return _fusion_spectrum_result(out, words, s.lo, s.hi)
+
+    def fusionSpectrumEvery(self, every, a=0, b=None, **request):
+        """Registers a spectrum (see fusionSpectrum) to run at the end of every `every`-th sub-step, after the tallies of
+        fusionYieldEvery and before the recorders, with epoch = the sub-step number + `epoch`; tau defaults to every * dt.
+        The table is copied.  Returns the operator's index (fpic_fusion_spectrum_register); at most FUSION_SPECTRUM_MAX_OPS."""
+        if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or not -(1 << 31) <= int(every) < 1 << 31:
+            raise FusionPicError(-1, ".every <- must be a signed 32-bit integer")
+        s = _fusion_spectrum_spec(int(every) * float(self.spec["dt"]), a, b, **request)
+        index = ctypes.c_int(-1)
+        self._check(self._lib.fpic_fusion_spectrum_register(self._h, ctypes.byref(s), int(every), ctypes.byref(index)))
+        if getattr(self, "_fspec_axes", None) is None:
+            self._fspec_axes = {}                     # the bins and the range of the registered spectra, by index: what a read needs
+        self._fspec_axes[index.value] = (s.bins, s.lo, s.hi)
+        return index.value
+
+    def fusionSpectrumRead(self, index, reset=False):
+        """the totals and the spectrum of a registered operator since its registration or its last reset, as fusionSpectrum
+        returns them (fpic_fusion_spectrum_read); reset=True zeroes them and `applications` behind the copy.  Exact for at
+        least 2**23 applications between two resets; nothing detects an overflow beyond that."""
+        # (an index that was not registered here: room for the cap, and the library refuses it)
+        bins, lo, hi = (getattr(self, "_fspec_axes", None) or {}).get(int(index), (FUSION_SPECTRUM_BINS_MAX, 0.0, 1.0))
+        out = FusionResult()
+        words = np.zeros((bins + 2, 2), dtype=np.uint64)
+        self._check(self._lib.fpic_fusion_spectrum_read(self._h, int(index), ctypes.byref(out), words.ctypes.data_as(ctypes.POINTER(ctypes.c_uint64)), 1 if reset else 0))
+        return _fusion_spectrum_result(out, words, lo, hi)
+
+    def clearFusionSpectra(self):
+        """drops every registered spectrum (fpic_fusion_spectrum_clear)"""
+        self._check(self._lib.fpic_fusion_spectrum_clear(self._h))
+        self._fspec_axes = {}
+
     # ---- series: the field at points and the state of tracer particles as rows (fpic_series_*)
     def series(self, points=None, tracers=None, species=0, scope="global"):
         """The rows of the current state of a CART3D box (fpic_series_now; an (r,z) handle is refused).  points: positions in
@@ -1554,6 +1669,10 @@ class ElectrostaticBoxPusher:
     fusionStats = CylindricalParticlePusher.fusionStats
     fusionGrid = CylindricalParticlePusher.fusionGrid
     clearFusion = CylindricalParticlePusher.clearFusion
+    fusionSpectrum = CylindricalParticlePusher.fusionSpectrum
+    fusionSpectrumEvery = CylindricalParticlePusher.fusionSpectrumEvery
+    fusionSpectrumRead = CylindricalParticlePusher.fusionSpectrumRead
+    clearFusionSpectra = CylindricalParticlePusher.clearFusionSpectra
     count = CylindricalParticlePusher.count
     series = CylindricalParticlePusher.series
     recordSeries = CylindricalParticlePusher.recordSeries
@@ -1696,6 +1815,22 @@ class BoxGroup:
     def clearFusion(self):
         """refused, see fusionYield"""
         raise FusionPicError(-5, _PAIR_DECOMPOSED % "clearFusion")
+
+    def fusionSpectrum(self, a=0, b=None, **request):
+        """refused, see fusionYield"""
+        raise FusionPicError(-5, _PAIR_DECOMPOSED % "fusionSpectrum")
+
+    def fusionSpectrumEvery(self, every, a=0, b=None, **request):
+        """refused, see fusionYield"""
+        raise FusionPicError(-5, _PAIR_DECOMPOSED % "fusionSpectrumEvery")
+
+    def fusionSpectrumRead(self, index, reset=False):
+        """refused, see fusionYield"""
+        raise FusionPicError(-5, _PAIR_DECOMPOSED % "fusionSpectrumRead")
+
+    def clearFusionSpectra(self):
+        """refused, see fusionYield"""
+        raise FusionPicError(-5, _PAIR_DECOMPOSED % "clearFusionSpectra")
 
     def count(self, where=None, species=0, every=None):
         """the whole box: the members' LOCAL counts (each its own particles) added up"""

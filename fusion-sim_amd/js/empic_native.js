@@ -491,6 +491,62 @@ function makeBox(spec, lib) {
         return grid;
     };
     out.clearFusion = function () { lib.clearFusion(h); };
+    // fusion product spectra (fpic_fusion_spectrum*): the yield of a fusionYield request distributed over an energy axis.
+    // request = the request of fusionYield and { axis: 'product' (default) or 'cm', bins (1 .. 256), lo, hi (J), qValue (J),
+    // productMass, otherMass (kg; axis 'product'), los: [x, y, z] (absent or zeros: isotropic emission) }.  fusionSpectrum ->
+    // the counts of fusionYield and { edges (Float64Array of bins + 1, J), bins (an array of BigInts in units of
+    // 2^unitExponent reactions), under, over (BigInts), yield (Float64Array, reactions) }: the bins, under and over add to
+    // reactionsExact.  fusionSpectrumEvery(every, request) -> the operator's index; fusionSpectrumRead(index, reset) -> its
+    // totals and words since registration or the last reset, reset = true zeroes them behind the copy; clearFusionSpectra()
+    // drops every spectrum
+    const spectrumAxes = new Map();
+    const spectrumArgs = function (request, tauDefault) {
+        const a = fusionArgs(request, tauDefault);
+        const real = function (name, v, dflt) {
+            if (v === undefined || v === null) v = dflt;
+            if (typeof v !== 'number') throw new RangeError('.' + name + ' <- expected a number');
+            return v;
+        };
+        const kind = request.axis === undefined || request.axis === null ? 'product' : request.axis;
+        if (kind !== 'product' && kind !== 'cm') throw new RangeError('.axis <- expected \'product\' or \'cm\'');
+        if (!Number.isInteger(request.bins) || request.bins < 1 || request.bins > 256) throw new RangeError('.bins <- must be 1 .. FPIC_FUSION_SPECTRUM_BINS_MAX (256)');
+        let los = request.los === undefined || request.los === null ? [0, 0, 0] : request.los;
+        if (!Array.isArray(los) || los.length !== 3 || !los.every((x) => typeof x === 'number')) throw new TypeError('.los <- expected three numbers');
+        const axis = Float64Array.from([kind === 'cm' ? 0 : 1, request.bins, real('lo', request.lo, undefined), real('hi', request.hi, undefined), real('qValue', request.qValue, 0),
+            real('productMass', request.productMass, 0), real('otherMass', request.otherMass, 0), los[0], los[1], los[2]]);
+        return [a[0], a[1], a[2], axis];
+    };
+    const spectrumResult = function (r, words, axis) {
+        r = fusionCounts(r);
+        const bins = axis.bins;
+        const entry = (k) => (words[2 * k] << 32n) + words[2 * k + 1];
+        r.edges = Float64Array.from({ length: bins + 1 }, (_, k) => axis.lo + (axis.hi - axis.lo) * k / bins);
+        r.bins = Array.from({ length: bins }, (_, k) => entry(k));
+        r.under = entry(bins);
+        r.over = entry(bins + 1);
+        r.yield = Float64Array.from(r.bins, (x) => Number(x) * Math.pow(2, r.unitExponent));
+        return r;
+    };
+    out.fusionSpectrum = function (request) {
+        const a = spectrumArgs(request, spec.dt);
+        const axis = { bins: a[3][1], lo: a[3][2], hi: a[3][3] };
+        const words = new BigUint64Array(2 * (axis.bins + 2));
+        return spectrumResult(lib.fusionSpectrum(h, a[0], a[1], a[2], a[3], words), words, axis);
+    };
+    out.fusionSpectrumEvery = function (every, request) {
+        if (!Number.isInteger(every) || every < -0x80000000 || every > 0x7fffffff) throw new RangeError('.every <- expected a 32-bit integer');
+        const a = spectrumArgs(request, every * spec.dt);
+        const index = lib.fusionSpectrumEvery(h, a[0], a[1], a[2], a[3], every);
+        spectrumAxes.set(index, { bins: a[3][1], lo: a[3][2], hi: a[3][3] });
+        return index;
+    };
+    out.fusionSpectrumRead = function (index, reset) {
+        if (!Number.isInteger(index) || index < -0x80000000 || index > 0x7fffffff) throw new RangeError('.index <- expected a 32-bit integer');
+        const axis = spectrumAxes.get(index) || { bins: 256, lo: 0, hi: 1 };      // (an unknown index: the library refuses it)
+        const words = new BigUint64Array(2 * (256 + 2));                          // (room for the cap: the addon checks it)
+        return spectrumResult(lib.fusionSpectrumRead(h, index, words, reset ? 1 : 0), words, axis);
+    };
+    out.clearFusionSpectra = function () { lib.clearFusionSpectra(h); spectrumAxes.clear(); };
     // series (fpic_series_*): the field at points and the state of tracer particles as rows of 8 doubles, now or recorded into a
     // device ring.  request = { points: [[x, y, z], ...] in metres (wrapped periodically), tracers: particle indices, species: one
     // index or one per tracer (default 0) }; either list may be missing, not both.  A point row is Ex Ey Ez phi Bx By Bz present,

@@ -1218,6 +1218,99 @@ static napi_value n_clear_fusion(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* the request of fusionSpectrum / fusionSpectrumEvery: the tally's three arrays (get_fusion_spec) and axis: Float64Array
+ * [axis, bins, lo, hi, q_value, product_mass, other_mass, los x, los y, los z].  The array's type and length and the two
+ * integers' ranges are checked here, the request itself by the library. */
+static int get_fusion_spectrum_spec(napi_env env, napi_value words, napi_value reals, napi_value sigma, napi_value axis, fpic_fusion_spectrum_spec* s)
+{
+    memset(s, 0, sizeof *s);
+    if (!get_fusion_spec(env, words, reals, sigma, &s->tally)) return 0;
+    napi_typedarray_type t; void* p; size_t len;
+    if (!get_typed(env, axis, &t, &p, &len)) return 0;
+    if (!p || t != napi_float64_array) { napi_throw_type_error(env, NULL, ".axis <- expected a Float64Array"); return 0; }
+    if (!check_len(env, "axis", len, 10)) return 0;
+    const double* a = (const double*)p;
+    for (int k = 0; k < 2; ++k)
+        if (!(a[k] >= -2147483648.0 && a[k] <= 2147483647.0) || a[k] != (double)(int)a[k]) {
+            napi_throw_range_error(env, NULL, ".axis <- axis and bins must be 32-bit integers");
+            return 0;
+        }
+    s->axis = (int32_t)a[0];
+    s->bins = (int32_t)a[1];
+    s->lo = a[2];
+    s->hi = a[3];
+    s->q_value = a[4];
+    s->product_mass = a[5];
+    s->other_mass = a[6];
+    for (int k = 0; k < 3; ++k) s->los[k] = a[7 + k];
+    return 1;
+}
+
+/* a BigUint64Array of `entries` x 2 words, or null / undefined (*data = NULL) */
+static int get_fusion_words(napi_env env, napi_value v, size_t entries, uint64_t** data)
+{
+    napi_typedarray_type t; void* p; size_t len;
+    *data = NULL;
+    if (!get_typed(env, v, &t, &p, &len)) return 0;
+    if (!p && !len) return 1;
+    if (!p || t != napi_biguint64_array) { napi_throw_type_error(env, NULL, ".words <- expected a BigUint64Array"); return 0; }
+    if (!check_len(env, "words", len, 2 * entries)) return 0;
+    *data = (uint64_t*)p;
+    return 1;
+}
+
+/* fusionSpectrum(h, words, reals, sigma, axis, out: BigUint64Array of (bins + 2) x 2 words or null) -> the counts */
+static napi_value n_fusion_spectrum(napi_env env, napi_callback_info info)
+{
+    napi_value argv[6]; fpic_handle* h; uint64_t* out;
+    fpic_fusion_spectrum_spec s;
+    if (!get_args(env, info, 6, argv, &h) || !get_fusion_spectrum_spec(env, argv[1], argv[2], argv[3], argv[4], &s)) return NULL;
+    if (s.bins < 1 || s.bins > FPIC_FUSION_SPECTRUM_BINS_MAX) { napi_throw_range_error(env, NULL, ".bins <- must be 1 .. FPIC_FUSION_SPECTRUM_BINS_MAX (256)"); return NULL; }
+    if (!get_fusion_words(env, argv[5], (size_t)s.bins + 2, &out)) return NULL;
+    fpic_fusion_result c;
+    memset(&c, 0, sizeof c);
+    if (fpic_fusion_spectrum(h, &s, &c, out) != FPIC_OK) return throw_fpic(env, h);
+    return fusion_object(env, &c);
+}
+
+/* fusionSpectrumEvery(h, words, reals, sigma, axis, every) -> the operator's index */
+static napi_value n_fusion_spectrum_every(napi_env env, napi_callback_info info)
+{
+    napi_value argv[6]; fpic_handle* h; double every;
+    fpic_fusion_spectrum_spec s;
+    if (!get_args(env, info, 6, argv, &h) || !get_fusion_spectrum_spec(env, argv[1], argv[2], argv[3], argv[4], &s) || !get_double(env, argv[5], &every)) return NULL;
+    if (!(every >= -2147483648.0 && every <= 2147483647.0) || every != (double)(int)every) { napi_throw_range_error(env, NULL, ".every <- must be a 32-bit integer"); return NULL; }
+    int index = -1;
+    if (fpic_fusion_spectrum_register(h, &s, (int)every, &index) != FPIC_OK) return throw_fpic(env, h);
+    napi_value v;
+    NAPI_OK(env, napi_create_int32(env, index, &v));
+    return v;
+}
+
+/* fusionSpectrumRead(h, index, out: BigUint64Array of (FPIC_FUSION_SPECTRUM_BINS_MAX + 2) x 2 words or null, reset: 0 or 1) ->
+ * the counts.  Only the library knows the operator's bins, so the array always has room for the cap: the first
+ * (bins + 2) x 2 words are written. */
+static napi_value n_fusion_spectrum_read(napi_env env, napi_callback_info info)
+{
+    napi_value argv[4]; fpic_handle* h; double index, reset; uint64_t* out;
+    if (!get_args(env, info, 4, argv, &h) || !get_double(env, argv[1], &index) || !get_fusion_words(env, argv[2], FPIC_FUSION_SPECTRUM_BINS_MAX + 2, &out) ||
+        !get_double(env, argv[3], &reset)) return NULL;
+    if (!(index >= -2147483648.0 && index <= 2147483647.0) || index != (double)(int)index) { napi_throw_range_error(env, NULL, ".index <- must be a 32-bit integer"); return NULL; }
+    fpic_fusion_result c;
+    memset(&c, 0, sizeof c);
+    if (fpic_fusion_spectrum_read(h, (int)index, &c, out, reset != 0) != FPIC_OK) return throw_fpic(env, h);
+    return fusion_object(env, &c);
+}
+
+/* clearFusionSpectra(h) */
+static napi_value n_clear_fusion_spectra(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1]; fpic_handle* h;
+    if (!get_args(env, info, 1, argv, &h)) return NULL;
+    if (fpic_fusion_spectrum_clear(h) != FPIC_OK) return throw_fpic(env, h);
+    return undefined(env);
+}
+
 /* select(h, species, axes: Int32Array, ranges: Float64Array (lo, hi per term), idMod, idRem, capacity, dtype (0: Float32Array,
  * 1: Float64Array), scope) -> { ids: Uint32Array, position, velocity, matched }.  capacity < 0: the count query first, then a
  * call with room for exactly that many rows; capacity 0: the count query alone.  The three arrays are null when `matched`
@@ -1501,6 +1594,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "histogram", n_histogram }, { "select", n_select }, { "load", n_load }, { "collide", n_collide }, { "collideEvery", n_collide_every }, { "collisionStats", n_collision_stats }, { "clearCollisions", n_clear_collisions },
         { "collidePair", n_collide_pair }, { "collidePairEvery", n_collide_pair_every }, { "pairStats", n_pair_stats }, { "clearPairs", n_clear_pairs },
         { "fusionYield", n_fusion_yield }, { "fusionYieldEvery", n_fusion_yield_every }, { "fusionStats", n_fusion_stats }, { "fusionGrid", n_fusion_grid }, { "clearFusion", n_clear_fusion },
+        { "fusionSpectrum", n_fusion_spectrum }, { "fusionSpectrumEvery", n_fusion_spectrum_every }, { "fusionSpectrumRead", n_fusion_spectrum_read }, { "clearFusionSpectra", n_clear_fusion_spectra },
         { "moments", n_moments },
         { "series", n_series }, { "recordSeries", n_record_series }, { "seriesHistory", n_series_history },
         { "modes", n_modes }, { "recordModes", n_record_modes }, { "modesHistory", n_modes_history },

@@ -948,6 +948,62 @@ int fpic_fusion_stats(fpic_handle* h, int index, int scope, fpic_fusion_result* 
 int fpic_fusion_grid(fpic_handle* h, int index, int64_t* grid, int reset);
 int fpic_fusion_clear(fpic_handle* h);
 
+/* ---- CART3D fusion product spectra: the yield of a fpic_fusion request (spec.tally) distributed over an energy axis, summed
+ * over all pairs of the box — the laboratory energy of one reaction product as a detector would see it (FPIC_FSPEC_PRODUCT:
+ * its width is the ion-temperature diagnostic, its shift along a line of sight separates beam-target from thermonuclear
+ * yield) or the reacting centre-of-mass energy (FPIC_FSPEC_CM: where the Gamow peak sits).  It is a tally and writes nothing
+ * to any particle.  The cells, the key (tag 0xF0510), the order, the pairs, the table and the integer q of every pair are
+ * those of fpic_fusion above, so THE WORDS ADD TO THE TALLY: the sum of all bins plus `under` plus `over` equals the yield
+ * fpic_fusion reports for spec.tally at the same epoch, as integers, and pairs, below, above, cells, overfull_cells,
+ * overfull_particles and unit_exponent are equal as well.  All arithmetic is double, every operation one of + - x / sqrt and
+ * rounded once; non-relativistic kinematics.
+ *   host numbers   m_a, m_b the species' masses, m3 = product_mass, m4 = other_mass: M = m_a + m_b; f_a = m_a / M,
+ *              f_b = m_b / M; m_ab = (m_a m_b) / M; cc = c c, c = 2.998e8; hk = (0.5 m_ab) cc; kf = ((2 m4) / (m3 (m3 + m4))) / cc;
+ *              h3 = (0.5 m3) cc; inv_w = bins / (hi - lo); a line of sight n = los / sqrt((lx lx + ly ly) + lz lz).
+ *   one pair   inside the table, owner o, partner p, g as in fpic_fusion: K = hk (g g).  Axis CM: x = K.  Axis PRODUCT:
+ *              Et = q_value + K, held to 0 from below; u3 = sqrt(Et kf); V_i = (f_o v_o,i) + (f_p v_p,i) with f_o the mass
+ *              fraction of the owner's species; w_i = V_i + (u3 n_i); x = h3 ((w_x w_x + w_y w_y) + w_z w_z).
+ *   isotropic  los all zero: n is drawn exactly, with no trigonometry, from the blocks Philox4x32-10(counter (id_o, epoch,
+ *              stream, 0xF0520 + 16 [the owner is of species_b and a != b] + a), key seed), a = 0 .. 7, two tries each, (w0, w1)
+ *              then (w2, w3): x1 = ((w + 0.5) 2^-31) - 1, x2 likewise, s = x1 x1 + x2 x2; the first try with s < 1 gives
+ *              r = sqrt(1 - s), n = ((2 x1) r, (2 x2) r, 1 - (2 s)); after sixteen rejections (probability 2e-11) n = (0, 0, 1).
+ *   binning    x < lo adds q to `under`, !(x < hi) to `over`; otherwise bin min((int)((x - lo) inv_w), bins - 1) gets q.
+ *   the words  words[bins + 2][2]: entry k < bins is bin k, entry bins is `under`, entry bins + 1 is `over`; an entry is
+ *              (hi, lo) with lo < 2^32 and stands for hi 2^32 + lo in units of 2^unit_exponent reactions.  A registered
+ *              operator is exact for at least 2^23 applications between two drains (fpic_fusion_spectrum_read with reset);
+ *              nothing detects an overflow beyond that.
+ * fpic_fusion_spectrum tallies now (synchronous): `out` is what fpic_fusion returns for spec.tally (the yield counts every
+ * pair inside the table, inside or outside [lo, hi)), `words` the (bins + 2) x 2 words; either may be NULL.
+ * fpic_fusion_spectrum_register copies the table and makes the spectrum run at the end of every sub-step whose number is a
+ * multiple of `every`, after the operators of fpic_fusion_register and before the recorders, in registration order, with
+ * epoch (uint32)(sub-step + spec.tally.epoch); its words accumulate on the device with no host synchronisation.  At most
+ * FPIC_FUSION_SPECTRUM_MAX_OPS operators.  fpic_fusion_spectrum_read copies the totals and the words since registration or
+ * the last reset and, with reset != 0, zeroes them and `applications` behind the copy in stream order (out and words may be
+ * NULL with reset != 0).  fpic_fusion_spectrum_clear drops every registered spectrum.  Registrations are not part of a
+ * checkpoint.
+ * Refused (FPIC_ERR_INVALID_ARG): a null spec, whatever fpic_fusion refuses of spec.tally, a reserved word that is not zero,
+ * an axis that is neither, bins outside 1 .. 256, lo not finite, hi <= lo or not finite, q_value not finite, (axis PRODUCT) a
+ * mass not (> 0 and finite), a line of sight that is not finite or whose norm is zero or not finite, every < 1, a fifth
+ * registration, an index outside the registered operators, a read with neither out, words nor reset; FPIC_ERR_STATE: a
+ * handle that is not CART3D, and a handle with a domain decomposition (as fpic_fusion: a rank cannot pair a cell alone). */
+#define FPIC_FUSION_SPECTRUM_MAX_OPS  4
+#define FPIC_FUSION_SPECTRUM_BINS_MAX 256
+#define FPIC_FSPEC_CM      0
+#define FPIC_FSPEC_PRODUCT 1
+typedef struct fpic_fusion_spectrum_spec {
+    fpic_fusion_spec tally;        /* the pairs and their yields */
+    int32_t  axis, bins;           /* FPIC_FSPEC_*; 1 .. FPIC_FUSION_SPECTRUM_BINS_MAX */
+    double   lo, hi;               /* J: the axis' range [lo, hi) */
+    double   q_value;              /* J: the reaction's energy release, may be negative */
+    double   product_mass, other_mass;   /* kg: the product that is binned and the other one (axis PRODUCT) */
+    double   los[3];               /* the line of sight; all zero: isotropic emission */
+    double   reserved[4];          /* zero */
+} fpic_fusion_spectrum_spec;
+int fpic_fusion_spectrum(fpic_handle* h, const fpic_fusion_spectrum_spec* spec, fpic_fusion_result* out, uint64_t* words);
+int fpic_fusion_spectrum_register(fpic_handle* h, const fpic_fusion_spectrum_spec* spec, int every, int* index);
+int fpic_fusion_spectrum_read(fpic_handle* h, int index, fpic_fusion_result* out, uint64_t* words, int reset);
+int fpic_fusion_spectrum_clear(fpic_handle* h);
+
 int fpic_sync(fpic_handle* h);
 int fpic_profile(fpic_handle* h, int enable);
 int fpic_get_stats(fpic_handle* h, fpic_stats* out);

@@ -1,0 +1,414 @@
+"""The fusion product spectrum (fpic_fusion_spectrum*) on a machine WITHOUT a GPU: the header declares the entry points and
+libfusionpic.so exports them, the ctypes mirror has the C layout, the rule (fusion-sim_amd/csrc/fes_fusion_spectrum_core.hpp)
+passes its g++ test and agrees bit for bit with the numpy restatement (tests/fusion_spectrum_reference.py) on random pairs, per
+axis, with a line of sight and with isotropic emission — both also as a stand-alone program under AddressSanitizer and UBSan —,
+the directions are unit vectors and isotropic, the kernel's LDS budget keeps two workgroups on a CU, the Python wrapper builds
+the request, a call without a handle fails cleanly, and the restatement alone reproduces the Doppler width of the D-T neutron
+line and the mean reacting energy of the Gamow peak.  The spectrum itself is checked on the GPU
+(tests/test_gpu_fusion_spectrum.py).
+
+Physics, measured here (test_the_neutron_line_has_brysks_width and test_the_cm_spectrum_sits_on_the_gamow_peak print it): 8 cells
+of about 2000 deuterons and 2000 tritons at 10 keV, sigma(E) = (A / E) exp(-B / sqrt(E)), B = 34.38 keV^1/2, a table of 4096
+points over 0.2 .. 300 keV, the neutron of a reaction releasing 17.59 MeV, 256 bins over 12.0 .. 16.2 MeV.  Over 8 seeds the
+yield-weighted standard deviation of the spectrum over Brysk's sqrt(2 m_n <E_n> T / (m_n + m_alpha)) is 0.9980 +- 0.0039 for
+isotropic emission and 0.9914 +- 0.0026 along the line of sight (1, 2, -2); the formula's own bias at this temperature (the
+spread of the reacting energy and of the centre-of-mass energy, which it neglects, both of order T / E_0 = 7e-4) is +0.0017.
+(32 other seeds, outside the suite: 1.003 +- 0.002 along that line of sight, 1.002 +- 0.002 isotropic.)  The yield-weighted
+mean of the centre-of-mass spectrum over the numpy quadrature of the Gamow integrand (39.38 keV) is 1.0042 +- 0.0035; halving
+n moves it by 7.7e-7.  The tolerances are three of those standard errors plus that bias (the width) and plus the table's
+interpolation error (the mean), all computed in the
+tests."""
+import ctypes
+import os
+import re
+import subprocess
+
+import numpy as np
+import pytest
+
+import fusion_reference as ref
+import fusion_spectrum_reference as sref
+from helpers import ROOT
+
+HEADER = os.path.join(ROOT, "include", "fusionpic.h")
+LIB = os.path.join(ROOT, "fusion-sim_amd", "lib", "libfusionpic.so")
+CSRC = os.path.join(ROOT, "fusion-sim_amd", "csrc")
+NATIVE = os.path.join(ROOT, "tests", "native", "fusion_spectrum_core_test.cpp")
+SPEC = r"fpic_handle\s*\*\s*h\s*,\s*const\s+fpic_fusion_spectrum_spec\s*\*\s*spec\s*,\s*"
+ENTRIES = {
+    "fpic_fusion_spectrum": SPEC + r"fpic_fusion_result\s*\*\s*out\s*,\s*uint64_t\s*\*\s*words",
+    "fpic_fusion_spectrum_register": SPEC + r"int\s+every\s*,\s*int\s*\*\s*index",
+    "fpic_fusion_spectrum_read": r"fpic_handle\s*\*\s*h\s*,\s*int\s+index\s*,\s*fpic_fusion_result\s*\*\s*out\s*,\s*uint64_t\s*\*\s*words\s*,\s*int\s+reset",
+    "fpic_fusion_spectrum_clear": r"fpic_handle\s*\*\s*h",
+}
+SAN = ["-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-fno-omit-frame-pointer"]
+EPS = float(np.finfo(np.float64).eps)
+MD, MT, MN, MA = 3.3435837724e-27, 5.0073567446e-27, 1.67492749804e-27, 6.6446573357e-27
+KEV = 1.602176634e-16
+Q_DT = 17590.0 * KEV
+
+
+@pytest.fixture(scope="module")
+def fp():
+    if not os.path.exists(LIB):
+        import __graft_entry__
+        __graft_entry__.build()
+    import fusionpic
+    return fusionpic
+
+
+def test_spectrum_declared_exported_and_listed(fp):
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    lib = ctypes.CDLL(LIB)
+    for name, args in ENTRIES.items():
+        assert re.search(r"\bint\s+%s\s*\(\s*%s\s*\)" % (name, args), text), name
+        assert hasattr(lib, name) and name in fp.ABI_FUNCTIONS
+    for name, value in (("MAX_OPS", 4), ("BINS_MAX", 256)):
+        assert re.search(r"#define\s+FPIC_FUSION_SPECTRUM_%s\s+%d\b" % (name, value), text) and getattr(fp, "FUSION_SPECTRUM_" + name) == value
+    for name, value in (("CM", 0), ("PRODUCT", 1)):
+        assert re.search(r"#define\s+FPIC_FSPEC_%s\s+%d\b" % (name, value), text) and getattr(fp, "FSPEC_" + name) == value == getattr(sref, name)
+    assert fp.KEV == KEV and sref.BINS_MAX == fp.FUSION_SPECTRUM_BINS_MAX and sref.DIR_TAG not in (ref.TAG, 0xC0120)
+
+
+def test_the_spectrum_keeps_two_workgroups_on_a_cu():
+    """the histogram of (256 + 2) x 2 64-bit words in front of the run's LDS of the pair pass stays within 64 KiB, and the
+    kernel is one of its own that takes the tally's helpers"""
+    pair = open(os.path.join(CSRC, "fes_pair_kernels.hpp")).read()
+    text = open(os.path.join(CSRC, "fes_fusion_spectrum_kernels.hpp")).read()
+    code = re.sub(r"//.*", "", text)
+    get = lambda name: int(re.search(r"constexpr\s+int\s+%s\s*=\s*(\d+)\s*;" % name, pair).group(1))
+    bins_max = int(re.search(r"#define\s+FPIC_FUSION_SPECTRUM_BINS_MAX\s+(\d+)", open(HEADER).read()).group(1))
+    assert re.search(r"kFspecEntriesMax\s*=\s*FPIC_FUSION_SPECTRUM_BINS_MAX\s*\+\s*2\s*;", code)
+    assert re.search(r"kFspecHistBytesMax\s*=\s*kFspecEntriesMax\s*\*\s*2\s*\*\s*sizeof\(unsigned long long\)\s*;", code)
+    assert re.search(r"kFspecLdsBytesMax\s*=\s*kFspecHistBytesMax\s*\+\s*kPairLdsBytes\s*;", code)
+    assert re.search(r"static_assert\(kFspecLdsBytesMax\s*<=\s*64\s*\*\s*1024", code)
+    hist = (bins_max + 2) * 2 * 8
+    run = (3 * 4 + 2) * 2 * get("kPairCellMax") + 4 * (2 * (get("kPairChunk") + 1) + 2)
+    assert hist == 4128 and hist + run <= 64 * 1024 and 2 * (hist + run) <= 160 * 1024
+    assert (bins_max + 3) * 2 * 8 + run <= 64 * 1024 < (2 * bins_max + 2) * 2 * 8 + run            # (the cap is the power of two that fits)
+    assert "fusion_tally_kernel" not in code and "pair_collide_kernel" not in code
+    assert all(name in code for name in ("pair_segment_of", "pair_bitonic", "pair_load", "collide_counts"))
+    core = open(os.path.join(CSRC, "fes_fusion_spectrum_core.hpp")).read()
+    assert "2^23" in core and "NOTHING DETECTS AN OVERFLOW" in core
+
+
+LAYOUT_C = r'''
+#include <stddef.h>
+#include <stdio.h>
+#include "fusionpic.h"
+#define F(m) printf("%s %zu\n", #m, offsetof(fpic_fusion_spectrum_spec, m));
+int main(void) {
+    printf("sizeof %zu\n", sizeof(fpic_fusion_spectrum_spec));
+    printf("tally.sizeof %zu\n", sizeof(fpic_fusion_spec));
+    F(tally) F(axis) F(bins) F(lo) F(hi) F(q_value) F(product_mass) F(other_mass) F(los) F(reserved)
+    return 0;
+}
+'''
+
+
+def test_ctypes_mirror_matches_the_c_layout(fp, tmp_path):
+    src, exe = tmp_path / "layout.c", tmp_path / "layout"
+    src.write_text(LAYOUT_C)
+    subprocess.check_call(["gcc", "-std=c99", "-Wall", "-I", os.path.join(ROOT, "include"), str(src), "-o", str(exe)])
+    got = dict(line.rsplit(" ", 1) for line in subprocess.check_output([str(exe)]).decode().splitlines())
+    assert int(got.pop("sizeof")) == ctypes.sizeof(fp.FusionSpectrumSpec)
+    assert int(got.pop("tally.sizeof")) == ctypes.sizeof(fp.FusionSpec)
+    assert len(got) == len(fp.FusionSpectrumSpec._fields_)
+    for name, off in got.items():
+        assert int(off) == getattr(fp.FusionSpectrumSpec, name).offset, name
+
+
+# ---- the header under g++
+_built = {}
+
+
+def native(tmp_path_factory, flags):
+    key = tuple(flags)
+    if key not in _built:
+        exe = tmp_path_factory.mktemp("fusion_spectrum_native") / "fusion_spectrum_core_test"
+        subprocess.check_call(["g++", "-std=c++17", "-Wall", "-ffp-contract=off", *flags, NATIVE, "-o", str(exe)])
+        _built[key] = str(exe)
+    return _built[key]
+
+
+def run(exe, *args):
+    out = subprocess.run([exe, *args], capture_output=True, timeout=120, env=dict(os.environ, UBSAN_OPTIONS="halt_on_error=1"))
+    assert out.returncode == 0, out.stdout.decode()[-2000:] + out.stderr.decode()[-2000:]
+    return out.stdout.decode()
+
+
+@pytest.mark.parametrize("flags", [["-O2"], SAN], ids=["plain", "sanitizers"])
+def test_spectrum_host_core(tmp_path_factory, flags):
+    # its own program with its own main: under the sanitizers their runtime is linked into it, nothing is preloaded anywhere
+    extra = os.environ.get("FPIC_NATIVE_CXXFLAGS", "").split() if flags == ["-O2"] else []
+    assert run(native(tmp_path_factory, flags + extra)).strip() == "ok"
+
+
+def random_pairs(seed, m, g_lo, g_hi):
+    """N_L, owners' ids and sides, and velocities whose relative speeds cover the table, both outsides and rest"""
+    rng = np.random.default_rng(seed)
+    n_l = rng.choice([1.0, 1.5, 2.0, 7.0, 64.0, 380.5, 1024.0, 2047.0, 2048.0], size=m)
+    ids = rng.integers(0, 1 << 32, m, dtype=np.uint64)
+    ids[:4] = (0, 1, (1 << 32) - 1, 1 << 31)
+    side_b = rng.integers(0, 2, m).astype(bool)
+    vp = rng.normal(0, 0.01, (m, 3))
+    speed = rng.uniform(0.5 * g_lo, 1.1 * g_hi, m)
+    axis = rng.normal(0, 1, (m, 3))
+    axis /= np.linalg.norm(axis, axis=1)[:, None]
+    vo = vp + speed[:, None] * axis
+    vo[:8] = vp[:8]                                                      # at rest relative to each other
+    vo[8:12] = 0.0                                                       # at rest in the laboratory
+    vp[8:12] = 0.0
+    vo[::2] = vo[::2].astype(np.float32)                                 # stored values are T: half of the pairs carry float32 values
+    vp[::2] = vp[::2].astype(np.float32)
+    return n_l, ids, side_b, vo, vp
+
+
+TABLES = [
+    dict(sigma=lambda g: 1e-28 * (1 + np.sin(40 * g) ** 2), n=97, g_lo=0.0, g_hi=0.03125, tau=1e-9, W=1e10, dV=1.0, like=False, m_a=MD, m_b=MT),
+    dict(sigma=lambda g: 3e-29 * np.exp(-0.01 / np.maximum(g, 1e-9)), n=4096, g_lo=0.0, g_hi=0.0301, tau=2.5e-11, W=3.7e12, dV=2.7e-11, like=True, m_a=MD, m_b=MD),
+    dict(sigma=lambda g: np.where(g > 0.012, 5e-30, 0.0), n=2, g_lo=0.001, g_hi=0.05, tau=1.0, W=1.0, dV=1e-30, like=False, m_a=MT, m_b=MD),
+]
+
+
+def axes_of(t, g_hi):
+    """the axes a table is run with: CM over a range that leaves pairs on both sides, the product isotropic and along a line of
+    sight; one with a single bin, one with 7, one with 256; one endothermic so far that Et <= 0 for every pair"""
+    hk = (0.5 * ((t["m_a"] * t["m_b"]) / (t["m_a"] + t["m_b"]))) * (ref.C * ref.C)
+    k_hi = hk * g_hi * g_hi
+    product = dict(q_value=Q_DT, product_mass=MN, other_mass=MA)
+    return [
+        dict(axis="cm", bins=7, lo=0.1 * k_hi, hi=0.6 * k_hi),
+        dict(axis="cm", bins=256, lo=0.0, hi=1.3 * k_hi),
+        dict(axis="product", bins=256, lo=13000.0 * KEV, hi=15200.0 * KEV, **product),
+        dict(axis="product", bins=7, lo=13800.0 * KEV, hi=14400.0 * KEV, los=(1.0, 2.0, -2.0), **product),
+        dict(axis="product", bins=1, lo=0.0, hi=200.0 * KEV, q_value=-2.0 * k_hi, product_mass=MN, other_mass=MA, los=(0.0, 0.0, 3.0)),
+    ]
+
+
+@pytest.mark.parametrize("flags", [["-O2"], SAN], ids=["plain", "sanitizers"])
+@pytest.mark.parametrize("case", range(len(TABLES)))
+def test_the_header_equals_the_reference_bit_for_bit(tmp_path_factory, tmp_path, flags, case):
+    t = TABLES[case]
+    g = t["g_lo"] + np.arange(t["n"]) * ((t["g_hi"] - t["g_lo"]) / (t["n"] - 1))
+    S = np.asarray(t["sigma"](g), dtype=np.float64)
+    seeds = dict(seed=0xD07F00D123456789 + case, stream=6 + case, epoch=4 + case)
+    req = ref.request(S, t["g_lo"], t["g_hi"], t["tau"], t["W"], t["dV"], like=t["like"], **seeds)
+    m = 4000
+    n_l, ids, side_b, vo, vp = random_pairs(200 + case, m, max(t["g_lo"], 0.002), t["g_hi"])
+    q, what, speed = ref.tally(req, n_l, vo, vp)
+    assert (what == 0).sum() > m // 2 and max(q) > 2 ** 30
+    hexes = lambda row: " ".join(float(x).hex() for x in row)
+    exe = native(tmp_path_factory, flags)
+    for number, kw in enumerate(axes_of(t, t["g_hi"])):
+        axis = sref.request(t["m_a"], t["m_b"], **kw)
+        x, tries = sref.pair_places(req, axis, speed, ids, side_b, vo, vp)
+        entry = sref.entry_of(axis, x)
+        inside = what == 0
+        if kw["axis"] == "product" and "los" not in kw:
+            assert (tries[inside] > 0).sum() > 100 and tries.max() < sref.TRIES
+        if number < 4:
+            assert len(set(entry[inside].tolist())) >= min(kw["bins"], 5) and (entry[inside] < kw["bins"]).sum() > 50
+        if number in (0, 3):
+            assert (entry[inside] == kw["bins"]).sum() > 5 and (entry[inside] == kw["bins"] + 1).sum() > 5
+        if number == 4:                                                   # Et <= 0: the product moves with the centre of mass
+            assert np.all(axis["q_value"] + sref.cm_energy(axis, speed[inside]) <= 0) and (entry[inside] == 0).sum() > 50
+        los = kw.get("los", (0.0, 0.0, 0.0))
+        lines = ["%d %s" % (t["n"], hexes([t["g_lo"], t["g_hi"], t["tau"], t["W"], t["dV"]]))] + [float(v).hex() for v in S]
+        lines += ["%d %d %d %d %d %d" % (axis["axis"], kw["bins"], t["like"], seeds["seed"], seeds["stream"], seeds["epoch"])]
+        lines += [hexes([kw["lo"], kw["hi"], kw["q_value"] if "q_value" in kw else 0.0, kw.get("product_mass", 0.0), kw.get("other_mass", 0.0), *los, t["m_a"], t["m_b"]])]
+        lines += [str(m)] + ["%s %d %d %s" % (float(n_l[k]).hex(), ids[k], side_b[k], hexes([*vo[k], *vp[k]])) for k in range(m)]
+        path = tmp_path / ("pairs%d.txt" % number)
+        path.write_text("\n".join(lines) + "\n")
+        out = run(exe, str(path)).splitlines()
+        assert out[0] == "e %d" % req["e"]
+        rows = [line.split() for line in out[1:]]
+        assert len(rows) == m
+        assert [(int(r[0]), int(r[1])) for r in rows] == list(zip(what.tolist(), q))
+        side = side_b & (not t["like"])
+        for k in np.flatnonzero(inside):
+            r = rows[k]
+            assert (int(r[2]), float.fromhex(r[3]).hex(), int(r[4])) == (int(entry[k]), float(x[k]).hex(), int(tries[k])), (number, k, r, side[k])
+
+
+# ---- the restatement by hand
+def test_directions_are_unit_vectors_and_isotropic():
+    req = ref.request([1e-28, 1e-28], 0.0, 1.0, 1e-9, 1.0, 1.0, seed=77, stream=3, epoch=9)
+    m = 100000
+    ids = np.arange(m, dtype=np.uint64)
+    n, tries = sref.directions(req, ids, np.zeros(m, dtype=bool))
+    other, _ = sref.directions(req, ids, np.ones(m, dtype=bool))
+    assert tries.max() < sref.TRIES and abs((tries > 0).mean() - (1 - np.pi / 4)) < 0.01
+    assert not np.array_equal(n[:100], other[:100])                       # species_b's side draws its own
+    norm2 = (n[:, 0] * n[:, 0] + n[:, 1] * n[:, 1]) + n[:, 2] * n[:, 2]
+    assert np.abs(norm2 - 1.0).max() <= 4 * EPS
+    # a uniform direction: <n_i> = 0 with variance 1/3; <n_i n_i> = 1/3 with variance 4/45; <n_i n_j> = 0 with variance 1/15
+    for i in range(3):
+        assert abs(n[:, i].mean()) <= 3 * np.sqrt(1.0 / 3.0 / m), i
+        assert abs((n[:, i] ** 2).mean() - 1.0 / 3.0) <= 3 * np.sqrt(4.0 / 45.0 / m), i
+        j = (i + 1) % 3
+        assert abs((n[:, i] * n[:, j]).mean()) <= 3 * np.sqrt(1.0 / 15.0 / m), (i, j)
+    # the fallback through the try helper: sixteen rejections leave (0, 0, 1)
+    ok, _ = sref.try_direction(np.full(sref.TRIES, 0xFFFFFFFF), np.full(sref.TRIES, 0xFFFFFF00))
+    assert not ok.any()
+    ok, hit = sref.try_direction(np.array([0x80000000]), np.array([0x80000000]))
+    assert ok[0] and hit[0, 2] == 1.0 and hit[0, 0] == 2.0 ** -31
+
+
+def test_binning_and_the_identity_by_hand():
+    axis = sref.request(MD, MT, axis="cm", bins=8, lo=1.0, hi=3.0)
+    assert axis["inv_w"] == 4.0 and sref.edges(axis).tolist() == [1.0, 1.25, 1.5, 1.75, 2.0, 2.25, 2.5, 2.75, 3.0]
+    x = np.array([1.0, np.nextafter(1.0, 0), 1.25, np.nextafter(1.25, 0), 3.0, np.nextafter(3.0, 0), np.nan, -np.inf, np.inf])
+    assert sref.entry_of(axis, x).tolist() == [0, 8, 1, 0, 9, 7, 9, 8, 9]
+    # the words of a spectrum add to the tally, whatever the axis
+    rng = np.random.default_rng(5)
+    n = 3000
+    v = rng.normal(0, 0.01, (n, 3)).astype(np.float32)
+    req = ref.request([1e-28, 2e-28, 4e-28, 3e-28], 0.0, 0.05, 1e-9, 1e10, 1.0, like=True)
+    cells = rng.integers(0, 2, n)
+    tally = ref.apply(req, 2, cells, np.arange(n), v)
+    hk = sref.request(MD, MD, axis="cm", bins=1, lo=0.0, hi=1.0)["hk"]
+    for kw in (dict(axis="cm", bins=5, lo=1e-4 * hk, hi=4e-4 * hk), dict(axis="product", bins=256, lo=500.0 * KEV, hi=5000.0 * KEV, q_value=3269.0 * KEV, product_mass=MN, other_mass=5.0064e-27)):
+        out = sref.apply(req, sref.request(MD, MD, **kw), 2, cells, np.arange(n), v, tally=tally)
+        assert sum(out["bins"]) + out["under"] + out["over"] == tally["reactions_exact"] > 2 ** 40 and sum(out["bins"]) > 0
+        assert all(out[k] == tally[k] for k in ("pairs", "below", "above", "cells", "unit_exponent"))
+    assert out["under"] == 0 and out["over"] == 0 and np.count_nonzero(out["bins"]) > 20      # the D-D neutron line at 2.45 MeV
+    zero = sref.apply(ref.request([0.0, 0.0], 0.0, 0.05, 1e-9, 1e10, 1.0, like=True), sref.request(MD, MD, axis="cm", bins=3, lo=0.0, hi=1.0), 2, cells, np.arange(n), v)
+    assert zero["bins"] == [0, 0, 0] and zero["under"] == zero["over"] == 0
+
+
+# ---- the wrapper
+def test_wrapper_builds_the_request(fp):
+    good = dict(sigma=[1e-28, 2e-28, 3e-28], g_lo=0, g_hi=0.03, bins=64, lo=13000 * fp.KEV, hi=15000 * fp.KEV)
+    s = fp._fusion_spectrum_spec(2e-9, 0, 1, q_value=Q_DT, product_mass=MN, other_mass=MA, seed=7, stream=8, epoch=9, **good)
+    t = s.tally
+    assert (t.species_a, t.species_b, t.seed, t.stream, t.epoch, t.tau, t.g_lo, t.g_hi, t.n) == (0, 1, 7, 8, 9, 2e-9, 0.0, 0.03, 3)
+    assert [t.sigma[k] for k in range(3)] == [1e-28, 2e-28, 3e-28] and not any(s.reserved) and not any(t.reserved)
+    assert (s.axis, s.bins, s.lo, s.hi, s.q_value, s.product_mass, s.other_mass, list(s.los)) == (fp.FSPEC_PRODUCT, 64, 13000 * fp.KEV, 15000 * fp.KEV, Q_DT, MN, MA, [0.0, 0.0, 0.0])
+    s = fp._fusion_spectrum_spec(2e-9, 2, axis="cm", los=(1, 2, -2), **good)
+    assert (s.tally.species_b, s.axis, list(s.los), s.q_value, s.product_mass) == (2, fp.FSPEC_CM, [1.0, 2.0, -2.0], 0.0, 0.0)
+    assert fp._fusion_spectrum_spec(2e-9, **dict(good, bins=0)).bins == 0                    # (the library refuses it)
+    for bad, prop in ((dict(axis="x"), ".axis"), (dict(axis=1), ".axis"), (dict(bins=None), ".bins"), (dict(bins=2.5), ".bins"), (dict(bins=1 << 31), ".bins"), (dict(lo=None), ".lo"),
+                      (dict(hi="x"), ".hi"), (dict(q_value="x"), ".q_value"), (dict(product_mass=None), ".product_mass"), (dict(other_mass="x"), ".other_mass"),
+                      (dict(los=(1, 2)), ".los"), (dict(los="abc"), ".los"), (dict(los=5), ".los"), (dict(sigma=None), ".sigma"), (dict(seed=-1), ".seed")):
+        with pytest.raises(fp.FusionPicError) as e:
+            fp._fusion_spectrum_spec(2e-9, **dict(good, **bad))
+        assert prop + " <- " in str(e.value), (bad, str(e.value))
+    words = np.array([[0, 5], [1, 7], [0, 0], [0, 2], [3, 1]], dtype=np.uint64)
+    got = fp._fusion_spectrum_result(fp.FusionResult(3, 10, 1, 2, 4, 0, 0, 4, 15, -60, 0), words, 1.0, 4.0)
+    assert got["bins"] == [5, (1 << 32) + 7, 0] and got["under"] == 2 and got["over"] == (3 << 32) + 1 and got["edges"].tolist() == [1.0, 2.0, 3.0, 4.0]
+    assert got["yield"].tolist() == [5 * 2.0 ** -60, ((1 << 32) + 7) * 2.0 ** -60, 0.0] and got["unit_exponent"] == -60
+    assert sum(got["bins"]) + got["under"] + got["over"] == got["reactions_exact"] == (4 << 32) + 15 and all(type(v) is int for v in got["bins"])
+
+
+def test_spectrum_without_a_handle(fp):
+    lib = fp.load_library()
+    s = fp._fusion_spectrum_spec(2e-9, sigma=[1e-28, 2e-28], g_lo=0.0, g_hi=0.03, axis="cm", bins=2, lo=0.0, hi=1.0)
+    out = fp.FusionResult(7, 7, 7, 7, 7, 7, 7, 7, 7, 7, 0)
+    index = ctypes.c_int(77)
+    words = (ctypes.c_uint64 * 8)(*([5] * 8))
+    assert lib.fpic_fusion_spectrum(None, ctypes.byref(s), ctypes.byref(out), words) == -1
+    assert b"null handle" in lib.fpic_last_error(None) and out.pairs == 7 and list(words) == [5] * 8
+    assert lib.fpic_fusion_spectrum_register(None, ctypes.byref(s), 1, ctypes.byref(index)) == -1 and index.value == 77
+    assert lib.fpic_fusion_spectrum_read(None, 0, ctypes.byref(out), words, 1) == -1 and out.applications == 7 and list(words) == [5] * 8
+    assert lib.fpic_fusion_spectrum_clear(None) == -1
+    assert b"null handle" in lib.fpic_last_error(None)
+
+
+# ---- physics, with the restatement alone
+KT_KEV, GAMOW_A, GAMOW_B = 10.0, 1e-24, 34.38
+MAB = MD * MT / (MD + MT)
+LOS = (1.0, 2.0, -2.0)
+E_LO, E_HI = 12000.0 * KEV, 16200.0 * KEV
+
+
+def gamow_of_g(g):
+    e = np.maximum(0.5 * MAB * (g * ref.C) ** 2 / KEV, 1e-300)
+    return GAMOW_A / e * np.exp(-GAMOW_B / np.sqrt(e))
+
+
+def gamow_moments():
+    """the mean and the variance (J, J^2) of the reacting centre-of-mass energy K over the Gamow integrand sigma g f(g) of two
+    Maxwellians at KT_KEV, by numpy quadrature"""
+    s = np.sqrt(KT_KEV * KEV / MD + KT_KEV * KEV / MT) / ref.C
+    g = np.linspace(0.0, 12.0 * s, 400001)[1:]
+    weight = gamow_of_g(g) * g * (g * g * np.exp(-g * g / (2.0 * s * s)))
+    K = 0.5 * MAB * (g * ref.C) ** 2
+    mean = float((weight * K).sum() / weight.sum())
+    return mean, float((weight * (K - mean) ** 2).sum() / weight.sum())
+
+
+_scenes = {}
+
+
+def dt_scene(seed, n_table=4096):
+    """8 cells of about 2000 deuterons and 2000 tritons at 10 keV (the scene of test_reactivity_of_two_maxwellians) and its
+    tally, once per seed"""
+    if (seed, n_table) not in _scenes:
+        rng = np.random.default_rng(seed)
+        vth_d, vth_t = (np.sqrt(KT_KEV * KEV / m) / ref.C for m in (MD, MT))
+        g_lo, g_hi = (np.sqrt(2.0 * e * KEV / MAB) / ref.C for e in (0.2, 300.0))
+        S = gamow_of_g(g_lo + np.arange(n_table) * ((g_hi - g_lo) / (n_table - 1)))
+        req = ref.request(S, g_lo, g_hi, 1e-9, 1e12, 1e-9, seed=seed)
+        na, nb = rng.integers(1900, 2049, 8), rng.integers(1900, 2049, 8)
+        cell_a, cell_b = np.repeat(np.arange(8), na), np.repeat(np.arange(8), nb)
+        va, vb = rng.normal(0, vth_d, (len(cell_a), 3)), rng.normal(0, vth_t, (len(cell_b), 3))
+        args = (8, cell_a, np.arange(len(cell_a)), va, cell_b, np.arange(len(cell_b)), vb)
+        _scenes[(seed, n_table)] = (req, args, ref.apply(req, *args))
+    return _scenes[(seed, n_table)]
+
+
+def moments_of(out):
+    """the yield-weighted mean and standard deviation of a binned spectrum (J), Sheppard's correction for the bin width
+    applied; nothing may lie outside the range"""
+    assert out["under"] == 0 and out["over"] == 0 and sum(out["bins"]) == out["reactions_exact"]
+    e = out["edges"]
+    mid, width = 0.5 * (e[1:] + e[:-1]), e[1] - e[0]
+    w = np.array([float(b) for b in out["bins"]])
+    mean = float((w * mid).sum() / w.sum())
+    return mean, float(np.sqrt((w * (mid - mean) ** 2).sum() / w.sum() - width * width / 12.0))
+
+
+@pytest.mark.parametrize("los", [None, LOS], ids=["isotropic", "line_of_sight"])
+def test_the_neutron_line_has_brysks_width(los):
+    """measured: width / Brysk 0.9980 +- 0.0039 (isotropic), 0.9914 +- 0.0026 (line of sight) over 8 seeds; bias +0.0017"""
+    T = KT_KEV * KEV
+    ratios = []
+    for seed in range(301, 309):
+        req, args, tally = dt_scene(seed)
+        axis = sref.request(MD, MT, axis="product", bins=256, lo=E_LO, hi=E_HI, q_value=Q_DT, product_mass=MN, other_mass=MA, los=los)
+        mean, sd = moments_of(sref.apply(req, axis, *args, tally=tally))
+        ratios.append(sd / np.sqrt(2.0 * MN * mean * T / (MN + MA)))
+    ratios = np.array(ratios)
+    mean_ratio, sem = float(ratios.mean()), float(ratios.std(ddof=1) / np.sqrt(len(ratios)))
+    # the formula keeps the Doppler term 2 m_n E_n T / (m_n + m_alpha) of the variance alone.  E_n = (m_alpha / (m_n + m_alpha))
+    # (Q + K) + m_n u3 (V . n) + m_n V^2 / 2 also varies with the reacting energy K and with V^2 (V the centre-of-mass velocity,
+    # each component of variance T / (m_d + m_t)): variances (m_alpha / (m_n + m_alpha))^2 var K and (3 / 2) (m_n / (m_d + m_t))^2 T^2,
+    # both of relative order T / E_0 and both from the quadrature, not from the spectrum
+    _, var_k = gamow_moments()
+    e0 = MA / (MN + MA) * Q_DT
+    brysk2 = 2.0 * MN * e0 * T / (MN + MA)
+    bias = ((MA / (MN + MA)) ** 2 * var_k + 1.5 * (MN / (MD + MT)) ** 2 * T * T) / (2.0 * brysk2)
+    print("%s: width / Brysk %.4f +- %.4f over %d seeds; the formula's bias %+.4f; T / E_0 = %.2g" % ("line of sight" if los else "isotropic", mean_ratio, sem, len(ratios), bias, T / e0))
+    assert sem < 0.02 and 0 < bias < 4 * T / e0                              # (measurements, not the check)
+    assert abs(mean_ratio - 1.0) <= 3.0 * sem + bias
+    fwhm_kev = 2.0 * np.sqrt(2.0 * np.log(2.0)) * np.sqrt(brysk2) / KEV
+    assert abs(fwhm_kev / (177.0 * np.sqrt(KT_KEV)) - 1.0) < 0.01            # Brysk's 177 sqrt(T / keV) keV
+
+
+def test_the_cm_spectrum_sits_on_the_gamow_peak():
+    """measured: mean / quadrature 1.0042 +- 0.0035 over 8 seeds, the Gamow mean 39.38 keV"""
+    want, _ = gamow_moments()
+    hi = 0.5 * MAB * (dt_scene(301)[0]["g_hi"] * ref.C) ** 2 * 1.0000001
+
+    def mean_of(seed, n_table):
+        req, args, tally = dt_scene(seed, n_table)
+        return moments_of(sref.apply(req, sref.request(MD, MT, axis="cm", bins=256, lo=0.0, hi=hi), *args, tally=tally))[0]
+
+    ratios = np.array([mean_of(seed, 4096) for seed in range(301, 309)]) / want
+    mean_ratio, sem = float(ratios.mean()), float(ratios.std(ddof=1) / np.sqrt(len(ratios)))
+    halved = abs(mean_of(301, 2048) / want - ratios[0])                     # the table's interpolation error: halving n
+    # pairs below 0.2 keV and above 300 keV are outside the table: their share of the integrand
+    print("cm: mean / quadrature %.4f +- %.4f over %d seeds (the Gamow mean is %.2f keV); halving n moves it by %.2g" % (mean_ratio, sem, len(ratios), want / KEV, halved))
+    assert sem < 0.02
+    assert abs(mean_ratio - 1.0) <= 3.0 * sem + halved
