@@ -7,21 +7,50 @@
 // A rank of a decomposition: the counting pass of load_keep_kernel over the indices, the scan of the chunks' counts, the
 // total copied back and held against the capacity — nothing has been touched until here —, then the writing pass and the
 // state domain_set_particles leaves: slot order = ascending id, the ids beside the particles.
+// A profiled load (fpic_load_profile) takes the same two routes with the instances of the kernels that read the tables; the
+// tables are laid out on the host (fesload::layout: a density table beside its cumulative masses) and uploaded per call into
+// Diag::load_tab.  Without a table the call is fpic_load's: the same instances, no buffer.
 
-template <typename T, bool POS, bool VEL>
-static void load_slots_launch(fpic_handle* h, const LoadArgs<T>& a)
+template <typename T, bool POS, bool VEL, typename Args>
+static void load_slots_launch(fpic_handle* h, const Args& a)
 {
     const size_t groups = (a.s1 + 3) / 4 - a.s0 / 4;
     const unsigned grid = static_cast<unsigned>(std::min<size_t>(kLoadBlocks, (groups + kLoadThreads - 1) / kLoadThreads));
-    load_slots_kernel<T, POS, VEL><<<grid, kLoadThreads, 0, h->stream>>>(a);
+    size_t lds = 0;   // the searched tables of a profiled load (stage_tables); at most kLoadLdsBytesMax
+    if constexpr (Args::kProfile) lds = FES_LOAD_TABLES_LDS ? a.q.lds_doubles * sizeof(double) : 0;
+    load_slots_kernel<T, POS, VEL, Args><<<grid, kLoadThreads, lds, h->stream>>>(a);
 }
 
-template <typename T>
-static int load_slots(fpic_handle* h, Species& s, const fesload::Rule& r, uint64_t* loaded)
+// the tables of a checked profile in the device buffer (grows to the largest request); q: the kernels' form
+static int load_tables(fpic_handle* h, const struct fpic_load_profile& p, fesload::Profile* q)
+{
+    Diag& g = h->es->diag;
+    const size_t bytes = fesload::layout(p, nullptr, nullptr, nullptr) * sizeof(double);
+    if (g.load_tab_bytes < bytes) {
+        if (g.load_tab) {
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            HIP_TRY(h, hipFree(g.load_tab));
+            h->bytes_grid -= g.load_tab_bytes;
+            g.load_tab = nullptr;
+            g.load_tab_bytes = 0;
+        }
+        if (int rc = dev_alloc(h, reinterpret_cast<void**>(&g.load_tab), bytes, &h->bytes_grid)) return rc;
+        g.load_tab_bytes = bytes;
+    }
+    std::vector<double> host(bytes / sizeof(double));
+    fesload::layout(p, host.data(), g.load_tab, q);
+    HIP_TRY(h, hipMemcpyAsync(g.load_tab, host.data(), bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // (host is pageable and leaves scope; every load ends synchronised)
+    return FPIC_OK;
+}
+
+template <typename T, typename Args = LoadArgs<T>>
+static int load_slots(fpic_handle* h, Species& s, const fesload::Rule& r, const fesload::Profile* q, uint64_t* loaded)
 {
     *loaded = r.count;
     if (!r.count) return FPIC_OK;
-    LoadArgs<T> a{};
+    Args a{};
+    if constexpr (Args::kProfile) a.q = *q;
     a.slab = static_cast<T*>(s.slab[s.cur]);
     a.id = s.ids_identity ? nullptr : s.id[s.cur];
     a.n_pad = s.n_pad;
@@ -29,9 +58,9 @@ static int load_slots(fpic_handle* h, Species& s, const fesload::Rule& r, uint64
     a.s1 = s.ids_identity ? static_cast<size_t>(r.first + r.count) : s.n;
     a.r = r;
     const bool pos = r.flags & FPIC_LOAD_POS, vel = r.flags & FPIC_LOAD_VEL;
-    if (pos && vel) load_slots_launch<T, true, true>(h, a);
-    else if (pos) load_slots_launch<T, true, false>(h, a);
-    else load_slots_launch<T, false, true>(h, a);
+    if (pos && vel) load_slots_launch<T, true, true, Args>(h, a);
+    else if (pos) load_slots_launch<T, true, false, Args>(h, a);
+    else load_slots_launch<T, false, true, Args>(h, a);
     HIP_TRY(h, hipGetLastError());
     if (pos) {   // (what set_particles sets after an upload of positions)
         s.binned = false;
@@ -42,8 +71,8 @@ static int load_slots(fpic_handle* h, Species& s, const fesload::Rule& r, uint64
     return FPIC_OK;
 }
 
-template <typename T>
-static int load_keep(fpic_handle* h, Species& s, const fesload::Rule& r, uint64_t* loaded)
+template <typename T, typename Args = KeepArgs<T>>
+static int load_keep(fpic_handle* h, Species& s, const fesload::Rule& r, const fesload::Profile* q, uint64_t* loaded)
 {
     State* st = h->es;
     const Domain& d = *st->dom;
@@ -59,7 +88,8 @@ static int load_keep(fpic_handle* h, Species& s, const fesload::Rule& r, uint64_
         const size_t total_at = (nchunks * sizeof(uint32_t) + 15) / 16 * 16;
         if (int rc = select_buffer(h, total_at + 16)) return rc;
         unsigned char* dev = static_cast<unsigned char*>(st->diag.sel);
-        KeepArgs<T> a{};
+        Args a{};
+        if constexpr (Args::kProfile) a.q = *q;
         a.slab = static_cast<T*>(s.slab[s.cur]);
         a.id = s.id[s.cur];
         a.n_pad = s.n_pad;
@@ -71,7 +101,9 @@ static int load_keep(fpic_handle* h, Species& s, const fesload::Rule& r, uint64_
         a.r = r;
         unsigned long long* total = reinterpret_cast<unsigned long long*>(dev + total_at);
         const unsigned grid = static_cast<unsigned>(std::min<size_t>(kLoadBlocks, nchunks));
-        load_keep_kernel<T, false><<<grid, kLoadThreads, 0, h->stream>>>(a);
+        size_t lds = 0;   // (as load_slots_launch)
+        if constexpr (Args::kProfile) lds = FES_LOAD_TABLES_LDS ? a.q.lds_doubles * sizeof(double) : 0;
+        load_keep_kernel<T, false, Args><<<grid, kLoadThreads, lds, h->stream>>>(a);
         load_scan_kernel<<<1, 1024, 0, h->stream>>>(a.chunk, nchunks, total);
         HIP_TRY(h, hipGetLastError());
         unsigned long long got = 0;
@@ -81,7 +113,7 @@ static int load_keep(fpic_handle* h, Species& s, const fesload::Rule& r, uint64_
             return fail(h, FPIC_ERR_INVALID_ARG, ".count <- rank %d would hold %llu particles of species %d, its capacity is %zu; nothing was changed", d.rank,
                         static_cast<unsigned long long>(base + got), static_cast<int>(&s - st->sp.data()), s.cap);
         kept = static_cast<size_t>(got);
-        if (kept) load_keep_kernel<T, true><<<grid, kLoadThreads, 0, h->stream>>>(a);
+        if (kept) load_keep_kernel<T, true, Args><<<grid, kLoadThreads, lds, h->stream>>>(a);
         HIP_TRY(h, hipGetLastError());
     }
     // the state domain_set_particles leaves: the live set holds the particles in slot order with their ids, the other set's
@@ -98,7 +130,9 @@ static int load_keep(fpic_handle* h, Species& s, const fesload::Rule& r, uint64_
     return FPIC_OK;
 }
 
-int load(fpic_handle* h, const fpic_load_spec* spec, uint64_t* loaded)
+int load(fpic_handle* h, const fpic_load_spec* spec, uint64_t* loaded) { return load_profile(h, spec, nullptr, loaded); }
+
+int load_profile(fpic_handle* h, const fpic_load_spec* spec, const struct fpic_load_profile* profile, uint64_t* loaded)
 {
     if (!spec) return fail(h, FPIC_ERR_INVALID_ARG, ".spec <- Non-optional property is undefined!");
     State* st = h->es;
@@ -107,12 +141,19 @@ int load(fpic_handle* h, const fpic_load_spec* spec, uint64_t* loaded)
     const int nsp = static_cast<int>(st->sp.size());
     const uint64_t have = decomposed || spec->species < 0 || spec->species >= nsp ? ~0ull : st->sp[spec->species].n;
     if (const char* why = fesload::check(*spec, nsp, have, L, decomposed)) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    if (profile)
+        if (const char* why = fesload::check_profile(*profile)) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
     Species& s = st->sp[spec->species];
     const fesload::Rule r = fesload::rule_of(*spec, have, L);
     uint64_t done = 0;
     int rc;
-    if (decomposed) rc = h->prec == FPIC_F32 ? load_keep<float>(h, s, r, &done) : load_keep<double>(h, s, r, &done);
-    else rc = h->prec == FPIC_F32 ? load_slots<float>(h, s, r, &done) : load_slots<double>(h, s, r, &done);
+    if (profile && fesload::any_table(*profile)) {
+        fesload::Profile q;
+        if (int rc0 = load_tables(h, *profile, &q)) return rc0;
+        if (decomposed) rc = h->prec == FPIC_F32 ? load_keep<float, KeepProfileArgs<float>>(h, s, r, &q, &done) : load_keep<double, KeepProfileArgs<double>>(h, s, r, &q, &done);
+        else rc = h->prec == FPIC_F32 ? load_slots<float, LoadProfileArgs<float>>(h, s, r, &q, &done) : load_slots<double, LoadProfileArgs<double>>(h, s, r, &q, &done);
+    } else if (decomposed) rc = h->prec == FPIC_F32 ? load_keep<float>(h, s, r, nullptr, &done) : load_keep<double>(h, s, r, nullptr, &done);
+    else rc = h->prec == FPIC_F32 ? load_slots<float>(h, s, r, nullptr, &done) : load_slots<double>(h, s, r, nullptr, &done);
     if (rc == FPIC_OK && loaded) *loaded = done;
     return rc;
 }

@@ -13,11 +13,17 @@
 //       rank's planes [z0, z0 + nzl); load_scan_kernel turns the counts into exclusive offsets and the total; WRITE = true
 //       regenerates, and a kept particle goes to slot base + offset[chunk] + (kept lanes below it): consecutive slots in
 //       ascending index, the id beside it.
-// No LDS beyond a few words, no atomics, no scratch.
+//   A profiled load (fpic_load_profile, the rule fes_load_profile_core.hpp) runs the same two kernels instantiated with
+//   LoadProfileArgs / KeepProfileArgs, which add the tables; the instances of fpic_load take LoadArgs / KeepArgs and read no
+//   table.  The tables are uploaded per call (at most 82 KB); a workgroup stages the SEARCHED ones - d and C of every axis
+//   with a density table, at most 49 200 bytes - in its LDS before its first particle (stage_tables): a search is ten
+//   dependent reads per axis, and the profiled instances hold two workgroups per CU by their registers, which 2 x 49 KB of
+//   the CU's 160 KiB do not lower.  The thermal and shear tables are read once per particle, through the caches.
+// The plain instances: no LDS beyond a few words.  No atomics, no scratch in any instance.
 #pragma once
 
 #include "fes_hist_kernels.hpp"
-#include "fes_load_core.hpp"
+#include "fes_load_profile_core.hpp"
 
 namespace fes {
 
@@ -32,7 +38,40 @@ struct LoadArgs {
     size_t n_pad;             // a multiple of 1024: a group of four slots stays inside the arrays
     size_t s0, s1;            // the slots [s0, s1) the pass visits
     fesload::Rule r;
+    static constexpr bool kProfile = false;
 };
+template <typename T>
+struct LoadProfileArgs : LoadArgs<T> {
+    fesload::Profile q;
+    static constexpr bool kProfile = true;
+};
+
+// Where the SEARCHED tables (d and C of every axis with a density table) are read from: 1 = staged once per workgroup in
+// its LDS, 0 = through the caches (the placement the choice was measured against; build with
+// EXTRA_HIPFLAGS=-DFES_LOAD_TABLES_LDS=0).  The thermal and shear tables are read once per particle and stay global.
+#ifndef FES_LOAD_TABLES_LDS
+#define FES_LOAD_TABLES_LDS 1
+#endif
+constexpr size_t kLoadLdsBytesMax = 3 * 2 * static_cast<size_t>(FPIC_LOAD_TABLE_MAX) * sizeof(double);
+static_assert(kLoadLdsBytesMax + 64 <= 64 * 1024, "a launch may ask for 64 KiB of LDS without an attribute; two workgroups per CU fit the 160 KiB");
+
+// the tables as the lanes read them: q with its searched tables copied to `lds` (q.lds_doubles doubles, the host's count)
+__device__ __forceinline__ fesload::Profile stage_tables(const fesload::Profile& q, double* lds)
+{
+    fesload::Profile s = q;
+#if FES_LOAD_TABLES_LDS
+    uint32_t at = 0;
+    for (int a = 0; a < 3; ++a) {
+        const uint32_t n = q.dk[a] ? q.dk[a] + 1 : 0;       // d[0 .. n) and C[0 .. n) lie side by side (fesload::layout)
+        for (uint32_t k = threadIdx.x; k < 2 * n; k += kLoadThreads) lds[at + k] = q.dens[a][k];
+        s.dens[a] = lds + at;
+        s.cum[a] = lds + at + n;
+        at += 2 * n;
+    }
+    __syncthreads();
+#endif
+    return s;
+}
 
 // the state of index i as the handle stores it
 template <typename T, bool POS, bool VEL>
@@ -53,9 +92,33 @@ __device__ __forceinline__ void load_state(const fesload::Rule& r, uint32_t i, T
     }
 }
 
+// the same with the tables of a profile
 template <typename T, bool POS, bool VEL>
-__global__ __launch_bounds__(kLoadThreads) void load_slots_kernel(LoadArgs<T> g)
+__device__ __forceinline__ void load_state(const fesload::Rule& r, const fesload::Profile& q, uint32_t i, T (&out)[6])
 {
+    double p[3] = {}, fq[3] = {}, theta = 0;
+    if (POS || r.waved || q.needs_pos) fesload::base_of(r, q, i, p, theta, fq);
+    if constexpr (VEL) {
+        double v[3];
+        fesload::velocity_of(r, q, i, theta, fq, v);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) out[3 + a] = static_cast<T>(v[a]);
+    }
+    if constexpr (POS) {
+        fesload::displace(r, theta, p);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) out[a] = wrap01(static_cast<T>(p[a]));
+    }
+}
+
+template <typename T, bool POS, bool VEL, typename Args = LoadArgs<T>>
+__global__ __launch_bounds__(kLoadThreads) void load_slots_kernel(Args g)
+{
+    fesload::Profile tab{};
+    if constexpr (Args::kProfile) {
+        extern __shared__ double load_lds[];
+        tab = stage_tables(g.q, load_lds);
+    }
     const size_t g0 = g.s0 / 4, g1 = (g.s1 + 3) / 4, stride = static_cast<size_t>(gridDim.x) * kLoadThreads;
     const uint64_t first = g.r.first, count = g.r.count;
     for (size_t v = g0 + static_cast<size_t>(blockIdx.x) * kLoadThreads + threadIdx.x; v < g1; v += stride) {
@@ -75,7 +138,10 @@ __global__ __launch_bounds__(kLoadThreads) void load_slots_kernel(LoadArgs<T> g)
         if (!in) continue;
         T st[4][6];
 #pragma unroll
-        for (int l = 0; l < 4; ++l) load_state<T, POS, VEL>(g.r, idx[l], st[l]);
+        for (int l = 0; l < 4; ++l) {
+            if constexpr (Args::kProfile) load_state<T, POS, VEL>(g.r, tab, idx[l], st[l]);
+            else load_state<T, POS, VEL>(g.r, idx[l], st[l]);
+        }
         constexpr int C0 = POS ? 0 : 3, C1 = VEL ? 6 : 3;
         if (in == 0xFu) {
 #pragma unroll
@@ -109,22 +175,34 @@ struct KeepArgs {
     size_t nchunks;
     int nz, z0, nzl;          // the rank owns the cell planes [z0, z0 + nzl)
     fesload::Rule r;
+    static constexpr bool kProfile = false;
+};
+template <typename T>
+struct KeepProfileArgs : KeepArgs<T> {
+    fesload::Profile q;
+    static constexpr bool kProfile = true;
 };
 
-template <typename T, bool WRITE>
-__global__ __launch_bounds__(kLoadThreads) void load_keep_kernel(KeepArgs<T> g)
+template <typename T, bool WRITE, typename Args = KeepArgs<T>>
+__global__ __launch_bounds__(kLoadThreads) void load_keep_kernel(Args g)
 {
     __shared__ uint32_t wave_kept[kLoadThreads / 64];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    fesload::Profile tab{};
+    if constexpr (Args::kProfile) {
+        extern __shared__ double load_lds[];
+        tab = stage_tables(g.q, load_lds);
+    }
     for (size_t c = blockIdx.x; c < g.nchunks; c += gridDim.x) {
         const uint64_t k = static_cast<uint64_t>(c) * kLoadChunk + threadIdx.x;
         const uint32_t i = static_cast<uint32_t>(g.r.first + k);
         T st[3] = {};
-        double theta = 0;
+        double theta = 0, fq[3] = {};
         bool keep = false;
         if (k < g.r.count) {
             double p[3];
-            fesload::base_of(g.r, i, p, theta);
+            if constexpr (Args::kProfile) fesload::base_of(g.r, tab, i, p, theta, fq);
+            else fesload::base_of(g.r, i, p, theta);
             fesload::displace(g.r, theta, p);
 #pragma unroll
             for (int a = 0; a < 3; ++a) st[a] = wrap01(static_cast<T>(p[a]));   // (load_state's arithmetic)
@@ -146,7 +224,8 @@ __global__ __launch_bounds__(kLoadThreads) void load_keep_kernel(KeepArgs<T> g)
             for (int w = 0; w < wave; ++w) slot += wave_kept[w];
             if (slot < g.limit) {   // (the host has checked the total against the capacity; the passes count alike)
                 double v[3];
-                fesload::velocity_of(g.r, i, theta, v);
+                if constexpr (Args::kProfile) fesload::velocity_of(g.r, tab, i, theta, fq, v);
+                else fesload::velocity_of(g.r, i, theta, v);
 #pragma unroll
                 for (int a = 0; a < 3; ++a) {
                     g.slab[a * g.n_pad + slot] = st[a];

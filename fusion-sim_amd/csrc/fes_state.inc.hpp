@@ -125,6 +125,8 @@ struct Diag {
     size_t mom_words = 0;
     void* sel = nullptr;                // the buffer of fpic_select (fes_select.inc.hpp): the cursor, then out_id[rows], out_state[6][rows]; grows to the largest request
     size_t sel_bytes = 0;
+    double* load_tab = nullptr;         // the tables of fpic_load_profile (fes_load.inc.hpp), uploaded per call; grows to the largest request
+    size_t load_tab_bytes = 0;
     unsigned long long* coll = nullptr; // the counts of fpic_collide (fes_collide.inc.hpp): four words per registered operator, four for a call
     std::vector<CollideOp> coll_ops;    // the registered operators, in registration order
     unsigned long long* pair = nullptr; // the counts of fpic_pair (fes_pair.inc.hpp): eight words per registered operator, eight for a call
@@ -152,7 +154,7 @@ inline void diag_release(Diag& g)
 {
     for (Recorder& r : g.rec)
         if (r.dev) (void)hipFree(r.dev);
-    for (void* p : { g.series_req.block, g.modes_req.block, static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom), g.sel, static_cast<void*>(g.coll), static_cast<void*>(g.pair),
+    for (void* p : { g.series_req.block, g.modes_req.block, static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom), g.sel, static_cast<void*>(g.load_tab), static_cast<void*>(g.coll), static_cast<void*>(g.pair),
                      static_cast<void*>(g.pair_seg[0]), static_cast<void*>(g.pair_seg[1]), static_cast<void*>(g.pair_index[0]), static_cast<void*>(g.pair_index[1]),
                      static_cast<void*>(g.fusion), static_cast<void*>(g.fusion_table),
                      static_cast<void*>(g.fspec), static_cast<void*>(g.fspec_table), static_cast<void*>(g.fspec_words) })

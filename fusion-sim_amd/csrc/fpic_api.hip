@@ -1479,6 +1479,12 @@ int fpic_load(fpic_handle* h, const fpic_load_spec* spec, uint64_t* loaded)
     BOX_ONLY(h, "fpic_load");
     return fes::load(h, spec, loaded);
 }
+int fpic_load_profile(fpic_handle* h, const fpic_load_spec* spec, const struct fpic_load_profile* profile, uint64_t* loaded)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_load_profile");
+    return fes::load_profile(h, spec, profile, loaded);
+}
 int fpic_collide(fpic_handle* h, const fpic_collide_spec* spec, fpic_collide_result* out)
 {
     CHECK_HANDLE(h);

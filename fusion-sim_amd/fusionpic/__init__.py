@@ -47,7 +47,7 @@ ABI_FUNCTIONS = [
     "fpic_energy_now", "fpic_energy_record", "fpic_energy_history", "fpic_histogram", "fpic_moments",
     "fpic_series_now", "fpic_series_record", "fpic_series_history",
     "fpic_modes_now", "fpic_modes_record", "fpic_modes_history",
-    "fpic_select", "fpic_load", "fpic_collide", "fpic_collide_register", "fpic_collide_stats", "fpic_collide_clear",
+    "fpic_select", "fpic_load", "fpic_load_profile", "fpic_collide", "fpic_collide_register", "fpic_collide_stats", "fpic_collide_clear",
     "fpic_pair", "fpic_pair_register", "fpic_pair_stats", "fpic_pair_clear",
     "fpic_fusion", "fpic_fusion_register", "fpic_fusion_stats", "fpic_fusion_grid", "fpic_fusion_clear",
     "fpic_fusion_spectrum", "fpic_fusion_spectrum_register", "fpic_fusion_spectrum_read", "fpic_fusion_spectrum_clear",
@@ -326,9 +326,66 @@ def _load_spec(box, species=0, first=0, count=None, seed=LOAD_SEED, stream=0, lo
     return s
 
 
-def _load_call(sim, s):
+LOAD_TABLE_MAX = 1025
+
+
+class LoadProfile(ctypes.Structure):
+    """mirror of fpic_load_profile (include/fusionpic.h)"""
+    _fields_ = [
+        ("density_n", ctypes.c_uint32 * 3), ("thermal_n", ctypes.c_uint32 * 3), ("shear_n", ctypes.c_uint32),
+        ("shear_axis", ctypes.c_int32), ("shear_component", ctypes.c_int32), ("reserved", ctypes.c_uint32 * 2),
+        ("density", ctypes.POINTER(ctypes.c_double) * 3), ("thermal", ctypes.POINTER(ctypes.c_double) * 3),
+        ("shear", ctypes.POINTER(ctypes.c_double)),
+    ]
+
+
+def _load_profile(density=None, thermal=None, shear=None):
+    """LoadProfile of the tables of a profiled load, or None if all three are None.  density, thermal: three entries, each
+    None or a one-dimensional array of numbers; shear: dict(axis=, component=, values=).  Only what the structure cannot
+    carry is refused here; the library checks the node counts and the values.  The arrays are kept alive by the result
+    (its `_tables`)."""
+    if density is None and thermal is None and shear is None:
+        return None
+    p = LoadProfile()
+    p._tables = []
+
+    def table(name, v):
+        try:
+            a = np.asarray(v, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise FusionPicError(-1, ".%s <- a table must be a one-dimensional array of numbers" % name)
+        a = np.ascontiguousarray(a) if a.ndim == 1 else a
+        if v is None or a.ndim != 1 or a.size >= 1 << 32:
+            raise FusionPicError(-1, ".%s <- a table must be a one-dimensional array of numbers" % name)
+        p._tables.append(a)
+        return a.size, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double))
+
+    for name, tabs, counts, ptrs in (("density", density, p.density_n, p.density), ("thermal", thermal, p.thermal_n, p.thermal)):
+        if tabs is None:
+            continue
+        if isinstance(tabs, (str, bytes, dict)) or not hasattr(tabs, "__len__") or len(tabs) != 3:
+            raise FusionPicError(-1, ".%s <- expected three entries (x, y, z), each None or a table" % name)
+        for a in range(3):
+            if tabs[a] is not None:
+                counts[a], ptrs[a] = table(name, tabs[a])
+    if shear is not None:
+        if not isinstance(shear, dict) or set(shear) != {"axis", "component", "values"}:
+            raise FusionPicError(-1, ".shear <- expected dict(axis=, component=, values=)")
+        for key, field in (("axis", "shear_axis"), ("component", "shear_component")):
+            v = shear[key]
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not -(1 << 31) <= int(v) < 1 << 31:
+                raise FusionPicError(-1, ".shear_%s <- must be 0, 1 or 2" % key)
+            setattr(p, field, int(v))
+        p.shear_n, p.shear = table("shear", shear["values"])
+    return p
+
+
+def _load_call(sim, s, profile=None):
     loaded = ctypes.c_uint64()
-    sim._check(sim._lib.fpic_load(sim._h, ctypes.byref(s), ctypes.byref(loaded)))
+    if profile is None:
+        sim._check(sim._lib.fpic_load(sim._h, ctypes.byref(s), ctypes.byref(loaded)))
+    else:
+        sim._check(sim._lib.fpic_load_profile(sim._h, ctypes.byref(s), ctypes.byref(profile), ctypes.byref(loaded)))
     return int(loaded.value)
 
 
@@ -868,6 +925,7 @@ def load_library(path=None):
     lib.fpic_modes_history.argtypes = [vp, ci, vp, vp, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
     lib.fpic_select.argtypes = [vp, ctypes.POINTER(SelectSpec), ci, ctypes.c_uint64, vp, vp, vp, ci, ctypes.POINTER(ctypes.c_uint64)]
     lib.fpic_load.argtypes = [vp, ctypes.POINTER(LoadSpec), ctypes.POINTER(ctypes.c_uint64)]
+    lib.fpic_load_profile.argtypes = [vp, ctypes.POINTER(LoadSpec), ctypes.POINTER(LoadProfile), ctypes.POINTER(ctypes.c_uint64)]
     lib.fpic_collide.argtypes = [vp, ctypes.POINTER(CollideSpec), ctypes.POINTER(CollideResult)]
     lib.fpic_collide_register.argtypes = [vp, ctypes.POINTER(CollideSpec), ci, ctypes.POINTER(ctypes.c_int)]
     lib.fpic_collide_stats.argtypes = [vp, ci, ci, ctypes.POINTER(CollideResult)]
@@ -1172,18 +1230,25 @@ class CylindricalParticlePusher:
         return [float(self.spec.get(k, 1.0)) for k in ("radius", "length_y", "height")]
 
     def load(self, species=0, first=0, count=None, seed=LOAD_SEED, stream=0, lo=None, hi=None, drift=0, vth=0, mode=None, xamp=0, xphase=0,
-             vamp=0, vphase=0, lattice=False, paired=False, position=True, velocity=True, append=False):
+             vamp=0, vphase=0, lattice=False, paired=False, position=True, velocity=True, append=False, density=None, thermal=None, shear=None):
         """Particles [first, first + count) of one species of a CART3D box generated on the device (fpic_load; an (r,z)
-        handle is refused): uniform in the sub-box [lo, hi) (metres; random, or a Kronecker lattice with lattice=True), a
-        drifting Maxwellian (drift, vth in units of c; paired=True makes the thermal parts of particles 2k and 2k + 1 exact
-        negatives), and a sinusoidal perturbation of the integer mode vector `mode`: a displacement xamp (metres) and a
-        velocity vamp (c) times sinpi(2 (theta + phase)), phases in turns.  Scalars broadcast to three components.  The
-        state of a particle depends on the request and its index alone — not on the precision, the decomposition or the
-        time of the call; two species loaded with one seed and stream coincide.  position / velocity choose what is
-        written.  On a rank of a decomposition the rank keeps the particles of its planes (count is needed; append=True
-        adds to what it holds).  Returns the number of particles written (kept)."""
+        handle is refused): in the sub-box [lo, hi) (metres; random, or a Kronecker lattice with lattice=True) with a
+        uniform density or a tabulated one, a drifting Maxwellian (drift, vth in units of c; paired=True makes the thermal
+        parts of particles 2k and 2k + 1 exact negatives), and a sinusoidal perturbation of the integer mode vector `mode`:
+        a displacement xamp (metres) and a velocity vamp (c) times sinpi(2 (theta + phase)), phases in turns.  Scalars
+        broadcast to three components.  The state of a particle depends on the request and its index alone — not on the
+        precision, the decomposition or the time of the call; two species loaded with one seed and stream coincide.
+        position / velocity choose what is written.  On a rank of a decomposition the rank keeps the particles of its
+        planes (count is needed; append=True adds to what it holds).  Returns the number of particles written (kept).
+
+        Profiles (fpic_load_profile): tables of 2 .. LOAD_TABLE_MAX nodes, uniformly spaced over [lo, hi] on their axis and
+        linear between the nodes; the profile is the product of its axes' tables.  density = (x, y, z), each None (uniform)
+        or a table of values >= 0: the positions follow it (a lattice load becomes a quiet start on the profile).  thermal
+        = (x, y, z), each None or a table of factors >= 0 that multiply vth at the particle's undisplaced position.  shear =
+        dict(axis=, component=, values=): drift[component] += table(position along axis).  With all three None the call
+        is fpic_load itself."""
         return _load_call(self, _load_spec(self._box_lengths(), species, first, count, seed, stream, lo, hi, drift, vth, mode, xamp, xphase,
-                                           vamp, vphase, lattice, paired, position, velocity, append))
+                                           vamp, vphase, lattice, paired, position, velocity, append), _load_profile(density, thermal, shear))
 
     # ---- Monte Carlo collisions with a prescribed background (fpic_collide*)
     def collide(self, kind, **request):

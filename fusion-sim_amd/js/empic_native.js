@@ -275,8 +275,8 @@ function makeBox(spec, lib) {
     // the loader (fpic_load): particles [first, first + count) of one species generated on the GPU.  request = { species, first,
     // count (default: to the end), seed (an integer up to 2^53 or a BigInt up to 2^64), stream, lo, hi (metres; default the whole
     // box), drift, vth (units of c), mode (three integers), xamp (metres), xphase, vamp (c), vphase (turns), lattice, paired,
-    // position, velocity (default true), append }; a number where three are expected is taken for all three -> the particles
-    // written (kept, on a rank of a decomposition)
+    // position, velocity (default true), append, density, thermal, shear (tabulated profiles along the axes: below) }; a number
+    // where three are expected is taken for all three -> the particles written (kept, on a rank of a decomposition)
     out.load = function (request) {
         if (request === null || typeof request !== 'object') throw new TypeError('.request <- expected { species, first, count, seed, ... }');
         const three = function (name, v, dflt) {
@@ -307,7 +307,32 @@ function makeBox(spec, lib) {
             Number(seed & 0xffffffffn), Number(seed >> 32n), whole('stream', request.stream, 0, 0, 0xffffffff), flags].concat(mode);
         const reals = [].concat(three('lo', request.lo, 0), three('hi', request.hi, [spec.radius, spec.length_y, spec.height]), three('drift', request.drift, 0),
             three('vth', request.vth, 0), three('xamp', request.xamp, 0), [real('xphase', request.xphase)], three('vamp', request.vamp, 0), [real('vphase', request.vphase)]);
-        return lib.load(h, whole('species', request.species, 0, 0, 0x7fffffff), Float64Array.from(words), Float64Array.from(reals));
+        const species = whole('species', request.species, 0, 0, 0x7fffffff);
+        // profiles (fpic_load_profile): density, thermal = [x, y, z], each null or a table (an array of numbers or a typed array:
+        // 2 .. 1025 nodes over [lo, hi] on its axis, linear between them); shear = { axis, component, values }.  Without any
+        // of the three keys the call is fpic_load itself.
+        const none = (v) => v === undefined || v === null;
+        if (none(request.density) && none(request.thermal) && none(request.shear)) return lib.load(h, species, Float64Array.from(words), Float64Array.from(reals));
+        const shape = [], tables = [];
+        const table = function (name, v) {
+            if (!(Array.isArray(v) || ArrayBuffer.isView(v)) || !Array.from(v).every((x) => typeof x === 'number')) throw new RangeError('.' + name + ' <- a table must be an array of numbers');
+            shape.push(v.length);
+            for (const x of v) tables.push(x);
+        };
+        for (const name of ['density', 'thermal']) {
+            const v = request[name];
+            if (none(v)) { shape.push(0, 0, 0); continue; }
+            if (!Array.isArray(v) || v.length !== 3) throw new RangeError('.' + name + ' <- expected three entries (x, y, z), each null or a table');
+            for (const t of v) { if (none(t)) shape.push(0); else table(name, t); }
+        }
+        if (none(request.shear)) shape.push(0, 0, 0);
+        else {
+            const sh = request.shear;
+            if (typeof sh !== 'object' || Array.isArray(sh)) throw new TypeError('.shear <- expected { axis, component, values }');
+            table('shear', sh.values);
+            shape.push(whole('shear_axis', sh.axis, 0, -0x80000000, 0x7fffffff), whole('shear_component', sh.component, 0, -0x80000000, 0x7fffffff));
+        }
+        return lib.load(h, species, Float64Array.from(words), Float64Array.from(reals), Float64Array.from(shape), Float64Array.from(tables));
     };
     // Monte Carlo collisions with a prescribed drifting Maxwellian (fpic_collide*).  request = { kind: 'exchange' | 'elastic' |
     // 'relax', species, either nu (1/s), sigmaN (density times cross-section, 1/m), tau (s; default the sub-step dt, every * dt

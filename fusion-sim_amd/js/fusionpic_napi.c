@@ -857,7 +857,8 @@ static napi_value n_histogram(napi_env env, napi_callback_info info)
 
 /* load(h, species, words: Float64Array [first, count (-1: to the end), seed low word, seed high word, stream, flags, mode x, y, z],
  * reals: Float64Array [lo 3, hi 3, drift 3, vth 3, xamp 3, xphase, vamp 3, vphase]) -> the particles written (kept on a rank of a
- * decomposition).  The arrays' lengths and the words' ranges are checked here, the request itself by the library. */
+ * decomposition).  The arrays' lengths and the words' ranges are checked here, the request itself by the library.
+ * load(h, species, words, reals, shape, tables): the same with the tables of a profile (fpic_load_profile; see below). */
 static napi_value n_load(napi_env env, napi_callback_info info)
 {
     napi_value argv[4]; fpic_handle* h; int sp;
@@ -894,7 +895,39 @@ static napi_value n_load(napi_env env, napi_callback_info info)
     }
     s.xphase = r[15]; s.vphase = r[19];
     uint64_t loaded = 0;
-    if (fpic_load(h, &s, &loaded) != FPIC_OK) return throw_fpic(env, h);
+    /* the optional tables of a profiled load (fpic_load_profile): shape: Float64Array [density nodes x, y, z, thermal nodes x, y, z,
+     * shear nodes, shear axis, shear component], tables: Float64Array, the tables one after the other in that order.  The
+     * lengths are checked here, the counts and the values by the library. */
+    napi_value more[6];
+    size_t argc = 6;
+    if (napi_get_cb_info(env, info, &argc, more, NULL, NULL) != napi_ok) return NULL;
+    napi_typedarray_type ts = napi_float64_array, tt = napi_float64_array; void *ps = NULL, *pt = NULL; size_t ls = 0, lt = 0;
+    if (argc >= 5 && !get_typed(env, more[4], &ts, &ps, &ls)) return NULL;
+    if (argc >= 6 && !get_typed(env, more[5], &tt, &pt, &lt)) return NULL;
+    if (ps) {
+        if (ts != napi_float64_array || (pt && tt != napi_float64_array)) { napi_throw_type_error(env, NULL, ".profile <- expected two Float64Arrays"); return NULL; }
+        if (!check_len(env, "shape", ls, 9)) return NULL;
+        const double* q = (const double*)ps;
+        double total = 0;
+        for (int k = 0; k < 9; ++k) {
+            const double least = k >= 7 ? -2147483648.0 : 0.0, most_k = k >= 7 ? 2147483647.0 : 4294967295.0;
+            if (!(q[k] >= least && q[k] <= most_k) || q[k] != (double)(int64_t)q[k]) {
+                napi_throw_range_error(env, NULL, ".profile <- node counts, shear axis and shear component must be integers within their fields");
+                return NULL;
+            }
+            if (k < 7) total += q[k];
+        }
+        if (!check_len(env, "tables", lt, (size_t)total)) return NULL;
+        struct fpic_load_profile p;
+        memset(&p, 0, sizeof p);
+        const double* at = (const double*)pt;
+        for (int a = 0; a < 3; ++a) { p.density_n[a] = (uint32_t)q[a]; if (p.density_n[a]) { p.density[a] = at; at += p.density_n[a]; } }
+        for (int a = 0; a < 3; ++a) { p.thermal_n[a] = (uint32_t)q[3 + a]; if (p.thermal_n[a]) { p.thermal[a] = at; at += p.thermal_n[a]; } }
+        p.shear_n = (uint32_t)q[6];
+        if (p.shear_n) p.shear = at;
+        p.shear_axis = (int32_t)q[7]; p.shear_component = (int32_t)q[8];
+        if (fpic_load_profile(h, &s, &p, &loaded) != FPIC_OK) return throw_fpic(env, h);
+    } else if (fpic_load(h, &s, &loaded) != FPIC_OK) return throw_fpic(env, h);
     napi_value v;
     NAPI_OK(env, napi_create_double(env, (double)loaded, &v));
     return v;

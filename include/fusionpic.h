@@ -750,6 +750,45 @@ typedef struct fpic_load_spec {
 } fpic_load_spec;
 int fpic_load(fpic_handle* h, const fpic_load_spec* spec, uint64_t* loaded);
 
+/* ---- CART3D particle loader with profiles: fpic_load with tabulated, separable profiles along the axes for the density,
+ * the thermal speed and one drift component.  Every flag and field of the request keeps its meaning, and so does what the
+ * state of particle i depends on: the request, the tables and i alone.  A null profile, or one whose node counts are all
+ * zero, is fpic_load bit for bit.
+ * A table of n nodes is uniformly spaced over the request's sub-box on its axis — node 0 at lo[a], node n - 1 at hi[a] —
+ * and linear between the nodes.  K = n - 1 is its number of intervals.  All arithmetic is double, every operation rounded
+ * once, and every operation of a position is one of + - * / sqrt.
+ *   density    C[0] = 0, C[j+1] = C[j] + 0.5 (d[j] + d[j+1]), summed in sequence on the host.  With f the unit fraction
+ *              fpic_load draws on that axis (random or lattice):
+ *                  t = f C[K];  j = the largest index with C[j] <= t, held to K - 1;  r = t - C[j];
+ *                  disc = d[j] d[j] + (2 (d[j+1] - d[j])) r, held to 0 from below;  den = d[j] + sqrt(disc);
+ *                  s = den > 0 ? (2 r) / den : 0, held to 1 from above;
+ *                  f' = (j + s) / K, and 1 - 2^-53 if that is not below 1.
+ *              An interval without mass is never chosen.  p_a = lo[a]/L_a + f' (hi[a] - lo[a])/L_a; theta, the
+ *              displacement, the cast and the wrap are fpic_load's.  An axis without a table has f' = f.  A lattice load
+ *              becomes a quiet start on the profile; a PAIRED load or two species on one stream stay exactly neutral.
+ *   lookup     a thermal or shear table of K intervals at the fraction f' of its axis: g = f' K; j = min((int) g, K - 1);
+ *              s = g - j; value = tab[j] + (tab[j+1] - tab[j]) s.
+ *   velocity   vth_eff[a] = ((vth[a] sx) sy) sz with sx, sy, sz the thermal tables' values at the UNDISPLACED position (a
+ *              missing table is a factor of exactly 1: no multiply); drift_eff[c] = drift[c] + shear(f' of shear_axis) for
+ *              c = shear_component; then fpic_load's velocity with vth_eff and drift_eff.
+ * Refused (FPIC_ERR_INVALID_ARG) besides what fpic_load refuses: a node count of 1 or above FPIC_LOAD_TABLE_MAX, a null
+ * table whose count is not zero, a value that is not finite, a negative density or thermal value, a density table whose
+ * total is 0, shear_axis or shear_component outside 0..2, a reserved word that is not zero.  Synchronous. */
+#define FPIC_LOAD_TABLE_MAX 1025          /* nodes of one table */
+/* (a struct tag, not a typedef: the tables and the call share the name as `struct stat` and stat() do, so the type is
+ * written `struct fpic_load_profile` in C and in C++) */
+struct fpic_load_profile {
+    uint32_t density_n[3];                /* nodes per axis: 0 = uniform, else 2 .. FPIC_LOAD_TABLE_MAX */
+    uint32_t thermal_n[3];                /* 0 = factor 1 */
+    uint32_t shear_n;                     /* 0 = none */
+    int32_t  shear_axis, shear_component; /* 0..2 each: drift[component] += table(position along axis) */
+    uint32_t reserved[2];                 /* zero */
+    const double* density[3];             /* >= 0, finite, at least one interval with mass */
+    const double* thermal[3];             /* >= 0, finite: multiplies vth[0..2] */
+    const double* shear;                  /* finite, units of c */
+};
+int fpic_load_profile(fpic_handle* h, const fpic_load_spec* spec, const struct fpic_load_profile* profile, uint64_t* loaded);
+
 /* ---- CART3D Monte Carlo collisions with a prescribed background: a drifting Maxwellian (drift, vth per axis, units of c)
  * that is not another species; the momentum and energy the species loses go to that reservoir.  The operator acts on the
  * stored velocities of one species (under full EM the half-time velocity, as fpic_histogram reads it), as a call or

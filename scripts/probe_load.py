@@ -1,4 +1,4 @@
-"""Measurements of the particle loader (fpic_load).  Two modes:
+"""Measurements of the particle loader (fpic_load, fpic_load_profile).  Three modes:
 
   ulps   the kernel's normals and sines against 50-digit values (tests/load_exact.py) over the 10^5 particles of its scene: an
          fp64 box loaded with vth = 1 (the velocities ARE the normals) and with vamp = 1 (the velocities ARE the sines).
@@ -8,6 +8,10 @@
          setRange uploads of the same population from a host block that already exists, (c) a plain fill of six arrays of
          that size (the write stream's floor), and the two-pass form on a rank of a two-rank decomposition that keeps half
          of what it generates.  HIP events on the handle's stream, one warm-up, the median of --calls repetitions.
+  profile  the same box and request, per precision and in one run: fpic_load (row (a) of `time`), the request with one
+         1025-node density table, with three, and with three density tables, three thermal tables and a shear table
+         (fpic_load_profile), and the setRange uploads (b) that are the floor of each.  Prints median, min, max and the
+         ratios to (a).
 """
 import argparse
 import json
@@ -109,11 +113,54 @@ def time_(args):
     print(json.dumps(out))
 
 
+def profile(args):
+    import numpy as np
+    import torch
+    import fusionpic as fp
+    n, grid = args.particles, args.grid
+    L = grid * 3e-4
+    request = dict(drift=(0.0, 0.0, 0.01), vth=1e-3, mode=(1, 0, 0), xamp=(1e-3 * L, 0, 0), vamp=(1e-5, 0, 0))
+    x = np.linspace(0.0, 1.0, 1025)
+    gauss, wavy, ramp = np.exp(-0.5 * ((x - 0.5) / 0.2) ** 2), 1.0 + 0.5 * np.cos(7 * x), 0.5 + x
+    tables = {
+        "load": {},
+        "density_1": dict(density=(gauss, None, None)),
+        "density_3": dict(density=(gauss, wavy, ramp)),
+        "density_3_thermal_3_shear": dict(density=(gauss, wavy, ramp), thermal=(ramp, gauss + 0.5, wavy), shear=dict(axis=1, component=2, values=0.01 * np.sin(9 * x))),
+    }
+    stream = torch.cuda.Stream()
+    out = {"particles": n, "grid": grid, "calls": args.calls}
+    for precision in ("fp32", "fp64"):
+        T = np.float32 if precision == "fp32" else np.float64
+        sim = fp.makeCylindricalParticlePusher(box_spec(grid, n, L), precision=precision)
+        sim.setStream(stream.cuda_stream)
+        res = {}
+        for name, tabs in tables.items():
+            res[name] = timed(torch, stream, args.calls, lambda: sim.load(**request, **tabs))
+        block = 1 << 23
+        rng = np.random.default_rng(1)
+        pos, vel = (rng.random((block, 3)) * L).astype(T), rng.normal(0, 1e-3, (block, 3)).astype(T)
+
+        def upload():
+            for first in range(0, n, block):
+                m = min(block, n - first)
+                sim.setRange(first, position=pos[:m], velocity=vel[:m])
+        res["setRange"] = timed(torch, stream, 1, upload)
+        sim.destroy()
+        del sim
+        torch.cuda.empty_cache()
+        res["over_load"] = {name: res[name][0] / res["load"][0] for name in tables}
+        res["below_setRange"] = {name: res[name][2] < res["setRange"][0] for name in tables}
+        out[precision] = res
+        print(precision, json.dumps(res), flush=True)
+    print(json.dumps(out))
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["ulps", "time"])
+    ap.add_argument("mode", choices=["ulps", "time", "profile"])
     ap.add_argument("--particles", type=int, default=500000000)
     ap.add_argument("--grid", type=int, default=256)
     ap.add_argument("--calls", type=int, default=5)
     a = ap.parse_args()
-    ulps(a) if a.mode == "ulps" else time_(a)
+    {"ulps": ulps, "time": time_, "profile": profile}[a.mode](a)
