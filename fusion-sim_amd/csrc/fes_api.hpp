@@ -42,6 +42,7 @@ int select(fpic_handle* h, const fpic_select_spec* spec, int scope, uint64_t cap
 // particle loader (fes_load.inc.hpp)
 int load(fpic_handle* h, const fpic_load_spec* spec, uint64_t* loaded);
 int load_profile(fpic_handle* h, const fpic_load_spec* spec, const struct fpic_load_profile* profile, uint64_t* loaded);
+int load_radial(fpic_handle* h, const fpic_load_spec* spec, const struct fpic_load_radial* radial, uint64_t* loaded);
 // Monte Carlo collisions with a prescribed background (fes_collide.inc.hpp)
 int collide(fpic_handle* h, const fpic_collide_spec* spec, fpic_collide_result* out);
 int collide_register(fpic_handle* h, const fpic_collide_spec* spec, int every, int* index);

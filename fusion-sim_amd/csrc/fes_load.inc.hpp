@@ -10,6 +10,8 @@
 // A profiled load (fpic_load_profile) takes the same two routes with the instances of the kernels that read the tables; the
 // tables are laid out on the host (fesload::layout: a density table beside its cumulative masses) and uploaded per call into
 // Diag::load_tab.  Without a table the call is fpic_load's: the same instances, no buffer.
+// A radial load (fpic_load_radial, the rule fes_load_radial_core.hpp) is the third set of instances on the same two routes;
+// its one block of tables (fesload::radial_layout) goes through the same buffer and is staged whole in the LDS.
 
 template <typename T, bool POS, bool VEL, typename Args>
 static void load_slots_launch(fpic_handle* h, const Args& a)
@@ -18,14 +20,15 @@ static void load_slots_launch(fpic_handle* h, const Args& a)
     const unsigned grid = static_cast<unsigned>(std::min<size_t>(kLoadBlocks, (groups + kLoadThreads - 1) / kLoadThreads));
     size_t lds = 0;   // the searched tables of a profiled load (stage_tables); at most kLoadLdsBytesMax
     if constexpr (Args::kProfile) lds = FES_LOAD_TABLES_LDS ? a.q.lds_doubles * sizeof(double) : 0;
+    if constexpr (Args::kRadial) lds = a.q.lds_doubles * sizeof(double);
     load_slots_kernel<T, POS, VEL, Args><<<grid, kLoadThreads, lds, h->stream>>>(a);
 }
 
 // the tables of a checked profile in the device buffer (grows to the largest request); q: the kernels' form
-static int load_tables(fpic_handle* h, const struct fpic_load_profile& p, fesload::Profile* q)
+// room for `bytes` of tables in the device buffer (grows to the largest request)
+static int load_tab_room(fpic_handle* h, size_t bytes)
 {
     Diag& g = h->es->diag;
-    const size_t bytes = fesload::layout(p, nullptr, nullptr, nullptr) * sizeof(double);
     if (g.load_tab_bytes < bytes) {
         if (g.load_tab) {
             HIP_TRY(h, hipStreamSynchronize(h->stream));
@@ -37,6 +40,14 @@ static int load_tables(fpic_handle* h, const struct fpic_load_profile& p, fesloa
         if (int rc = dev_alloc(h, reinterpret_cast<void**>(&g.load_tab), bytes, &h->bytes_grid)) return rc;
         g.load_tab_bytes = bytes;
     }
+    return FPIC_OK;
+}
+
+static int load_tables(fpic_handle* h, const struct fpic_load_profile& p, fesload::Profile* q)
+{
+    Diag& g = h->es->diag;
+    const size_t bytes = fesload::layout(p, nullptr, nullptr, nullptr) * sizeof(double);
+    if (int rc = load_tab_room(h, bytes)) return rc;
     std::vector<double> host(bytes / sizeof(double));
     fesload::layout(p, host.data(), g.load_tab, q);
     HIP_TRY(h, hipMemcpyAsync(g.load_tab, host.data(), bytes, hipMemcpyHostToDevice, h->stream));
@@ -44,13 +55,26 @@ static int load_tables(fpic_handle* h, const struct fpic_load_profile& p, fesloa
     return FPIC_OK;
 }
 
-template <typename T, typename Args = LoadArgs<T>>
-static int load_slots(fpic_handle* h, Species& s, const fesload::Rule& r, const fesload::Profile* q, uint64_t* loaded)
+// the same for a checked radial request
+static int load_tables(fpic_handle* h, const struct fpic_load_radial& p, const double (&L)[3], fesload::Radial* q)
+{
+    Diag& g = h->es->diag;
+    const size_t bytes = fesload::radial_layout(p, L, nullptr, nullptr, nullptr) * sizeof(double);
+    if (int rc = load_tab_room(h, bytes)) return rc;
+    std::vector<double> host(bytes / sizeof(double));
+    fesload::radial_layout(p, L, host.data(), g.load_tab, q);
+    HIP_TRY(h, hipMemcpyAsync(g.load_tab, host.data(), bytes, hipMemcpyHostToDevice, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    return FPIC_OK;
+}
+
+template <typename T, typename Args = LoadArgs<T>, typename Tables = fesload::Profile>
+static int load_slots(fpic_handle* h, Species& s, const fesload::Rule& r, const Tables* q, uint64_t* loaded)
 {
     *loaded = r.count;
     if (!r.count) return FPIC_OK;
     Args a{};
-    if constexpr (Args::kProfile) a.q = *q;
+    if constexpr (Args::kProfile || Args::kRadial) a.q = *q;
     a.slab = static_cast<T*>(s.slab[s.cur]);
     a.id = s.ids_identity ? nullptr : s.id[s.cur];
     a.n_pad = s.n_pad;
@@ -71,8 +95,8 @@ static int load_slots(fpic_handle* h, Species& s, const fesload::Rule& r, const 
     return FPIC_OK;
 }
 
-template <typename T, typename Args = KeepArgs<T>>
-static int load_keep(fpic_handle* h, Species& s, const fesload::Rule& r, const fesload::Profile* q, uint64_t* loaded)
+template <typename T, typename Args = KeepArgs<T>, typename Tables = fesload::Profile>
+static int load_keep(fpic_handle* h, Species& s, const fesload::Rule& r, const Tables* q, uint64_t* loaded)
 {
     State* st = h->es;
     const Domain& d = *st->dom;
@@ -89,7 +113,7 @@ static int load_keep(fpic_handle* h, Species& s, const fesload::Rule& r, const f
         if (int rc = select_buffer(h, total_at + 16)) return rc;
         unsigned char* dev = static_cast<unsigned char*>(st->diag.sel);
         Args a{};
-        if constexpr (Args::kProfile) a.q = *q;
+        if constexpr (Args::kProfile || Args::kRadial) a.q = *q;
         a.slab = static_cast<T*>(s.slab[s.cur]);
         a.id = s.id[s.cur];
         a.n_pad = s.n_pad;
@@ -103,6 +127,7 @@ static int load_keep(fpic_handle* h, Species& s, const fesload::Rule& r, const f
         const unsigned grid = static_cast<unsigned>(std::min<size_t>(kLoadBlocks, nchunks));
         size_t lds = 0;   // (as load_slots_launch)
         if constexpr (Args::kProfile) lds = FES_LOAD_TABLES_LDS ? a.q.lds_doubles * sizeof(double) : 0;
+        if constexpr (Args::kRadial) lds = a.q.lds_doubles * sizeof(double);
         load_keep_kernel<T, false, Args><<<grid, kLoadThreads, lds, h->stream>>>(a);
         load_scan_kernel<<<1, 1024, 0, h->stream>>>(a.chunk, nchunks, total);
         HIP_TRY(h, hipGetLastError());
@@ -147,13 +172,37 @@ int load_profile(fpic_handle* h, const fpic_load_spec* spec, const struct fpic_l
     const fesload::Rule r = fesload::rule_of(*spec, have, L);
     uint64_t done = 0;
     int rc;
+    const fesload::Profile* const none = nullptr;
     if (profile && fesload::any_table(*profile)) {
         fesload::Profile q;
         if (int rc0 = load_tables(h, *profile, &q)) return rc0;
         if (decomposed) rc = h->prec == FPIC_F32 ? load_keep<float, KeepProfileArgs<float>>(h, s, r, &q, &done) : load_keep<double, KeepProfileArgs<double>>(h, s, r, &q, &done);
         else rc = h->prec == FPIC_F32 ? load_slots<float, LoadProfileArgs<float>>(h, s, r, &q, &done) : load_slots<double, LoadProfileArgs<double>>(h, s, r, &q, &done);
-    } else if (decomposed) rc = h->prec == FPIC_F32 ? load_keep<float>(h, s, r, nullptr, &done) : load_keep<double>(h, s, r, nullptr, &done);
-    else rc = h->prec == FPIC_F32 ? load_slots<float>(h, s, r, nullptr, &done) : load_slots<double>(h, s, r, nullptr, &done);
+    } else if (decomposed) rc = h->prec == FPIC_F32 ? load_keep<float>(h, s, r, none, &done) : load_keep<double>(h, s, r, none, &done);
+    else rc = h->prec == FPIC_F32 ? load_slots<float>(h, s, r, none, &done) : load_slots<double>(h, s, r, none, &done);
+    if (rc == FPIC_OK && loaded) *loaded = done;
+    return rc;
+}
+
+int load_radial(fpic_handle* h, const fpic_load_spec* spec, const struct fpic_load_radial* radial, uint64_t* loaded)
+{
+    if (!spec) return fail(h, FPIC_ERR_INVALID_ARG, ".spec <- Non-optional property is undefined!");
+    if (!radial) return fail(h, FPIC_ERR_INVALID_ARG, ".radial <- Non-optional property is undefined!");
+    State* st = h->es;
+    const bool decomposed = st->dom != nullptr;
+    const double L[3] = { st->lx, st->ly, st->lz };
+    const int nsp = static_cast<int>(st->sp.size());
+    const uint64_t have = decomposed || spec->species < 0 || spec->species >= nsp ? ~0ull : st->sp[spec->species].n;
+    if (const char* why = fesload::check(*spec, nsp, have, L, decomposed)) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    if (const char* why = fesload::check_radial(*radial, L)) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    Species& s = st->sp[spec->species];
+    const fesload::Rule r = fesload::rule_of(*spec, have, L);
+    fesload::Radial q;
+    if (int rc0 = load_tables(h, *radial, L, &q)) return rc0;
+    uint64_t done = 0;
+    int rc;
+    if (decomposed) rc = h->prec == FPIC_F32 ? load_keep<float, KeepRadialArgs<float>>(h, s, r, &q, &done) : load_keep<double, KeepRadialArgs<double>>(h, s, r, &q, &done);
+    else rc = h->prec == FPIC_F32 ? load_slots<float, LoadRadialArgs<float>>(h, s, r, &q, &done) : load_slots<double, LoadRadialArgs<double>>(h, s, r, &q, &done);
     if (rc == FPIC_OK && loaded) *loaded = done;
     return rc;
 }

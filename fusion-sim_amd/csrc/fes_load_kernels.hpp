@@ -19,11 +19,16 @@
 //   with a density table, at most 49 200 bytes - in its LDS before its first particle (stage_tables): a search is ten
 //   dependent reads per axis, and the profiled instances hold two workgroups per CU by their registers, which 2 x 49 KB of
 //   the CU's 160 KiB do not lower.  The thermal and shear tables are read once per particle, through the caches.
+//   A radial load (fpic_load_radial, the rule fes_load_radial_core.hpp) is a third set of instances of the same two kernels,
+//   with LoadRadialArgs / KeepRadialArgs.  Its tables - d and C of the density and up to four tables read once per particle,
+//   at most 6 x 1025 doubles = 49 200 bytes, the profiled instances' bound - are ALL staged in the workgroup's LDS
+//   (stage_radial).  The 52 halvings of the radius are the same straight line of fp64 operations in every lane.
 // The plain instances: no LDS beyond a few words.  No atomics, no scratch in any instance.
 #pragma once
 
 #include "fes_hist_kernels.hpp"
 #include "fes_load_profile_core.hpp"
+#include "fes_load_radial_core.hpp"
 
 namespace fes {
 
@@ -39,11 +44,17 @@ struct LoadArgs {
     size_t s0, s1;            // the slots [s0, s1) the pass visits
     fesload::Rule r;
     static constexpr bool kProfile = false;
+    static constexpr bool kRadial = false;
 };
 template <typename T>
 struct LoadProfileArgs : LoadArgs<T> {
     fesload::Profile q;
     static constexpr bool kProfile = true;
+};
+template <typename T>
+struct LoadRadialArgs : LoadArgs<T> {
+    fesload::Radial q;
+    static constexpr bool kRadial = true;
 };
 
 // Where the SEARCHED tables (d and C of every axis with a density table) are read from: 1 = staged once per workgroup in
@@ -70,6 +81,23 @@ __device__ __forceinline__ fesload::Profile stage_tables(const fesload::Profile&
     }
     __syncthreads();
 #endif
+    return s;
+}
+
+static_assert(6 * static_cast<size_t>(FPIC_LOAD_TABLE_MAX) * sizeof(double) <= kLoadLdsBytesMax, "the tables of a radial load fit the same bound");
+
+// the tables of a radial load as the lanes read them: the whole block (q.lds_doubles doubles from q.dens on) copied to `lds`
+__device__ __forceinline__ fesload::Radial stage_radial(const fesload::Radial& q, double* lds)
+{
+    fesload::Radial s = q;
+    for (uint32_t k = threadIdx.x; k < q.lds_doubles; k += kLoadThreads) lds[k] = q.dens[k];
+    s.dens = lds;
+    s.cum = lds + (q.cum - q.dens);
+    if (q.tk) s.therm = lds + (q.therm - q.dens);
+    if (q.rk) s.ur = lds + (q.ur - q.dens);
+    if (q.zk) s.ut = lds + (q.ut - q.dens);
+    if (q.ak) s.ua = lds + (q.ua - q.dens);
+    __syncthreads();
     return s;
 }
 
@@ -111,6 +139,25 @@ __device__ __forceinline__ void load_state(const fesload::Rule& r, const fesload
     }
 }
 
+// the same with the tables of a radial load
+template <typename T, bool POS, bool VEL>
+__device__ __forceinline__ void load_state(const fesload::Rule& r, const fesload::Radial& q, uint32_t i, T (&out)[6])
+{
+    double p[3] = {}, dir[3] = {}, theta = 0, rho = 0;
+    if (POS || r.waved || q.needs_pos) fesload::radial_base_of(r, q, i, p, theta, rho, dir);
+    if constexpr (VEL) {
+        double v[3];
+        fesload::radial_velocity_of(r, q, i, theta, rho, dir, v);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) out[3 + a] = static_cast<T>(v[a]);
+    }
+    if constexpr (POS) {
+        fesload::displace(r, theta, p);
+#pragma unroll
+        for (int a = 0; a < 3; ++a) out[a] = wrap01(static_cast<T>(p[a]));
+    }
+}
+
 template <typename T, bool POS, bool VEL, typename Args = LoadArgs<T>>
 __global__ __launch_bounds__(kLoadThreads) void load_slots_kernel(Args g)
 {
@@ -118,6 +165,11 @@ __global__ __launch_bounds__(kLoadThreads) void load_slots_kernel(Args g)
     if constexpr (Args::kProfile) {
         extern __shared__ double load_lds[];
         tab = stage_tables(g.q, load_lds);
+    }
+    fesload::Radial rad{};
+    if constexpr (Args::kRadial) {
+        extern __shared__ double load_lds[];
+        rad = stage_radial(g.q, load_lds);
     }
     const size_t g0 = g.s0 / 4, g1 = (g.s1 + 3) / 4, stride = static_cast<size_t>(gridDim.x) * kLoadThreads;
     const uint64_t first = g.r.first, count = g.r.count;
@@ -139,7 +191,8 @@ __global__ __launch_bounds__(kLoadThreads) void load_slots_kernel(Args g)
         T st[4][6];
 #pragma unroll
         for (int l = 0; l < 4; ++l) {
-            if constexpr (Args::kProfile) load_state<T, POS, VEL>(g.r, tab, idx[l], st[l]);
+            if constexpr (Args::kRadial) load_state<T, POS, VEL>(g.r, rad, idx[l], st[l]);
+            else if constexpr (Args::kProfile) load_state<T, POS, VEL>(g.r, tab, idx[l], st[l]);
             else load_state<T, POS, VEL>(g.r, idx[l], st[l]);
         }
         constexpr int C0 = POS ? 0 : 3, C1 = VEL ? 6 : 3;
@@ -176,11 +229,17 @@ struct KeepArgs {
     int nz, z0, nzl;          // the rank owns the cell planes [z0, z0 + nzl)
     fesload::Rule r;
     static constexpr bool kProfile = false;
+    static constexpr bool kRadial = false;
 };
 template <typename T>
 struct KeepProfileArgs : KeepArgs<T> {
     fesload::Profile q;
     static constexpr bool kProfile = true;
+};
+template <typename T>
+struct KeepRadialArgs : KeepArgs<T> {
+    fesload::Radial q;
+    static constexpr bool kRadial = true;
 };
 
 template <typename T, bool WRITE, typename Args = KeepArgs<T>>
@@ -193,15 +252,21 @@ __global__ __launch_bounds__(kLoadThreads) void load_keep_kernel(Args g)
         extern __shared__ double load_lds[];
         tab = stage_tables(g.q, load_lds);
     }
+    fesload::Radial rad{};
+    if constexpr (Args::kRadial) {
+        extern __shared__ double load_lds[];
+        rad = stage_radial(g.q, load_lds);
+    }
     for (size_t c = blockIdx.x; c < g.nchunks; c += gridDim.x) {
         const uint64_t k = static_cast<uint64_t>(c) * kLoadChunk + threadIdx.x;
         const uint32_t i = static_cast<uint32_t>(g.r.first + k);
         T st[3] = {};
-        double theta = 0, fq[3] = {};
+        double theta = 0, fq[3] = {}, rho = 0, dir[3] = {};
         bool keep = false;
         if (k < g.r.count) {
             double p[3];
-            if constexpr (Args::kProfile) fesload::base_of(g.r, tab, i, p, theta, fq);
+            if constexpr (Args::kRadial) fesload::radial_base_of(g.r, rad, i, p, theta, rho, dir);
+            else if constexpr (Args::kProfile) fesload::base_of(g.r, tab, i, p, theta, fq);
             else fesload::base_of(g.r, i, p, theta);
             fesload::displace(g.r, theta, p);
 #pragma unroll
@@ -224,7 +289,8 @@ __global__ __launch_bounds__(kLoadThreads) void load_keep_kernel(Args g)
             for (int w = 0; w < wave; ++w) slot += wave_kept[w];
             if (slot < g.limit) {   // (the host has checked the total against the capacity; the passes count alike)
                 double v[3];
-                if constexpr (Args::kProfile) fesload::velocity_of(g.r, tab, i, theta, fq, v);
+                if constexpr (Args::kRadial) fesload::radial_velocity_of(g.r, rad, i, theta, rho, dir, v);
+                else if constexpr (Args::kProfile) fesload::velocity_of(g.r, tab, i, theta, fq, v);
                 else fesload::velocity_of(g.r, i, theta, v);
 #pragma unroll
                 for (int a = 0; a < 3; ++a) {

@@ -1485,6 +1485,12 @@ int fpic_load_profile(fpic_handle* h, const fpic_load_spec* spec, const struct f
     BOX_ONLY(h, "fpic_load_profile");
     return fes::load_profile(h, spec, profile, loaded);
 }
+int fpic_load_radial(fpic_handle* h, const fpic_load_spec* spec, const struct fpic_load_radial* radial, uint64_t* loaded)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_load_radial");
+    return fes::load_radial(h, spec, radial, loaded);
+}
 int fpic_collide(fpic_handle* h, const fpic_collide_spec* spec, fpic_collide_result* out)
 {
     CHECK_HANDLE(h);

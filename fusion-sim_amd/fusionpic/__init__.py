@@ -47,7 +47,7 @@ ABI_FUNCTIONS = [
     "fpic_energy_now", "fpic_energy_record", "fpic_energy_history", "fpic_histogram", "fpic_moments",
     "fpic_series_now", "fpic_series_record", "fpic_series_history",
     "fpic_modes_now", "fpic_modes_record", "fpic_modes_history",
-    "fpic_select", "fpic_load", "fpic_load_profile", "fpic_collide", "fpic_collide_register", "fpic_collide_stats", "fpic_collide_clear",
+    "fpic_select", "fpic_load", "fpic_load_profile", "fpic_load_radial", "fpic_collide", "fpic_collide_register", "fpic_collide_stats", "fpic_collide_clear",
     "fpic_pair", "fpic_pair_register", "fpic_pair_stats", "fpic_pair_clear",
     "fpic_fusion", "fpic_fusion_register", "fpic_fusion_stats", "fpic_fusion_grid", "fpic_fusion_clear",
     "fpic_fusion_spectrum", "fpic_fusion_spectrum_register", "fpic_fusion_spectrum_read", "fpic_fusion_spectrum_clear",
@@ -380,9 +380,75 @@ def _load_profile(density=None, thermal=None, shear=None):
     return p
 
 
-def _load_call(sim, s, profile=None):
+LOAD_SPHERE, LOAD_CYLINDER = 1, 2
+_LOAD_GEOMETRIES = {"sphere": LOAD_SPHERE, "cylinder": LOAD_CYLINDER}
+
+
+class LoadRadial(ctypes.Structure):
+    """mirror of fpic_load_radial (include/fusionpic.h)"""
+    _fields_ = [
+        ("geometry", ctypes.c_uint32), ("axis", ctypes.c_int32), ("center", ctypes.c_double * 3), ("r_max", ctypes.c_double),
+        ("density_n", ctypes.c_uint32), ("thermal_n", ctypes.c_uint32), ("radial_n", ctypes.c_uint32), ("azimuthal_n", ctypes.c_uint32),
+        ("axial_n", ctypes.c_uint32), ("reserved", ctypes.c_uint32 * 3),
+        ("density", ctypes.POINTER(ctypes.c_double)), ("thermal", ctypes.POINTER(ctypes.c_double)), ("radial", ctypes.POINTER(ctypes.c_double)),
+        ("azimuthal", ctypes.POINTER(ctypes.c_double)), ("axial", ctypes.POINTER(ctypes.c_double)),
+    ]
+
+
+_RADIAL_KEYS = {"geometry", "center", "r_max", "axis", "density", "thermal", "flow_radial", "flow_azimuthal", "flow_axial"}
+
+
+def _load_radial(radial):
+    """LoadRadial of the `radial` argument of load(): dict(geometry="sphere" | "cylinder" (or the code), center=(x, y, z),
+    r_max=, axis=0, density=, thermal=, flow_radial=, flow_azimuthal=, flow_axial=), every table None or a one-dimensional
+    array of numbers.  Only what the structure cannot carry is refused here; the library checks the rest.  The arrays are
+    kept alive by the result (its `_tables`)."""
+    if not isinstance(radial, dict) or not set(radial) <= _RADIAL_KEYS or not {"geometry", "center", "r_max"} <= set(radial):
+        raise FusionPicError(-1, ".radial <- expected dict(geometry=, center=, r_max=[, axis=, density=, thermal=, flow_radial=, flow_azimuthal=, flow_axial=])")
+    p = LoadRadial()
+    p._tables = []
+    g = radial["geometry"]
+    g = _LOAD_GEOMETRIES.get(g, g) if isinstance(g, str) else g
+    if isinstance(g, bool) or not isinstance(g, (int, np.integer)) or not 0 <= int(g) < 1 << 32:
+        raise FusionPicError(-1, ".geometry <- must be 'sphere' or 'cylinder'")
+    p.geometry = int(g)
+    ax = radial.get("axis", 0)
+    if isinstance(ax, bool) or not isinstance(ax, (int, np.integer)) or not -(1 << 31) <= int(ax) < 1 << 31:
+        raise FusionPicError(-1, ".axis <- must be 0, 1 or 2")
+    p.axis = int(ax)
+    try:
+        c = [float(x) for x in radial["center"]]
+        if len(c) != 3:
+            raise ValueError
+    except (TypeError, ValueError):
+        raise FusionPicError(-1, ".center <- must be three numbers")
+    p.center[:] = c
+    try:
+        p.r_max = float(radial["r_max"])
+    except (TypeError, ValueError):
+        raise FusionPicError(-1, ".r_max <- must be a number")
+    for key, name in (("density", "density"), ("thermal", "thermal"), ("flow_radial", "radial"), ("flow_azimuthal", "azimuthal"), ("flow_axial", "axial")):
+        v = radial.get(key)
+        if v is None:
+            continue
+        try:
+            a = np.asarray(v, dtype=np.float64)
+        except (TypeError, ValueError):
+            raise FusionPicError(-1, ".%s <- a table must be a one-dimensional array of numbers" % key)
+        if a.ndim != 1 or a.size >= 1 << 32:
+            raise FusionPicError(-1, ".%s <- a table must be a one-dimensional array of numbers" % key)
+        a = np.ascontiguousarray(a)
+        p._tables.append(a)
+        setattr(p, name + "_n", a.size)
+        setattr(p, name, a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)))
+    return p
+
+
+def _load_call(sim, s, profile=None, radial=None):
     loaded = ctypes.c_uint64()
-    if profile is None:
+    if radial is not None:
+        sim._check(sim._lib.fpic_load_radial(sim._h, ctypes.byref(s), ctypes.byref(radial), ctypes.byref(loaded)))
+    elif profile is None:
         sim._check(sim._lib.fpic_load(sim._h, ctypes.byref(s), ctypes.byref(loaded)))
     else:
         sim._check(sim._lib.fpic_load_profile(sim._h, ctypes.byref(s), ctypes.byref(profile), ctypes.byref(loaded)))
@@ -926,6 +992,7 @@ def load_library(path=None):
     lib.fpic_select.argtypes = [vp, ctypes.POINTER(SelectSpec), ci, ctypes.c_uint64, vp, vp, vp, ci, ctypes.POINTER(ctypes.c_uint64)]
     lib.fpic_load.argtypes = [vp, ctypes.POINTER(LoadSpec), ctypes.POINTER(ctypes.c_uint64)]
     lib.fpic_load_profile.argtypes = [vp, ctypes.POINTER(LoadSpec), ctypes.POINTER(LoadProfile), ctypes.POINTER(ctypes.c_uint64)]
+    lib.fpic_load_radial.argtypes = [vp, ctypes.POINTER(LoadSpec), ctypes.POINTER(LoadRadial), ctypes.POINTER(ctypes.c_uint64)]
     lib.fpic_collide.argtypes = [vp, ctypes.POINTER(CollideSpec), ctypes.POINTER(CollideResult)]
     lib.fpic_collide_register.argtypes = [vp, ctypes.POINTER(CollideSpec), ci, ctypes.POINTER(ctypes.c_int)]
     lib.fpic_collide_stats.argtypes = [vp, ci, ci, ctypes.POINTER(CollideResult)]
@@ -1230,7 +1297,8 @@ class CylindricalParticlePusher:
         return [float(self.spec.get(k, 1.0)) for k in ("radius", "length_y", "height")]
 
     def load(self, species=0, first=0, count=None, seed=LOAD_SEED, stream=0, lo=None, hi=None, drift=0, vth=0, mode=None, xamp=0, xphase=0,
-             vamp=0, vphase=0, lattice=False, paired=False, position=True, velocity=True, append=False, density=None, thermal=None, shear=None):
+             vamp=0, vphase=0, lattice=False, paired=False, position=True, velocity=True, append=False, density=None, thermal=None, shear=None,
+             radial=None):
         """Particles [first, first + count) of one species of a CART3D box generated on the device (fpic_load; an (r,z)
         handle is refused): in the sub-box [lo, hi) (metres; random, or a Kronecker lattice with lattice=True) with a
         uniform density or a tabulated one, a drifting Maxwellian (drift, vth in units of c; paired=True makes the thermal
@@ -1246,9 +1314,22 @@ class CylindricalParticlePusher:
         or a table of values >= 0: the positions follow it (a lattice load becomes a quiet start on the profile).  thermal
         = (x, y, z), each None or a table of factors >= 0 that multiply vth at the particle's undisplaced position.  shear =
         dict(axis=, component=, values=): drift[component] += table(position along axis).  With all three None the call
-        is fpic_load itself."""
-        return _load_call(self, _load_spec(self._box_lengths(), species, first, count, seed, stream, lo, hi, drift, vth, mode, xamp, xphase,
-                                           vamp, vphase, lattice, paired, position, velocity, append), _load_profile(density, thermal, shear))
+        is fpic_load itself.
+
+        Radial bodies (fpic_load_radial): radial = dict(geometry="sphere" | "cylinder", center=(x, y, z), r_max= (metres),
+        axis=0 (the cylinder's), density=, thermal=, flow_radial=, flow_azimuthal=, flow_axial=): tables of 2 ..
+        LOAD_TABLE_MAX nodes over [0, r_max], linear between the nodes.  The particles fill the ball (the column over
+        [lo, hi] of its axis) with that density (None: uniform in the volume); thermal multiplies vth; the flows (units of
+        c) add to the drift along the radius, about the axis and along it (the last two: the cylinder only).  A body that
+        reaches across the periodic boundary wraps.  radial= does not combine with density=, thermal= or shear=
+        (ValueError)."""
+        s = _load_spec(self._box_lengths(), species, first, count, seed, stream, lo, hi, drift, vth, mode, xamp, xphase,
+                       vamp, vphase, lattice, paired, position, velocity, append)
+        if radial is not None:
+            if density is not None or thermal is not None or shear is not None:
+                raise ValueError("load(): radial= does not combine with density=, thermal= or shear=")
+            return _load_call(self, s, radial=_load_radial(radial))
+        return _load_call(self, s, _load_profile(density, thermal, shear))
 
     # ---- Monte Carlo collisions with a prescribed background (fpic_collide*)
     def collide(self, kind, **request):

@@ -312,6 +312,25 @@ function makeBox(spec, lib) {
         // 2 .. 1025 nodes over [lo, hi] on its axis, linear between them); shear = { axis, component, values }.  Without any
         // of the three keys the call is fpic_load itself.
         const none = (v) => v === undefined || v === null;
+        // a radial body (fpic_load_radial): radial = { geometry: 'sphere' | 'cylinder', center: [x, y, z], r_max, axis (the
+        // cylinder's, default 0), density, thermal, flow_radial, flow_azimuthal, flow_axial (tables of 2 .. 1025 nodes over
+        // [0, r_max]) }; it does not combine with density, thermal or shear
+        if (!none(request.radial)) {
+            const rd = request.radial;
+            if (typeof rd !== 'object' || Array.isArray(rd)) throw new TypeError('.radial <- expected { geometry, center, r_max, ... }');
+            if (!none(request.density) || !none(request.thermal) || !none(request.shear)) throw new RangeError('.radial <- does not combine with density, thermal or shear');
+            const geometry = rd.geometry === 'sphere' ? 1 : rd.geometry === 'cylinder' ? 2 : rd.geometry;
+            const head = [whole('geometry', geometry, 0, 0, 0xffffffff), whole('axis', rd.axis, 0, -0x80000000, 0x7fffffff)].concat(three('center', rd.center, null), [real('r_max', rd.r_max)]);
+            const counts = [], values = [];
+            for (const name of ['density', 'thermal', 'flow_radial', 'flow_azimuthal', 'flow_axial']) {
+                const v = rd[name];
+                if (none(v)) { counts.push(0); continue; }
+                if (!(Array.isArray(v) || ArrayBuffer.isView(v)) || !Array.from(v).every((x) => typeof x === 'number')) throw new RangeError('.' + name + ' <- a table must be an array of numbers');
+                counts.push(v.length);
+                for (const x of v) values.push(x);
+            }
+            return lib.load(h, species, Float64Array.from(words), Float64Array.from(reals), Float64Array.from(head.concat(counts)), Float64Array.from(values));
+        }
         if (none(request.density) && none(request.thermal) && none(request.shear)) return lib.load(h, species, Float64Array.from(words), Float64Array.from(reals));
         const shape = [], tables = [];
         const table = function (name, v) {

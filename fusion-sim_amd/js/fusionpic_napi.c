@@ -904,7 +904,35 @@ static napi_value n_load(napi_env env, napi_callback_info info)
     napi_typedarray_type ts = napi_float64_array, tt = napi_float64_array; void *ps = NULL, *pt = NULL; size_t ls = 0, lt = 0;
     if (argc >= 5 && !get_typed(env, more[4], &ts, &ps, &ls)) return NULL;
     if (argc >= 6 && !get_typed(env, more[5], &tt, &pt, &lt)) return NULL;
-    if (ps) {
+    if (ps && ls == 11) {
+        /* a radial load (fpic_load_radial): shape: Float64Array [geometry, axis, center x, y, z, r_max, density nodes, thermal
+         * nodes, radial, azimuthal and axial flow nodes] (eleven entries tell it from a profile's nine), tables: the tables one
+         * after the other in that order */
+        if (ts != napi_float64_array || (pt && tt != napi_float64_array)) { napi_throw_type_error(env, NULL, ".radial <- expected two Float64Arrays"); return NULL; }
+        const double* q = (const double*)ps;
+        double total = 0;
+        for (int k = 0; k < 11; ++k) {
+            if (k >= 2 && k <= 5) continue;
+            const double least = k == 1 ? -2147483648.0 : 0.0, most_k = k == 1 ? 2147483647.0 : 4294967295.0;
+            if (!(q[k] >= least && q[k] <= most_k) || q[k] != (double)(int64_t)q[k]) {
+                napi_throw_range_error(env, NULL, ".radial <- geometry, axis and the node counts must be integers within their fields");
+                return NULL;
+            }
+            if (k >= 6) total += q[k];
+        }
+        if (!check_len(env, "tables", lt, (size_t)total)) return NULL;
+        struct fpic_load_radial p;
+        memset(&p, 0, sizeof p);
+        const double* at = (const double*)pt;
+        p.geometry = (uint32_t)q[0]; p.axis = (int32_t)q[1];
+        p.center[0] = q[2]; p.center[1] = q[3]; p.center[2] = q[4]; p.r_max = q[5];
+        p.density_n = (uint32_t)q[6]; if (p.density_n) { p.density = at; at += p.density_n; }
+        p.thermal_n = (uint32_t)q[7]; if (p.thermal_n) { p.thermal = at; at += p.thermal_n; }
+        p.radial_n = (uint32_t)q[8]; if (p.radial_n) { p.radial = at; at += p.radial_n; }
+        p.azimuthal_n = (uint32_t)q[9]; if (p.azimuthal_n) { p.azimuthal = at; at += p.azimuthal_n; }
+        p.axial_n = (uint32_t)q[10]; if (p.axial_n) p.axial = at;
+        if (fpic_load_radial(h, &s, &p, &loaded) != FPIC_OK) return throw_fpic(env, h);
+    } else if (ps) {
         if (ts != napi_float64_array || (pt && tt != napi_float64_array)) { napi_throw_type_error(env, NULL, ".profile <- expected two Float64Arrays"); return NULL; }
         if (!check_len(env, "shape", ls, 9)) return NULL;
         const double* q = (const double*)ps;

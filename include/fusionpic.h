@@ -789,6 +789,62 @@ struct fpic_load_profile {
 };
 int fpic_load_profile(fpic_handle* h, const fpic_load_spec* spec, const struct fpic_load_profile* profile, uint64_t* loaded);
 
+/* ---- CART3D particle loader with radial profiles: a spherical or a cylindrical population whose density, thermal speed and
+ * flows are tables of the radius — a hot spot in a shell with an implosion velocity, a pinch with an axial drift, a rotating
+ * column.  Every flag and field of the request keeps its meaning (lo and hi only on the cylinder's own axis), and so does
+ * what the state of particle i depends on: the request, the tables and i alone.
+ * A table of n nodes is uniformly spaced over [0, r_max] — node 0 on the centre (the axis), node n - 1 at r_max — and linear
+ * between the nodes.  K = n - 1 is its number of intervals, rho the radius in units of r_max.  All arithmetic is double,
+ * every operation rounded once; the radius takes only + - * / and comparisons.  f0, f1, f2 are the unit fractions fpic_load
+ * draws on the three axes (random or lattice).
+ *   mass       in units of the node spacing, with d0 = d[j], D = d[j+1] - d[j], J = (double) j, the mass of interval j up to
+ *              the place s in [0, 1], in Horner form ("x s" multiplies the sum so far by s, "a + (..)" adds a to it):
+ *                sphere (weight rho^2)    JJ = J J;  a1 = d0 JJ;  a2 = d0 J + 0.5 (D JJ);  a3 = (d0 + (2 J) D) / 3;  a4 = 0.25 D;
+ *                                         M_j(s) = (a1 + (a2 + (a3 + a4 s) s) s) s
+ *                cylinder (weight rho)    a1 = d0 J;  a2 = 0.5 (d0 + D J);  a3 = D / 3;
+ *                                         M_j(s) = (a1 + (a2 + a3 s) s) s
+ *              C[0] = 0, C[j+1] = C[j] + M_j(1), summed in sequence on the host, M_j(1) by the same evaluation at s = 1.
+ *   radius     f = f0 for the sphere, the fraction of axis b for the cylinder:
+ *                  t = f C[K];  j = the largest index with C[j] <= t, held to K - 1;  r = t - C[j];
+ *                  lo = 0, hi = 1; 52 times: mid = 0.5 (lo + hi); if M_j(mid) <= r then lo = mid, else hi = mid;  s = lo;
+ *                  rho = (J + s) / K, and 1 - 2^-53 if that is not below 1.
+ *              An interval without mass is never chosen.  density_n = 0 is the table {1, 1}: uniform in the volume (the
+ *              area).  A lattice load is a quiet start on the profile.
+ *   direction  sphere:    mu = 2 f1 - 1;  q = sqrt(1 - mu mu);  cs = cospi(2 f2), sn = sinpi(2 f2);  dir = (q cs, q sn, mu).
+ *              cylinder about axis a, with b = (a + 1) mod 3 and c = (a + 2) mod 3:
+ *                         dir_a = 0, dir_b = cospi(2 f_c), dir_c = sinpi(2 f_c).
+ *   position   in box fractions: p_k = center[k]/L_k + (rho (r_max/L_k)) dir_k; along the cylinder's axis fpic_load's own
+ *              p_a = lo[a]/L_a + f_a (hi[a] - lo[a])/L_a.  theta, the displacement, the cast and the wrap are fpic_load's: a
+ *              body that reaches across the periodic boundary wraps.
+ *   velocity   the tables are read by fpic_load_profile's lookup at f' = rho (of the UNDISPLACED position).
+ *              vth_eff[k] = vth[k] thermal(rho) (no table: a factor of exactly 1, no multiply);
+ *              sphere:    drift_eff[k] = drift[k] + u_r dir_k
+ *              cylinder:  drift_eff[a] = drift[a] + u_a;  drift_eff[b] = (drift[b] + u_r dir_b) + u_t (-dir_c);
+ *                         drift_eff[c] = (drift[c] + u_r dir_c) + u_t dir_b
+ *              with u_r, u_t, u_a the radial, azimuthal and axial tables' values (a flow without a table adds nothing);
+ *              then fpic_load's velocity with vth_eff and drift_eff.
+ * Refused (FPIC_ERR_INVALID_ARG) besides what fpic_load refuses: a null request, an unknown geometry, an axis outside 0..2
+ * (a sphere: other than 0), r_max that is not positive and finite, 2 r_max above the box length on an axis the body spans
+ * (the sphere: all three, the cylinder: the two across its axis), a centre outside [0, L], a node count of 1 or above
+ * FPIC_LOAD_TABLE_MAX, a null table whose count is not zero, a value that is not finite, a negative density or thermal
+ * value, a density table whose total mass is 0, azimuthal_n or axial_n for the sphere, a reserved word that is not zero.
+ * FPIC_ERR_STATE: a handle that is not CART3D.  Synchronous. */
+#define FPIC_LOAD_SPHERE   1u
+#define FPIC_LOAD_CYLINDER 2u
+struct fpic_load_radial {                 /* (a tag, as struct fpic_load_profile) */
+    uint32_t geometry;                    /* FPIC_LOAD_SPHERE or FPIC_LOAD_CYLINDER */
+    int32_t  axis;                        /* the cylinder's axis 0..2; a sphere: 0 */
+    double   center[3], r_max;            /* metres; the cylinder ignores center[axis] */
+    uint32_t density_n, thermal_n, radial_n, azimuthal_n, axial_n;   /* nodes; 0 = none (density: uniform in volume) */
+    uint32_t reserved[3];                 /* zero */
+    const double* density;                /* >= 0, finite, at least one interval with mass */
+    const double* thermal;                /* >= 0, finite: multiplies vth */
+    const double* radial;                 /* finite, units of c: the flow along dir */
+    const double* azimuthal;              /* the cylinder: the flow about the axis */
+    const double* axial;                  /* the cylinder: the flow along the axis */
+};
+int fpic_load_radial(fpic_handle* h, const fpic_load_spec* spec, const struct fpic_load_radial* radial, uint64_t* loaded);
+
 /* ---- CART3D Monte Carlo collisions with a prescribed background: a drifting Maxwellian (drift, vth per axis, units of c)
  * that is not another species; the momentum and energy the species loses go to that reservoir.  The operator acts on the
  * stored velocities of one species (under full EM the half-time velocity, as fpic_histogram reads it), as a call or

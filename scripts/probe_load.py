@@ -1,4 +1,4 @@
-"""Measurements of the particle loader (fpic_load, fpic_load_profile).  Three modes:
+"""Measurements of the particle loader (fpic_load, fpic_load_profile, fpic_load_radial).  Four modes:
 
   ulps   the kernel's normals and sines against 50-digit values (tests/load_exact.py) over the 10^5 particles of its scene: an
          fp64 box loaded with vth = 1 (the velocities ARE the normals) and with vamp = 1 (the velocities ARE the sines).
@@ -12,6 +12,9 @@
          1025-node density table, with three, and with three density tables, three thermal tables and a shear table
          (fpic_load_profile), and the setRange uploads (b) that are the floor of each.  Prints median, min, max and the
          ratios to (a).
+  radial   the same box and request, per precision and in one run: fpic_load, fpic_load_profile with three density tables,
+         and fpic_load_radial for a sphere with a 1025-node density, the same with thermal and radial-flow tables, and a
+         cylinder with all five tables.  Prints median, min, max and the ratios to fpic_load.
 """
 import argparse
 import json
@@ -156,11 +159,46 @@ def profile(args):
     print(json.dumps(out))
 
 
+def radial(args):
+    import numpy as np
+    import torch
+    import fusionpic as fp
+    n, grid = args.particles, args.grid
+    L = grid * 3e-4
+    request = dict(drift=(0.0, 0.0, 0.01), vth=1e-3, mode=(1, 0, 0), xamp=(1e-3 * L, 0, 0), vamp=(1e-5, 0, 0))
+    x = np.linspace(0.0, 1.0, 1025)
+    gauss, wavy, ramp = np.exp(-0.5 * ((x - 0.5) / 0.2) ** 2), 1.0 + 0.5 * np.cos(7 * x), 0.5 + x
+    ball = dict(geometry="sphere", center=(0.5 * L, 0.5 * L, 0.5 * L), r_max=0.4 * L)
+    column = dict(ball, geometry="cylinder", axis=2)
+    cases = {
+        "load": {},
+        "density_3": dict(density=(gauss, wavy, ramp)),
+        "sphere_density": dict(radial=dict(ball, density=gauss)),
+        "sphere_density_thermal_flow": dict(radial=dict(ball, density=gauss, thermal=ramp, flow_radial=-0.01 * x)),
+        "cylinder_all_five": dict(radial=dict(column, density=gauss, thermal=ramp, flow_radial=-0.01 * x, flow_azimuthal=0.02 * x, flow_axial=0.01 * wavy)),
+    }
+    stream = torch.cuda.Stream()
+    out = {"particles": n, "grid": grid, "calls": args.calls}
+    for precision in ("fp32", "fp64"):
+        sim = fp.makeCylindricalParticlePusher(box_spec(grid, n, L), precision=precision)
+        sim.setStream(stream.cuda_stream)
+        res = {}
+        for name, extra in cases.items():
+            res[name] = timed(torch, stream, args.calls, lambda: sim.load(**request, **extra))
+        sim.destroy()
+        del sim
+        torch.cuda.empty_cache()
+        res["over_load"] = {name: res[name][0] / res["load"][0] for name in cases}
+        out[precision] = res
+        print(precision, json.dumps(res), flush=True)
+    print(json.dumps(out))
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
-    ap.add_argument("mode", choices=["ulps", "time", "profile"])
+    ap.add_argument("mode", choices=["ulps", "time", "profile", "radial"])
     ap.add_argument("--particles", type=int, default=500000000)
     ap.add_argument("--grid", type=int, default=256)
     ap.add_argument("--calls", type=int, default=5)
     a = ap.parse_args()
-    {"ulps": ulps, "time": time_, "profile": profile}[a.mode](a)
+    {"ulps": ulps, "time": time_, "profile": profile, "radial": radial}[a.mode](a)
