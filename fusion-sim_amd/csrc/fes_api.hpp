@@ -48,6 +48,11 @@ int collide(fpic_handle* h, const fpic_collide_spec* spec, fpic_collide_result* 
 int collide_register(fpic_handle* h, const fpic_collide_spec* spec, int every, int* index);
 int collide_stats(fpic_handle* h, int index, int scope, fpic_collide_result* out);
 int collide_clear(fpic_handle* h);
+// prescribed external forces (fes_force.inc.hpp)
+int force(fpic_handle* h, const fpic_force_spec* spec, fpic_force_result* out);
+int force_register(fpic_handle* h, const fpic_force_spec* spec, int* index);
+int force_stats(fpic_handle* h, int index, int scope, fpic_force_result* out);
+int force_clear(fpic_handle* h);
 // binary Coulomb collisions between the species of the box (fes_pair.inc.hpp)
 int pair(fpic_handle* h, const fpic_pair_spec* spec, fpic_pair_result* out);
 int pair_register(fpic_handle* h, const fpic_pair_spec* spec, int every, int* index);

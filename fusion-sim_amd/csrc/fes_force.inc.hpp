@@ -1,0 +1,172 @@
+// fes_force.inc.hpp: the prescribed external forces of a CART3D handle (fpic_force, fpic_force_register, fpic_force_stats,
+// fpic_force_clear) — part of fes_api.hip's translation unit (included there after fes_collide.inc.hpp, inside namespace fes).
+// The rule and the checks of a request are fes_force_core.hpp, the pass fes_force_kernels.hpp.
+//
+// One launch per application over the slots [0, n) and, while a migration rides on the next push, the arrivals behind them
+// (one range, as collide_enqueue).  The handle keeps one device block: fesforce::kWords tally words and room for three taper
+// tables per registered request, and one more of each for the call that is applied now.  A request's tables are copied at
+// the call — the tapers to the device, the envelope to the host, where it is read once per application.  A registered
+// request is enqueued by the hook diag_after_substep with no host synchronisation and no collective; fpic_force_stats
+// reads its words.
+
+constexpr int kForceNow = FPIC_FORCE_MAX_OPS;            // the words and tables of fpic_force
+constexpr size_t kForceTabDoubles = 3 * static_cast<size_t>(FPIC_FORCE_TABLE_MAX);   // per request
+
+static int force_room(fpic_handle* h)
+{
+    Diag& g = h->es->diag;
+    if (g.force) return FPIC_OK;
+    void* p = nullptr;
+    const size_t words = static_cast<size_t>(FPIC_FORCE_MAX_OPS + 1) * fesforce::kWords * sizeof(unsigned long long);
+    const size_t bytes = words + static_cast<size_t>(FPIC_FORCE_MAX_OPS + 1) * kForceTabDoubles * sizeof(double);
+    if (int rc = dev_alloc(h, &p, bytes, &h->bytes_grid)) return rc;
+    g.force = static_cast<unsigned long long*>(p);
+    g.force_tab = reinterpret_cast<double*>(static_cast<unsigned char*>(p) + words);
+    HIP_TRY(h, hipMemsetAsync(g.force, 0, words, h->stream));
+    return FPIC_OK;
+}
+
+// a checked request into place `at`: its tally words zeroed, its taper tables on the device, the envelope in `op`
+static int force_hold(fpic_handle* h, const fpic_force_spec& spec, int at, ForceOp& op)
+{
+    Diag& g = h->es->diag;
+    if (int rc = force_room(h)) return rc;
+    op.spec = spec;
+    op.applications = 0;
+    op.envelope.assign(spec.envelope, spec.envelope + spec.envelope_n);
+    op.spec.envelope = nullptr;
+    HIP_TRY(h, hipMemsetAsync(g.force + at * fesforce::kWords, 0, fesforce::kWords * sizeof(unsigned long long), h->stream));
+    double* tab = g.force_tab + at * kForceTabDoubles;
+    bool any = false;
+    for (int a = 0; a < 3; ++a) {
+        op.taper[a] = nullptr;
+        op.spec.taper[a] = nullptr;
+        if (!spec.taper_n[a]) continue;
+        HIP_TRY(h, hipMemcpyAsync(tab, spec.taper[a], spec.taper_n[a] * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        op.taper[a] = tab;
+        tab += spec.taper_n[a];
+        any = true;
+    }
+    if (any) HIP_TRY(h, hipStreamSynchronize(h->stream));   // (the caller's tables are pageable and may change after the call)
+    return FPIC_OK;
+}
+
+// one application of `op` at s = `at` (the request is active there), its tallies added to `words`: enqueued, nothing waited for
+template <typename T>
+static int force_enqueue(fpic_handle* h, const ForceOp& op, uint64_t at, unsigned long long* words)
+{
+    State* st = h->es;
+    const Species& sp = st->sp[op.spec.species];
+    const size_t slots = std::min(sp.n + sp.tail_count, sp.n_pad);   // (the arrivals of a riding migration follow at tail_first = n)
+    if (!slots) return FPIC_OK;
+    const double L[3] = { st->lx, st->ly, st->lz };
+    ForceArgs<T> a{};
+    a.slab = static_cast<T*>(sp.slab[sp.cur]);
+    a.n_pad = sp.n_pad;
+    a.s1 = slots;
+    a.dead = st->dom ? 1 : 0;
+    a.words = words;
+    a.r = fesforce::rule_of(op.spec, L, sp.charge, sp.mass, h->spec.dt, at, op.envelope.data(), op.taper);
+    const size_t groups = (slots + 3) / 4;
+    const unsigned grid = static_cast<unsigned>(std::min<size_t>(kForceBlocks, (groups + kForceThreads - 1) / kForceThreads));
+    if (a.r.whole && !a.r.tapered) {
+        force_kernel<T, true><<<grid, kForceThreads, 0, h->stream>>>(a);
+    } else {
+        size_t lds = 0;
+        for (int k = 0; k < 3; ++k) lds += op.spec.taper_n[k] * sizeof(double);
+        force_kernel<T, false><<<grid, kForceThreads, lds, h->stream>>>(a);
+    }
+    HIP_TRY(h, hipGetLastError());
+    return FPIC_OK;
+}
+
+static int force_apply(fpic_handle* h, const ForceOp& op, uint64_t at, unsigned long long* words)
+{
+    return h->prec == FPIC_F32 ? force_enqueue<float>(h, op, at, words) : force_enqueue<double>(h, op, at, words);
+}
+
+static const char* force_check(fpic_handle* h, const fpic_force_spec* spec)
+{
+    const State* st = h->es;
+    const double L[3] = { st->lx, st->ly, st->lz };
+    return fesforce::check(spec, static_cast<int>(st->sp.size()), L);
+}
+
+int force(fpic_handle* h, const fpic_force_spec* spec, fpic_force_result* out)
+{
+    State* st = h->es;
+    if (const char* why = force_check(h, spec)) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    if (out) *out = fpic_force_result{};
+    const uint64_t at = st->diag.substep + spec->epoch;
+    if (!fesforce::active(*spec, at)) return FPIC_OK;
+    ForceOp op;
+    if (int rc = force_hold(h, *spec, kForceNow, op)) return rc;
+    unsigned long long* words = st->diag.force + kForceNow * fesforce::kWords;
+    if (int rc = force_apply(h, op, at, words)) return rc;
+    uint64_t got[fesforce::kWords] = {};
+    HIP_TRY(h, hipMemcpyAsync(got, words, sizeof(got), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (out) {
+        out->applications = 1;
+        fesforce::result_of(got, st->sp[spec->species].mass, st->W, out);
+    }
+    return FPIC_OK;
+}
+
+int force_register(fpic_handle* h, const fpic_force_spec* spec, int* index)
+{
+    Diag& g = h->es->diag;
+    if (const char* why = force_check(h, spec)) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    if (const char* why = fesforce::check_register(static_cast<int>(g.force_ops.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    const int at = static_cast<int>(g.force_ops.size());
+    ForceOp op;
+    if (int rc = force_hold(h, *spec, at, op)) return rc;
+    g.force_ops.push_back(std::move(op));
+    if (index) *index = at;
+    return FPIC_OK;
+}
+
+int force_stats(fpic_handle* h, int index, int scope, fpic_force_result* out)
+{
+    State* st = h->es;
+    Diag& g = st->diag;
+    if (!out) return fail(h, FPIC_ERR_INVALID_ARG, ".out <- Non-optional property is undefined!");
+    if (const char* why = fesforce::check_index(index, static_cast<int>(g.force_ops.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    bool collective = false;
+    if (int rc = diag_scope(h, scope, collective)) return rc;
+    uint64_t got[fesforce::kWords] = {};
+    HIP_TRY(h, hipMemcpyAsync(got, g.force + index * fesforce::kWords, sizeof(got), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (collective) {
+        uint64_t parts[fesforce::kSumWords];
+        fesforce::split_words(got, parts);
+        if (int rc = diag_sum_ranks(h, parts, fesforce::kSumWords)) return rc;
+        fesforce::join_words(parts, got);
+    }
+    const ForceOp& op = g.force_ops[index];
+    *out = fpic_force_result{};
+    out->applications = op.applications;   // (the same on every rank: not summed)
+    fesforce::result_of(got, st->sp[op.spec.species].mass, st->W, out);
+    return FPIC_OK;
+}
+
+int force_clear(fpic_handle* h)
+{
+    h->es->diag.force_ops.clear();   // (applications in flight keep their words and tables; a later registration rewrites its own in stream order)
+    return FPIC_OK;
+}
+
+// the hook's part (diag_after_substep, directly after the sub-step is counted): every registered request that is active,
+// in registration order; nothing registered: nothing is enqueued
+static int force_after_substep(fpic_handle* h, uint64_t substep)
+{
+    Diag& g = h->es->diag;
+    for (size_t k = 0; k < g.force_ops.size(); ++k) {
+        ForceOp& op = g.force_ops[k];
+        const uint64_t at = substep + op.spec.epoch;
+        if (!fesforce::active(op.spec, at)) continue;
+        op.applications++;
+        if (int rc = force_apply(h, op, at, g.force + k * fesforce::kWords)) return rc;
+    }
+    return FPIC_OK;
+}

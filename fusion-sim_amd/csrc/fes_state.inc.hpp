@@ -83,6 +83,15 @@ struct CollideOp {
     uint64_t applications;
 };
 
+// a prescribed external force (fes_force.inc.hpp): the request (its table pointers are not kept), the host's copy of the
+// envelope table, where its taper tables lie on the device, the applications so far
+struct ForceOp {
+    fpic_force_spec spec;
+    std::vector<double> envelope;
+    const double* taper[3];
+    uint64_t applications;
+};
+
 // a registered binary collision operator (fes_pair.inc.hpp): the request, its period in sub-steps, the applications so far
 struct PairOp {
     fpic_pair_spec spec;
@@ -129,6 +138,11 @@ struct Diag {
     size_t load_tab_bytes = 0;
     unsigned long long* coll = nullptr; // the counts of fpic_collide (fes_collide.inc.hpp): four words per registered operator, four for a call
     std::vector<CollideOp> coll_ops;    // the registered operators, in registration order
+    // fpic_force (fes_force.inc.hpp): one block - per registered request and one more for a call, fesforce::kWords tally words,
+    // then room for three taper tables each (force_tab points into the block)
+    unsigned long long* force = nullptr;
+    double* force_tab = nullptr;
+    std::vector<ForceOp> force_ops;     // the registered requests, in registration order
     unsigned long long* pair = nullptr; // the counts of fpic_pair (fes_pair.inc.hpp): eight words per registered operator, eight for a call
     std::vector<PairOp> pair_ops;       // the registered operators, in registration order
     // the cell index of fpic_pair, one per side (species_a, species_b): pair_seg[s] = 4 + cells words (zeros, then per cell
@@ -154,7 +168,7 @@ inline void diag_release(Diag& g)
 {
     for (Recorder& r : g.rec)
         if (r.dev) (void)hipFree(r.dev);
-    for (void* p : { g.series_req.block, g.modes_req.block, static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom), g.sel, static_cast<void*>(g.load_tab), static_cast<void*>(g.coll), static_cast<void*>(g.pair),
+    for (void* p : { g.series_req.block, g.modes_req.block, static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom), g.sel, static_cast<void*>(g.load_tab), static_cast<void*>(g.coll), static_cast<void*>(g.force), static_cast<void*>(g.pair),
                      static_cast<void*>(g.pair_seg[0]), static_cast<void*>(g.pair_seg[1]), static_cast<void*>(g.pair_index[0]), static_cast<void*>(g.pair_index[1]),
                      static_cast<void*>(g.fusion), static_cast<void*>(g.fusion_table),
                      static_cast<void*>(g.fspec), static_cast<void*>(g.fspec_table), static_cast<void*>(g.fspec_words) })

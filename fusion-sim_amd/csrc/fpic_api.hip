@@ -1509,6 +1509,30 @@ int fpic_collide_stats(fpic_handle* h, int index, int scope, fpic_collide_result
     BOX_ONLY(h, "fpic_collide_stats");
     return fes::collide_stats(h, index, scope, out);
 }
+int fpic_force(fpic_handle* h, const fpic_force_spec* spec, fpic_force_result* out)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_force");
+    return fes::force(h, spec, out);
+}
+int fpic_force_register(fpic_handle* h, const fpic_force_spec* spec, int* index)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_force_register");
+    return fes::force_register(h, spec, index);
+}
+int fpic_force_stats(fpic_handle* h, int index, int scope, fpic_force_result* out)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_force_stats");
+    return fes::force_stats(h, index, scope, out);
+}
+int fpic_force_clear(fpic_handle* h)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_force_clear");
+    return fes::force_clear(h);
+}
 int fpic_collide_clear(fpic_handle* h)
 {
     CHECK_HANDLE(h);

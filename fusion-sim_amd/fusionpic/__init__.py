@@ -51,6 +51,7 @@ ABI_FUNCTIONS = [
     "fpic_pair", "fpic_pair_register", "fpic_pair_stats", "fpic_pair_clear",
     "fpic_fusion", "fpic_fusion_register", "fpic_fusion_stats", "fpic_fusion_grid", "fpic_fusion_clear",
     "fpic_fusion_spectrum", "fpic_fusion_spectrum_register", "fpic_fusion_spectrum_read", "fpic_fusion_spectrum_clear",
+    "fpic_force", "fpic_force_register", "fpic_force_stats", "fpic_force_clear",
 ]
 
 
@@ -533,6 +534,141 @@ def _collide_counts(r):
     return {"applications": int(r.applications), "candidates": int(r.candidates), "collided": int(r.collided), "clipped": int(r.clipped)}
 
 
+FORCE_FIELD, FORCE_ACCEL = 0, 1
+FORCE_MAX_WAVES, FORCE_MAX_OPS, FORCE_TABLE_MAX = 4, 8, 1025
+FORCE_FOREVER = (1 << 64) - 1
+FORCE_KINDS = {"field": FORCE_FIELD, "accel": FORCE_ACCEL}
+FORCE_FIX_BITS = 80
+
+
+class ForceWave(ctypes.Structure):
+    """mirror of fpic_force_wave (include/fusionpic.h)"""
+    _fields_ = [("amp", ctypes.c_double * 3), ("mode", ctypes.c_int32 * 3), ("reserved", ctypes.c_int32), ("nu", ctypes.c_double), ("phase", ctypes.c_double)]
+
+
+class ForceSpec(ctypes.Structure):
+    """mirror of fpic_force_spec"""
+    _fields_ = [
+        ("species", ctypes.c_int32), ("kind", ctypes.c_int32), ("nwaves", ctypes.c_int32), ("reserved_i32", ctypes.c_int32),
+        ("epoch", ctypes.c_uint64), ("start", ctypes.c_uint64), ("stop", ctypes.c_uint64),
+        ("lo", ctypes.c_double * 3), ("hi", ctypes.c_double * 3), ("wave", ForceWave * FORCE_MAX_WAVES),
+        ("taper_n", ctypes.c_uint32 * 3), ("envelope_n", ctypes.c_uint32),
+        ("taper", ctypes.POINTER(ctypes.c_double) * 3), ("envelope", ctypes.POINTER(ctypes.c_double)), ("reserved", ctypes.c_double * 4),
+    ]
+
+
+class ForceResult(ctypes.Structure):
+    """mirror of fpic_force_result"""
+    _fields_ = [("applications", ctypes.c_uint64), ("kicked", ctypes.c_uint64), ("work_fixed", ctypes.c_uint64 * 2),
+                ("impulse_fixed", (ctypes.c_uint64 * 2) * 3), ("work", ctypes.c_double), ("impulse", ctypes.c_double * 3)]
+
+
+def _force_spec(dt, L, waves=None, species=0, kind="field", lo=None, hi=None, taper=(None, None, None), envelope=None, epoch=0):
+    """ForceSpec of a force request, and the arrays its table pointers point into (keep them until the call has returned).
+    waves: dicts {amp (a number or three), mode (three integers, default 0), nu (turns per sub-step) or frequency (Hz, becomes
+    nu = frequency dt), phase (turns)}.  lo, hi (metres; a number is taken for all three axes) default to the whole box.
+    taper: per axis None or the nodes of a table over [lo, hi].  envelope: None (always active, amplitude 1) or {start, stop,
+    values}: active for start <= s <= stop, `values` (optional) the nodes of a table over that span.  Only what the structure
+    cannot carry is refused here; the library checks the rest."""
+    s = ForceSpec()
+    keep = []
+
+    def whole(name, v, bits, signed=False):
+        lo_, hi_ = (-(1 << bits - 1), 1 << bits - 1) if signed else (0, 1 << bits)
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo_ <= int(v) < hi_:
+            raise FusionPicError(-1, ".%s <- must be %s %d-bit integer" % (name, "a signed" if signed else "an unsigned", bits))
+        return int(v)
+
+    def three(name, v):
+        try:
+            if np.ndim(v) == 0:
+                v = [v, v, v]
+            if len(v) != 3:
+                raise ValueError
+            return [float(x) for x in v]
+        except (TypeError, ValueError):
+            raise FusionPicError(-1, ".%s <- must be a number or three of them" % name)
+
+    def real(name, v):
+        try:
+            return float(v)
+        except (TypeError, ValueError):
+            raise FusionPicError(-1, ".%s <- must be a number" % name)
+
+    def table(name, v):
+        try:
+            a = np.asarray(v, dtype=np.float64)
+        except (TypeError, ValueError):
+            a = None
+        if a is None or a.ndim != 1 or a.size >= 1 << 32:
+            raise FusionPicError(-1, ".%s <- a table must be a sequence of numbers" % name)
+        a = np.ascontiguousarray(a)
+        keep.append(a)
+        return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(a.size)
+
+    if isinstance(kind, str):
+        if kind not in FORCE_KINDS:
+            raise FusionPicError(-1, ".kind <- must be one of %s" % ", ".join(sorted(FORCE_KINDS)))
+        kind = FORCE_KINDS[kind]
+    s.kind = whole("kind", kind, 32, signed=True)
+    s.species = whole("species", species, 32, signed=True)
+    s.epoch = whole("epoch", epoch, 64)
+    if waves is None or isinstance(waves, dict) or not hasattr(waves, "__len__"):
+        raise FusionPicError(-1, ".waves <- must be a list of 1 .. 4 waves")
+    s.nwaves = whole("nwaves", len(waves), 32, signed=True)
+    for k, w in enumerate(list(waves)[:FORCE_MAX_WAVES]):
+        if not isinstance(w, dict) or set(w) - {"amp", "mode", "nu", "frequency", "phase"} or "amp" not in w:
+            raise FusionPicError(-1, ".waves <- a wave is {amp, mode, nu | frequency, phase}")
+        if "nu" in w and "frequency" in w:
+            raise FusionPicError(-1, ".nu <- give either nu or frequency, not both")
+        s.wave[k].amp[:] = three("amp", w["amp"])
+        mode = w.get("mode", (0, 0, 0))
+        if np.ndim(mode) != 1 or len(mode) != 3:
+            raise FusionPicError(-1, ".mode <- must be three integers")
+        s.wave[k].mode[:] = [whole("mode", m, 32, signed=True) for m in mode]
+        s.wave[k].nu = real("frequency", w["frequency"]) * dt if "frequency" in w else real("nu", w.get("nu", 0.0))
+        s.wave[k].phase = real("phase", w.get("phase", 0.0))
+    s.lo[:] = three("lo", 0.0 if lo is None else lo)
+    s.hi[:] = three("hi", L if hi is None else hi)
+    if not isinstance(taper, (list, tuple)) or len(taper) != 3:
+        raise FusionPicError(-1, ".taper <- must be three tables (None: no table)")
+    for a, t in enumerate(taper):
+        if t is not None:
+            s.taper[a], s.taper_n[a] = table("taper", t)
+    s.start, s.stop = 0, FORCE_FOREVER
+    if envelope is not None:
+        if not isinstance(envelope, dict) or set(envelope) - {"start", "stop", "values"}:
+            raise FusionPicError(-1, ".envelope <- must be {start, stop, values}")
+        s.start = whole("start", envelope.get("start", 0), 64)
+        s.stop = whole("stop", envelope.get("stop", FORCE_FOREVER), 64)
+        if envelope.get("values") is not None:
+            s.envelope, s.envelope_n = table("envelope", envelope["values"])
+    return s, keep
+
+
+def _force_signed(words):
+    v = int(words[0]) | int(words[1]) << 64
+    return v - (1 << 128) if v >> 127 else v
+
+
+def _force_dict(r):
+    """work_fixed and impulse_fixed as Python integers (the 128-bit two's complement sums, units of 2^-80)"""
+    return {"applications": int(r.applications), "kicked": int(r.kicked), "work_fixed": _force_signed(r.work_fixed),
+            "impulse_fixed": [_force_signed(r.impulse_fixed[a]) for a in range(3)], "work": float(r.work), "impulse": [float(r.impulse[a]) for a in range(3)]}
+
+
+def _force_sum(parts, mass, W):
+    """the members' integers added up and the doubles formed from the sums as the library forms them: the scale of the energy
+    diagnostics times the double nearest to the sum 2^-80 (NaN where a member met a term outside the range)"""
+    ke, pm = 0.5 * mass * W * SPEED_OF_LIGHT * SPEED_OF_LIGHT, mass * W * SPEED_OF_LIGHT
+    near = lambda total: float(total) * 2.0 ** -FORCE_FIX_BITS
+    out = {"applications": parts[0]["applications"], "kicked": sum(p["kicked"] for p in parts), "work_fixed": sum(p["work_fixed"] for p in parts),
+           "impulse_fixed": [sum(p["impulse_fixed"][a] for p in parts) for a in range(3)]}
+    out["work"] = float("nan") if any(p["work"] != p["work"] for p in parts) else ke * near(out["work_fixed"])
+    out["impulse"] = [float("nan") if any(p["impulse"][a] != p["impulse"][a] for p in parts) else pm * near(out["impulse_fixed"][a]) for a in range(3)]
+    return out
+
+
 PAIR_MAX_OPS = 8
 PAIR_CELL_MAX = 2048
 PAIR_SEED = 0x7A1C12ABE
@@ -997,6 +1133,10 @@ def load_library(path=None):
     lib.fpic_collide_register.argtypes = [vp, ctypes.POINTER(CollideSpec), ci, ctypes.POINTER(ctypes.c_int)]
     lib.fpic_collide_stats.argtypes = [vp, ci, ci, ctypes.POINTER(CollideResult)]
     lib.fpic_collide_clear.argtypes = [vp]
+    lib.fpic_force.argtypes = [vp, ctypes.POINTER(ForceSpec), ctypes.POINTER(ForceResult)]
+    lib.fpic_force_register.argtypes = [vp, ctypes.POINTER(ForceSpec), ctypes.POINTER(ctypes.c_int)]
+    lib.fpic_force_stats.argtypes = [vp, ci, ci, ctypes.POINTER(ForceResult)]
+    lib.fpic_force_clear.argtypes = [vp]
     lib.fpic_pair.argtypes = [vp, ctypes.POINTER(PairSpec), ctypes.POINTER(PairResult)]
     lib.fpic_pair_register.argtypes = [vp, ctypes.POINTER(PairSpec), ci, ctypes.POINTER(ctypes.c_int)]
     lib.fpic_pair_stats.argtypes = [vp, ci, ci, ctypes.POINTER(PairResult)]
@@ -1369,6 +1509,41 @@ class CylindricalParticlePusher:
     def clearCollisions(self):
         """drops every registered collision operator (fpic_collide_clear)"""
         self._check(self._lib.fpic_collide_clear(self._h))
+
+    # ---- prescribed external forces (fpic_force*)
+    def force(self, **request):
+        """Kicks the stored velocities of one species of the box with a prescribed field or acceleration, now (fpic_force; an
+        (r,z) handle is refused).  waves=[dict(amp=, mode=(0, 0, 0), frequency= | nu=, phase=0)] (1 .. 4 plane waves; amp in
+        V/m for kind="field", m/s^2 for kind="accel"; frequency in Hz becomes nu = frequency dt turns per sub-step),
+        species=0, lo=None, hi=None (the window in metres; default the whole box), taper=(None, None, None) (per axis the
+        nodes of a table over the window), envelope=None | dict(start=, stop=, values=) (active for start <= s <= stop,
+        s = sub-steps since create + epoch; values: the nodes of a table over that span), epoch=0.  Returns {applications,
+        kicked, work_fixed, impulse_fixed (exact integers, units of 2^-80 c^2 and c), work (J), impulse (kg m/s)}."""
+        s, keep = _force_spec(float(self.spec["dt"]), self._box_lengths(), **request)
+        out = ForceResult()
+        self._check(self._lib.fpic_force(self._h, ctypes.byref(s), ctypes.byref(out)))
+        del keep
+        return _force_dict(out)
+
+    def forceOn(self, **request):
+        """Registers a force (see force) to run at the end of every sub-step at which it is active, before every other
+        registered operator and every recorder.  Returns the request's index (fpic_force_register)."""
+        s, keep = _force_spec(float(self.spec["dt"]), self._box_lengths(), **request)
+        index = ctypes.c_int(-1)
+        self._check(self._lib.fpic_force_register(self._h, ctypes.byref(s), ctypes.byref(index)))
+        del keep
+        return index.value
+
+    def forceStats(self, index, scope="global"):
+        """the totals of a registered force since its registration (fpic_force_stats); 'global' on a rank with a communicator
+        sums the ranks' integers (collective)"""
+        out = ForceResult()
+        self._check(self._lib.fpic_force_stats(self._h, int(index), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope], ctypes.byref(out)))
+        return _force_dict(out)
+
+    def clearForces(self):
+        """drops every registered force (fpic_force_clear)"""
+        self._check(self._lib.fpic_force_clear(self._h))
 
     # ---- binary Coulomb collisions between the species of the box (fpic_pair*)
     def collidePair(self, a=0, b=None, **request):
@@ -1805,6 +1980,10 @@ class ElectrostaticBoxPusher:
     collideEvery = CylindricalParticlePusher.collideEvery
     collisionStats = CylindricalParticlePusher.collisionStats
     clearCollisions = CylindricalParticlePusher.clearCollisions
+    force = CylindricalParticlePusher.force
+    forceOn = CylindricalParticlePusher.forceOn
+    forceStats = CylindricalParticlePusher.forceStats
+    clearForces = CylindricalParticlePusher.clearForces
     collidePair = CylindricalParticlePusher.collidePair
     collidePairEvery = CylindricalParticlePusher.collidePairEvery
     pairStats = CylindricalParticlePusher.pairStats
@@ -1924,6 +2103,33 @@ class BoxGroup:
     def clearCollisions(self):
         for m in self.sims:
             m.clearCollisions()
+
+    def _force_scales(self, request_species):
+        m = self.sims[0]
+        W = float(m.spec.get("macro_weight", 1.0))
+        return m.masses[request_species], W if W > 0 else 1.0   # (as the library takes it)
+
+    def force(self, **request):
+        """force() of every member with the same request; the members' integers added up and the doubles formed from the
+        sums (applications: the first member's)"""
+        return _force_sum([m.force(**request) for m in self.sims], *self._force_scales(int(request.get("species", 0))))
+
+    def forceOn(self, **request):
+        """forceOn() of every member with the same request; the index (the same on every member)"""
+        index = [m.forceOn(**request) for m in self.sims][0]
+        self._force_species = getattr(self, "_force_species", {})
+        self._force_species[index] = int(request.get("species", 0))
+        return index
+
+    def forceStats(self, index):
+        """the whole box: the members' LOCAL integers added up, the doubles formed from the sums (applications: the first member's)"""
+        parts = [m.forceStats(index, "local") for m in self.sims]
+        return _force_sum(parts, *self._force_scales(self._force_species[int(index)]))
+
+    def clearForces(self):
+        for m in self.sims:
+            m.clearForces()
+        self._force_species = {}
 
     def collidePair(self, a=0, b=None, **request):
         """refused (FPIC_ERR_STATE), as by every member: between two migrations the particles of a cell can sit on two

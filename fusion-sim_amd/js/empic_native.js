@@ -421,6 +421,91 @@ function makeBox(spec, lib) {
         return lib.collisionStats(h, index, scopeOf(scope));
     };
     out.clearCollisions = function () { lib.clearCollisions(h); };
+    // prescribed external forces (fpic_force*).  request = { waves: [{ amp (V/m or m/s^2; a number is taken for all three),
+    // mode: [mx, my, mz], frequency (Hz) | nu (turns per sub-step), phase (turns) }] (1 .. 4), species, kind: 'field' |
+    // 'accel', lo, hi (the window in metres; default the whole box), taper: [x, y, z] (each null or the nodes of a table over
+    // the window), envelope: { start, stop, values } (active for start <= s <= stop, s = sub-steps since create + epoch;
+    // integers up to 2^53 or BigInts up to 2^64), epoch }.  force -> { applications, kicked, workFixed, impulseFixed (BigInt:
+    // the exact sums, units of 2^-80 c^2 and c), work (J), impulse (kg m/s) }; forceOn(request) -> the request's index;
+    // forceStats(index, scope) -> its totals since registration; clearForces() drops every request
+    const FORCE_KINDS = { field: 0, accel: 1 };
+    const forceArgs = function (request) {
+        if (request === null || typeof request !== 'object' || Array.isArray(request)) throw new TypeError('.request <- expected { waves, species, kind, lo, hi, taper, envelope, epoch }');
+        const given = (v) => v !== undefined && v !== null;
+        const three = function (name, v, dflt) {
+            if (!given(v)) v = dflt;
+            if (typeof v === 'number') v = [v, v, v];
+            if (!(Array.isArray(v) || ArrayBuffer.isView(v)) || v.length !== 3 || !Array.from(v).every((x) => typeof x === 'number')) throw new RangeError('.' + name + ' <- expected a number or three of them');
+            return Array.from(v);
+        };
+        const whole = function (name, v, dflt, least, most) {
+            if (!given(v)) v = dflt;
+            if (!Number.isInteger(v) || v < least || v > most) throw new RangeError('.' + name + ' <- expected an integer within its field');
+            return v;
+        };
+        const real = function (name, v, dflt) {
+            if (!given(v)) v = dflt;
+            if (typeof v !== 'number') throw new RangeError('.' + name + ' <- expected a number');
+            return v;
+        };
+        const wide = function (name, v, dflt) {
+            if (!given(v)) v = dflt;
+            if (typeof v === 'number') {
+                if (!Number.isInteger(v) || v < 0 || v > Number.MAX_SAFE_INTEGER) throw new RangeError('.' + name + ' <- expected an integer up to 2^53, or a BigInt up to 2^64');
+                v = BigInt(v);
+            }
+            if (typeof v !== 'bigint' || v < 0n || v >= (1n << 64n)) throw new RangeError('.' + name + ' <- expected an integer up to 2^53, or a BigInt up to 2^64');
+            return [Number(v & 0xffffffffn), Number(v >> 32n)];
+        };
+        let kind = given(request.kind) ? request.kind : 'field';
+        if (typeof kind === 'string') {
+            if (!(kind in FORCE_KINDS)) throw new RangeError(".kind <- must be one of 'field', 'accel'");
+            kind = FORCE_KINDS[kind];
+        }
+        kind = whole('kind', kind, undefined, -0x80000000, 0x7fffffff);
+        const waves = request.waves;
+        if (!Array.isArray(waves)) throw new TypeError('.waves <- expected a list of 1 .. 4 waves');
+        const modes = new Array(12).fill(0), wreals = new Array(20).fill(0);
+        waves.slice(0, 4).forEach(function (w, k) {
+            if (w === null || typeof w !== 'object' || !given(w.amp)) throw new TypeError('.waves <- a wave is { amp, mode, nu | frequency, phase }');
+            if (given(w.nu) && given(w.frequency)) throw new RangeError('.nu <- give either nu or frequency, not both');
+            const amp = three('amp', w.amp, 0), mode = given(w.mode) ? w.mode : [0, 0, 0];
+            if (!Array.isArray(mode) || mode.length !== 3) throw new RangeError('.mode <- expected three integers');
+            for (let a = 0; a < 3; ++a) { modes[3 * k + a] = whole('mode', mode[a], 0, -0x80000000, 0x7fffffff); wreals[5 * k + a] = amp[a]; }
+            wreals[5 * k + 3] = given(w.frequency) ? real('frequency', w.frequency, 0) * spec.dt : real('nu', w.nu, 0);
+            wreals[5 * k + 4] = real('phase', w.phase, 0);
+        });
+        const box = [spec.radius, spec.length_y, spec.height].map((v) => (typeof v === 'number' ? v : 1));
+        const counts = [], tables = [];
+        const table = function (name, t) {
+            if (!given(t)) { counts.push(0); return; }
+            if (!(Array.isArray(t) || ArrayBuffer.isView(t)) || !Array.from(t).every((x) => typeof x === 'number')) throw new RangeError('.' + name + ' <- a table must be a list of numbers');
+            counts.push(t.length);
+            for (const x of t) tables.push(x);
+        };
+        const taper = given(request.taper) ? request.taper : [null, null, null];
+        if (!Array.isArray(taper) || taper.length !== 3) throw new RangeError('.taper <- expected three entries (x, y, z), each null or a table');
+        for (const t of taper) table('taper', t);
+        const env = given(request.envelope) ? request.envelope : {};
+        if (typeof env !== 'object' || Array.isArray(env)) throw new TypeError('.envelope <- expected { start, stop, values }');
+        table('envelope', env.values);
+        const words = [kind, waves.length].concat(wide('epoch', request.epoch, 0), wide('start', env.start, 0), wide('stop', env.stop, (1n << 64n) - 1n), modes, counts);
+        const reals = three('lo', request.lo, 0).concat(three('hi', request.hi, box), wreals);
+        return [whole('species', request.species, 0, 0, 0x7fffffff), Float64Array.from(words), Float64Array.from(reals), Float64Array.from(tables)];
+    };
+    out.force = function (request) {
+        const a = forceArgs(request);
+        return lib.force(h, a[0], a[1], a[2], a[3]);
+    };
+    out.forceOn = function (request) {
+        const a = forceArgs(request);
+        return lib.forceOn(h, a[0], a[1], a[2], a[3]);
+    };
+    out.forceStats = function (index, scope) {
+        if (!Number.isInteger(index) || index < -0x80000000 || index > 0x7fffffff) throw new RangeError('.index <- expected a 32-bit integer');
+        return lib.forceStats(h, index, scopeOf(scope));
+    };
+    out.clearForces = function () { lib.clearForces(h); };
     // binary Coulomb collisions between the species of the box (Takizuka-Abe; fpic_pair*).  request = { a, b (default a: like
     // particles), logLambda, tau (s; default the sub-step dt, every * dt for collidePairEvery), seed (an integer up to 2^53 or a
     // BigInt up to 2^64), stream, epoch }.  collidePair -> { applications, pairs, strong, cells, overfullCells,

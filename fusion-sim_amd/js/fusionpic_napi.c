@@ -1055,6 +1055,150 @@ static napi_value n_clear_collisions(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* the request of force / forceOn: words: Float64Array [kind, nwaves, epoch, start, stop (each 64-bit one as its low and its
+ * high 32-bit word), the four waves' modes (12), taper_n (3), envelope_n], reals: Float64Array [lo 3, hi 3, per wave amp 3,
+ * nu, phase], tables: Float64Array, the taper tables and the envelope table one after the other.  The arrays' lengths and the
+ * words' ranges are checked here, the request itself by the library (which copies the tables during the call). */
+#define FORCE_WORDS 24
+#define FORCE_REALS 26
+static int get_force_spec(napi_env env, int sp, napi_value words, napi_value reals, napi_value tables, fpic_force_spec* s)
+{
+    napi_typedarray_type tw, tr, tt; void *pw, *pr, *pt; size_t lw, lr, lt;
+    if (!get_typed(env, words, &tw, &pw, &lw) || !get_typed(env, reals, &tr, &pr, &lr) || !get_typed(env, tables, &tt, &pt, &lt)) return 0;
+    if (!pw || !pr || tw != napi_float64_array || tr != napi_float64_array || tt != napi_float64_array) {
+        napi_throw_type_error(env, NULL, ".request <- expected three Float64Arrays");
+        return 0;
+    }
+    if (!check_len(env, "words", lw, FORCE_WORDS) || !check_len(env, "reals", lr, FORCE_REALS)) return 0;
+    const double* w = (const double*)pw;
+    const double* r = (const double*)pr;
+    for (int k = 0; k < FORCE_WORDS; ++k) {
+        const int is_signed = k < 2 || (k >= 8 && k < 20);
+        const double least = is_signed ? -2147483648.0 : 0.0, most = is_signed ? 2147483647.0 : 4294967295.0;
+        const double mag = w[k] < 0 ? -w[k] : w[k];
+        if (!(w[k] >= least && w[k] <= most) || mag != (double)(uint64_t)mag) {
+            napi_throw_range_error(env, NULL, ".request <- kind, nwaves, epoch, start, stop, mode and the node counts must be integers within their fields");
+            return 0;
+        }
+    }
+    memset(s, 0, sizeof *s);
+    s->species = sp;
+    s->kind = (int32_t)w[0];
+    s->nwaves = (int32_t)w[1];
+    s->epoch = (uint64_t)(uint32_t)w[2] | (uint64_t)(uint32_t)w[3] << 32;
+    s->start = (uint64_t)(uint32_t)w[4] | (uint64_t)(uint32_t)w[5] << 32;
+    s->stop = (uint64_t)(uint32_t)w[6] | (uint64_t)(uint32_t)w[7] << 32;
+    for (int a = 0; a < 3; ++a) { s->lo[a] = r[a]; s->hi[a] = r[3 + a]; }
+    for (int k = 0; k < FPIC_FORCE_MAX_WAVES; ++k) {
+        for (int a = 0; a < 3; ++a) { s->wave[k].mode[a] = (int32_t)w[8 + 3 * k + a]; s->wave[k].amp[a] = r[6 + 5 * k + a]; }
+        s->wave[k].nu = r[6 + 5 * k + 3];
+        s->wave[k].phase = r[6 + 5 * k + 4];
+    }
+    double total = 0;
+    for (int a = 0; a < 4; ++a) total += w[20 + a];
+    if (total != (double)lt) {
+        napi_throw_range_error(env, NULL, ".tables <- its length must be the sum of the node counts");
+        return 0;
+    }
+    const double* at = (const double*)pt;
+    for (int a = 0; a < 3; ++a) {
+        s->taper_n[a] = (uint32_t)w[20 + a];
+        if (s->taper_n[a]) { s->taper[a] = at; at += s->taper_n[a]; }
+    }
+    s->envelope_n = (uint32_t)w[23];
+    if (s->envelope_n) s->envelope = at;
+    return 1;
+}
+
+/* a 128-bit two's complement sum (low word, high word) as a BigInt */
+static napi_value fixed_bigint(napi_env env, const uint64_t* f)
+{
+    uint64_t mag[2] = { f[0], f[1] };
+    const int neg = (int)(f[1] >> 63);
+    if (neg) {
+        mag[0] = ~f[0] + 1;
+        mag[1] = ~f[1] + (mag[0] == 0 ? 1 : 0);
+    }
+    napi_value v;
+    NAPI_OK(env, napi_create_bigint_words(env, neg, 2, mag, &v));
+    return v;
+}
+
+static napi_value force_object(napi_env env, const fpic_force_result* c)
+{
+    napi_value o, v, arr;
+    NAPI_OK(env, napi_create_object(env, &o));
+    NAPI_OK(env, napi_create_double(env, (double)c->applications, &v));
+    NAPI_OK(env, napi_set_named_property(env, o, "applications", v));
+    NAPI_OK(env, napi_create_double(env, (double)c->kicked, &v));
+    NAPI_OK(env, napi_set_named_property(env, o, "kicked", v));
+    v = fixed_bigint(env, c->work_fixed);
+    if (!v) return NULL;
+    NAPI_OK(env, napi_set_named_property(env, o, "workFixed", v));
+    NAPI_OK(env, napi_create_array_with_length(env, 3, &arr));
+    for (uint32_t a = 0; a < 3; ++a) {
+        v = fixed_bigint(env, c->impulse_fixed[a]);
+        if (!v) return NULL;
+        NAPI_OK(env, napi_set_element(env, arr, a, v));
+    }
+    NAPI_OK(env, napi_set_named_property(env, o, "impulseFixed", arr));
+    NAPI_OK(env, napi_create_double(env, c->work, &v));
+    NAPI_OK(env, napi_set_named_property(env, o, "work", v));
+    NAPI_OK(env, napi_create_array_with_length(env, 3, &arr));
+    for (uint32_t a = 0; a < 3; ++a) {
+        NAPI_OK(env, napi_create_double(env, c->impulse[a], &v));
+        NAPI_OK(env, napi_set_element(env, arr, a, v));
+    }
+    NAPI_OK(env, napi_set_named_property(env, o, "impulse", arr));
+    return o;
+}
+
+/* force(h, species, words, reals, tables) -> { applications, kicked, workFixed, impulseFixed, work, impulse } */
+static napi_value n_force(napi_env env, napi_callback_info info)
+{
+    napi_value argv[5]; fpic_handle* h; int sp;
+    fpic_force_spec s;
+    if (!get_args(env, info, 5, argv, &h) || !get_species(env, argv[1], &sp) || !get_force_spec(env, sp, argv[2], argv[3], argv[4], &s)) return NULL;
+    fpic_force_result c;
+    memset(&c, 0, sizeof c);
+    if (fpic_force(h, &s, &c) != FPIC_OK) return throw_fpic(env, h);
+    return force_object(env, &c);
+}
+
+/* forceOn(h, species, words, reals, tables) -> the request's index */
+static napi_value n_force_on(napi_env env, napi_callback_info info)
+{
+    napi_value argv[5]; fpic_handle* h; int sp;
+    fpic_force_spec s;
+    if (!get_args(env, info, 5, argv, &h) || !get_species(env, argv[1], &sp) || !get_force_spec(env, sp, argv[2], argv[3], argv[4], &s)) return NULL;
+    int index = -1;
+    if (fpic_force_register(h, &s, &index) != FPIC_OK) return throw_fpic(env, h);
+    napi_value v;
+    NAPI_OK(env, napi_create_int32(env, index, &v));
+    return v;
+}
+
+/* forceStats(h, index, scope) -> { applications, kicked, workFixed, impulseFixed, work, impulse } */
+static napi_value n_force_stats(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3]; fpic_handle* h; double index; int scope;
+    if (!get_args(env, info, 3, argv, &h) || !get_double(env, argv[1], &index) || !get_scope(env, argv[2], &scope)) return NULL;
+    if (!(index >= -2147483648.0 && index <= 2147483647.0) || index != (double)(int)index) { napi_throw_range_error(env, NULL, ".index <- must be a 32-bit integer"); return NULL; }
+    fpic_force_result c;
+    memset(&c, 0, sizeof c);
+    if (fpic_force_stats(h, (int)index, scope, &c) != FPIC_OK) return throw_fpic(env, h);
+    return force_object(env, &c);
+}
+
+/* clearForces(h) */
+static napi_value n_clear_forces(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1]; fpic_handle* h;
+    if (!get_args(env, info, 1, argv, &h)) return NULL;
+    if (fpic_force_clear(h) != FPIC_OK) return throw_fpic(env, h);
+    return undefined(env);
+}
+
 /* the request of collidePair / collidePairEvery: words: Float64Array [species_a, species_b, seed low word, seed high word,
  * stream, epoch], reals: Float64Array [log_lambda, tau].  The arrays' lengths and the words' ranges are checked here, the
  * request itself by the library. */
@@ -1653,6 +1797,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "domainStats", n_domain_stats },
         { "energy", n_energy }, { "recordEnergy", n_record_energy }, { "energyHistory", n_energy_history },
         { "histogram", n_histogram }, { "select", n_select }, { "load", n_load }, { "collide", n_collide }, { "collideEvery", n_collide_every }, { "collisionStats", n_collision_stats }, { "clearCollisions", n_clear_collisions },
+        { "force", n_force }, { "forceOn", n_force_on }, { "forceStats", n_force_stats }, { "clearForces", n_clear_forces },
         { "collidePair", n_collide_pair }, { "collidePairEvery", n_collide_pair_every }, { "pairStats", n_pair_stats }, { "clearPairs", n_clear_pairs },
         { "fusionYield", n_fusion_yield }, { "fusionYieldEvery", n_fusion_yield_every }, { "fusionStats", n_fusion_stats }, { "fusionGrid", n_fusion_grid }, { "clearFusion", n_clear_fusion },
         { "fusionSpectrum", n_fusion_spectrum }, { "fusionSpectrumEvery", n_fusion_spectrum_every }, { "fusionSpectrumRead", n_fusion_spectrum_read }, { "clearFusionSpectra", n_clear_fusion_spectra },

@@ -1099,6 +1099,89 @@ int fpic_fusion_spectrum_register(fpic_handle* h, const fpic_fusion_spectrum_spe
 int fpic_fusion_spectrum_read(fpic_handle* h, int index, fpic_fusion_result* out, uint64_t* words, int reset);
 int fpic_fusion_spectrum_clear(fpic_handle* h);
 
+/* ---- CART3D prescribed external forces: a field (V/m) or an acceleration (m/s^2) given in closed form — up to four
+ * plane waves over the box, a window, tapers along the axes and an envelope in time — that kicks the stored velocities of
+ * one species, as a call or registered to run after every sub-step.  It acts per particle at the particle's own stored
+ * position: no grid, no gather, the fields and their diagnostics untouched, and a decomposed box takes it as one handle does.
+ * The result depends on the request, s and the particle's own state alone — not on the slot, the binning, the rank or the id;
+ * no random number is drawn.  All arithmetic is double, every operation rounded once; p is the stored position in box
+ * fractions, v the stored velocity in units of c (under both solvers the half-time velocity, the position at the integer
+ * time), T the handle's precision.
+ *   numbers    (host, once per application) s = (uint64)(sub-step count + epoch), the count being the handle's own since
+ *              create (as fpic_collide_register counts).  kq = (charge dt) / (mass c) for FPIC_FORCE_FIELD,
+ *              kq = dt / c for FPIC_FORCE_ACCEL (the same for every species).  lo_f[a] = lo[a] / L_a, hi_f[a] = hi[a] / L_a,
+ *              w[a] = hi_f[a] - lo_f[a].  Per wave k: tw = nu_k (double) s, tfrac_k = tw - floor(tw) (nu in turns per
+ *              sub-step).  The request is ACTIVE iff start <= s <= stop; an inactive one enqueues nothing and counts no
+ *              application.  Envelope table of K intervals (K + 1 nodes, node 0 at s = start, node K at s = stop):
+ *              g = ((double)(s - start) K) / (double)(stop - start), j = min((int) g, K - 1), r = g - j,
+ *              env = tab[j] + (tab[j+1] - tab[j]) r; without a table env = 1.  scale = kq env.
+ *   window     a live particle is inside iff lo_f[a] <= p[a] < hi_f[a] on all three axes (compared in double); one outside
+ *              keeps every bit and is not counted.
+ *   taper      per axis with a table of K intervals (node 0 at lo, node K at hi): f = (p[a] - lo_f[a]) / w[a], and the
+ *              lookup of fpic_load_profile: g = f K, j = min((int) g, K - 1), s = g - j, value = tab[j] + (tab[j+1] -
+ *              tab[j]) s.  taper = (tx ty) tz over the tables present (a missing table: no multiply).
+ *   waves      theta = (m0 p0 + m1 p1) + m2 p2 (the modes as doubles), arg = (theta - tfrac_k) + phase_k,
+ *              c_k = cospi(2 arg) (the device's function, as the loader's); zero mode, nu and phase give exactly 1.
+ *   kick       e[a] = amp_0[a] c_0, then e[a] = e[a] + amp_k[a] c_k for k = 1 ..; sc = scale, or scale taper with any taper
+ *              table; d[a] = sc e[a]; v'[a] = v[a] + d[a], stored as (T) v'[a].  Every inside particle is stored and
+ *              counted as `kicked`, also when d is zero.
+ * Positions are never written, so the fields stay valid and fpic_precalc is not needed.  A dead slot of a rank of a
+ * decomposition is skipped and not counted.
+ * Where the kick sits.  The hook runs after the move, at the new position and the new time.  Without B a kick there equals
+ * adding the field to the two half-kicks of the next push: the leapfrog scheme with the total field.  With B the external
+ * kick comes wholly before the Boris rotation instead of straddling it; the difference is an operator-splitting term of
+ * order (omega_c dt) times the kick.
+ * Tallies (exact: the fixed point of the energy diagnostics, units of 2^-80, 128-bit two's complement, low word first).  Per
+ * kicked particle work_fixed gains floor(|(T)v'|^2 2^80) - floor(|v|^2 2^80), the squared norms ((x x + y y) + z z) of the
+ * stored values in double, and impulse_fixed[a] gains floor((T)v'[a] 2^80) - floor(v[a] 2^80).  work = (0.5 m W c^2) times
+ * the double nearest to the sum 2^-80 (J); impulse[a] = (m W c) times the same of its sum (kg m/s).  A term outside the
+ * diagnostics' range (|term| >= 2^15, or not finite) adds nothing and makes its double NaN.
+ * fpic_force applies the request now, at the current count (synchronous), and returns its tallies (applications 1, or 0 when
+ * the request is not active).  fpic_force_register makes it run at the end of every sub-step, directly after the sub-step
+ * is counted and before every other registered operator and every recorder — all of them see the kicked state — in
+ * registration order; at most FPIC_FORCE_MAX_OPS requests, *index names the request.  The tables are copied at the call.
+ * Nothing is synchronised: fpic_force_stats reads the totals since registration (scope as for the diagnostics: GLOBAL with a
+ * communicator adds the ranks' integers, whatever the decomposition; applications is the same on every rank and is not
+ * summed).  fpic_force_clear drops every request.  Registrations are not part of a checkpoint.
+ * Refused (FPIC_ERR_INVALID_ARG): a null spec, an unknown kind, a species the handle does not have, nwaves outside 1 ..
+ * FPIC_FORCE_MAX_WAVES, a value that is not finite (amp, nu, phase, lo, hi, a table's node), a window not within
+ * 0 <= lo < hi <= L, |mode| > 2^15, a node count of 1 or above FPIC_FORCE_TABLE_MAX, a null table with a node count,
+ * start > stop, an envelope table with stop == start or stop == FPIC_FORCE_FOREVER, a reserved word that is not zero, a
+ * ninth registration, an index outside the registered requests; FPIC_ERR_STATE: a handle that is not CART3D. */
+#define FPIC_FORCE_FIELD     0
+#define FPIC_FORCE_ACCEL     1
+#define FPIC_FORCE_MAX_WAVES 4
+#define FPIC_FORCE_MAX_OPS   8
+#define FPIC_FORCE_TABLE_MAX 1025
+#define FPIC_FORCE_FOREVER   (~(uint64_t)0)
+typedef struct fpic_force_wave {
+    double  amp[3];                /* V/m (FIELD) or m/s^2 (ACCEL) */
+    int32_t mode[3];               /* whole periods over the box per axis, |m| <= 2^15 */
+    int32_t reserved;              /* zero */
+    double  nu, phase;             /* turns per sub-step; turns */
+} fpic_force_wave;
+typedef struct fpic_force_spec {
+    int32_t  species, kind;        /* FPIC_FORCE_FIELD 0, _ACCEL 1 */
+    int32_t  nwaves, reserved_i32; /* 1 .. FPIC_FORCE_MAX_WAVES; zero */
+    uint64_t epoch, start, stop;   /* s = sub-step count + epoch; active for start <= s <= stop (FPIC_FORCE_FOREVER: no end) */
+    double   lo[3], hi[3];         /* the window, metres: 0 <= lo < hi <= L (the whole box: 0 and L) */
+    fpic_force_wave wave[FPIC_FORCE_MAX_WAVES];
+    uint32_t taper_n[3], envelope_n;   /* nodes; 0 = no table */
+    const double* taper[3];
+    const double* envelope;
+    double   reserved[4];          /* zero */
+} fpic_force_spec;
+typedef struct fpic_force_result {
+    uint64_t applications, kicked;
+    uint64_t work_fixed[2];        /* low word, high word */
+    uint64_t impulse_fixed[3][2];
+    double   work, impulse[3];     /* J; kg m/s */
+} fpic_force_result;
+int fpic_force(fpic_handle* h, const fpic_force_spec* spec, fpic_force_result* out);
+int fpic_force_register(fpic_handle* h, const fpic_force_spec* spec, int* index);
+int fpic_force_stats(fpic_handle* h, int index, int scope, fpic_force_result* out);
+int fpic_force_clear(fpic_handle* h);
+
 int fpic_sync(fpic_handle* h);
 int fpic_profile(fpic_handle* h, int enable);
 int fpic_get_stats(fpic_handle* h, fpic_stats* out);
