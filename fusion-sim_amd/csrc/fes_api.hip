@@ -26,6 +26,7 @@
 //   fes_load.inc.hpp        the particle loader: a population generated on the device, a rank keeping the particles of its planes
 //   fes_collide.inc.hpp     Monte Carlo collisions with a prescribed background, now or registered to run after sub-steps
 //   fes_force.inc.hpp       prescribed external forces (waves, window, tapers, envelope), now or registered to run after sub-steps
+//   fes_gas.inc.hpp         windowed background collisions with a tabulated cross-section and exact tallies, now or registered
 //   fes_pair.inc.hpp        binary Coulomb collisions between the species (Takizuka-Abe): the cell index of a request, the pairing pass
 //   fes_fusion.inc.hpp      fusion yield tallies between the species: fes_pair's cell index, the tally pass, the cell grids
 //   fes_fusion_spectrum.inc.hpp   fusion product spectra: the tally's pairs and yields binned over an energy axis
@@ -41,6 +42,7 @@
 #include "fes_load_kernels.hpp"
 #include "fes_collide_kernels.hpp"
 #include "fes_force_kernels.hpp"
+#include "fes_gas_kernels.hpp"
 #include "fes_pair_kernels.hpp"
 #include "fes_fusion_kernels.hpp"
 #include "fes_fusion_spectrum_kernels.hpp"
@@ -363,6 +365,7 @@ namespace {
 #include "fes_load.inc.hpp"
 #include "fes_collide.inc.hpp"
 #include "fes_force.inc.hpp"
+#include "fes_gas.inc.hpp"
 #include "fes_pair.inc.hpp"
 #include "fes_fusion.inc.hpp"
 #include "fes_fusion_spectrum.inc.hpp"
@@ -372,8 +375,8 @@ namespace {
 
 // the recording hook, at the end of every sub-step of every path (substeps(), group_run()): counts the sub-step, applies the
 // registered external forces that are active (fes_force.inc.hpp: everything below sees the kicked state), then the
-// registered collision operators that are due (fes_collide.inc.hpp against the background, then fes_pair.inc.hpp between the
-// species: the rows below see the collided state), then the fusion yield tallies that are due (fes_fusion.inc.hpp: they read
+// registered collision operators that are due (fes_collide.inc.hpp against the background, then fes_gas.inc.hpp against the
+// windowed background, then fes_pair.inc.hpp between the species: the rows below see the collided state), then the fusion yield tallies that are due (fes_fusion.inc.hpp: they read
 // the collided velocities and write no particle) and the fusion product spectra (fes_fusion_spectrum.inc.hpp), then every
 // recorder that is due — the energy rows, the series, the modes, which share the counter and nothing else — enqueues its row
 // into its ring.  No host synchronisation, no collective; recording off: nothing is enqueued.
@@ -385,6 +388,8 @@ static int diag_after_substep(fpic_handle* h)
         if (int rc = force_after_substep(h, g.substep)) return rc;
     if (!g.coll_ops.empty())
         if (int rc = collide_after_substep(h, g.substep)) return rc;
+    if (!g.gas_ops.empty())
+        if (int rc = gas_after_substep(h, g.substep)) return rc;
     if (!g.pair_ops.empty())
         if (int rc = pair_after_substep(h, g.substep)) return rc;
     if (!g.fusion_ops.empty())

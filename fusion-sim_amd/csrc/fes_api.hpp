@@ -53,6 +53,11 @@ int force(fpic_handle* h, const fpic_force_spec* spec, fpic_force_result* out);
 int force_register(fpic_handle* h, const fpic_force_spec* spec, int* index);
 int force_stats(fpic_handle* h, int index, int scope, fpic_force_result* out);
 int force_clear(fpic_handle* h);
+// windowed background collisions with a tabulated cross-section (fes_gas.inc.hpp)
+int gas(fpic_handle* h, const fpic_gas_spec* spec, fpic_gas_result* out);
+int gas_register(fpic_handle* h, const fpic_gas_spec* spec, int every, int* index);
+int gas_stats(fpic_handle* h, int index, int scope, fpic_gas_result* out);
+int gas_clear(fpic_handle* h);
 // binary Coulomb collisions between the species of the box (fes_pair.inc.hpp)
 int pair(fpic_handle* h, const fpic_pair_spec* spec, fpic_pair_result* out);
 int pair_register(fpic_handle* h, const fpic_pair_spec* spec, int every, int* index);

@@ -1,0 +1,192 @@
+// fes_gas.inc.hpp: the windowed background collisions with a tabulated cross-section of a CART3D handle (fpic_gas,
+// fpic_gas_register, fpic_gas_stats, fpic_gas_clear) — part of fes_api.hip's translation unit (included there after
+// fes_force.inc.hpp, inside namespace fes).  The rule and the checks of a request are fes_gas_core.hpp, the pass
+// fes_gas_kernels.hpp.
+//
+// One launch per application over the slots [0, n) and, while a migration rides on the next push, the arrivals behind them
+// (one range, as collide_enqueue).  The handle keeps one device block: fesgas::kWords tally words and room for the
+// cross-section table and three taper tables per registered operator, and one more of each for the call that is applied now.
+// A request's tables are copied at the call: to the device, and the cross-sections to the host too, where the candidate
+// bound is formed.  Per request the host chooses which test the pass makes first (gas_window_first) and whether its
+// candidates go through the LDS queue (gas_compacts); DESIGN 4.23 has the measurements behind the thresholds.  A registered
+// operator is enqueued by the hook diag_after_substep with no host synchronisation and no collective; fpic_gas_stats reads
+// its words.
+//
+// TEST SWITCH (FPIC_GAS_FORMS, read once): which form runs, for measuring one against the other.  A sum of 1 (the word
+// first), 2 (the window first), 4 (the wave-shared loop), 8 (the LDS queue); 0 or unset: the host's choices.  Every form
+// gives the same particles.
+
+constexpr int kGasNow = FPIC_GAS_MAX_OPS;                // the words and tables of fpic_gas
+constexpr size_t kGasTabDoubles = static_cast<size_t>(FPIC_GAS_TABLE_MAX) + 3 * static_cast<size_t>(FPIC_GAS_TAPER_MAX);   // per request
+
+static int gas_forms()
+{
+    static const int forms = [] { const char* v = std::getenv("FPIC_GAS_FORMS"); return v ? std::atoi(v) : 0; }();
+    return forms;
+}
+
+static int gas_room(fpic_handle* h)
+{
+    Diag& g = h->es->diag;
+    if (g.gas) return FPIC_OK;
+    void* p = nullptr;
+    const size_t words = static_cast<size_t>(FPIC_GAS_MAX_OPS + 1) * fesgas::kWords * sizeof(unsigned long long);
+    const size_t bytes = words + static_cast<size_t>(FPIC_GAS_MAX_OPS + 1) * kGasTabDoubles * sizeof(double);
+    if (int rc = dev_alloc(h, &p, bytes, &h->bytes_grid)) return rc;
+    g.gas = static_cast<unsigned long long*>(p);
+    g.gas_tab = reinterpret_cast<double*>(static_cast<unsigned char*>(p) + words);
+    HIP_TRY(h, hipMemsetAsync(g.gas, 0, words, h->stream));
+    return FPIC_OK;
+}
+
+// a checked request into place `at`: its tally words zeroed, its tables on the device, the cross-sections in `op` too
+static int gas_hold(fpic_handle* h, const fpic_gas_spec& spec, int every, int at, GasOp& op)
+{
+    Diag& g = h->es->diag;
+    if (int rc = gas_room(h)) return rc;
+    op.spec = spec;
+    op.every = every;
+    op.applications = 0;
+    op.sigma.assign(spec.sigma, spec.sigma + spec.n);
+    op.spec.sigma = nullptr;
+    HIP_TRY(h, hipMemsetAsync(g.gas + at * fesgas::kWords, 0, fesgas::kWords * sizeof(unsigned long long), h->stream));
+    double* tab = g.gas_tab + at * kGasTabDoubles;
+    HIP_TRY(h, hipMemcpyAsync(tab, op.sigma.data(), op.sigma.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    op.dev_sigma = tab;
+    tab += spec.n;
+    for (int a = 0; a < 3; ++a) {
+        op.taper[a] = nullptr;
+        op.spec.taper[a] = nullptr;
+        if (!spec.taper_n[a]) continue;
+        HIP_TRY(h, hipMemcpyAsync(tab, spec.taper[a], spec.taper_n[a] * sizeof(double), hipMemcpyHostToDevice, h->stream));
+        op.taper[a] = tab;
+        tab += spec.taper_n[a];
+    }
+    HIP_TRY(h, hipStreamSynchronize(h->stream));   // (the tables are pageable and may change after the call)
+    return FPIC_OK;
+}
+
+template <typename T, bool WINDOW_FIRST>
+static void gas_launch(fpic_handle* h, const GasArgs<T>& a, unsigned grid, bool compact)
+{
+    if (compact) gas_kernel<T, WINDOW_FIRST, true><<<grid, kGasThreads, 0, h->stream>>>(a);
+    else gas_kernel<T, WINDOW_FIRST, false><<<grid, kGasThreads, 0, h->stream>>>(a);
+}
+
+// one application of `op` at `epoch`, its tallies added to `words`: enqueued, nothing waited for
+template <typename T>
+static int gas_enqueue(fpic_handle* h, const GasOp& op, uint32_t epoch, unsigned long long* words)
+{
+    State* st = h->es;
+    const Species& sp = st->sp[op.spec.species];
+    const size_t slots = std::min(sp.n + sp.tail_count, sp.n_pad);   // (the arrivals of a riding migration follow at tail_first = n)
+    const double L[3] = { st->lx, st->ly, st->lz };
+    GasArgs<T> a{};
+    a.r = fesgas::rule_of(op.spec, L, epoch, op.sigma.data(), op.dev_sigma, op.taper);
+    if (!slots || a.r.K == 0) return FPIC_OK;   // (nothing can collide: nothing is launched)
+    a.slab = static_cast<T*>(sp.slab[sp.cur]);
+    a.id = sp.ids_identity ? nullptr : sp.id[sp.cur];
+    a.n_pad = sp.n_pad;
+    a.s1 = slots;
+    a.dead = st->dom ? 1 : 0;
+    a.words = words;
+    const size_t groups = (slots + 3) / 4;
+    const unsigned grid = static_cast<unsigned>(std::min<size_t>(kGasBlocks, (groups + kGasThreads - 1) / kGasThreads));
+    const int forms = gas_forms();
+    const bool window_first = forms & 2 ? true : forms & 1 ? false : gas_window_first(a.r);
+    const bool compact = forms & 8 ? true : forms & 4 ? false : gas_compacts(a.r.K);
+    if (window_first) gas_launch<T, true>(h, a, grid, compact);
+    else gas_launch<T, false>(h, a, grid, compact);
+    HIP_TRY(h, hipGetLastError());
+    return FPIC_OK;
+}
+
+static int gas_apply(fpic_handle* h, const GasOp& op, uint32_t epoch, unsigned long long* words)
+{
+    return h->prec == FPIC_F32 ? gas_enqueue<float>(h, op, epoch, words) : gas_enqueue<double>(h, op, epoch, words);
+}
+
+static const char* gas_check(fpic_handle* h, const fpic_gas_spec* spec)
+{
+    const State* st = h->es;
+    const double L[3] = { st->lx, st->ly, st->lz };
+    return fesgas::check(spec, static_cast<int>(st->sp.size()), L);
+}
+
+int gas(fpic_handle* h, const fpic_gas_spec* spec, fpic_gas_result* out)
+{
+    State* st = h->es;
+    if (const char* why = gas_check(h, spec)) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    if (out) *out = fpic_gas_result{};
+    const double p_max = -std::expm1(-fesgas::x_max_of(*spec));
+    if (static_cast<uint64_t>(std::ldexp(p_max, 32)) == 0) return FPIC_OK;   // (K = 0: nothing is launched, nothing is held)
+    GasOp op;
+    if (int rc = gas_hold(h, *spec, 1, kGasNow, op)) return rc;
+    unsigned long long* words = st->diag.gas + kGasNow * fesgas::kWords;
+    if (int rc = gas_apply(h, op, spec->epoch, words)) return rc;
+    uint64_t got[fesgas::kWords] = {};
+    HIP_TRY(h, hipMemcpyAsync(got, words, sizeof(got), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (out) {
+        out->applications = 1;
+        fesgas::result_of(got, st->sp[spec->species].mass, st->W, out);
+    }
+    return FPIC_OK;
+}
+
+int gas_register(fpic_handle* h, const fpic_gas_spec* spec, int every, int* index)
+{
+    Diag& g = h->es->diag;
+    if (const char* why = gas_check(h, spec)) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    if (const char* why = fesgas::check_register(every, static_cast<int>(g.gas_ops.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    const int at = static_cast<int>(g.gas_ops.size());
+    GasOp op;
+    if (int rc = gas_hold(h, *spec, every, at, op)) return rc;
+    g.gas_ops.push_back(std::move(op));
+    if (index) *index = at;
+    return FPIC_OK;
+}
+
+int gas_stats(fpic_handle* h, int index, int scope, fpic_gas_result* out)
+{
+    State* st = h->es;
+    Diag& g = st->diag;
+    if (!out) return fail(h, FPIC_ERR_INVALID_ARG, ".out <- Non-optional property is undefined!");
+    if (const char* why = fesgas::check_index(index, static_cast<int>(g.gas_ops.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    bool collective = false;
+    if (int rc = diag_scope(h, scope, collective)) return rc;
+    uint64_t got[fesgas::kWords] = {};
+    HIP_TRY(h, hipMemcpyAsync(got, g.gas + index * fesgas::kWords, sizeof(got), hipMemcpyDeviceToHost, h->stream));
+    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (collective) {
+        uint64_t parts[fesgas::kSumWords];
+        fesgas::split_words(got, parts);
+        if (int rc = diag_sum_ranks(h, parts, fesgas::kSumWords)) return rc;
+        fesgas::join_words(parts, got);
+    }
+    const GasOp& op = g.gas_ops[index];
+    *out = fpic_gas_result{};
+    out->applications = op.applications;   // (the same on every rank: not summed)
+    fesgas::result_of(got, st->sp[op.spec.species].mass, st->W, out);
+    return FPIC_OK;
+}
+
+int gas_clear(fpic_handle* h)
+{
+    h->es->diag.gas_ops.clear();   // (applications in flight keep their words and tables; a later registration rewrites its own in stream order)
+    return FPIC_OK;
+}
+
+// the hook's part (diag_after_substep, after the operators of fpic_collide_register): every registered operator that is due,
+// in registration order; nothing registered: nothing is enqueued
+static int gas_after_substep(fpic_handle* h, uint64_t substep)
+{
+    Diag& g = h->es->diag;
+    for (size_t k = 0; k < g.gas_ops.size(); ++k) {
+        GasOp& op = g.gas_ops[k];
+        if (substep % static_cast<uint64_t>(op.every)) continue;
+        op.applications++;
+        if (int rc = gas_apply(h, op, static_cast<uint32_t>(substep + op.spec.epoch), g.gas + k * fesgas::kWords)) return rc;
+    }
+    return FPIC_OK;
+}

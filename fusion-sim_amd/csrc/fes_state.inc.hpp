@@ -92,6 +92,17 @@ struct ForceOp {
     uint64_t applications;
 };
 
+// a windowed background collision operator (fes_gas.inc.hpp): the request (its table pointers are not kept), its period in
+// sub-steps, the host's copy of the cross-sections, where its tables lie on the device, the applications so far
+struct GasOp {
+    fpic_gas_spec spec;
+    int every;
+    std::vector<double> sigma;
+    const double* dev_sigma;
+    const double* taper[3];
+    uint64_t applications;
+};
+
 // a registered binary collision operator (fes_pair.inc.hpp): the request, its period in sub-steps, the applications so far
 struct PairOp {
     fpic_pair_spec spec;
@@ -143,6 +154,11 @@ struct Diag {
     unsigned long long* force = nullptr;
     double* force_tab = nullptr;
     std::vector<ForceOp> force_ops;     // the registered requests, in registration order
+    // fpic_gas (fes_gas.inc.hpp): one block - per registered operator and one more for a call, fesgas::kWords tally words,
+    // then room for the cross-section table and three taper tables each (gas_tab points into the block)
+    unsigned long long* gas = nullptr;
+    double* gas_tab = nullptr;
+    std::vector<GasOp> gas_ops;         // the registered operators, in registration order
     unsigned long long* pair = nullptr; // the counts of fpic_pair (fes_pair.inc.hpp): eight words per registered operator, eight for a call
     std::vector<PairOp> pair_ops;       // the registered operators, in registration order
     // the cell index of fpic_pair, one per side (species_a, species_b): pair_seg[s] = 4 + cells words (zeros, then per cell
@@ -168,7 +184,7 @@ inline void diag_release(Diag& g)
 {
     for (Recorder& r : g.rec)
         if (r.dev) (void)hipFree(r.dev);
-    for (void* p : { g.series_req.block, g.modes_req.block, static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom), g.sel, static_cast<void*>(g.load_tab), static_cast<void*>(g.coll), static_cast<void*>(g.force), static_cast<void*>(g.pair),
+    for (void* p : { g.series_req.block, g.modes_req.block, static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom), g.sel, static_cast<void*>(g.load_tab), static_cast<void*>(g.coll), static_cast<void*>(g.force), static_cast<void*>(g.gas), static_cast<void*>(g.pair),
                      static_cast<void*>(g.pair_seg[0]), static_cast<void*>(g.pair_seg[1]), static_cast<void*>(g.pair_index[0]), static_cast<void*>(g.pair_index[1]),
                      static_cast<void*>(g.fusion), static_cast<void*>(g.fusion_table),
                      static_cast<void*>(g.fspec), static_cast<void*>(g.fspec_table), static_cast<void*>(g.fspec_words) })

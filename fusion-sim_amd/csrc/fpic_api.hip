@@ -1533,6 +1533,30 @@ int fpic_force_clear(fpic_handle* h)
     BOX_ONLY(h, "fpic_force_clear");
     return fes::force_clear(h);
 }
+int fpic_gas(fpic_handle* h, const fpic_gas_spec* spec, fpic_gas_result* out)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_gas");
+    return fes::gas(h, spec, out);
+}
+int fpic_gas_register(fpic_handle* h, const fpic_gas_spec* spec, int every, int* index)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_gas_register");
+    return fes::gas_register(h, spec, every, index);
+}
+int fpic_gas_stats(fpic_handle* h, int index, int scope, fpic_gas_result* out)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_gas_stats");
+    return fes::gas_stats(h, index, scope, out);
+}
+int fpic_gas_clear(fpic_handle* h)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_gas_clear");
+    return fes::gas_clear(h);
+}
 int fpic_collide_clear(fpic_handle* h)
 {
     CHECK_HANDLE(h);

@@ -52,6 +52,7 @@ ABI_FUNCTIONS = [
     "fpic_fusion", "fpic_fusion_register", "fpic_fusion_stats", "fpic_fusion_grid", "fpic_fusion_clear",
     "fpic_fusion_spectrum", "fpic_fusion_spectrum_register", "fpic_fusion_spectrum_read", "fpic_fusion_spectrum_clear",
     "fpic_force", "fpic_force_register", "fpic_force_stats", "fpic_force_clear",
+    "fpic_gas", "fpic_gas_register", "fpic_gas_stats", "fpic_gas_clear",
 ]
 
 
@@ -669,6 +670,120 @@ def _force_sum(parts, mass, W):
     return out
 
 
+GAS_EXCHANGE, GAS_ELASTIC = 0, 1
+GAS_MAX_OPS, GAS_TABLE_MAX, GAS_TAPER_MAX = 8, 4096, 1025
+GAS_SEED = 0x6A5C0111DE
+GAS_KINDS = {"exchange": GAS_EXCHANGE, "elastic": GAS_ELASTIC}
+
+
+class GasSpec(ctypes.Structure):
+    """mirror of fpic_gas_spec (include/fusionpic.h)"""
+    _fields_ = [
+        ("species", ctypes.c_int32), ("kind", ctypes.c_int32), ("seed", ctypes.c_uint64), ("stream", ctypes.c_uint32), ("epoch", ctypes.c_uint32),
+        ("density", ctypes.c_double), ("tau", ctypes.c_double), ("g_lo", ctypes.c_double), ("g_hi", ctypes.c_double),
+        ("n", ctypes.c_int32), ("reserved_i", ctypes.c_int32), ("sigma", ctypes.POINTER(ctypes.c_double)),
+        ("drift", ctypes.c_double * 3), ("vth", ctypes.c_double * 3), ("mass_ratio", ctypes.c_double),
+        ("lo", ctypes.c_double * 3), ("hi", ctypes.c_double * 3), ("taper_n", ctypes.c_uint32 * 3), ("reserved_u", ctypes.c_uint32),
+        ("taper", ctypes.POINTER(ctypes.c_double) * 3), ("reserved", ctypes.c_double * 4),
+    ]
+
+
+class GasResult(ctypes.Structure):
+    """mirror of fpic_gas_result"""
+    _fields_ = [("applications", ctypes.c_uint64), ("candidates", ctypes.c_uint64), ("collided", ctypes.c_uint64), ("below", ctypes.c_uint64),
+                ("above", ctypes.c_uint64), ("energy_fixed", ctypes.c_uint64 * 2), ("momentum_fixed", (ctypes.c_uint64 * 2) * 3),
+                ("energy", ctypes.c_double), ("momentum", ctypes.c_double * 3)]
+
+
+def _gas_spec(tau_default, L, kind, species=0, density=None, tau=None, sigma=None, g_lo=None, g_hi=None, drift=0, vth=0, mass_ratio=None,
+              lo=None, hi=None, taper=(None, None, None), seed=GAS_SEED, stream=0, epoch=0):
+    """GasSpec of a windowed background collision request, and the arrays its table pointers point into (keep them until the
+    call has returned).  kind: a code or "exchange" / "elastic".  density (m^-3) the peak density of the background, tau (s;
+    None: tau_default) the time one application stands for, sigma (m^2) the cross-sections at relative speeds uniform from
+    g_lo to g_hi (units of c; sigma_table() makes one from a function of the energy).  drift, vth (units of c; scalars
+    broadcast) and mass_ratio as for collide().  lo, hi (metres; a number is taken for all three axes) default to the whole
+    box; taper: per axis None or the nodes (each in [0, 1]) of a table over [lo, hi], whose product is the density as a
+    fraction of `density`.  Only what the structure cannot carry is refused here; the library checks the rest."""
+    s = GasSpec()
+    keep = []
+
+    def whole(name, v, bits, signed=False):
+        lo_, hi_ = (-(1 << bits - 1), 1 << bits - 1) if signed else (0, 1 << bits)
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo_ <= int(v) < hi_:
+            raise FusionPicError(-1, ".%s <- must be %s %d-bit integer" % (name, "a signed" if signed else "an unsigned", bits))
+        return int(v)
+
+    def three(name, v):
+        try:
+            if np.ndim(v) == 0:
+                v = [v, v, v]
+            if len(v) != 3:
+                raise ValueError
+            return [float(x) for x in v]
+        except (TypeError, ValueError):
+            raise FusionPicError(-1, ".%s <- must be a number or three of them" % name)
+
+    def real(name, v):
+        if v is None:
+            raise FusionPicError(-1, ".%s <- Non-optional property is undefined!" % name)
+        try:
+            return float(v)
+        except (TypeError, ValueError):
+            raise FusionPicError(-1, ".%s <- must be a number" % name)
+
+    def table(name, v, most):
+        try:
+            a = np.asarray(v, dtype=np.float64)
+        except (TypeError, ValueError):
+            a = None
+        if a is None or a.ndim != 1 or a.size > most:
+            raise FusionPicError(-1, ".%s <- a table must be a sequence of at most %d numbers" % (name, most))
+        a = np.ascontiguousarray(a)
+        keep.append(a)
+        return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(a.size)
+
+    if isinstance(kind, str):
+        if kind not in GAS_KINDS:
+            raise FusionPicError(-1, ".kind <- must be one of %s" % ", ".join(sorted(GAS_KINDS)))
+        kind = GAS_KINDS[kind]
+    s.kind = whole("kind", kind, 32, signed=True)
+    s.species = whole("species", species, 32, signed=True)
+    s.seed, s.stream, s.epoch = whole("seed", seed, 64), whole("stream", stream, 32), whole("epoch", epoch, 32)
+    s.density = real("density", density)
+    s.tau = real("tau", tau_default if tau is None else tau)
+    s.g_lo, s.g_hi = real("g_lo", g_lo), real("g_hi", g_hi)
+    if sigma is None:
+        raise FusionPicError(-1, ".sigma <- Non-optional property is undefined!")
+    s.sigma, s.n = table("sigma", sigma, (1 << 31) - 1)
+    s.drift[:], s.vth[:] = three("drift", drift), three("vth", vth)
+    s.mass_ratio = (float("inf") if s.kind == GAS_ELASTIC else 0.0) if mass_ratio is None else real("mass_ratio", mass_ratio)
+    s.lo[:] = three("lo", 0.0 if lo is None else lo)
+    s.hi[:] = three("hi", L if hi is None else hi)
+    if not isinstance(taper, (list, tuple)) or len(taper) != 3:
+        raise FusionPicError(-1, ".taper <- must be three tables (None: no table)")
+    for a, t in enumerate(taper):
+        if t is not None:
+            s.taper[a], s.taper_n[a] = table("taper", t, (1 << 32) - 1)
+    return s, keep
+
+
+def _gas_dict(r):
+    """energy_fixed and momentum_fixed as Python integers (the 128-bit two's complement sums, units of 2^-80): the species' gains"""
+    return {"applications": int(r.applications), "candidates": int(r.candidates), "collided": int(r.collided), "below": int(r.below), "above": int(r.above),
+            "energy_fixed": _force_signed(r.energy_fixed), "momentum_fixed": [_force_signed(r.momentum_fixed[a]) for a in range(3)],
+            "energy": float(r.energy), "momentum": [float(r.momentum[a]) for a in range(3)]}
+
+
+def _gas_sum(parts, mass, W):
+    """the members' integers added up and the doubles formed from the sums as the library forms them (_force_sum)"""
+    t = _force_sum([dict(applications=p["applications"], kicked=p["collided"], work_fixed=p["energy_fixed"], impulse_fixed=p["momentum_fixed"],
+                         work=p["energy"], impulse=p["momentum"]) for p in parts], mass, W)
+    out = {k: sum(p[k] for p in parts) for k in ("candidates", "below", "above")}
+    out.update(applications=t["applications"], collided=t["kicked"], energy_fixed=t["work_fixed"], momentum_fixed=t["impulse_fixed"],
+               energy=t["work"], momentum=t["impulse"])
+    return out
+
+
 PAIR_MAX_OPS = 8
 PAIR_CELL_MAX = 2048
 PAIR_SEED = 0x7A1C12ABE
@@ -1137,6 +1252,10 @@ def load_library(path=None):
     lib.fpic_force_register.argtypes = [vp, ctypes.POINTER(ForceSpec), ctypes.POINTER(ctypes.c_int)]
     lib.fpic_force_stats.argtypes = [vp, ci, ci, ctypes.POINTER(ForceResult)]
     lib.fpic_force_clear.argtypes = [vp]
+    lib.fpic_gas.argtypes = [vp, ctypes.POINTER(GasSpec), ctypes.POINTER(GasResult)]
+    lib.fpic_gas_register.argtypes = [vp, ctypes.POINTER(GasSpec), ci, ctypes.POINTER(ctypes.c_int)]
+    lib.fpic_gas_stats.argtypes = [vp, ci, ci, ctypes.POINTER(GasResult)]
+    lib.fpic_gas_clear.argtypes = [vp]
     lib.fpic_pair.argtypes = [vp, ctypes.POINTER(PairSpec), ctypes.POINTER(PairResult)]
     lib.fpic_pair_register.argtypes = [vp, ctypes.POINTER(PairSpec), ci, ctypes.POINTER(ctypes.c_int)]
     lib.fpic_pair_stats.argtypes = [vp, ci, ci, ctypes.POINTER(PairResult)]
@@ -1544,6 +1663,47 @@ class CylindricalParticlePusher:
     def clearForces(self):
         """drops every registered force (fpic_force_clear)"""
         self._check(self._lib.fpic_force_clear(self._h))
+
+    # ---- windowed background collisions with a tabulated cross-section (fpic_gas*)
+    def collideGas(self, kind, **request):
+        """One application, now, of a collision operator against a background gas that fills a window of the box
+        (fpic_gas; an (r,z) handle is refused).  kind: "exchange" or "elastic", as collide().  density= (m^-3, the peak),
+        tau= (s, default the sub-step dt), sigma=, g_lo=, g_hi= (the cross-section table in m^2 over the relative speed in
+        units of c, as tallyFusion takes it), drift=, vth=, mass_ratio= (the background, as collide()), lo=, hi= (the
+        window in metres; default the whole box), taper=(None, None, None) (per axis the nodes in [0, 1] of the density
+        profile over the window), seed=, stream=, epoch=.  Returns {applications, candidates, collided, below, above,
+        energy_fixed, momentum_fixed (exact integers, units of 2^-80 c^2 and c), energy (J), momentum (kg m/s)}: what the
+        species gained; the reservoir took the negatives."""
+        s, keep = _gas_spec(float(self.spec["dt"]), self._box_lengths(), kind, **request)
+        out = GasResult()
+        self._check(self._lib.fpic_gas(self._h, ctypes.byref(s), ctypes.byref(out)))
+        del keep
+        return _gas_dict(out)
+
+    def collideGasEvery(self, every, kind=None, **request):
+        """Registers a windowed background collision operator (see collideGas) to run at the end of every `every`-th
+        sub-step, after the operators of collideEvery and before those of collidePairEvery, with epoch = the sub-step
+        number + `epoch`; tau defaults to every * dt.  Returns the operator's index (fpic_gas_register)."""
+        if kind is None:
+            raise FusionPicError(-1, ".kind <- Non-optional property is undefined!")
+        if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or not -(1 << 31) <= int(every) < 1 << 31:
+            raise FusionPicError(-1, ".every <- must be a signed 32-bit integer")
+        s, keep = _gas_spec(int(every) * float(self.spec["dt"]), self._box_lengths(), kind, **request)
+        index = ctypes.c_int(-1)
+        self._check(self._lib.fpic_gas_register(self._h, ctypes.byref(s), int(every), ctypes.byref(index)))
+        del keep
+        return index.value
+
+    def gasStats(self, index, scope="global"):
+        """the totals of a registered operator since its registration (fpic_gas_stats); 'global' on a rank with a
+        communicator sums the ranks' integers (collective)"""
+        out = GasResult()
+        self._check(self._lib.fpic_gas_stats(self._h, int(index), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope], ctypes.byref(out)))
+        return _gas_dict(out)
+
+    def clearGas(self):
+        """drops every registered windowed background collision operator (fpic_gas_clear)"""
+        self._check(self._lib.fpic_gas_clear(self._h))
 
     # ---- binary Coulomb collisions between the species of the box (fpic_pair*)
     def collidePair(self, a=0, b=None, **request):
@@ -1984,6 +2144,10 @@ class ElectrostaticBoxPusher:
     forceOn = CylindricalParticlePusher.forceOn
     forceStats = CylindricalParticlePusher.forceStats
     clearForces = CylindricalParticlePusher.clearForces
+    collideGas = CylindricalParticlePusher.collideGas
+    collideGasEvery = CylindricalParticlePusher.collideGasEvery
+    gasStats = CylindricalParticlePusher.gasStats
+    clearGas = CylindricalParticlePusher.clearGas
     collidePair = CylindricalParticlePusher.collidePair
     collidePairEvery = CylindricalParticlePusher.collidePairEvery
     pairStats = CylindricalParticlePusher.pairStats
@@ -2130,6 +2294,28 @@ class BoxGroup:
         for m in self.sims:
             m.clearForces()
         self._force_species = {}
+
+    def collideGas(self, kind, **request):
+        """collideGas() of every member with the same request; the members' integers added up and the doubles formed from
+        the sums (applications: the first member's)"""
+        return _gas_sum([m.collideGas(kind, **request) for m in self.sims], *self._force_scales(int(request.get("species", 0))))
+
+    def collideGasEvery(self, every, kind=None, **request):
+        """collideGasEvery() of every member with the same request; the index (the same on every member)"""
+        index = [m.collideGasEvery(every, kind, **request) for m in self.sims][0]
+        self._gas_species = getattr(self, "_gas_species", {})
+        self._gas_species[index] = int(request.get("species", 0))
+        return index
+
+    def gasStats(self, index):
+        """the whole box: the members' LOCAL integers added up, the doubles formed from the sums (applications: the first member's)"""
+        parts = [m.gasStats(index, "local") for m in self.sims]
+        return _gas_sum(parts, *self._force_scales(self._gas_species[int(index)]))
+
+    def clearGas(self):
+        for m in self.sims:
+            m.clearGas()
+        self._gas_species = {}
 
     def collidePair(self, a=0, b=None, **request):
         """refused (FPIC_ERR_STATE), as by every member: between two migrations the particles of a cell can sit on two

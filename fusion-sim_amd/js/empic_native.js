@@ -506,6 +506,77 @@ function makeBox(spec, lib) {
         return lib.forceStats(h, index, scopeOf(scope));
     };
     out.clearForces = function () { lib.clearForces(h); };
+    // windowed background collisions with a tabulated cross-section (fpic_gas*).  request = { kind: 'exchange' | 'elastic',
+    // species, density (m^-3, the peak), tau (s; default the sub-step dt, every * dt for collideGasEvery), sigma (the
+    // cross-sections in m^2, 2 .. 4096 of them), gLo, gHi (their first and last relative speed, units of c), drift, vth,
+    // massRatio (the background, as collide), lo, hi (the window in metres; default the whole box), taper: [x, y, z] (each
+    // null or the nodes in [0, 1] of the density profile over the window), seed, stream, epoch }.  collideGas ->
+    // { applications, candidates, collided, below, above, energyFixed, momentumFixed (BigInt: the exact sums of what the
+    // species gained, units of 2^-80 c^2 and c), energy (J), momentum (kg m/s) }; collideGasEvery(every, request) -> the
+    // operator's index; gasStats(index, scope) -> its totals since registration; clearGas() drops every such operator
+    const GAS_KINDS = { exchange: 0, elastic: 1 };
+    const gasArgs = function (request, tauDefault) {
+        if (request === null || typeof request !== 'object' || Array.isArray(request)) throw new TypeError('.request <- expected { kind, species, density, tau, sigma, gLo, gHi, drift, vth, massRatio, lo, hi, taper, seed, stream, epoch }');
+        const given = (v) => v !== undefined && v !== null;
+        const three = function (name, v, dflt) {
+            if (!given(v)) v = dflt;
+            if (typeof v === 'number') v = [v, v, v];
+            if (!(Array.isArray(v) || ArrayBuffer.isView(v)) || v.length !== 3 || !Array.from(v).every((x) => typeof x === 'number')) throw new RangeError('.' + name + ' <- expected a number or three of them');
+            return Array.from(v);
+        };
+        const whole = function (name, v, dflt, least, most) {
+            if (!given(v)) v = dflt;
+            if (!Number.isInteger(v) || v < least || v > most) throw new RangeError('.' + name + ' <- expected an integer within its field');
+            return v;
+        };
+        const real = function (name, v, dflt) {
+            if (!given(v)) v = dflt;
+            if (typeof v !== 'number') throw new RangeError('.' + name + ' <- expected a number');
+            return v;
+        };
+        let kind = request.kind;
+        if (typeof kind === 'string') {
+            if (!(kind in GAS_KINDS)) throw new RangeError(".kind <- must be one of 'exchange', 'elastic'");
+            kind = GAS_KINDS[kind];
+        }
+        kind = whole('kind', kind, undefined, -0x80000000, 0x7fffffff);
+        let seed = given(request.seed) ? request.seed : 0x6A5C0111DE;
+        if (typeof seed === 'number') {
+            if (!Number.isInteger(seed) || seed < 0 || seed > Number.MAX_SAFE_INTEGER) throw new RangeError('.seed <- expected an integer up to 2^53, or a BigInt up to 2^64');
+            seed = BigInt(seed);
+        }
+        if (typeof seed !== 'bigint' || seed < 0n || seed >= (1n << 64n)) throw new RangeError('.seed <- expected an integer up to 2^53, or a BigInt up to 2^64');
+        const box = [spec.radius, spec.length_y, spec.height].map((v) => (typeof v === 'number' ? v : 1));
+        const counts = [], tables = [];
+        const table = function (name, t, needed) {
+            if (!given(t) && !needed) { counts.push(0); return; }
+            if (!(Array.isArray(t) || ArrayBuffer.isView(t)) || t.length > 0x7fffffff || !Array.from(t).every((x) => typeof x === 'number')) throw new RangeError('.' + name + ' <- a table must be a list of numbers');
+            counts.push(t.length);
+            for (const x of t) tables.push(x);
+        };
+        table('sigma', request.sigma, true);
+        const taper = given(request.taper) ? request.taper : [null, null, null];
+        if (!Array.isArray(taper) || taper.length !== 3) throw new RangeError('.taper <- expected three entries (x, y, z), each null or a table');
+        for (const t of taper) table('taper', t, false);
+        const words = [kind, Number(seed & 0xffffffffn), Number(seed >> 32n), whole('stream', request.stream, 0, 0, 0xffffffff), whole('epoch', request.epoch, 0, 0, 0xffffffff)].concat(counts);
+        const reals = [real('density', request.density, undefined), real('tau', request.tau, tauDefault), real('gLo', request.gLo, undefined), real('gHi', request.gHi, undefined)].concat(
+            three('drift', request.drift, 0), three('vth', request.vth, 0), [real('massRatio', request.massRatio, kind === 1 ? Infinity : 0)], three('lo', request.lo, 0), three('hi', request.hi, box));
+        return [whole('species', request.species, 0, 0, 0x7fffffff), Float64Array.from(words), Float64Array.from(reals), Float64Array.from(tables)];
+    };
+    out.collideGas = function (request) {
+        const a = gasArgs(request, spec.dt);
+        return lib.collideGas(h, a[0], a[1], a[2], a[3]);
+    };
+    out.collideGasEvery = function (every, request) {
+        if (!Number.isInteger(every) || every < -0x80000000 || every > 0x7fffffff) throw new RangeError('.every <- expected a 32-bit integer');
+        const a = gasArgs(request, every * spec.dt);
+        return lib.collideGasEvery(h, a[0], a[1], a[2], a[3], every);
+    };
+    out.gasStats = function (index, scope) {
+        if (!Number.isInteger(index) || index < -0x80000000 || index > 0x7fffffff) throw new RangeError('.index <- expected a 32-bit integer');
+        return lib.gasStats(h, index, scopeOf(scope));
+    };
+    out.clearGas = function () { lib.clearGas(h); };
     // binary Coulomb collisions between the species of the box (Takizuka-Abe; fpic_pair*).  request = { a, b (default a: like
     // particles), logLambda, tau (s; default the sub-step dt, every * dt for collidePairEvery), seed (an integer up to 2^53 or a
     // BigInt up to 2^64), stream, epoch }.  collidePair -> { applications, pairs, strong, cells, overfullCells,

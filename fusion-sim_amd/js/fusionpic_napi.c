@@ -1199,6 +1199,138 @@ static napi_value n_clear_forces(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* the request of collideGas / collideGasEvery: words: Float64Array [kind, seed low word, seed high word, stream, epoch, n,
+ * taper_n (3)], reals: Float64Array [density, tau, g_lo, g_hi, drift 3, vth 3, mass_ratio, lo 3, hi 3], tables: Float64Array,
+ * the cross-sections and the taper tables one after the other.  The arrays' lengths and the words' ranges are checked here,
+ * the request itself by the library (which copies the tables during the call). */
+#define GAS_WORDS 9
+#define GAS_REALS 17
+static int get_gas_spec(napi_env env, int sp, napi_value words, napi_value reals, napi_value tables, fpic_gas_spec* s)
+{
+    napi_typedarray_type tw, tr, tt; void *pw, *pr, *pt; size_t lw, lr, lt;
+    if (!get_typed(env, words, &tw, &pw, &lw) || !get_typed(env, reals, &tr, &pr, &lr) || !get_typed(env, tables, &tt, &pt, &lt)) return 0;
+    if (!pw || !pr || tw != napi_float64_array || tr != napi_float64_array || tt != napi_float64_array) {
+        napi_throw_type_error(env, NULL, ".request <- expected three Float64Arrays");
+        return 0;
+    }
+    if (!check_len(env, "words", lw, GAS_WORDS) || !check_len(env, "reals", lr, GAS_REALS)) return 0;
+    const double* w = (const double*)pw;
+    const double* r = (const double*)pr;
+    for (int k = 0; k < GAS_WORDS; ++k) {
+        const int is_signed = k == 0 || k == 5;
+        const double least = is_signed ? -2147483648.0 : 0.0, most = is_signed ? 2147483647.0 : 4294967295.0;
+        const double mag = w[k] < 0 ? -w[k] : w[k];
+        if (!(w[k] >= least && w[k] <= most) || mag != (double)(uint64_t)mag) {
+            napi_throw_range_error(env, NULL, ".request <- kind, seed, stream, epoch and the node counts must be integers within their fields");
+            return 0;
+        }
+    }
+    memset(s, 0, sizeof *s);
+    s->species = sp;
+    s->kind = (int32_t)w[0];
+    s->seed = (uint64_t)(uint32_t)w[1] | (uint64_t)(uint32_t)w[2] << 32;
+    s->stream = (uint32_t)w[3];
+    s->epoch = (uint32_t)w[4];
+    s->n = (int32_t)w[5];
+    s->density = r[0];
+    s->tau = r[1];
+    s->g_lo = r[2];
+    s->g_hi = r[3];
+    for (int a = 0; a < 3; ++a) { s->drift[a] = r[4 + a]; s->vth[a] = r[7 + a]; s->lo[a] = r[11 + a]; s->hi[a] = r[14 + a]; }
+    s->mass_ratio = r[10];
+    double total = w[5] > 0 ? w[5] : 0;
+    for (int a = 0; a < 3; ++a) total += w[6 + a];
+    if (total != (double)lt) {
+        napi_throw_range_error(env, NULL, ".tables <- its length must be the sum of the node counts");
+        return 0;
+    }
+    const double* at = (const double*)pt;
+    if (s->n > 0) { s->sigma = at; at += s->n; }
+    for (int a = 0; a < 3; ++a) {
+        s->taper_n[a] = (uint32_t)w[6 + a];
+        if (s->taper_n[a]) { s->taper[a] = at; at += s->taper_n[a]; }
+    }
+    return 1;
+}
+
+static napi_value gas_object(napi_env env, const fpic_gas_result* c)
+{
+    napi_value o, v, arr;
+    NAPI_OK(env, napi_create_object(env, &o));
+    const char* names[5] = { "applications", "candidates", "collided", "below", "above" };
+    const uint64_t counts[5] = { c->applications, c->candidates, c->collided, c->below, c->above };
+    for (int k = 0; k < 5; ++k) {
+        NAPI_OK(env, napi_create_double(env, (double)counts[k], &v));
+        NAPI_OK(env, napi_set_named_property(env, o, names[k], v));
+    }
+    v = fixed_bigint(env, c->energy_fixed);
+    if (!v) return NULL;
+    NAPI_OK(env, napi_set_named_property(env, o, "energyFixed", v));
+    NAPI_OK(env, napi_create_array_with_length(env, 3, &arr));
+    for (uint32_t a = 0; a < 3; ++a) {
+        v = fixed_bigint(env, c->momentum_fixed[a]);
+        if (!v) return NULL;
+        NAPI_OK(env, napi_set_element(env, arr, a, v));
+    }
+    NAPI_OK(env, napi_set_named_property(env, o, "momentumFixed", arr));
+    NAPI_OK(env, napi_create_double(env, c->energy, &v));
+    NAPI_OK(env, napi_set_named_property(env, o, "energy", v));
+    NAPI_OK(env, napi_create_array_with_length(env, 3, &arr));
+    for (uint32_t a = 0; a < 3; ++a) {
+        NAPI_OK(env, napi_create_double(env, c->momentum[a], &v));
+        NAPI_OK(env, napi_set_element(env, arr, a, v));
+    }
+    NAPI_OK(env, napi_set_named_property(env, o, "momentum", arr));
+    return o;
+}
+
+/* collideGas(h, species, words, reals, tables) -> { applications, candidates, collided, below, above, energyFixed, momentumFixed, energy, momentum } */
+static napi_value n_collide_gas(napi_env env, napi_callback_info info)
+{
+    napi_value argv[5]; fpic_handle* h; int sp;
+    fpic_gas_spec s;
+    if (!get_args(env, info, 5, argv, &h) || !get_species(env, argv[1], &sp) || !get_gas_spec(env, sp, argv[2], argv[3], argv[4], &s)) return NULL;
+    fpic_gas_result c;
+    memset(&c, 0, sizeof c);
+    if (fpic_gas(h, &s, &c) != FPIC_OK) return throw_fpic(env, h);
+    return gas_object(env, &c);
+}
+
+/* collideGasEvery(h, species, words, reals, tables, every) -> the operator's index */
+static napi_value n_collide_gas_every(napi_env env, napi_callback_info info)
+{
+    napi_value argv[6]; fpic_handle* h; int sp; double every;
+    fpic_gas_spec s;
+    if (!get_args(env, info, 6, argv, &h) || !get_species(env, argv[1], &sp) || !get_gas_spec(env, sp, argv[2], argv[3], argv[4], &s) || !get_double(env, argv[5], &every)) return NULL;
+    if (!(every >= -2147483648.0 && every <= 2147483647.0) || every != (double)(int)every) { napi_throw_range_error(env, NULL, ".every <- must be a 32-bit integer"); return NULL; }
+    int index = -1;
+    if (fpic_gas_register(h, &s, (int)every, &index) != FPIC_OK) return throw_fpic(env, h);
+    napi_value v;
+    NAPI_OK(env, napi_create_int32(env, index, &v));
+    return v;
+}
+
+/* gasStats(h, index, scope) -> as collideGas */
+static napi_value n_gas_stats(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3]; fpic_handle* h; double index; int scope;
+    if (!get_args(env, info, 3, argv, &h) || !get_double(env, argv[1], &index) || !get_scope(env, argv[2], &scope)) return NULL;
+    if (!(index >= -2147483648.0 && index <= 2147483647.0) || index != (double)(int)index) { napi_throw_range_error(env, NULL, ".index <- must be a 32-bit integer"); return NULL; }
+    fpic_gas_result c;
+    memset(&c, 0, sizeof c);
+    if (fpic_gas_stats(h, (int)index, scope, &c) != FPIC_OK) return throw_fpic(env, h);
+    return gas_object(env, &c);
+}
+
+/* clearGas(h) */
+static napi_value n_clear_gas(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1]; fpic_handle* h;
+    if (!get_args(env, info, 1, argv, &h)) return NULL;
+    if (fpic_gas_clear(h) != FPIC_OK) return throw_fpic(env, h);
+    return undefined(env);
+}
+
 /* the request of collidePair / collidePairEvery: words: Float64Array [species_a, species_b, seed low word, seed high word,
  * stream, epoch], reals: Float64Array [log_lambda, tau].  The arrays' lengths and the words' ranges are checked here, the
  * request itself by the library. */
@@ -1798,6 +1930,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "energy", n_energy }, { "recordEnergy", n_record_energy }, { "energyHistory", n_energy_history },
         { "histogram", n_histogram }, { "select", n_select }, { "load", n_load }, { "collide", n_collide }, { "collideEvery", n_collide_every }, { "collisionStats", n_collision_stats }, { "clearCollisions", n_clear_collisions },
         { "force", n_force }, { "forceOn", n_force_on }, { "forceStats", n_force_stats }, { "clearForces", n_clear_forces },
+        { "collideGas", n_collide_gas }, { "collideGasEvery", n_collide_gas_every }, { "gasStats", n_gas_stats }, { "clearGas", n_clear_gas },
         { "collidePair", n_collide_pair }, { "collidePairEvery", n_collide_pair_every }, { "pairStats", n_pair_stats }, { "clearPairs", n_clear_pairs },
         { "fusionYield", n_fusion_yield }, { "fusionYieldEvery", n_fusion_yield_every }, { "fusionStats", n_fusion_stats }, { "fusionGrid", n_fusion_grid }, { "clearFusion", n_clear_fusion },
         { "fusionSpectrum", n_fusion_spectrum }, { "fusionSpectrumEvery", n_fusion_spectrum_every }, { "fusionSpectrumRead", n_fusion_spectrum_read }, { "clearFusionSpectra", n_clear_fusion_spectra },

@@ -1182,6 +1182,95 @@ int fpic_force_register(fpic_handle* h, const fpic_force_spec* spec, int* index)
 int fpic_force_stats(fpic_handle* h, int index, int scope, fpic_force_result* out);
 int fpic_force_clear(fpic_handle* h);
 
+/* ---- CART3D windowed background collisions with a tabulated cross-section: the Monte Carlo operator of fpic_collide
+ * against a background gas that occupies a WINDOW of the box with a separable density profile, whose cross-section is a
+ * table over the relative speed, and whose exchange of momentum and energy with the species is tallied exactly — a gas puff,
+ * a neutral-beam target, a cold edge layer, a beam dump.  EXCHANGE and ELASTIC as fpic_collide has them; there is no RELAX.
+ * It acts per particle at the particle's own stored position, so a decomposed box takes it as one handle does.  What
+ * happens to particle i (the id the box carries) depends on the request, the epoch, i and its stored state alone — not on
+ * the slot, the binning or the rank.  All arithmetic is double, every operation rounded once; p is the stored position in
+ * box fractions, v the stored velocity in units of c, T the handle's precision.
+ *   words      W(b) = Philox4x32-10(counter (i, epoch, stream, 0x6A500 + b), key (seed_lo, seed_hi)): a tag of its own
+ *              (fpic_load 0x10AD, fpic_collide 0xC0110/1, fpic_pair 0xC0120.., fpic_fusion 0xF0510), so a gas operator
+ *              never correlates with another operator on the same seed.  W(0) = (w0, w1, w2, w3): candidate, acceptance,
+ *              two direction words; W(1): the partner's three normals n[a] (the loader's Box-Muller step).
+ *   numbers    (host, once per application) column = (density c) tau with c = 2.998e8 (m^-2: sigma column is a number);
+ *              dg = (g_hi - g_lo) / (n - 1), inv_dg = (n - 1) / (g_hi - g_lo); per interval k = 0 .. n - 2
+ *              b_k = max(S[k], S[k+1]) g_{k+1} with g_{k+1} = g_lo + (k+1) dg, the last interval with g_hi;
+ *              x_max = column max_k b_k — the interval-wise bound, not max(S) g_hi: a resonance does not pay for its peak
+ *              at every speed; P_max = -expm1(-x_max); K = (uint64) ldexp(P_max, 32); M = mass_ratio / (1 + mass_ratio),
+ *              1 for +inf; lo_f[a] = lo[a] / L_a, hi_f[a] = hi[a] / L_a, w[a] = hi_f[a] - lo_f[a].
+ *   candidate  a live particle with lo_f[a] <= p[a] < hi_f[a] on all three axes (fpic_force's window, compared in
+ *              double) and (uint64) w0 < K: integers and stored values, so candidacy never depends on rounding.  It is a
+ *              SET: which of the two tests a pass makes first is its own choice.
+ *   partner    vb[a] = drift[a] + vth[a] n[a]; d[a] = v[a] - vb[a]; g = sqrt((d0 d0 + d1 d1) + d2 d2) (fpic_collide's).
+ *   table      g < g_lo: counted `below`; g >= g_hi (or NaN): counted `above`; neither collides.  Else fpic_fusion's
+ *              lookup: t = (g - g_lo) inv_dg, k = min((int) t, n - 2), sigma = S[k] + (t - k) (S[k+1] - S[k]), then
+ *              sigma = min(sigma, max S).
+ *   acceptance rho = (tx ty) tz over the taper tables present, fpic_force's taper rule (f = (p[a] - lo_f[a]) / w[a],
+ *              g' = f K, j = min((int) g', K - 1), s = g' - j, tab[j] + (tab[j+1] - tab[j]) s); x = ((column rho) sigma) g,
+ *              without any taper table x = (column sigma) g; x = min(x, x_max); u = (w1 + 0.5) 2^-32; the candidate
+ *              collides iff u x_max < x.  This is the linearised null-collision acceptance of fpic_collide: a candidate
+ *              is accepted with x / x_max, not with (1 - exp(-x)) / P_max — exact where x_max << 1.  The nodes of a taper
+ *              lie in [0, 1] so that rho <= 1 and the bound holds; the hold to x_max guards the last roundings.
+ *   EXCHANGE   v' = vb.
+ *   ELASTIC    c = 1 - 2 (w2 + 0.5) 2^-32, s = sqrt(1 - c c), phi = w3 2^-32, nhat = (s cospi(2 phi), s sinpi(2 phi), c);
+ *              t = g nhat[a]; r = d[a] - t; q = M r; v'[a] = v[a] - q (fpic_collide's, operation for operation).
+ * A particle that does not collide keeps every bit; positions are never written; a dead slot of a rank of a decomposition
+ * is never counted.
+ * Tallies (exact: the fixed point of fpic_force and the energy diagnostics, units of 2^-80, 128-bit two's complement, low
+ * word first).  Per collided particle energy_fixed gains floor(|(T)v'|^2 2^80) - floor(|v|^2 2^80), the squared norms
+ * ((x x + y y) + z z) of the stored values in double, and momentum_fixed[a] gains floor((T)v'[a] 2^80) - floor(v[a] 2^80):
+ * the SPECIES' gains; the reservoir takes the negatives.  energy = (0.5 m W c^2) times the double nearest to the sum 2^-80
+ * (J), momentum[a] = (m W c) times the same of its sum (kg m/s).  A term outside the diagnostics' range (|term| >= 2^15, or
+ * not finite) adds nothing and makes its double NaN.
+ * fpic_gas applies the request now (synchronous) and returns its result (applications 1); K = 0 — a zero density, an
+ * all-zero table — launches nothing and returns zeros, as fpic_collide does.fpic_gas_register makes it run at the end of every sub-step with
+ * substep % every == 0, after the operators of fpic_collide_register and before those of fpic_pair_register, in
+ * registration order, with epoch (uint32)(substep + spec.epoch); at most FPIC_GAS_MAX_OPS operators, *index names the
+ * operator.  The tables are copied at the call.  Nothing is synchronised: fpic_gas_stats reads the totals since
+ * registration (GLOBAL with a communicator adds the ranks' integers; applications is the same on every rank and is not
+ * summed).  fpic_gas_clear drops every operator (those of fpic_collide_register stay).  Registrations are not part of a
+ * checkpoint.
+ * Refused (FPIC_ERR_INVALID_ARG): a null spec, an unknown kind, a species the handle does not have, a reserved word that
+ * is not zero, a density that is negative or not finite, a tau that is not positive and finite, n outside 2 ..
+ * FPIC_GAS_TABLE_MAX, a null table, g_lo negative or not finite, g_hi not above g_lo or not finite, a cross-section that
+ * is negative or not finite, a drift or vth that is not finite, a negative vth, a mass_ratio that is not positive for
+ * ELASTIC or not 0 for EXCHANGE, a window not within 0 <= lo < hi <= L, a taper node count of 1 or above
+ * FPIC_GAS_TAPER_MAX, a null taper with a node count, a taper node outside [0, 1], an x_max that is not finite, every
+ * below 1, a ninth registration, an index outside the registered operators; FPIC_ERR_STATE: a handle that is not CART3D. */
+#define FPIC_GAS_EXCHANGE  0
+#define FPIC_GAS_ELASTIC   1
+#define FPIC_GAS_MAX_OPS   8
+#define FPIC_GAS_TABLE_MAX 4096
+#define FPIC_GAS_TAPER_MAX 1025
+typedef struct fpic_gas_spec {
+    int32_t  species, kind;        /* FPIC_GAS_EXCHANGE 0, _ELASTIC 1 */
+    uint64_t seed;
+    uint32_t stream, epoch;
+    double   density;              /* m^-3: the peak density of the background, >= 0 and finite */
+    double   tau;                  /* s: the time one application stands for, > 0 and finite */
+    double   g_lo, g_hi;           /* units of c: the table's first and last relative speed */
+    int32_t  n, reserved_i;        /* table entries, 2 .. FPIC_GAS_TABLE_MAX; zero */
+    const double* sigma;           /* n cross-sections, m^2 */
+    double   drift[3], vth[3];     /* the background, units of c; vth >= 0 */
+    double   mass_ratio;           /* m_background / m_species > 0, +inf allowed; ELASTIC only, else 0 */
+    double   lo[3], hi[3];         /* the window, metres: 0 <= lo < hi <= L (the whole box: 0 and L) */
+    uint32_t taper_n[3], reserved_u;   /* nodes, 0 = no table, else 2 .. FPIC_GAS_TAPER_MAX; zero */
+    const double* taper[3];        /* the density over the window as a fraction of `density`: nodes in [0, 1] */
+    double   reserved[4];          /* zero */
+} fpic_gas_spec;
+typedef struct fpic_gas_result {
+    uint64_t applications, candidates, collided, below, above;
+    uint64_t energy_fixed[2];      /* low word, high word */
+    uint64_t momentum_fixed[3][2];
+    double   energy, momentum[3];  /* J; kg m/s: the species' gains */
+} fpic_gas_result;
+int fpic_gas(fpic_handle* h, const fpic_gas_spec* spec, fpic_gas_result* out);
+int fpic_gas_register(fpic_handle* h, const fpic_gas_spec* spec, int every, int* index);
+int fpic_gas_stats(fpic_handle* h, int index, int scope, fpic_gas_result* out);
+int fpic_gas_clear(fpic_handle* h);
+
 int fpic_sync(fpic_handle* h);
 int fpic_profile(fpic_handle* h, int enable);
 int fpic_get_stats(fpic_handle* h, fpic_stats* out);
