@@ -14,6 +14,7 @@ import re
 
 import numpy as np
 
+import gas_reference as gasref
 import pair_scene
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -240,7 +241,7 @@ def compares_face_b(index):
     return index % 2 == 1
 
 
-def can_have_rebinned(sc, steps):
+def can_have_rebinned(sc, steps, position_kinds=POSITION_KINDS):
     """per step: True for a substeps after which a fused re-binning push can have reordered the particles — sort_interval > 0, an
     electrostatic cycle, and more than sort_interval sub-steps since the particles were last put into the caller's order or
     binned afresh (the first sub-step bins; the re-binning push is the sort_interval + 1st)"""
@@ -250,7 +251,7 @@ def can_have_rebinned(sc, steps):
             since += st["k"]
             out.append(sc["solver"] != "yee" and sc["sort_interval"] > 0 and since > sc["sort_interval"])
         else:
-            if (st["kind"] in POSITION_KINDS and st["what"] != "velocity") or st["kind"] in ("loadCheckpoint", "sort"):
+            if (st["kind"] in position_kinds and st["what"] != "velocity") or st["kind"] in ("loadCheckpoint", "sort"):
                 since = 0
             out.append(False)
     return out
@@ -389,3 +390,538 @@ def pending_rebinning():
 
 
 NAMED = {"pending_rebinning": pending_rebinning}
+
+
+# ================================================================================================ generation 2
+# The six newest operator families under the same relations (tests/test_gpu_sequences2.py).  Generation 1 above stays what it
+# is: tests/test_sequence_model.py pins its scenes and step lists to digests.  The scene of a generation-2 seed is the
+# generation-1 scene of that seed with more operators registered; its steps are drawn by their own generator.
+STATE_KINDS2 = STATE_KINDS + ("force_field", "force_accel", "gas_exchange", "gas_elastic", "load_profile", "load_radial")
+READ_KINDS2 = READ_KINDS + ("fusionYield", "fusionSpectrum")
+STATS_KINDS2 = ("forceStats", "gasStats", "fusionStats", "fusionGrid", "fusionSpectrumRead")      # on scenes with registered operators
+POSITION_KINDS2 = POSITION_KINDS + ("load_profile", "load_radial")
+READS2 = 6
+GAS_G = (0.05, 0.3)
+GROUP_GAS_G = (0.02, 1.5)          # (a group's particles stream at up to 0.9 along z, and after a cold reload most relative speeds lie below 0.05)
+FUSION_G, FUSION_NODES = (0.02, 0.3), 64
+LOS = (1.0, 2.0, -2.0)
+FORCE_FIELD_AMP, FORCE_ACCEL_AMP = 1e6, 3e16      # V/m on electrons (100 times that on the ions), m/s^2
+
+# chosen by tests/test_sequence_model.py's conditions (coverage and no vacuous request); none is skipped at run time
+SEEDS2 = [0, 9, 10, 15, 16, 35, 38, 101, 107, 116, 122, 149]
+
+
+def gas_compact_range():
+    """kGasCompactMin, kGasCompactMax of the kernel header: the K between which the queue serves a request"""
+    text = open(os.path.join(ROOT, "fusion-sim_amd", "csrc", "fes_gas_kernels.hpp")).read()
+    m = re.search(r"kGasCompactMin\s*=\s*1ull\s*<<\s*(\d+)\s*,\s*kGasCompactMax\s*=\s*1ull\s*<<\s*(\d+)\s*;", text)
+    return 1 << int(m.group(1)), 1 << int(m.group(2))
+
+
+def gas_window_first_max():
+    """kGasWindowFirstMax of the kernel header: the share of the box's volume below which the window is tested first"""
+    text = open(os.path.join(ROOT, "fusion-sim_amd", "csrc", "fes_gas_kernels.hpp")).read()
+    return float(re.search(r"constexpr\s+double\s+kGasWindowFirstMax\s*=\s*([0-9.eE+-]+)\s*;", text).group(1))
+
+
+def gas_table(g=GAS_G):
+    """sigma g constant over the table: a candidate inside the table is accepted with nearly the local density's share, so
+    that a request with a handful of candidates still collides somebody"""
+    lo, hi = g
+    return 3e-19 * (lo / np.linspace(lo, hi, 96 if g == GAS_G else 1024))
+
+
+def fusion_table():
+    return 1e-28 * (1.0 + np.sin(40.0 * np.linspace(FUSION_G[0], FUSION_G[1], FUSION_NODES)) ** 2)
+
+
+def gas_density(K, tau, g=GAS_G):
+    """the density at which a request has (within a few units) the candidate word bound K"""
+    return -math.log1p(-K * 2.0 ** -32) / (C * tau * gasref.bound(gas_table(g), g[0], g[1]))
+
+
+def window_volume(kw, lengths=L):
+    if "lo" not in kw:
+        return 1.0
+    return float(np.prod([(kw["hi"][a] - kw["lo"][a]) / lengths[a] for a in range(3)]))
+
+
+def _window(rng, which, lengths=L):
+    """whole: the box; narrow: a strict sub-box of 0.125 .. 0.343 of the volume; wide: one of 0.512 .. 0.857"""
+    if which == "whole":
+        return {}
+    span = rng.uniform(0.5, 0.7, 3) if which == "narrow" else rng.uniform(0.8, 0.95, 3)
+    lo = rng.uniform(0, 1, 3) * (1 - span)
+    return dict(lo=[float(lo[a] * lengths[a]) for a in range(3)], hi=[float((lo[a] + span[a]) * lengths[a]) for a in range(3)])
+
+
+def _tapers(rng, least, most):
+    """tables on 0 .. 3 axes, of 2, 5 or 9 nodes"""
+    out = [None, None, None]
+    for a in rng.permutation(3)[:int(rng.integers(0, 4))]:
+        out[int(a)] = [float(x) for x in rng.uniform(least, most, int(rng.choice([2, 5, 9])))]
+    return out
+
+
+def _waves(rng, n, amp):
+    out = []
+    for _ in range(n):
+        mode = rng.integers(-3, 4, 3)
+        if not mode.any():
+            mode[int(rng.integers(0, 3))] = 1
+        out.append(dict(amp=[float(x) for x in rng.normal(0, amp, 3)], mode=[int(m) for m in mode],
+                        nu=float(rng.uniform(0.05, 0.45) * rng.choice([-1.0, 1.0])), phase=float(rng.random())))
+    return out
+
+
+def _force_kw(rng, kind, species, window, epoch, envelope=None, scale=1.0, lengths=L):
+    amp = FORCE_ACCEL_AMP if kind == "accel" else FORCE_FIELD_AMP * (1 if species == 0 else 100)
+    kw = dict(kind=kind, species=species, waves=_waves(rng, int(rng.choice([1, 4, 2, 3], p=[0.3, 0.3, 0.2, 0.2])), amp * scale), taper=_tapers(rng, 0.5, 1.5),
+              epoch=epoch, **_window(rng, window, lengths))
+    if envelope is not None:
+        kw["envelope"] = envelope
+    return kw
+
+
+def _gas_kw(rng, what, species, window, tau, K, background, g=GAS_G, lengths=L, taper_min=0.6):
+    kw = dict(species=species, density=gas_density(K, tau, g), tau=tau, sigma=gas_table(g), g_lo=g[0], g_hi=g[1], seed=int(rng.integers(1, 1 << 40)),
+              stream=int(rng.integers(0, 8)), epoch=int(rng.integers(0, 1000)), taper=_tapers(rng, taper_min, 1.0), **background, **_window(rng, window, lengths))
+    if what == "elastic":
+        kw["mass_ratio"] = 2.0 if background is BACKGROUND else 0.05
+    return kw
+
+
+def _gas_side(rng):
+    lo, hi = gas_compact_range()
+    side = int(rng.integers(0, 4))
+    return (lo * 0.9, lo * 1.1, hi * 0.9, hi * 1.1)[side], ("below_lo", "above_lo", "below_hi", "above_hi")[side]
+
+
+def _fusion_kw(rng, tau):
+    return dict(sigma=fusion_table(), g_lo=FUSION_G[0], g_hi=FUSION_G[1], tau=tau, seed=int(rng.integers(1, 1 << 40)), stream=int(rng.integers(0, 8)),
+                epoch=int(rng.integers(0, 1000)))
+
+
+def spectrum_axis(masses, a, b, form):
+    """the axis of a spectrum of species a with b (None: with itself): "cm", or the laboratory energy of the lighter reactant
+    re-emitted ("product": isotropic, "los": along LOS) with a q_value of the size of the reacting energy; the ranges leave yield
+    below and above"""
+    ma, mb = masses[a], masses[a if b is None else b]
+    hk = 0.5 * (ma * mb / (ma + mb)) * C * C
+    if form == "cm":
+        return dict(axis="cm", bins=7, lo=hk * 0.04 ** 2, hi=hk * 0.2 ** 2)
+    m3, m4 = min(ma, mb), max(ma, mb)
+    w = (0.05, 0.2) if b is None else (0.08, 0.25)
+    out = dict(axis="product", bins=16, lo=0.5 * m3 * C * C * w[0] ** 2, hi=0.5 * m3 * C * C * w[1] ** 2, q_value=hk * 0.01, product_mass=m3, other_mass=m4)
+    if form == "los":
+        out["los"] = LOS
+    return out
+
+
+def _registered2(sc, rng, every=None, envelope=(None, None)):
+    """the generation-2 operators of a scene with registered operators, beside collide_every, pair_every and the recorders:
+    two forces on different species (the first with an envelope from sub-step envelope[0] to envelope[1]), a windowed
+    background operator, a yield tally and a spectrum; every: the periods of the last three (drawn from 1 .. 3)"""
+    every = every or [int(x) for x in rng.integers(1, 4, 3)]
+    e0 = int(rng.integers(0, 1000))
+    a = int(rng.integers(2, 4)) if envelope[0] is None else envelope[0]
+    b = a + int(rng.integers(3, 6)) if envelope[1] is None else envelope[1]
+    first = int(rng.integers(0, 2))
+    sc["force_on"] = [
+        _force_kw(rng, "field", first, ("whole", "narrow", "wide")[int(rng.integers(0, 3))], e0, envelope=dict(start=e0 + a, stop=e0 + b, values=[0.3, 1.0, 0.5]), scale=0.3),
+        _force_kw(rng, "accel", 1 - first, ("whole", "wide")[int(rng.integers(0, 2))], int(rng.integers(0, 1000)), scale=0.3)]
+    sc["force_window"] = (a, b)
+    lo, hi = gas_compact_range()
+    what = ("exchange", "elastic")[int(rng.integers(0, 2))]
+    sc["gas_every"] = dict(every=every[0], kind=what,
+                           kw=_gas_kw(rng, what, 0, ("whole", "narrow", "wide")[int(rng.integers(0, 3))], every[0] * sc["dt"], math.sqrt(lo * hi), BACKGROUND))
+    unlike = bool(rng.random() < 0.5)
+    sc["fusion_every"] = dict(every=every[1], a=0, b=1 if unlike else None, kw=_fusion_kw(rng, every[1] * sc["dt"]))
+    unlike = bool(rng.random() < 0.5)
+    form = ("product", "los", "cm")[int(rng.integers(0, 3))]
+    sc["spectrum_every"] = dict(every=every[2], a=0, b=1 if unlike else None, form=form,
+                                kw=dict(_fusion_kw(rng, every[2] * sc["dt"]), **spectrum_axis(sc["masses"], 0, 1 if unlike else None, form)))
+
+
+def scene2(seed):
+    sc = scene(seed)
+    sc["generation"] = 2
+    if sc["registered"]:
+        _registered2(sc, np.random.default_rng([0x5CE92, seed]))
+    return sc
+
+
+def _read2(rng, kind, sc, saved, index):
+    if kind in READ_KINDS:
+        return _read(rng, kind, sc, saved, index)
+    if kind in STATS_KINDS2:
+        return dict(kind=kind, species=0)
+    like = bool(rng.random() < 0.5)
+    a = int(rng.integers(0, 2))
+    b = None if like else 1 - a
+    r = dict(kind=kind, species=a, a=a, b=b, kw=_fusion_kw(rng, sc["dt"]))
+    if kind == "fusionSpectrum":
+        r["form"] = ("product", "los", "cm")[int(rng.integers(0, 3))]
+        r["kw"].update(spectrum_axis(sc["masses"], a, b, r["form"]))
+    return r
+
+
+def _sub_box(rng):
+    lo = [float(x) for x in rng.uniform(0, 0.4, 3) * L]
+    return lo, [float(lo[a] + rng.uniform(0.3, 0.6) * L[a]) for a in range(3)]
+
+
+def _table(rng, least, most, nodes=None):
+    return [float(x) for x in rng.uniform(least, most, int(rng.integers(2, 10)) if nodes is None else nodes)]
+
+
+def _radial(rng, lengths=L, flow=0.01):
+    """a sphere or a cylinder with density, thermal and flow tables; half of them reach across the periodic boundary"""
+    sphere = bool(rng.random() < 0.4)
+    axis = 0 if sphere else int(rng.integers(0, 3))
+    spanned = [a for a in range(3) if sphere or a != axis]
+    r_max = float(rng.uniform(0.5, 0.95) * min(lengths[a] for a in spanned) / 2)
+    center = [float(x) for x in rng.random(3) * lengths]
+    if rng.random() < 0.5:
+        center[spanned[int(rng.integers(0, len(spanned)))]] = float(rng.uniform(0, 0.5) * r_max)
+    out = dict(geometry="sphere" if sphere else "cylinder", center=center, r_max=r_max, axis=axis, density=_table(rng, 0.1, 1.0, 5), thermal=_table(rng, 0.5, 1.5, 4),
+               flow_radial=[float(x) for x in rng.normal(0, flow, 3)])
+    if not sphere:
+        out.update(flow_azimuthal=[float(x) for x in rng.normal(0, flow, 4)], flow_axial=[float(x) for x in rng.normal(0, flow, 2)])
+    return out
+
+
+def radial_is_across(radial, lengths=L):
+    spanned = [a for a in range(3) if radial["geometry"] == "sphere" or a != radial["axis"]]
+    return any(radial["center"][a] - radial["r_max"] < 0 or radial["center"][a] + radial["r_max"] > lengths[a] for a in spanned)
+
+
+def sequence2(seed, nsteps=None):
+    """the steps of a generation-2 seed: 14 to 17 state-changing operations of STATE_KINDS2, the first a substeps, each with
+    READS2 reading calls of READ_KINDS2 and, on a scene with registered operators, every read of STATS_KINDS2.  A force step
+    carries `t`, the sub-steps the handle has behind it (a one-shot force's time is the handle's own count plus its epoch),
+    and `active`: whether its envelope holds then."""
+    sc = scene2(seed)
+    rng = np.random.default_rng([0x0B52, seed])
+    ns = len(sc["counts"])
+    nsteps = int(rng.integers(14, 18)) if nsteps is None else nsteps
+    others = [k for k in STATE_KINDS2 if k != "substeps"]
+    cycle = [others[i] for i in rng.permutation(len(others))]
+    at = t = 0
+    seen = {k: 0 for k in STATE_KINDS2}
+    saved = []
+    last_substeps = -1
+    steps = []
+    for index in range(nsteps):
+        if index == 0 or (steps[-1]["kind"] != "substeps" and rng.random() < 0.6) or (steps[-1]["kind"] == "substeps" and rng.random() < 0.1):
+            kind = "substeps"
+        else:
+            kind = cycle[at % len(cycle)]
+            at += 1
+            if kind == "loadCheckpoint" and not any(s < last_substeps for s in saved):
+                kind = cycle[at % len(cycle)]
+                at += 1
+        st = dict(kind=kind, tag=index + 1, precalc=False)
+        if kind in STATE_KINDS and kind != "substeps" and kind != "loadCheckpoint":
+            st = dict(_step1(rng, sc, kind), tag=index + 1, precalc=False)
+        elif kind == "substeps":
+            st["k"] = int(rng.choice([1, 2, 3, 5]))
+            t += st["k"]
+            last_substeps = index
+        elif kind == "loadCheckpoint":
+            files = [f for f, s in enumerate(saved) if s < last_substeps]
+            st["file"] = files[int(rng.integers(0, len(files)))]
+        elif kind.startswith("force_"):
+            species = int(rng.integers(0, ns))
+            window = "whole" if species == 2 else ("whole", "narrow", "wide")[int(rng.integers(0, 3))]      # (the third species may have one particle)
+            epoch = int(rng.integers(0, 1000))
+            envelope, active = None, True
+            if rng.random() < 0.5:
+                s = epoch + t
+                if rng.random() < 0.7:
+                    envelope = dict(start=max(0, s - int(rng.integers(0, 3))), stop=s + int(rng.integers(1, 4)))
+                else:
+                    active = False
+                    start = s + int(rng.integers(1, 4)) if s < 4 or rng.random() < 0.5 else s - int(rng.integers(2, 5))
+                    envelope = dict(start=start, stop=start + 1 if start < s else start + 3)      # (over before s, or not begun)
+                envelope["values"] = _table(rng, 0.2, 1.2, int(rng.integers(3, 6))) if rng.random() < 0.6 else None
+            st.update(what=kind[len("force_"):], window=window, active=active, t=t, kw=_force_kw(rng, kind[len("force_"):], species, window, epoch, envelope))
+        elif kind.startswith("gas_"):
+            what = kind[len("gas_"):]
+            K, side = _gas_side(rng)
+            low = side.endswith("_lo")             # (few candidates: the first species, and no small window)
+            species = 0 if low else int(rng.integers(0, 2))
+            window = ("whole", "wide")[int(rng.integers(0, 2))] if low else ("whole", "narrow", "wide")[int(rng.integers(0, 3))]
+            st.update(what=what, side=side, window=window, kw=_gas_kw(rng, what, species, window, sc["dt"], K, BACKGROUND, taper_min=0.9 if low else 0.6))
+        elif kind in ("load_profile", "load_radial"):
+            species = int(rng.integers(0, 2))
+            n = sc["counts"][species]
+            first = int(rng.integers(1, n - 1))
+            lo, hi = _sub_box(rng)
+            st.update(species=species, first=first, count=int(rng.integers(1, n - first)), what=("position", "velocity", "both")[int(rng.integers(0, 3))],
+                      seed=int(rng.integers(1, 1 << 40)), stream=int(rng.integers(0, 8)), lo=lo, hi=hi, drift=[float(x) for x in rng.normal(0, 0.01, 3)],
+                      vth=float(rng.uniform(0.01, 0.05)), lattice=bool(rng.random() < 0.5))
+            if kind == "load_profile":
+                axes = rng.permutation(3)[:int(rng.integers(1, 4))]
+                st["density"] = [_table(rng, 0.1, 1.0) if a in axes else None for a in range(3)]
+                st["thermal"] = [_table(rng, 0.5, 1.5) if rng.random() < 0.5 else None for a in range(3)] if rng.random() < 0.6 else None
+                st["shear"] = dict(axis=int(rng.integers(0, 3)), component=int(rng.integers(0, 3)), values=[float(x) for x in rng.normal(0, 0.01, int(rng.integers(2, 8)))]) \
+                    if rng.random() < 0.6 else None
+            else:
+                st["radial"] = _radial(rng)
+        else:
+            raise AssertionError(kind)
+        if kind in POSITION_KINDS2 and st["what"] != "velocity":
+            st["precalc"] = sc["solver"] != "none" or bool(rng.random() < 0.5)
+        off = (seed * 4 + STATE_KINDS2.index(kind) * 5 + seen[kind] * READS2) % len(READ_KINDS2)
+        seen[kind] += 1
+        st["reads"] = [_read2(rng, READ_KINDS2[(off + i) % len(READ_KINDS2)], sc, saved, index) for i in range(READS2)]
+        if sc["registered"]:
+            st["reads"] += [_read2(rng, k, sc, saved, index) for k in STATS_KINDS2]
+        steps.append(st)
+    return steps
+
+
+def _step1(rng, sc, kind):
+    """a step of a generation-1 kind other than substeps and loadCheckpoint, drawn as sequence() draws it"""
+    ns = len(sc["counts"])
+    st = dict(kind=kind)
+    species = int(rng.integers(0, ns))
+    if kind == "set":
+        st.update(species=species, what=("position", "velocity", "both")[int(rng.integers(0, 3))])
+    elif kind in ("setRange", "load"):
+        species = int(rng.integers(0, 2))
+        n = sc["counts"][species]
+        first = int(rng.integers(1, n - 1))
+        st.update(species=species, first=first, count=int(rng.integers(1, n - first)), what=("position", "velocity", "both")[int(rng.integers(0, 3))])
+        if kind == "load":
+            lo, hi = _sub_box(rng)
+            st.update(seed=int(rng.integers(1, 1 << 40)), stream=int(rng.integers(0, 8)), lo=lo, hi=hi, drift=[float(x) for x in rng.normal(0, 0.01, 3)],
+                      vth=float(rng.uniform(0.01, 0.05)), lattice=bool(rng.random() < 0.5), paired=bool(rng.random() < 0.4))
+    elif kind.startswith("collide_"):
+        what = kind[len("collide_"):]
+        kw = dict(species=0, seed=int(rng.integers(1, 1 << 40)), stream=int(rng.integers(0, 8)), epoch=int(rng.integers(0, 1000)), **BACKGROUND)
+        if what == "relax":
+            kw["nu_tau"] = float(rng.uniform(0.1, 0.5))
+        else:
+            kw["nu_tau"], st["side"] = _threshold_rate(rng)
+            if what == "elastic":
+                kw["mass_ratio"] = float(rng.choice([0.5, 2.0]))
+        st.update(what=what, kw=kw)
+    elif kind in ("pair_like", "pair_unlike"):
+        a = int(rng.integers(0, 2))
+        st.update(a=a, b=None if kind == "pair_like" else 1 - a,
+                  kw=dict(log_lambda=LOG_LAMBDA, tau=sc["tau_like"][a] if kind == "pair_like" else sc["tau_unlike"],
+                          seed=int(rng.integers(1, 1 << 40)), stream=int(rng.integers(0, 8)), epoch=int(rng.integers(0, 1000))))
+    elif kind != "sort":
+        raise AssertionError(kind)
+    return st
+
+
+def substeps_of(steps):
+    return sum(st.get("k", 0) for st in steps)
+
+
+def epoch_control():
+    """(seed, step index) of the control of the one-shot force's time: the first active force without an envelope on a handle
+    with sub-steps behind it (a twin given epoch + t + 1 must differ)"""
+    for seed in SEEDS2:
+        for i, st in enumerate(sequence2(seed)):
+            if st["kind"].startswith("force_") and "envelope" not in st["kw"] and st["t"] > 0:
+                return seed, i
+    raise AssertionError("no force step for the control")
+
+
+# ---- the references of the suite on a state: per species dict(frac=, vel=, cell=, ids=) — the stored box fractions and
+# velocities in the caller's order and the deposit's cells.  On the CPU the state is initial_state(); the GPU tests read it
+# from a handle just before the call they check.
+TALLY_KEYS = ("sigma", "g_lo", "g_hi", "tau", "seed", "stream", "epoch")
+
+
+def cell_volume(sc):
+    """as the library forms it"""
+    return (sc["L"][0] / sc["shape"][0]) * (sc["L"][1] / sc["shape"][1]) * (sc["L"][2] / sc["shape"][2])
+
+
+def initial_state(sc):
+    out = []
+    shape = np.array(sc["shape"])
+    for sp, n in enumerate(sc["counts"]):
+        pos, vel = particles(sc["seed"], 1000 + sp, n)
+        frac = pos / np.array(sc["L"])
+        ijk = np.minimum((frac * shape).astype(np.int64), shape - 1)
+        out.append(dict(frac=frac, vel=vel, cell=ijk[:, 0] + shape[0] * (ijk[:, 1] + shape[1] * ijk[:, 2]), ids=np.arange(n)))
+    return out
+
+
+def gas_want(sc, state, what, kw):
+    """gas_reference's counts of a windowed background request on a state"""
+    req = gasref.request(sc["L"], dict(exchange=gasref.EXCHANGE, elastic=gasref.ELASTIC)[what], **{k: v for k, v in kw.items() if k != "species"})
+    s = state[kw["species"]]
+    return gasref.counts(gasref.apply(req, s["ids"], s["frac"], s["vel"]))
+
+
+def fusion_want(sc, state, a, b, kw):
+    """fusion_reference's tally of species a with b (None: with itself), and its request"""
+    import fusion_reference as fref
+    req = fref.request(*[kw[k] for k in TALLY_KEYS[:4]], sc["macro_weight"], cell_volume(sc), seed=kw["seed"], stream=kw["stream"], epoch=kw["epoch"], like=b is None)
+    args = [state[a]["cell"], state[a]["ids"], state[a]["vel"]] + ([] if b is None else [state[b]["cell"], state[b]["ids"], state[b]["vel"]])
+    return req, fref.apply(req, int(np.prod(sc["shape"])), *args)
+
+
+def spectrum_want(sc, state, a, b, kw):
+    """fusion_spectrum_reference's spectrum of the same"""
+    import fusion_spectrum_reference as sref
+    req, tally = fusion_want(sc, state, a, b, kw)
+    axis = sref.request(sc["masses"][a], sc["masses"][a if b is None else b], **{k: v for k, v in kw.items() if k not in TALLY_KEYS})
+    args = [state[a]["cell"], state[a]["ids"], state[a]["vel"]] + ([] if b is None else [state[b]["cell"], state[b]["ids"], state[b]["vel"]])
+    return sref.apply(req, axis, int(np.prod(sc["shape"])), *args, tally=tally)
+
+
+def force_inside(sc, state, kw):
+    """the particles of the request's species inside its window"""
+    lo = np.array(kw.get("lo", (0.0, 0.0, 0.0))) / np.array(sc["L"])
+    hi = np.array(kw.get("hi", sc["L"])) / np.array(sc["L"])
+    p = state[kw["species"]]["frac"]
+    return int(np.all((lo <= p) & (p < hi), axis=1).sum())
+
+
+# ---- the named sequence of the resets: fusionGrid(reset=True) and fusionSpectrumRead(reset=True) zero "behind the copy"
+def resets():
+    """A scene with operators registered (the tally and the spectrum every sub-step, so that no piece is empty); the steps
+    marked `reset` are followed, after their reads, by both reads with reset: directly after a substeps, after a one-shot
+    operation, and after a loadCheckpoint."""
+    sc = scene(RESET_SEED)
+    assert sc["registered"]
+    sc.update(solver="poisson_fft", precision="fp32", sort_interval=2, staged=False, dt=5e-12, name="resets", generation=2)
+    sc["spec"] = dict(sc["spec"], solver="poisson_fft", dt=5e-12)
+    sc["recorders"]["modes"]["fields"] = ["ex", "ey", "ez", "phi", "rho"]
+    rng = np.random.default_rng([0x9E9D, RESET_SEED])
+    _registered2(sc, rng, every=[2, 1, 1])
+    relax = dict(species=0, seed=78, stream=3, epoch=9, nu_tau=0.3, **BACKGROUND)
+    plain_reads = ("moments", "fusionYield", "count", "fusionSpectrum")
+    plan = [
+        (dict(kind="substeps", k=3, reset=True), plain_reads),
+        (dict(kind="substeps", k=2), ("getParticles", "energy", "select", "getCells")),
+        (dict(kind="collide_relax", what="relax", kw=relax, reset=True), plain_reads),
+        (dict(kind="substeps", k=2), ("saveCheckpoint", "moments", "count", "fusionYield")),
+        (dict(kind="substeps", k=3), ("histogram_lds", "series", "modes", "readField")),
+        (dict(kind="loadCheckpoint", file=0, reset=True), plain_reads),
+        (dict(kind="substeps", k=2), ("moments", "fusionSpectrum", "energy", "getRange")),
+    ]
+    steps, saved = [], []
+    for index, (st, kinds) in enumerate(plan):
+        st = dict(dict(tag=index + 1, precalc=False), **st)
+        st["reads"] = [_read2(rng, k, sc, saved, index) for k in kinds + STATS_KINDS2]
+        steps.append(st)
+    return sc, steps
+
+
+RESET_SEED = 301
+NAMED2 = {"resets": resets}
+
+
+# ---- relation 3, generation 2: the six GROUP_CASES with a force and a windowed background operator registered beside the
+# background operator, one-shot forces and windowed collisions of both kinds, a full reload from a density profile and one
+# from a radial body, and the refusal of both fusion calls once
+GROUP_STATE_KINDS2 = ("step", "force_field", "force_accel", "gas_exchange", "gas_elastic", "reload_profile", "reload_radial", "fusion_refused")
+GROUP_KICK_MAX = 0.02          # the thermal speed of GROUP_BACKGROUND: no application may change a velocity by more
+
+
+def group_lengths(index):
+    return tuple(1e-3 * s for s in GROUP_CASES[index]["shape"])
+
+
+def group_dt(index):
+    case = GROUP_CASES[index]
+    return em_dt(case["shape"], group_lengths(index)) if case["em"] else 5e-12
+
+
+def group_case2(index):
+    case = group_case(index)
+    rng = np.random.default_rng([0x64092, index, 1])
+    lengths, dt = group_lengths(index), group_dt(index)
+    e0 = int(rng.integers(0, 1000))
+    case["force_on"] = _force_kw(rng, ("field", "accel")[index % 2], 0, ("wide", "whole", "narrow")[index % 3], e0,
+                                 envelope=dict(start=e0 + 2, stop=e0 + 9, values=[0.3, 1.0, 0.5]), scale=0.1, lengths=lengths)
+    lo, hi = gas_compact_range()
+    every = 1 + (index + 1) % 3
+    what = ("exchange", "elastic")[index % 2]
+    case["gas_every"] = dict(every=every, kind=what, kw=_gas_kw(rng, what, 0, ("whole", "narrow", "wide")[index % 3], every * dt, math.sqrt(lo * hi), GROUP_BACKGROUND,
+                                                                g=GROUP_GAS_G, lengths=lengths))
+    return case
+
+
+def group_sequence2(index):
+    """17 operations on a group and on one handle: frames, and between them each kind of GROUP_STATE_KINDS2 once; two reads after each"""
+    rng = np.random.default_rng([0x64092, index])
+    n = 3000
+    lengths, dt = group_lengths(index), group_dt(index)
+    others = [k for k in GROUP_STATE_KINDS2 if k != "step"]
+    cycle = [others[i] for i in rng.permutation(len(others))]
+    steps, at = [], 0
+    for i in range(17):
+        if i % 2 == 0 or at >= len(cycle):
+            st = dict(kind="step")
+        else:
+            kind = cycle[at]
+            at += 1
+            st = dict(kind=kind)
+            if kind.startswith("force_"):
+                what = kind[len("force_"):]
+                window = ("whole", "narrow", "wide")[int(rng.integers(0, 3))]
+                st.update(what=what, window=window, kw=_force_kw(rng, what, 0, window, int(rng.integers(0, 1000)), scale=0.2, lengths=lengths))
+            elif kind.startswith("gas_"):
+                what = kind[len("gas_"):]
+                K, side = _gas_side(rng)
+                low = side.endswith("_lo")
+                window = "whole" if low else ("whole", "narrow", "wide")[int(rng.integers(0, 3))]
+                st.update(what=what, side=side, window=window, kw=_gas_kw(rng, what, 0, window, dt, K, GROUP_BACKGROUND, g=GROUP_GAS_G, lengths=lengths,
+                                                                          taper_min=0.9 if low else 0.6))
+            elif kind.startswith("reload_"):
+                pop = dict(first=0, count=n, seed=int(rng.integers(1, 1 << 40)), stream=int(rng.integers(0, 8)), drift=(0.0, 0.01, 0.0), vth=0.02,
+                           lattice=bool(rng.random() < 0.5))
+                if kind == "reload_profile":
+                    pop.update(density=[_table(rng, 0.2, 1.0), None, _table(rng, 0.2, 1.0)], thermal=[None, _table(rng, 0.5, 1.2), None],
+                               shear=dict(axis=2, component=0, values=[float(x) for x in rng.normal(0, 0.005, 5)]))
+                else:
+                    pop["radial"] = _radial(rng, lengths, flow=0.005)
+                st["population"] = pop
+        reads = []
+        for j in range(2):
+            kind = GROUP_READ_KINDS[(index + 2 * i + j) % len(GROUP_READ_KINDS)]
+            r = dict(kind=kind)
+            if kind in ("count", "select"):
+                lo = float(rng.uniform(0.0, 0.6))
+                r.update(where={"xyz"[int(rng.integers(0, 3))]: (lo, lo + 0.3), "vz": (None, float(rng.uniform(-0.01, 0.03)))},
+                         every=(3, int(rng.integers(0, 3))) if rng.random() < 0.5 else None)
+            elif kind == "histogram":
+                r.update(axes=("z", "vz"), bins=(24, 32), ranges=((0.0, 1.0), (-0.3, 0.3)))
+            elif kind == "moments":
+                r.update(which="order1")
+            reads.append(r)
+        st["reads"] = reads
+        steps.append(st)
+    return steps
+
+
+def kick_bound(kw, dt, charge=QE, mass=ME):
+    """the largest |dv| (units of c) one application of a force request can give a component: kq sum_k max|amp_k| times the
+    largest taper product and envelope value"""
+    kq = dt / C if kw["kind"] == "accel" else abs(charge) * dt / (mass * C)
+    amp = sum(max(abs(x) for x in w["amp"]) for w in kw["waves"])
+    taper = float(np.prod([1.0 if t is None else max(abs(x) for x in t) for t in kw["taper"]]))
+    env = kw.get("envelope") or {}
+    return kq * amp * taper * (max(abs(x) for x in env["values"]) if env.get("values") else 1.0)
+
+
+# ---- the second resume: all six families registered, the periods dividing RESUME_T, a force envelope across the cut
+RESUME2_EVERY = dict(collide=RESUME_EVERY[0], pair=RESUME_EVERY[1], gas=3, fusion=2, spectrum=1)
+RESUME2_ENVELOPE = (RESUME_T - 2, RESUME_T + 2)
+
+
+def resume_scene2(solver, precision):
+    sc = resume_scene(solver, precision)
+    sc["generation"] = 2
+    _registered2(sc, np.random.default_rng([0x5CE92, 1000]), every=[RESUME2_EVERY["gas"], RESUME2_EVERY["fusion"], RESUME2_EVERY["spectrum"]], envelope=RESUME2_ENVELOPE)
+    return sc
