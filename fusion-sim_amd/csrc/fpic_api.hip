@@ -217,6 +217,21 @@ int record_spill(fpic_handle* h)
     return FPIC_OK;
 }
 
+// The lookahead, in sub-steps, that the censuses count with from the re-binning launch being issued on (bin_slot in
+// fpic_push.hpp; spec.bin_lookahead).  Adaptive: half the sub-steps pushed on the bins now being left, plus this launch's
+// own: it files the states it loads and pushes them on the old bins, so if the coming period is as long as the last, the new
+// bins serve sub-steps nsub .. since + nsub after the filed state, and the particles then stray as far behind their bins
+// as ahead of them.  (profiles/rz_rebin_lookahead.txt: at a period of four launches of two sub-steps, 5 and 6 beat 4)
+constexpr int kMaxLookahead = 64;
+int next_lookahead(const fpic_handle* h, int nsub)
+{
+    if (h->lookahead_mode < 0) return 0;
+    if (h->lookahead_mode > 0) return h->lookahead_mode;
+    if (h->spec.sort_interval > 0) return 0;
+    const unsigned long long half = h->substeps_since_bin / 2 + static_cast<unsigned long long>(nsub);
+    return half < static_cast<unsigned long long>(kMaxLookahead) ? static_cast<int>(half) : kMaxLookahead;
+}
+
 template <typename T>
 int launch_push(fpic_handle* h, int nsub)
 {
@@ -244,6 +259,11 @@ int launch_push(fpic_handle* h, int nsub)
     const bool fuse = h->binned && h->spec.unfused_deposit != 1;
     const bool sums = fuse && sizeof(T) == 4 && h->spec.unfused_deposit == 0 && h->spec.shape == FPIC_SHAPE_REF11; // the fused sums are the sprite's
     const bool scatter = fuse && h->scatter_pending;
+    // the tables this re-binning launch fills were laid out from a census keyed with h->lookahead: it classifies what it
+    // loads with that value, and counts what it leaves (as every launch up to the next re-binning will) with the next one
+    a.look_load = static_cast<T>(h->lookahead) * a.step_factor;
+    if (scatter) h->lookahead = next_lookahead(h, nsub);
+    a.look_census = static_cast<T>(h->lookahead) * a.step_factor;
     TileArgs<T> t{};
     t.ntx = h->ntx; t.ntz = h->ntz; t.ntiles = h->ntiles;
     t.work = h->work2[h->wl]; t.nwork = h->nwork2[h->wl];
@@ -298,6 +318,7 @@ int launch_push(fpic_handle* h, int nsub)
         else push_kernel<T, false><<<blocks_for(lanes), 256, 0, h->stream>>>(a);
     }
     h->t_substep += static_cast<unsigned long long>(nsub);
+    h->substeps_since_bin = (scatter ? 0ull : h->substeps_since_bin) + static_cast<unsigned long long>(nsub); // (a re-binning launch files what it loads)
     timing_end(h);
     HIP_TRY(h, hipGetLastError());
     if (fuse) {
@@ -370,6 +391,10 @@ int launch_bin(fpic_handle* h)
     h->scatter_pending = false;
     h->binned = true;
     h->deposits_since_bin = 0;
+    // bin_count_kernel and the scatter key on the position.  A fixed lookahead holds from the first census on (the first
+    // re-binning launch already files by it); the adaptive one has no period to go by yet
+    h->lookahead = h->lookahead_mode > 0 ? h->lookahead_mode : 0;
+    h->substeps_since_bin = 0;
     h->last_spill = 0;
     h->spill_pending[0] = h->spill_pending[1] = false; // counts taken before this binning say nothing now
     h->sort_passes++;
@@ -874,6 +899,8 @@ int fpic_create(const fpic_spec* spec, fpic_handle** out)
     h->outbox_cap = h->n / 2;
     if (const char* v = std::getenv("FPIC_TEST_OUTBOX_RECORDS")) h->outbox_cap = static_cast<size_t>(std::strtoull(v, nullptr, 10));
     h->test_count_pass = std::getenv("FPIC_TEST_COUNT_PASS") != nullptr;
+    h->lookahead_mode = spec->bin_lookahead;
+    if (const char* v = std::getenv("FPIC_BIN_LOOKAHEAD")) h->lookahead_mode = static_cast<int>(std::strtol(v, nullptr, 10));
     int rc = FPIC_OK;
     if (h->n >= 0xFFFFFFFFull - 4096) rc = fail(nullptr, FPIC_ERR_INVALID_ARG, ".nparticles <- at most 2^32 particles per device");
     else if (spec->geometry == FPIC_GEOM_CYL_RZ && h->ntiles > static_cast<uint32_t>(kMaxTiles)) rc = fail(nullptr, FPIC_ERR_INVALID_ARG, ".nr <- grid of %d x %d cells exceeds %d tiles of %d^2 cells", h->nr, h->nz, kMaxTiles, kTileSide);
@@ -974,6 +1001,11 @@ int fpic_set_particles(fpic_handle* h, const void* pos_aos, const void* vel_aos,
     }
     if (pos_aos) { // positions changed under the bins
         h->binned = false;
+        h->census_fresh = h->chunk_census_fresh = h->scatter_pending = false;
+        h->lookahead = 0;
+    } else if (vel_aos && h->lookahead) {
+        // velocities changed under a census keyed along them: a re-binning launch would file the states it loads in other
+        // bins than the ranges were reserved for.  The next re-binning is a first binning again (position key).
         h->census_fresh = h->chunk_census_fresh = h->scatter_pending = false;
     }
     if (pos_aos || vel_aos) h->sums_fresh = false;
@@ -1118,6 +1150,9 @@ int fpic_deposit(fpic_handle* h)
             }
             // the count roughly doubles per frame: 0.4 % two frames ago is about 2 % now
             rebin = h->last_spill * 256 > h->n;
+            // with a lookahead the particles start a period that far BEHIND their bins and close in: the count is then as
+            // high as at the period's end, and falling.  It says nothing until they have passed their bins
+            if (h->lookahead > 0 && h->substeps_since_bin <= static_cast<unsigned long long>(h->lookahead)) rebin = false;
         }
     }
     if (rebin) {
@@ -1324,6 +1359,7 @@ int fpic_load_checkpoint(fpic_handle* h, const char* path)
     h->sums_fresh = h->census_fresh = h->chunk_census_fresh = h->scatter_pending = false;
     h->spill_pending[0] = h->spill_pending[1] = false;
     h->last_spill = 0;
+    h->lookahead = 0;
     iota_kernel<<<blocks_for(h->n), 256, 0, h->stream>>>(h->id[h->cur], h->n);
     HIP_TRY(h, hipGetLastError());
     const int rc = h->prec == FPIC_F32 ? load_state<float>(h, fc.f) : load_state<double>(h, fc.f);

@@ -90,6 +90,13 @@ struct fpic_handle {
     bool test_count_pass = false;      // FPIC_TEST_COUNT_PASS: the re-binning launch counts its items itself (tests)
     bool binned = false;
     int deposits_since_bin = 0;
+    // The bins' lookahead (fpic_push.hpp, bin_slot) in whole sub-steps: what the census of every fused push since the last
+    // binning was keyed with, hence what the next re-binning launch must classify the states it loads with.  It changes
+    // only as a re-binning launch is issued (that launch loads with the old value and counts with the new one).  After a
+    // first binning (fpic_sort keys on the position) it is 0 in adaptive mode and the fixed value otherwise.
+    int lookahead = 0;
+    int lookahead_mode = 0;       // spec.bin_lookahead (FPIC_BIN_LOOKAHEAD overrides: measurements)
+    unsigned long long substeps_since_bin = 0; // pushed on the live bins, the re-binning launch's own included
     unsigned long long t_substep = 0; // counter-based RNG mode: global index of the next sub-step
     bool sums_fresh = false;      // cell_sums already holds the sums of the current particle state (fused push)
     bool census_fresh = false;    // tile_count holds the census of the current particle state (fused push)

@@ -45,6 +45,9 @@ struct PushArgs {
     uint32_t seed_lo, seed_hi;
     unsigned long long t0; // global index of this launch's first sub-step
     int raster_bits;       // spec.raster_subpixel_bits: 0 = ideal point sprites, b = drawn as a rasteriser with b sub-pixel bits does
+    // the bins' lookahead (bin_slot): a state is filed in the tile of position + look * velocity.  look_load keys the states a
+    // re-binning launch LOADS (what the census it is laid out from used), look_census the final states of this launch
+    T look_load, look_census;
 };
 
 // Philox4x32-10 (Salmon et al., SC'11; Random123 constants).  Extension mode only:
@@ -306,6 +309,31 @@ struct TileNeighbourhood {
     }
 };
 
+// The bin a state is filed in: the LDS slot (TileNeighbourhood::slot) and the global bin `key`.  look == 0: the tile of the
+// state's own sprite cell.  look != 0: the tile of where the state will be `look` (seconds' worth of step_factor) later on a
+// straight line, x + look * v, clamped into the unit square (else everything bound for the wall would share the clipped
+// bin and run the global path for a whole period); a state that IS outside the unit square, or NaN, goes to the clipped bin
+// as before.  Between two binnings the displacement from the bin then runs from -look to period - look instead of from 0
+// to period.  The bins decide where a particle is stored and which windows serve it, never a result.  All three sites
+// that classify a state (the census of final states, the re-binning launch's count pass and its pass B) call this one
+// function: the ranges reserved from the census hold exactly what pass B files.
+template <typename T>
+__device__ __forceinline__ int bin_slot(const Particle<T>& q, T look, const TileNeighbourhood& nb, int nr, int nz, uint32_t& key)
+{
+    int ic = 0, jc = 0;
+    const bool visible = sprite_cell(q, nr, nz, ic, jc);
+    if (look != static_cast<T>(0) && visible) { // (uniform over the launch)
+        const T px = q.x + look * q.vx, py = q.y + look * q.vy, pz = q.z + look * q.vz;
+        const T pr = sqrt_(px * px + py * py);
+        // (written so that NaN, from an infinite velocity, lands on 0)
+        const T cr = pr >= static_cast<T>(0) ? (pr <= static_cast<T>(1) ? pr : static_cast<T>(1)) : static_cast<T>(0);
+        const T cz = pz >= static_cast<T>(0) ? (pz <= static_cast<T>(1) ? pz : static_cast<T>(1)) : static_cast<T>(0);
+        ic = static_cast<int>(cr * static_cast<T>(nr));
+        jc = static_cast<int>(cz * static_cast<T>(nz));
+    }
+    return nb.slot(visible, ic, jc, key);
+}
+
 // What happens to a particle's final state besides being stored.  NoSums: nothing.
 // WindowSums: the scatter's stage 1 (programMoments01's vertex colour summed per
 // nearest cell, see fpic_kernels.hpp) fused into the push: the workgroup owns the
@@ -329,12 +357,13 @@ struct WindowSums {
     unsigned* spilled;           // lane-local count of particles outside the window
     unsigned* own_census;        // lane-local count of final states in the workgroup's own tile
     int raster_bits;             // 0: ideal sprites; b: the sprite's cell as a rasteriser with b sub-pixel bits places it
+    T look;                      // the census's lookahead (PushArgs::look_census)
     __device__ __forceinline__ void add(const Particle<T>& q, int nr, int nz) const
     {
         int ic = 0, jc = 0;
-        bool visible = sprite_cell(q, nr, nz, ic, jc);   // the bins always follow the ideal cell
+        bool visible = sprite_cell(q, nr, nz, ic, jc);   // the sums' cell; the bins follow the ideal cell of bin_slot's position
         uint32_t key;
-        const int s = nb.slot(visible, ic, jc, key);
+        const int s = bin_slot(q, look, nb, nr, nz, key);
         // nearly every particle is still in the workgroup's own tile: those are counted in a register (64 lanes
         // adding to ONE LDS word are serialised), the others by LDS atomics
         if (s == kOwnSlot) ++*own_census;
@@ -488,8 +517,9 @@ __global__ __launch_bounds__(256) void push_kernel(PushArgs<T> a)
 // global float atomics in 256-byte pieces after the chunk.
 //
 // SCATTER (needs FUSE) makes this launch the re-binning as well.  The bin of a
-// particle is the tile of the state it is LOADED with — exactly what the previous
-// launch's census counted, from which the host has laid out dst_tile_start.  The
+// particle is bin_slot of the state it is LOADED with (its tile, or with a lookahead the
+// tile it is heading for) — exactly what the previous launch's census counted with the
+// same lookahead, from which the host has laid out dst_tile_start.  The
 // workgroup first counts its chunk per bin, reserves one range per bin, then pushes
 // and stores each final state at range + rank of arrival in the other particle set.
 // With float state the leavers (particles bound for another bin of the neighbourhood than
@@ -591,7 +621,7 @@ __global__ __launch_bounds__(push_threads<CTR>()) void push_tiles_kernel(PushArg
             Particle<T> q[PPT];
             load_state<T, CTR>(a, base, cnt, q);
             if constexpr (FUSE)
-                advance_state<T, CTR>(a, tab, WindowSums<T, SUMS>{ lsums, lcensus, ti0 - kTileHalo, tj0 - kTileHalo, nb, t.cell_sums, t.tile_count, &my_spill, &my_own, a.raster_bits }, cnt, q);
+                advance_state<T, CTR>(a, tab, WindowSums<T, SUMS>{ lsums, lcensus, ti0 - kTileHalo, tj0 - kTileHalo, nb, t.cell_sums, t.tile_count, &my_spill, &my_own, a.raster_bits, a.look_census }, cnt, q);
             else
                 advance_state<T, CTR>(a, tab, NoSums{}, cnt, q);
             store_state<T, CTR>(a, base, cnt, q);
@@ -609,20 +639,24 @@ __global__ __launch_bounds__(push_threads<CTR>()) void push_tiles_kernel(PushArg
         for (size_t g = g_begin + threadIdx.x; g < g_end; g += kPushThreads) {
             const size_t base = g * PPT;
             const int cnt = (base + PPT <= a.n) ? PPT : static_cast<int>(a.n - base);
-            T px[PPT], py[PPT], pz[PPT];
+            T px[PPT], py[PPT], pz[PPT], pvx[PPT] = {}, pvy[PPT] = {}, pvz[PPT] = {};
             load_lane<T, PPT>(a.slab + 0 * a.stride, base, px);
             load_lane<T, PPT>(a.slab + 1 * a.stride, base, py);
             load_lane<T, PPT>(a.slab + 2 * a.stride, base, pz);
+            if (a.look_load != static_cast<T>(0)) { // (uniform) the key looks ahead along the velocity
+                load_lane<T, PPT>(a.slab + 3 * a.stride, base, pvx);
+                load_lane<T, PPT>(a.slab + 4 * a.stride, base, pvy);
+                load_lane<T, PPT>(a.slab + 5 * a.stride, base, pvz);
+            }
 #pragma unroll
             for (int k = 0; k < PPT; ++k) {
                 if (k < cnt) {
                     Particle<T> p;
                     p.x = px[k]; p.y = py[k]; p.z = pz[k];
+                    p.vx = pvx[k]; p.vy = pvy[k]; p.vz = pvz[k];
                     p.r = sqrt_(p.x * p.x + p.y * p.y);
-                    int ic = 0, jc = 0;
-                    const bool visible = sprite_cell(p, a.nr, a.nz, ic, jc);
                     uint32_t key;
-                    const int sl = nb.slot(visible, ic, jc, key);
+                    const int sl = bin_slot(p, a.look_load, nb, a.nr, a.nz, key);
                     if (sl == kOwnSlot) ++own_count;
                     else if (sl >= 0) __hip_atomic_fetch_add(lrank + sl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
                 }
@@ -687,10 +721,8 @@ __global__ __launch_bounds__(push_threads<CTR>()) void push_tiles_kernel(PushArg
                 dest[k] = 0; pid[k] = 0; slot_of[k] = -2;
                 if (k < cnt) {
                     pid[k] = t.id[base + k];
-                    int ic = 0, jc = 0;
-                    const bool visible = sprite_cell(q[k], a.nr, a.nz, ic, jc);
                     uint32_t key;
-                    const int sl = nb.slot(visible, ic, jc, key);
+                    const int sl = bin_slot(q[k], a.look_load, nb, a.nr, a.nz, key);
                     slot_of[k] = sl;
                     if (sl >= 0 && sl != kOwnSlot) { if (!box_len) dest[k] = lrange[sl] + __hip_atomic_fetch_add(lrank + sl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
                     else if (sl < 0) dest[k] = t.dst_tile_start[key] + atomicAdd(t.dst_tile_cursor + key, 1u); // beyond the 5x5 tiles: rare
@@ -709,7 +741,7 @@ __global__ __launch_bounds__(push_threads<CTR>()) void push_tiles_kernel(PushArg
                     if (leaves) dest[k] = i;
                 }
             }
-            advance_state<T, CTR>(a, tab, WindowSums<T, SUMS>{ lsums, lcensus, ti0 - kTileHalo, tj0 - kTileHalo, nb, t.cell_sums, t.tile_count, &my_spill, &my_own, a.raster_bits }, cnt, q);
+            advance_state<T, CTR>(a, tab, WindowSums<T, SUMS>{ lsums, lcensus, ti0 - kTileHalo, tj0 - kTileHalo, nb, t.cell_sums, t.tile_count, &my_spill, &my_own, a.raster_bits, a.look_census }, cnt, q);
 #pragma unroll
             for (int k = 0; k < PPT; ++k) {
                 const bool leaves = k < cnt && slot_of[k] >= 0 && slot_of[k] != kOwnSlot;

@@ -71,7 +71,7 @@ class Spec(ctypes.Structure):
         ("unfused_deposit", ctypes.c_int32), ("rng_mode", ctypes.c_int32), ("rng_seed_lo", ctypes.c_uint32),
         ("rng_seed_hi", ctypes.c_uint32), ("geometry", ctypes.c_int32), ("solver", ctypes.c_int32), ("ny", ctypes.c_int32),
         ("shape", ctypes.c_int32), ("length_y", ctypes.c_double), ("macro_weight", ctypes.c_double),
-        ("raster_subpixel_bits", ctypes.c_int32), ("reserved_i32", ctypes.c_int32), ("reserved", ctypes.c_double * 5),
+        ("raster_subpixel_bits", ctypes.c_int32), ("bin_lookahead", ctypes.c_int32), ("reserved", ctypes.c_double * 5),
     ]
 
 
@@ -1323,7 +1323,7 @@ class CylindricalParticlePusher:
     """Object returned by makeCylindricalParticlePusher (empic.js:1528)."""
 
     def __init__(self, spec, precision="fp32", device=0, count=0, compat=True, sort_interval=0, fuse_deposit=True,
-                 rng="reference", seed=0, library=None, shape="ref11", raster_subpixel_bits=0):
+                 rng="reference", seed=0, library=None, shape="ref11", raster_subpixel_bits=0, bin_lookahead=0):
         _validate_spec(spec)
         self._lib = library or load_library()
         self.spec = dict(spec)
@@ -1343,6 +1343,8 @@ class CylindricalParticlePusher:
         # density()'s point sprites as a rasteriser with that many sub-pixel bits draws them (0 / absent: ideal sprites)
         s.raster_subpixel_bits = int(spec.get("raster_subpixel_bits", raster_subpixel_bits))
         s.rng_seed_lo, s.rng_seed_hi = int(seed) & 0xFFFFFFFF, (int(seed) >> 32) & 0xFFFFFFFF
+        # sub-steps the re-binning looks ahead along the velocity (0: adaptive with sort_interval=0, else none; -1: off; k: fixed)
+        s.bin_lookahead = int(bin_lookahead)
         self.precision = s.precision
         self.nr, self.nz = int(spec["nr"]), int(spec["nz"])
         self.n = int(count) if count else int(spec["nparticles"]) ** 2

@@ -183,7 +183,15 @@ typedef struct fpic_spec {
                                usually have 8.  Only the cell a particle's 11x11 stamp is centred on changes (one cell
                                lower for a coordinate within 2^-(b+1) pixel above a pixel edge).  Carved out of the
                                former reserved[6]: same size and offsets, ABI unchanged */
-    int32_t reserved_i32;
+    int32_t bin_lookahead;  /* (r,z) push: the re-binning files a particle in the tile of position + k sub-steps of its
+                               velocity instead of the tile it is in, so that over a binning period it drifts from -k to
+                               period - k sub-steps away from its bin instead of from 0 to the period.  Speed only:
+                               no result depends on the bins.
+                               0: default — adaptive (half the last period plus one launch, at most 64 sub-steps) when
+                               sort_interval == 0, none when sort_interval > 0;  -1: off in every mode;  k > 0: k sub-steps
+                               in every mode.
+                               The first binning and fpic_sort always key on the position.  Carved out of the former
+                               reserved_i32: same size and offsets, ABI unchanged */
     double reserved[5];
 } fpic_spec;
 
