@@ -30,6 +30,7 @@
 //   fes_pair.inc.hpp        binary Coulomb collisions between the species (Takizuka-Abe): the cell index of a request, the pairing pass
 //   fes_fusion.inc.hpp      fusion yield tallies between the species: fes_pair's cell index, the tally pass, the cell grids
 //   fes_fusion_spectrum.inc.hpp   fusion product spectra: the tally's pairs and yields binned over an energy axis
+//   fes_remove.inc.hpp      absorbing particle sinks: the mark, scan and move passes of one request, the state a removal leaves, renumbering
 //   fes_mom.inc.hpp         the fluid moment grids: the sweeps of one request, the held planes' places, the ranks' sum
 //   fes_series.inc.hpp      the series: rows of field points and tracer particles, now or into a ring, the ranks' selection
 //   fes_modes.inc.hpp       the modes: Fourier amplitudes of the node fields at chosen wave vectors, now or into a ring, the ranks' sum
@@ -46,6 +47,7 @@
 #include "fes_pair_kernels.hpp"
 #include "fes_fusion_kernels.hpp"
 #include "fes_fusion_spectrum_kernels.hpp"
+#include "fes_remove_kernels.hpp"
 #include "fes_mom_kernels.hpp"
 #include "fes_series_kernels.hpp"
 #include "fes_modes_kernels.hpp"
@@ -79,7 +81,8 @@ uint64_t last_spill(const fpic_handle* h) { return h->es->last_spill; }
 bool is_decomposed(const fpic_handle* h) { return h->es && h->es->dom != nullptr; }
 uint64_t species_count(const fpic_handle* h, int species)
 {
-    return species >= 0 && species < static_cast<int>(h->es->sp.size()) ? h->es->sp[species].n : ~0ull;
+    // (a thinned species has no caller's order to hold a count against: the call it is asked for refuses by name)
+    return species >= 0 && species < static_cast<int>(h->es->sp.size()) && !h->es->sp[species].thinned ? h->es->sp[species].n : ~0ull;
 }
 
 int create(fpic_handle* h)
@@ -190,6 +193,7 @@ int set_particles(fpic_handle* h, int species, const void* pos_aos, const void* 
 {
     if (int rc = check_species(h, species)) return rc;
     Species& s = h->es->sp[species];
+    if (int rc = refuse_thinned(h, s, "fpic_set_particles")) return rc;
     if (first > s.n || n > s.n - first)
         return fail(h, FPIC_ERR_INVALID_ARG, ".position <- particles [%llu, %llu) do not lie within the species' %zu", static_cast<unsigned long long>(first),
                     static_cast<unsigned long long>(first + n), s.n);
@@ -229,6 +233,7 @@ int get_particles(fpic_handle* h, int species, void* pos_aos, void* vel_aos, int
     if (h->es->dom) return fail(h, FPIC_ERR_STATE, "a decomposed handle holds a changing subset of the particles: read it with fpic_domain_get_particles");
     if (int rc = check_species(h, species)) return rc;
     const Species& s = h->es->sp[species];
+    if (int rc = refuse_thinned(h, s, "fpic_get_particles")) return rc;
     if (dtype != FPIC_F32 && dtype != FPIC_F64) return fail(h, FPIC_ERR_INVALID_ARG, ".dtype <- must be 0 (f32) or 1 (f64)");
     if (int rc = check_range(h, s, from, n, stride)) return rc;
     int rc = FPIC_OK;
@@ -250,6 +255,7 @@ int get_cells(fpic_handle* h, int species, int32_t* cells, uint64_t from, uint64
     if (int rc = check_species(h, species)) return rc;
     if (!cells) return fail(h, FPIC_ERR_INVALID_ARG, ".cells <- Non-optional property is undefined!");
     const Species& s = h->es->sp[species];
+    if (int rc = refuse_thinned(h, s, "fpic_get_cells")) return rc;
     if (int rc = check_range(h, s, from, n, stride)) return rc;
     if (!s.n || !n) return FPIC_OK;
     return h->prec == FPIC_F32 ? download_cells<float>(h, s, cells, from, n, stride) : download_cells<double>(h, s, cells, from, n, stride);
@@ -369,6 +375,7 @@ namespace {
 #include "fes_pair.inc.hpp"
 #include "fes_fusion.inc.hpp"
 #include "fes_fusion_spectrum.inc.hpp"
+#include "fes_remove.inc.hpp"
 #include "fes_mom.inc.hpp"
 #include "fes_series.inc.hpp"
 #include "fes_modes.inc.hpp"
@@ -396,6 +403,10 @@ static int diag_after_substep(fpic_handle* h)
         if (int rc = fusion_after_substep(h, g.substep)) return rc;
     if (!g.fspec_ops.empty())
         if (int rc = fspec_after_substep(h, g.substep)) return rc;
+    // the particle sinks (fes_remove.inc.hpp): the tallies above saw the particles that leave now, the rows below see the
+    // thinned box.  Each due application waits for one 8-byte count: the host has to learn the new n
+    if (!g.remove_ops.empty())
+        if (int rc = remove_after_substep(h, g.substep)) return rc;
     const bool f32 = h->prec == FPIC_F32;
     for (int k = 0; k < kRecorders; ++k) {
         void* row = rec_due(g.rec[k], g.substep);
@@ -533,6 +544,8 @@ int domain_init(fpic_handle* h, int rank, int world, int ghost_planes, int migra
 {
     State* st = h->es;
     if (st->dom) return fail(h, FPIC_ERR_STATE, "the handle is already decomposed");
+    for (const Species& s : st->sp)
+        if (int rc = refuse_thinned(h, s, "fpic_domain_init")) return rc;
     if (int rc0 = em_close_any(h)) return rc0;
     if (world < 1 || rank < 0 || rank >= world) return fail(h, FPIC_ERR_INVALID_ARG, ".rank <- %d is outside a world of %d", rank, world);
     if (st->nz % world) return fail(h, FPIC_ERR_INVALID_ARG, ".world <- the %d planes along z do not divide into %d slabs", st->nz, world);

@@ -58,6 +58,12 @@ int gas(fpic_handle* h, const fpic_gas_spec* spec, fpic_gas_result* out);
 int gas_register(fpic_handle* h, const fpic_gas_spec* spec, int every, int* index);
 int gas_stats(fpic_handle* h, int index, int scope, fpic_gas_result* out);
 int gas_clear(fpic_handle* h);
+// absorbing particle sinks and the renumbering of a thinned species (fes_remove.inc.hpp)
+int remove(fpic_handle* h, const fpic_remove_spec* spec, fpic_remove_result* out);
+int remove_register(fpic_handle* h, const fpic_remove_spec* spec, int every, int* index);
+int remove_stats(fpic_handle* h, int index, int scope, fpic_remove_result* out);
+int remove_clear(fpic_handle* h);
+int renumber(fpic_handle* h, int species, uint64_t* n);
 // binary Coulomb collisions between the species of the box (fes_pair.inc.hpp)
 int pair(fpic_handle* h, const fpic_pair_spec* spec, fpic_pair_result* out);
 int pair_register(fpic_handle* h, const fpic_pair_spec* spec, int every, int* index);

@@ -252,6 +252,8 @@ int load_rank_checkpoint(fpic_handle* h, const char* path)
 int save_checkpoint(fpic_handle* h, const char* path)
 {
     State* st = h->es;
+    for (const Species& s : st->sp)   // (the file holds the particles in the caller's order; a thinned species has none)
+        if (int rc = refuse_thinned(h, s, "fpic_save_checkpoint")) return rc;
     if (int rc = em_close_any(h)) return rc;    // (the file holds B of the integer time; a rank forms it from what it holds)
     if (st->dom) return save_rank_checkpoint(h, path);
     HIP_TRY(h, hipStreamSynchronize(h->stream));

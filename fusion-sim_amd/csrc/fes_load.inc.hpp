@@ -169,6 +169,7 @@ int load_profile(fpic_handle* h, const fpic_load_spec* spec, const struct fpic_l
     if (profile)
         if (const char* why = fesload::check_profile(*profile)) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
     Species& s = st->sp[spec->species];
+    if (int rc0 = refuse_thinned(h, s, "fpic_load")) return rc0;
     const fesload::Rule r = fesload::rule_of(*spec, have, L);
     uint64_t done = 0;
     int rc;
@@ -196,6 +197,7 @@ int load_radial(fpic_handle* h, const fpic_load_spec* spec, const struct fpic_lo
     if (const char* why = fesload::check(*spec, nsp, have, L, decomposed)) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
     if (const char* why = fesload::check_radial(*radial, L)) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
     Species& s = st->sp[spec->species];
+    if (int rc0 = refuse_thinned(h, s, "fpic_load_radial")) return rc0;
     const fesload::Rule r = fesload::rule_of(*spec, have, L);
     fesload::Radial q;
     if (int rc0 = load_tables(h, *radial, L, &q)) return rc0;

@@ -28,7 +28,7 @@ static int series_upload(fpic_handle* h, const fpic_series_spec& spec, SeriesReq
 {
     State* st = h->es;
     std::vector<uint64_t> counts;
-    for (const Species& sp : st->sp) counts.push_back(sp.n);
+    for (const Species& sp : st->sp) counts.push_back(id_span_of(sp));   // (a thinned species keeps ids up to its span)
     if (const char* why = fesser::check(spec, static_cast<int>(st->sp.size()), st->dom ? nullptr : counts.data())) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
     if (spec.npoints) {
         if (!st->fields_ready) return fail(h, FPIC_ERR_STATE, "series of points before precalc(): the fields of the current particle positions have not been computed");

@@ -33,7 +33,12 @@ struct Species {
     size_t chunk_census_items = 0;     // work items the census has room for
     uint64_t layout = 0;               // counts the changes of the live bin table (what a joint work list is built from)
     void* em_args = nullptr;           // EmPushArgs of the last full-EM launch, resident for the kernel's out-of-line paths
+    // fpic_remove (fes_remove.inc.hpp) has taken particles out: the ids are no longer 0 .. n - 1 but lie below id_span (one past
+    // the largest id the species was ever given; it does not shrink).  The caller-order calls are refused until fpic_renumber
+    bool thinned = false;
+    uint64_t id_span = 0;              // read through id_span_of(): n while the species is not thinned
 };
+inline uint64_t id_span_of(const Species& s) { return s.thinned ? s.id_span : s.n; }
 
 // the series diagnostic (fes_series.inc.hpp): a request's copies on the device — one allocation holding the points' normalised
 // coordinates (T [npoints][3]) and, per species that has tracers, the sorted ids, their entries and the bitmap filter
@@ -101,6 +106,14 @@ struct GasOp {
     const double* dev_sigma;
     const double* taper[3];
     uint64_t applications;
+};
+
+// a registered particle sink (fes_remove.inc.hpp): the request, its period in sub-steps, the applications and the live
+// particles they scanned so far (the other totals are a row on the device)
+struct RemoveOp {
+    fpic_remove_spec spec;
+    int every;
+    uint64_t applications, scanned;
 };
 
 // a registered binary collision operator (fes_pair.inc.hpp): the request, its period in sub-steps, the applications so far
@@ -179,6 +192,10 @@ struct Diag {
     double* fspec_table = nullptr;
     unsigned long long* fspec_words = nullptr;
     std::vector<FspecOp> fspec_ops;     // the registered spectra, in registration order
+    // fpic_remove (fes_remove.inc.hpp): rows of kDiagWords words - the totals of each registered operator, one more for the last
+    // application, one whose first word is the mark pass's counter, then the move pass's partial rows (kRemoveBlocks of them)
+    unsigned long long* remove = nullptr;
+    std::vector<RemoveOp> remove_ops;   // the registered sinks, in registration order
 };
 inline void diag_release(Diag& g)
 {
@@ -187,7 +204,7 @@ inline void diag_release(Diag& g)
     for (void* p : { g.series_req.block, g.modes_req.block, static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom), g.sel, static_cast<void*>(g.load_tab), static_cast<void*>(g.coll), static_cast<void*>(g.force), static_cast<void*>(g.gas), static_cast<void*>(g.pair),
                      static_cast<void*>(g.pair_seg[0]), static_cast<void*>(g.pair_seg[1]), static_cast<void*>(g.pair_index[0]), static_cast<void*>(g.pair_index[1]),
                      static_cast<void*>(g.fusion), static_cast<void*>(g.fusion_table),
-                     static_cast<void*>(g.fspec), static_cast<void*>(g.fspec_table), static_cast<void*>(g.fspec_words) })
+                     static_cast<void*>(g.fspec), static_cast<void*>(g.fspec_table), static_cast<void*>(g.fspec_words), static_cast<void*>(g.remove) })
         if (p) (void)hipFree(p);
     for (unsigned long long* p : g.fusion_grid)
         if (p) (void)hipFree(p);
@@ -243,6 +260,15 @@ struct State {
     struct Domain* dom = nullptr; // z-slab decomposition over several GPUs (fpic_domain_init)
     Diag diag;
 };
+
+// the refusal of a call that addresses particles in the caller's order (get / set particles and cells, the loaders, the
+// checkpoint, the decomposition) on a species fpic_remove has thinned: those paths scatter by id into arrays of n entries
+inline int refuse_thinned(fpic_handle* h, const Species& s, const char* name)
+{
+    if (!s.thinned) return FPIC_OK;
+    return fail(h, FPIC_ERR_STATE, "%s addresses particles in the caller's order, and species %d has lost particles to fpic_remove: its %zu ids are no longer 0 .. n-1 (they lie below %llu); read it with fpic_select, or call fpic_renumber first",
+                name, static_cast<int>(&s - h->es->sp.data()), s.n, static_cast<unsigned long long>(s.id_span));
+}
 
 // Spatial decomposition: rank r of `world` owns the particles whose cell lies in the
 // planes [z0, z0 + nzl) and G ghost planes on either side, in which its particles may still sit and deposit

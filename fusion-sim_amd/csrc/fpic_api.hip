@@ -980,7 +980,7 @@ int fpic_set_particles(fpic_handle* h, const void* pos_aos, const void* vel_aos,
 {
     CHECK_HANDLE(h);
     if (h->es) {
-        if (n != h->n) return fail(h, FPIC_ERR_INVALID_ARG, ".position <- expected %zu particles, got %llu", h->n, static_cast<unsigned long long>(n));
+        if (n != h->n && fes::species_count(h, 0) != ~0ull) return fail(h, FPIC_ERR_INVALID_ARG, ".position <- expected %zu particles, got %llu", h->n, static_cast<unsigned long long>(n));
         return fes::set_particles(h, 0, pos_aos, vel_aos, 0, n, dtype);
     }
     if (n != h->n) return fail(h, FPIC_ERR_INVALID_ARG, ".position <- expected %zu particles, got %llu", h->n, static_cast<unsigned long long>(n));
@@ -1592,6 +1592,36 @@ int fpic_gas_clear(fpic_handle* h)
     CHECK_HANDLE(h);
     BOX_ONLY(h, "fpic_gas_clear");
     return fes::gas_clear(h);
+}
+int fpic_remove(fpic_handle* h, const fpic_remove_spec* spec, fpic_remove_result* out)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_remove");
+    return fes::remove(h, spec, out);
+}
+int fpic_remove_register(fpic_handle* h, const fpic_remove_spec* spec, int every, int* index)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_remove_register");
+    return fes::remove_register(h, spec, every, index);
+}
+int fpic_remove_stats(fpic_handle* h, int index, int scope, fpic_remove_result* out)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_remove_stats");
+    return fes::remove_stats(h, index, scope, out);
+}
+int fpic_remove_clear(fpic_handle* h)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_remove_clear");
+    return fes::remove_clear(h);
+}
+int fpic_renumber(fpic_handle* h, int species, uint64_t* n)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_renumber");
+    return fes::renumber(h, species, n);
 }
 int fpic_collide_clear(fpic_handle* h)
 {

@@ -53,6 +53,7 @@ ABI_FUNCTIONS = [
     "fpic_fusion_spectrum", "fpic_fusion_spectrum_register", "fpic_fusion_spectrum_read", "fpic_fusion_spectrum_clear",
     "fpic_force", "fpic_force_register", "fpic_force_stats", "fpic_force_clear",
     "fpic_gas", "fpic_gas_register", "fpic_gas_stats", "fpic_gas_clear",
+    "fpic_remove", "fpic_remove_register", "fpic_remove_stats", "fpic_remove_clear", "fpic_renumber",
 ]
 
 
@@ -784,6 +785,50 @@ def _gas_sum(parts, mass, W):
     return out
 
 
+REMOVE_OUTSIDE = 1
+REMOVE_MAX_OPS = 8
+
+
+class RemoveSpec(ctypes.Structure):
+    """mirror of fpic_remove_spec (include/fusionpic.h)"""
+    _fields_ = [
+        ("species", ctypes.c_int32), ("nterms", ctypes.c_int32), ("axis", ctypes.c_int32 * 8), ("lo", ctypes.c_double * 8),
+        ("hi", ctypes.c_double * 8), ("id_mod", ctypes.c_uint32), ("id_rem", ctypes.c_uint32), ("flags", ctypes.c_uint32),
+        ("reserved_u", ctypes.c_uint32), ("reserved", ctypes.c_double * 4),
+    ]
+
+
+class RemoveResult(ctypes.Structure):
+    """mirror of fpic_remove_result"""
+    _fields_ = [("applications", ctypes.c_uint64), ("scanned", ctypes.c_uint64), ("removed", ctypes.c_uint64),
+                ("energy_fixed", ctypes.c_uint64 * 2), ("momentum_fixed", (ctypes.c_uint64 * 2) * 3),
+                ("energy", ctypes.c_double), ("momentum", ctypes.c_double * 3), ("charge", ctypes.c_double)]
+
+
+def _remove_spec(where, species, every, outside):
+    """RemoveSpec of a sink: the predicate as select() takes it (_select_spec), outside=True removes what does NOT match"""
+    if not isinstance(outside, (bool, np.bool_)):
+        raise FusionPicError(-1, ".outside <- must be True or False")
+    q = _select_spec(where, species, every)
+    s = RemoveSpec()
+    s.species, s.nterms, s.id_mod, s.id_rem = q.species, q.nterms, q.id_mod, q.id_rem
+    for t in range(8):
+        s.axis[t], s.lo[t], s.hi[t] = q.axis[t], q.lo[t], q.hi[t]
+    s.flags = REMOVE_OUTSIDE if outside else 0
+    return s
+
+
+def _remove_dict(r):
+    """energy_fixed and momentum_fixed as Python integers (the 128-bit two's complement sums, units of 2^-80): what the species lost"""
+    return {"applications": int(r.applications), "scanned": int(r.scanned), "removed": int(r.removed),
+            "energy_fixed": _force_signed(r.energy_fixed), "momentum_fixed": [_force_signed(r.momentum_fixed[a]) for a in range(3)],
+            "energy": float(r.energy), "momentum": [float(r.momentum[a]) for a in range(3)], "charge": float(r.charge)}
+
+
+_REMOVE_DECOMPOSED = ("%s needs an undecomposed handle: a rank's dead slots and the arrivals of a migration that rides on its next push "
+                      "would need a protocol of their own to compact")
+
+
 PAIR_MAX_OPS = 8
 PAIR_CELL_MAX = 2048
 PAIR_SEED = 0x7A1C12ABE
@@ -1256,6 +1301,11 @@ def load_library(path=None):
     lib.fpic_gas_register.argtypes = [vp, ctypes.POINTER(GasSpec), ci, ctypes.POINTER(ctypes.c_int)]
     lib.fpic_gas_stats.argtypes = [vp, ci, ci, ctypes.POINTER(GasResult)]
     lib.fpic_gas_clear.argtypes = [vp]
+    lib.fpic_remove.argtypes = [vp, ctypes.POINTER(RemoveSpec), ctypes.POINTER(RemoveResult)]
+    lib.fpic_remove_register.argtypes = [vp, ctypes.POINTER(RemoveSpec), ci, ctypes.POINTER(ctypes.c_int)]
+    lib.fpic_remove_stats.argtypes = [vp, ci, ci, ctypes.POINTER(RemoveResult)]
+    lib.fpic_remove_clear.argtypes = [vp]
+    lib.fpic_renumber.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_uint64)]
     lib.fpic_pair.argtypes = [vp, ctypes.POINTER(PairSpec), ctypes.POINTER(PairResult)]
     lib.fpic_pair_register.argtypes = [vp, ctypes.POINTER(PairSpec), ci, ctypes.POINTER(ctypes.c_int)]
     lib.fpic_pair_stats.argtypes = [vp, ci, ci, ctypes.POINTER(PairResult)]
@@ -1552,6 +1602,52 @@ class CylindricalParticlePusher:
     def count(self, where=None, species=0, every=None, scope="global"):
         """how many particles select() would return (the count query of fpic_select: nothing is delivered)"""
         return _select_count(self, _select_spec(where, species, every), scope)
+
+    # ---- absorbing sinks: the particles a predicate names leave the species, exactly accounted for (fpic_remove*)
+    def remove(self, where=None, species=0, every=None, outside=False):
+        """Removes, now, the live particles of one species of a CART3D box that select(where, species, every) would return
+        (fpic_remove; an (r,z) handle and a decomposed handle are refused) — with outside=True those that pass `every` and
+        do NOT lie in the window (the window is a brick: outside=True keeps the interior).  Survivors keep their state, their
+        id and their order.  Returns {applications, scanned, removed, energy_fixed, momentum_fixed (exact integers, units of
+        2^-80 of c^2 resp. c), energy (J), momentum (kg m/s), charge (C)}: what the species lost.  A species that has lost
+        particles is thinned: read it with select(); getParticles, set, load and saveCheckpoint are refused until
+        renumber().  With the electrostatic solver the call re-deposits and re-solves; under full EM the fields stay."""
+        s = _remove_spec(where, species, every, outside)
+        out = RemoveResult()
+        self._check(self._lib.fpic_remove(self._h, ctypes.byref(s), ctypes.byref(out)))
+        return _remove_dict(out)
+
+    def removeEvery(self, period, where=None, species=0, every=None, outside=False):
+        """Registers a sink (see remove) to run at the end of every `period`-th sub-step, after the fusion tallies and
+        before the recorders.  Each due application waits for one 8-byte count from the device.  Returns the operator's
+        index (fpic_remove_register)."""
+        if isinstance(period, bool) or not isinstance(period, (int, np.integer)) or not -(1 << 31) <= int(period) < 1 << 31:
+            raise FusionPicError(-1, ".every <- must be a signed 32-bit integer")
+        s = _remove_spec(where, species, every, outside)
+        index = ctypes.c_int()
+        self._check(self._lib.fpic_remove_register(self._h, ctypes.byref(s), int(period), ctypes.byref(index)))
+        return index.value
+
+    def removeStats(self, index, scope="global"):
+        """the totals of a registered sink since its registration (fpic_remove_stats)"""
+        out = RemoveResult()
+        self._check(self._lib.fpic_remove_stats(self._h, int(index), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope], ctypes.byref(out)))
+        return _remove_dict(out)
+
+    def clearRemovals(self):
+        """drops every registered sink (fpic_remove_clear)"""
+        self._check(self._lib.fpic_remove_clear(self._h))
+
+    def renumber(self, species=0):
+        """Gives the survivors of a thinned species the ids 0 .. n-1 in ascending old id (fpic_renumber) and returns n; the
+        caller-order calls and the checkpoint then work on the n survivors.  A no-op on a species that is not thinned."""
+        n = ctypes.c_uint64()
+        self._check(self._lib.fpic_renumber(self._h, int(species), ctypes.byref(n)))
+        if hasattr(self, "counts"):
+            self.counts[int(species)] = int(n.value)
+        if int(species) == 0:
+            self.n = int(n.value)
+        return int(n.value)
 
     # ---- the loader: a population generated on the device (fpic_load)
     def _box_lengths(self):
@@ -2150,6 +2246,11 @@ class ElectrostaticBoxPusher:
     collideGasEvery = CylindricalParticlePusher.collideGasEvery
     gasStats = CylindricalParticlePusher.gasStats
     clearGas = CylindricalParticlePusher.clearGas
+    remove = CylindricalParticlePusher.remove
+    removeEvery = CylindricalParticlePusher.removeEvery
+    removeStats = CylindricalParticlePusher.removeStats
+    clearRemovals = CylindricalParticlePusher.clearRemovals
+    renumber = CylindricalParticlePusher.renumber
     collidePair = CylindricalParticlePusher.collidePair
     collidePairEvery = CylindricalParticlePusher.collidePairEvery
     pairStats = CylindricalParticlePusher.pairStats
@@ -2318,6 +2419,27 @@ class BoxGroup:
         for m in self.sims:
             m.clearGas()
         self._gas_species = {}
+
+    def remove(self, where=None, species=0, every=None, outside=False):
+        """refused (FPIC_ERR_STATE), as by every member: a rank's dead slots and its migration tail would need a protocol
+        of their own"""
+        raise FusionPicError(-5, _REMOVE_DECOMPOSED % "remove")
+
+    def removeEvery(self, period, where=None, species=0, every=None, outside=False):
+        """refused, see remove"""
+        raise FusionPicError(-5, _REMOVE_DECOMPOSED % "removeEvery")
+
+    def removeStats(self, index, scope="global"):
+        """refused, see remove"""
+        raise FusionPicError(-5, _REMOVE_DECOMPOSED % "removeStats")
+
+    def clearRemovals(self):
+        """refused, see remove"""
+        raise FusionPicError(-5, _REMOVE_DECOMPOSED % "clearRemovals")
+
+    def renumber(self, species=0):
+        """refused, see remove"""
+        raise FusionPicError(-5, _REMOVE_DECOMPOSED % "renumber")
 
     def collidePair(self, a=0, b=None, **request):
         """refused (FPIC_ERR_STATE), as by every member: between two migrations the particles of a cell can sit on two

@@ -272,6 +272,48 @@ function makeBox(spec, lib) {
         const f64 = request.dtype === undefined ? fp64 : request.dtype === 'fp64';
         return lib.select(h, request.species || 0, Int32Array.from(codes), Float64Array.from(ranges), every[0], every[1], capacity, f64 ? 1 : 0, scopeOf(scope));
     };
+    // absorbing sinks (fpic_remove*): the particles select() would return leave the species, exactly accounted for.  request =
+    // { species (default 0), where, every: as select(), outside: true removes the particles that pass `every` and do NOT lie in
+    // the window }.  remove -> { applications, scanned, removed, energyFixed, momentumFixed (BigInt, units of 2^-80 c^2 and c:
+    // what the species lost), energy (J), momentum (kg m/s), charge (C) }; removeEvery(period, request) -> the operator's index
+    // (it runs after every period-th sub-step and waits for one 8-byte count); removeStats(index, scope) -> its totals;
+    // clearRemovals() drops every sink; renumber(species) gives the survivors of a thinned species the ids 0 .. n-1 and returns n
+    const removeArgs = function (request) {
+        if (request === undefined || request === null) request = {};
+        if (typeof request !== 'object' || Array.isArray(request)) throw new TypeError('.request <- expected { species, where, every, outside }');
+        const where = request.where === undefined || request.where === null ? {} : request.where;
+        if (typeof where !== 'object' || Array.isArray(where)) throw new TypeError('.where <- expected { axis: [lo, hi], ... }');
+        const codes = [], ranges = [];
+        for (const [name, r] of Object.entries(where)) {
+            if (!(name in HIST_AXES)) throw new RangeError('.axis <- must be one of x, y, z, vx, vy, vz, v2');
+            if (!Array.isArray(r) || r.length !== 2 || !r.every((x) => x === null || x === undefined || typeof x === 'number')) throw new RangeError('.range <- expected one [lo, hi] per axis, null for the infinite side');
+            codes.push(HIST_AXES[name]);
+            ranges.push(r[0] === null || r[0] === undefined ? -Infinity : r[0], r[1] === null || r[1] === undefined ? Infinity : r[1]);
+        }
+        const every = request.every === undefined || request.every === null ? [0, 0] : request.every;
+        if (!Array.isArray(every) || every.length !== 2 || !every.every((k) => Number.isInteger(k) && k >= 0 && k <= 0xffffffff)) throw new RangeError('.every <- expected [mod, rem] of unsigned 32-bit integers');
+        if (request.outside !== undefined && typeof request.outside !== 'boolean') throw new TypeError('.outside <- must be true or false');
+        return [request.species || 0, Int32Array.from(codes), Float64Array.from(ranges), every[0], every[1], request.outside ? 1 : 0];
+    };
+    out.remove = function (request) {
+        const a = removeArgs(request);
+        return lib.remove(h, a[0], a[1], a[2], a[3], a[4], a[5]);
+    };
+    out.removeEvery = function (period, request) {
+        if (!Number.isInteger(period)) throw new RangeError('.every <- must be an integer');
+        const a = removeArgs(request);
+        return lib.removeEvery(h, a[0], a[1], a[2], a[3], a[4], a[5], period);
+    };
+    out.removeStats = function (index, scope) {
+        if (!Number.isInteger(index)) throw new RangeError('.index <- must be an integer');
+        return lib.removeStats(h, index, scopeOf(scope));
+    };
+    out.clearRemovals = function () { lib.clearRemovals(h); };
+    out.renumber = function (species) {
+        const sp = species || 0, n = lib.renumber(h, sp);
+        counts[sp] = n;      // (getParticles and set size their arrays by it)
+        return n;
+    };
     // the loader (fpic_load): particles [first, first + count) of one species generated on the GPU.  request = { species, first,
     // count (default: to the end), seed (an integer up to 2^53 or a BigInt up to 2^64), stream, lo, hi (metres; default the whole
     // box), drift, vth (units of c), mode (three integers), xamp (metres), xphase, vamp (c), vphase (turns), lattice, paired,

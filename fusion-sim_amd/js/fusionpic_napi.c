@@ -1331,6 +1331,131 @@ static napi_value n_clear_gas(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* the request of remove / removeEvery: species, axes: Int32Array, ranges: Float64Array (lo, hi per term), idMod, idRem,
+ * outside (0 | 1) — args[1 .. 6].  The arrays' lengths are checked here, the request itself by the library. */
+static int get_remove_spec(napi_env env, const napi_value* argv, fpic_remove_spec* s)
+{
+    int sp; double mod, rem, outside;
+    if (!get_species(env, argv[1], &sp) || !get_double(env, argv[4], &mod) || !get_double(env, argv[5], &rem) || !get_double(env, argv[6], &outside)) return 0;
+    napi_typedarray_type ta, tr; void *pa, *pr; size_t la, lr;
+    if (!get_typed(env, argv[2], &ta, &pa, &la) || !get_typed(env, argv[3], &tr, &pr, &lr)) return 0;
+    if ((la && (!pa || !pr)) || ta != napi_int32_array || tr != napi_float64_array) {
+        napi_throw_type_error(env, NULL, ".where <- expected Int32Array axes and Float64Array ranges");
+        return 0;
+    }
+    if (la > FPIC_SELECT_MAX_TERMS) { napi_throw_range_error(env, NULL, ".nterms <- must be 0 .. 7"); return 0; }
+    if (!check_len(env, "range", lr, 2 * la)) return 0;
+    if (!(mod >= 0 && mod <= 4294967295.0 && rem >= 0 && rem <= 4294967295.0) || mod != (double)(uint32_t)mod || rem != (double)(uint32_t)rem) {
+        napi_throw_range_error(env, NULL, ".every <- expected [mod, rem] of unsigned 32-bit integers");
+        return 0;
+    }
+    if (outside != 0 && outside != 1) { napi_throw_range_error(env, NULL, ".outside <- must be true or false"); return 0; }
+    memset(s, 0, sizeof *s);
+    s->species = sp; s->nterms = (int32_t)la;
+    for (size_t t = 0; t < la; ++t) {
+        s->axis[t] = ((const int32_t*)pa)[t];
+        s->lo[t] = ((const double*)pr)[2 * t];
+        s->hi[t] = ((const double*)pr)[2 * t + 1];
+    }
+    s->id_mod = (uint32_t)mod; s->id_rem = (uint32_t)rem;
+    s->flags = outside != 0 ? FPIC_REMOVE_OUTSIDE : 0u;
+    return 1;
+}
+
+static napi_value remove_object(napi_env env, const fpic_remove_result* c)
+{
+    napi_value o, v, arr;
+    NAPI_OK(env, napi_create_object(env, &o));
+    const char* names[3] = { "applications", "scanned", "removed" };
+    const uint64_t counts[3] = { c->applications, c->scanned, c->removed };
+    for (int k = 0; k < 3; ++k) {
+        NAPI_OK(env, napi_create_double(env, (double)counts[k], &v));
+        NAPI_OK(env, napi_set_named_property(env, o, names[k], v));
+    }
+    v = fixed_bigint(env, c->energy_fixed);
+    if (!v) return NULL;
+    NAPI_OK(env, napi_set_named_property(env, o, "energyFixed", v));
+    NAPI_OK(env, napi_create_array_with_length(env, 3, &arr));
+    for (uint32_t a = 0; a < 3; ++a) {
+        v = fixed_bigint(env, c->momentum_fixed[a]);
+        if (!v) return NULL;
+        NAPI_OK(env, napi_set_element(env, arr, a, v));
+    }
+    NAPI_OK(env, napi_set_named_property(env, o, "momentumFixed", arr));
+    NAPI_OK(env, napi_create_double(env, c->energy, &v));
+    NAPI_OK(env, napi_set_named_property(env, o, "energy", v));
+    NAPI_OK(env, napi_create_array_with_length(env, 3, &arr));
+    for (uint32_t a = 0; a < 3; ++a) {
+        NAPI_OK(env, napi_create_double(env, c->momentum[a], &v));
+        NAPI_OK(env, napi_set_element(env, arr, a, v));
+    }
+    NAPI_OK(env, napi_set_named_property(env, o, "momentum", arr));
+    NAPI_OK(env, napi_create_double(env, c->charge, &v));
+    NAPI_OK(env, napi_set_named_property(env, o, "charge", v));
+    return o;
+}
+
+/* remove(h, species, axes, ranges, idMod, idRem, outside) -> { applications, scanned, removed, energyFixed, momentumFixed, energy, momentum, charge } */
+static napi_value n_remove(napi_env env, napi_callback_info info)
+{
+    napi_value argv[7]; fpic_handle* h;
+    fpic_remove_spec s;
+    if (!get_args(env, info, 7, argv, &h) || !get_remove_spec(env, argv, &s)) return NULL;
+    fpic_remove_result c;
+    memset(&c, 0, sizeof c);
+    if (fpic_remove(h, &s, &c) != FPIC_OK) return throw_fpic(env, h);
+    return remove_object(env, &c);
+}
+
+/* removeEvery(h, species, axes, ranges, idMod, idRem, outside, period) -> the operator's index */
+static napi_value n_remove_every(napi_env env, napi_callback_info info)
+{
+    napi_value argv[8]; fpic_handle* h; double every;
+    fpic_remove_spec s;
+    if (!get_args(env, info, 8, argv, &h) || !get_remove_spec(env, argv, &s) || !get_double(env, argv[7], &every)) return NULL;
+    if (!(every >= -2147483648.0 && every <= 2147483647.0) || every != (double)(int)every) { napi_throw_range_error(env, NULL, ".every <- must be a 32-bit integer"); return NULL; }
+    int index = -1;
+    if (fpic_remove_register(h, &s, (int)every, &index) != FPIC_OK) return throw_fpic(env, h);
+    napi_value v;
+    NAPI_OK(env, napi_create_int32(env, index, &v));
+    return v;
+}
+
+/* removeStats(h, index, scope) -> as remove */
+static napi_value n_remove_stats(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3]; fpic_handle* h; double index; int scope;
+    if (!get_args(env, info, 3, argv, &h) || !get_double(env, argv[1], &index) || !get_scope(env, argv[2], &scope)) return NULL;
+    if (!(index >= -2147483648.0 && index <= 2147483647.0) || index != (double)(int)index) { napi_throw_range_error(env, NULL, ".index <- must be a 32-bit integer"); return NULL; }
+    fpic_remove_result c;
+    memset(&c, 0, sizeof c);
+    if (fpic_remove_stats(h, (int)index, scope, &c) != FPIC_OK) return throw_fpic(env, h);
+    return remove_object(env, &c);
+}
+
+/* clearRemovals(h) */
+static napi_value n_clear_removals(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1]; fpic_handle* h;
+    if (!get_args(env, info, 1, argv, &h)) return NULL;
+    if (fpic_remove_clear(h) != FPIC_OK) return throw_fpic(env, h);
+    return undefined(env);
+}
+
+/* renumber(h, species) -> the species' particle count */
+static napi_value n_renumber(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2]; fpic_handle* h; int sp;
+    if (!get_args(env, info, 2, argv, &h) || !get_species(env, argv[1], &sp)) return NULL;
+    uint64_t n = 0;
+    if (fpic_renumber(h, sp, &n) != FPIC_OK) return throw_fpic(env, h);
+    g_box->count[sp] = (size_t)n;   /* (the caller-order arrays are checked against it from now on) */
+    if (sp == 0) g_box->n = (size_t)n;
+    napi_value v;
+    NAPI_OK(env, napi_create_double(env, (double)n, &v));
+    return v;
+}
+
 /* the request of collidePair / collidePairEvery: words: Float64Array [species_a, species_b, seed low word, seed high word,
  * stream, epoch], reals: Float64Array [log_lambda, tau].  The arrays' lengths and the words' ranges are checked here, the
  * request itself by the library. */
@@ -1931,6 +2056,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "histogram", n_histogram }, { "select", n_select }, { "load", n_load }, { "collide", n_collide }, { "collideEvery", n_collide_every }, { "collisionStats", n_collision_stats }, { "clearCollisions", n_clear_collisions },
         { "force", n_force }, { "forceOn", n_force_on }, { "forceStats", n_force_stats }, { "clearForces", n_clear_forces },
         { "collideGas", n_collide_gas }, { "collideGasEvery", n_collide_gas_every }, { "gasStats", n_gas_stats }, { "clearGas", n_clear_gas },
+        { "remove", n_remove }, { "removeEvery", n_remove_every }, { "removeStats", n_remove_stats }, { "clearRemovals", n_clear_removals }, { "renumber", n_renumber },
         { "collidePair", n_collide_pair }, { "collidePairEvery", n_collide_pair_every }, { "pairStats", n_pair_stats }, { "clearPairs", n_clear_pairs },
         { "fusionYield", n_fusion_yield }, { "fusionYieldEvery", n_fusion_yield_every }, { "fusionStats", n_fusion_stats }, { "fusionGrid", n_fusion_grid }, { "clearFusion", n_clear_fusion },
         { "fusionSpectrum", n_fusion_spectrum }, { "fusionSpectrumEvery", n_fusion_spectrum_every }, { "fusionSpectrumRead", n_fusion_spectrum_read }, { "clearFusionSpectra", n_clear_fusion_spectra },

@@ -1279,6 +1279,81 @@ int fpic_gas_register(fpic_handle* h, const fpic_gas_spec* spec, int every, int*
 int fpic_gas_stats(fpic_handle* h, int index, int scope, fpic_gas_result* out);
 int fpic_gas_clear(fpic_handle* h);
 
+/* ---- CART3D absorbing particle sinks: the particles of ONE species that a predicate over x y z vx vy vz |v|^2 names are
+ * taken out of the species on the device, and what left is accounted for exactly — a wall, a limiter or divertor plate, a
+ * beam dump, a loss cone, an evaporative cut of the tail, an absorbing edge layer.  Undecomposed handles only.
+ *   predicate  species, nterms, axis, lo, hi, id_mod, id_rem are fpic_select_spec's, with its meaning: a live particle
+ *              MATCHES iff fpic_select would select it — every term compared in double, a NaN matches nothing, then the id
+ *              rule.  flags = 0: the matching particles are removed.  FPIC_REMOVE_OUTSIDE: the live particles that pass
+ *              the id rule and do NOT match every term are removed (the intervals are ANDed, an absorbing edge is the
+ *              complement of a brick: "keep the interior" is this flag).  nterms = 0 removes every particle the id rule
+ *              passes; with the flag it removes nothing.
+ *   survivors  keep every bit of their state and their id.  After the call the species holds n' = n - removed particles in
+ *              slots [0, n'), in the slot order they had before (stable): the state after is a function of the state
+ *              before, not of any atomic's order.
+ *   result     applications; scanned (the live particles before each application, summed); removed; energy_fixed,
+ *              momentum_fixed[a]: exact sums in the fixed point of the energy diagnostics (units of 2^-80, 128-bit two's
+ *              complement, low word first) of floor(|v|^2 2^80) and floor(v[a] 2^80) over the removed particles, from the
+ *              stored velocity, the squared norm ((x x + y y) + z z) in double — what the species LOST; a term >= 2^15 in
+ *              magnitude or not finite adds nothing and makes its double NaN (fpic_energy's rule).  energy = (0.5 m W
+ *              c^2) times the double nearest to the sum 2^-80 (J), momentum[a] = (m W c) times the same (kg m/s), charge =
+ *              removed x the species' charge x macro_weight in double (C).
+ * fpic_remove applies the request now (synchronous, as fpic_gas) and returns its result (applications 1).
+ * fpic_remove_register makes it run at the end of every sub-step with substep % every == 0, after the fusion spectra and
+ * before the recorders: the tallies of that sub-step see the particles that are about to leave, the recorded rows see the
+ * thinned box.  Operators run in registration order, at most FPIC_REMOVE_MAX_OPS of them; *index names the operator.
+ * UNLIKE the other registered operators a due application reads one 8-byte total back to the host and waits for it: the
+ * host has to learn the new particle count.  fpic_remove_stats reads the totals since registration (scope: LOCAL or
+ * GLOBAL, the same on an undecomposed handle).  fpic_remove_clear drops every registered operator.  Registrations are not
+ * part of a checkpoint.
+ * What a removal leaves.  One that took nothing changes nothing: no buffer is swapped, no field or bin table touched.  One
+ * that took a particle leaves the species as an upload leaves one (the next sub-step re-bins), and marks it THINNED: its
+ * ids are no longer 0 .. n-1, they lie below the species' id span (one past the largest id it was ever given, which does
+ * not shrink).  Electrostatic solver (poisson_fft): if the fields were ready the call itself deposits the survivors'
+ * charge and solves, so E is the field of the survivors; fields that were not ready stay so.  Full EM (yee): E, B and the
+ * readiness are left untouched — the charge of a removed particle stays in the lattice E as a static source, as the
+ * surface charge of an absorbing wall does; Gauss's law is not re-imposed.
+ * Everything that works per particle or by id keeps working on a thinned species (the push, deposits, fpic_sort, energy,
+ * histograms, moments, modes, fpic_select — the way to read a thinned species back —, the series, whose row of a removed
+ * tracer is zeros and whose tracer ids are bounded by the id span, fpic_collide, fpic_gas, fpic_force, fpic_pair,
+ * fpic_fusion, fpic_fusion_spectrum).  Everything that addresses particles in the caller's order is refused on a thinned
+ * species with FPIC_ERR_STATE: fpic_get_particles_of / _range, fpic_get_cells_of / _range, fpic_set_particles_of / _range,
+ * fpic_load*, fpic_save_checkpoint, fpic_domain_init.
+ * fpic_renumber gives every survivor the id "number of live ids below mine" (on the device: a bitmap over the id span and
+ * a popcount scan), clears the mark and sets the id span to n; *n receives n.  Positions, velocities and fields do not
+ * change.  After it the caller-order calls and the checkpoint work again on the n survivors, in ascending old id.  A no-op
+ * that returns n on a species that is not thinned.  Synchronous.  Refused (FPIC_ERR_STATE) while a series recording or a
+ * registered operator of any kind exists on the handle: both name ids or draw per-id random words, which would silently
+ * change meaning.
+ * Refused (FPIC_ERR_INVALID_ARG): a null spec, everything fpic_select refuses of a request (nterms outside 0 .. 7, an axis
+ * code outside 0 .. 6, the same axis twice, a NaN bound or not lo < hi, entries past nterms that are not zero, id_rem >=
+ * id_mod when id_mod > 1, a species the handle does not have), an unknown flag, a reserved word that is not zero, every
+ * below 1, a ninth registration, an index outside the registered operators, a null out of fpic_remove_stats;
+ * FPIC_ERR_STATE: a handle that is not CART3D; a decomposed handle (all five calls: a rank's dead slots and its migration
+ * tail would need a protocol of their own). */
+#define FPIC_REMOVE_OUTSIDE  1u
+#define FPIC_REMOVE_MAX_OPS  8
+typedef struct fpic_remove_spec {
+    int32_t  species, nterms;   /* as fpic_select_spec */
+    int32_t  axis[8];
+    double   lo[8], hi[8];
+    uint32_t id_mod, id_rem;
+    uint32_t flags, reserved_u; /* FPIC_REMOVE_OUTSIDE or 0; zero */
+    double   reserved[4];       /* zero */
+} fpic_remove_spec;
+typedef struct fpic_remove_result {
+    uint64_t applications, scanned, removed;
+    uint64_t energy_fixed[2];      /* low word, high word */
+    uint64_t momentum_fixed[3][2];
+    double   energy, momentum[3];  /* J; kg m/s: what the species lost */
+    double   charge;               /* C */
+} fpic_remove_result;
+int fpic_remove(fpic_handle* h, const fpic_remove_spec* spec, fpic_remove_result* out);
+int fpic_remove_register(fpic_handle* h, const fpic_remove_spec* spec, int every, int* index);
+int fpic_remove_stats(fpic_handle* h, int index, int scope, fpic_remove_result* out);
+int fpic_remove_clear(fpic_handle* h);
+int fpic_renumber(fpic_handle* h, int species, uint64_t* n);
+
 int fpic_sync(fpic_handle* h);
 int fpic_profile(fpic_handle* h, int enable);
 int fpic_get_stats(fpic_handle* h, fpic_stats* out);

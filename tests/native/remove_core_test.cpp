@@ -1,0 +1,134 @@
+// Host test of fusion-sim_amd/csrc/fes_remove_core.hpp (the rule of the absorbing particle sinks and the checks of a
+// request): the request as the selection's, who leaves under both flags, every refusal by its message, the registration
+// and index checks, and the conversion of a row of totals to the result, the NaN rule included.  Built with g++
+// -ffp-contract=off by tests/test_remove_host.py; prints "ok" and exits 0, or names the first failed check and exits 1.
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <limits>
+
+#include "../../fusion-sim_amd/csrc/fes_remove_core.hpp"
+
+static int failures = 0;
+#define CHECK(c)                                                                 \
+    do {                                                                         \
+        if (!(c)) { std::printf("FAILED %s:%d: %s\n", __FILE__, __LINE__, #c); ++failures; } \
+    } while (0)
+
+static fpic_remove_spec good()
+{
+    fpic_remove_spec s;
+    std::memset(&s, 0, sizeof s);
+    s.species = 0; s.nterms = 3;
+    s.axis[0] = FPIC_AXIS_X; s.axis[1] = FPIC_AXIS_VX; s.axis[2] = FPIC_AXIS_V2;
+    s.lo[0] = 0.25; s.hi[0] = 0.5;
+    s.lo[1] = -std::numeric_limits<double>::infinity(); s.hi[1] = 0.1;
+    s.lo[2] = 1e-4; s.hi[2] = std::numeric_limits<double>::infinity();
+    s.id_mod = 7; s.id_rem = 3;
+    return s;
+}
+static bool names(const char* msg, const char* property) { return msg && std::strncmp(msg, property, std::strlen(property)) == 0; }
+
+static void request()
+{
+    const fpic_remove_spec s = good();
+    const fpic_select_spec q = fesrem::select_of(s);
+    CHECK(q.species == 0 && q.nterms == 3 && q.id_mod == 7 && q.id_rem == 3);
+    for (int t = 0; t < 8; ++t) CHECK(q.axis[t] == s.axis[t] && q.lo[t] == s.lo[t] && q.hi[t] == s.hi[t]);
+    for (int k = 0; k < 4; ++k) CHECK(q.reserved[k] == 0);
+    CHECK(fessel::arrays_of(q) == (1u | 1u << 3 | 0x38u));
+}
+
+static void flags()
+{
+    // (in the terms, passes the id rule) -> leaves
+    CHECK(fesrem::removes(true, true, 0) && !fesrem::removes(false, true, 0));
+    CHECK(!fesrem::removes(true, false, 0) && !fesrem::removes(false, false, 0));
+    CHECK(!fesrem::removes(true, true, FPIC_REMOVE_OUTSIDE) && fesrem::removes(false, true, FPIC_REMOVE_OUTSIDE));
+    CHECK(!fesrem::removes(true, false, FPIC_REMOVE_OUTSIDE) && !fesrem::removes(false, false, FPIC_REMOVE_OUTSIDE));   // the id rule restricts who can leave at all
+    fpic_remove_spec s = good();
+    CHECK(!fesrem::never(s));
+    s.flags = FPIC_REMOVE_OUTSIDE; CHECK(!fesrem::never(s));
+    std::memset(&s, 0, sizeof s);
+    CHECK(!fesrem::never(s));                      // no term: everybody the id rule passes
+    s.flags = FPIC_REMOVE_OUTSIDE; CHECK(fesrem::never(s));   // ... and with the flag nobody
+}
+
+static void refusals()
+{
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    fpic_remove_spec s = good();
+    CHECK(fesrem::check(&s, 1) == nullptr);
+    CHECK(names(fesrem::check(nullptr, 1), ".spec <- "));
+    s.flags = FPIC_REMOVE_OUTSIDE; CHECK(fesrem::check(&s, 1) == nullptr);
+    // everything fpic_select refuses of a request
+    s = good(); s.nterms = -1; CHECK(names(fesrem::check(&s, 1), ".nterms <- "));
+    s = good(); s.nterms = 8; CHECK(names(fesrem::check(&s, 1), ".nterms <- "));
+    s = good(); s.species = 1; CHECK(names(fesrem::check(&s, 1), ".species <- ")); CHECK(fesrem::check(&s, 2) == nullptr);
+    s = good(); s.species = -1; CHECK(names(fesrem::check(&s, 1), ".species <- "));
+    s = good(); s.axis[0] = 7; CHECK(names(fesrem::check(&s, 1), ".axis <- "));
+    s = good(); s.axis[2] = FPIC_AXIS_X; CHECK(names(fesrem::check(&s, 1), ".axis <- the same axis twice"));
+    s = good(); s.lo[0] = nan; CHECK(names(fesrem::check(&s, 1), ".range <- "));
+    s = good(); s.lo[0] = 0.5; CHECK(names(fesrem::check(&s, 1), ".range <- "));
+    s = good(); s.id_rem = 7; CHECK(names(fesrem::check(&s, 1), ".id_rem <- "));
+    s = good(); s.id_mod = 1; s.id_rem = 9; CHECK(fesrem::check(&s, 1) == nullptr);
+    s = good(); s.axis[3] = 1; CHECK(names(fesrem::check(&s, 1), ".axis <- entries past nterms"));
+    s = good(); s.hi[5] = nan; CHECK(names(fesrem::check(&s, 1), ".axis <- entries past nterms"));
+    s = good(); s.reserved[3] = 1; CHECK(names(fesrem::check(&s, 1), ".reserved <- "));
+    s = good(); s.reserved[0] = nan; CHECK(names(fesrem::check(&s, 1), ".reserved <- "));
+    // its own
+    s = good(); s.flags = 2; CHECK(names(fesrem::check(&s, 1), ".flags <- "));
+    s = good(); s.flags = FPIC_REMOVE_OUTSIDE | 0x80000000u; CHECK(names(fesrem::check(&s, 1), ".flags <- "));
+    s = good(); s.reserved_u = 1; CHECK(names(fesrem::check(&s, 1), ".reserved <- "));
+    std::memset(&s, 0, sizeof s);
+    CHECK(fesrem::check(&s, 1) == nullptr);
+    CHECK(fesrem::check_register(1, 0) == nullptr && fesrem::check_register(1000, FPIC_REMOVE_MAX_OPS - 1) == nullptr);
+    CHECK(names(fesrem::check_register(0, 0), ".every <- ") && names(fesrem::check_register(-3, 0), ".every <- "));
+    CHECK(names(fesrem::check_register(1, FPIC_REMOVE_MAX_OPS), ".spec <- "));
+    CHECK(fesrem::check_index(0, 1) == nullptr && names(fesrem::check_index(1, 1), ".index <- ") && names(fesrem::check_index(-1, 1), ".index <- ") &&
+          names(fesrem::check_index(0, 0), ".index <- "));
+}
+
+static void results()
+{
+    const double mass = 9.109e-31, charge = -1.602e-19, W = 2.5e5, c = 2.998e8;
+    uint64_t w[fesrem::kRowWords] = {};
+    fpic_remove_result r;
+    std::memset(&r, 0xff, sizeof r);
+    r.applications = 7; r.scanned = 9;
+    fesrem::result_of(w, mass, charge, W, &r);
+    CHECK(r.applications == 7 && r.scanned == 9);     // (not the row's to set)
+    CHECK(r.removed == 0 && r.energy == 0 && r.momentum[0] == 0 && r.momentum[2] == 0 && r.charge == 0 && r.energy_fixed[1] == 0);
+    // three particles; |v|^2 sum = 3 2^-80 2^78 = 0.75, vx sum = -0.5 (two's complement), vy = 2^-80 (one unit)
+    w[0] = 3;
+    w[1] = 0; w[2] = 3ull << 14;         // 3 * 2^78 = (3 << 14) * 2^64
+    const unsigned __int128 half = static_cast<unsigned __int128>(1) << 79, neg = ~half + 1;
+    w[3] = static_cast<uint64_t>(neg); w[4] = static_cast<uint64_t>(neg >> 64);
+    w[5] = 1; w[6] = 0;
+    w[9] = 0x7ff8000000000000ull;        // (the diagnostics' maximum: not read)
+    fesrem::result_of(w, mass, charge, W, &r);
+    CHECK(r.removed == 3 && r.energy_fixed[0] == 0 && r.energy_fixed[1] == (3ull << 14) && r.momentum_fixed[0][1] == w[4] && r.momentum_fixed[1][0] == 1);
+    CHECK(r.energy == 0.5 * mass * W * c * c * 0.75);
+    CHECK(r.momentum[0] == mass * W * c * -0.5);
+    CHECK(r.momentum[1] == mass * W * c * 0x1p-80 && r.momentum[2] == 0);
+    CHECK(r.charge == 3.0 * charge * W);
+    // the NaN rule: a sum that met a term outside the range reports NaN, the others stay
+    w[10] = 1u | 1u << 2;
+    fesrem::result_of(w, mass, charge, W, &r);
+    CHECK(std::isnan(r.energy) && std::isnan(r.momentum[1]) && r.momentum[0] == mass * W * c * -0.5 && r.momentum[2] == 0 && r.removed == 3);
+    CHECK(r.energy_fixed[1] == (3ull << 14));         // (the words are handed over as they are)
+    w[10] = 0xf;
+    fesrem::result_of(w, mass, charge, W, &r);
+    CHECK(std::isnan(r.energy) && std::isnan(r.momentum[0]) && std::isnan(r.momentum[1]) && std::isnan(r.momentum[2]) && r.charge == 3.0 * charge * W);
+}
+
+int main()
+{
+    request();
+    flags();
+    refusals();
+    results();
+    if (failures) return 1;
+    std::printf("ok\n");
+    return 0;
+}
