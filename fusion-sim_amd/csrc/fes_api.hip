@@ -31,6 +31,7 @@
 //   fes_fusion.inc.hpp      fusion yield tallies between the species: fes_pair's cell index, the tally pass, the cell grids
 //   fes_fusion_spectrum.inc.hpp   fusion product spectra: the tally's pairs and yields binned over an energy axis
 //   fes_remove.inc.hpp      absorbing particle sinks: the mark, scan and move passes of one request, the state a removal leaves, renumbering
+//   fes_inject.inc.hpp      particle sources: the capacity a species grows into, the generation pass of one request, the state an injection leaves
 //   fes_mom.inc.hpp         the fluid moment grids: the sweeps of one request, the held planes' places, the ranks' sum
 //   fes_series.inc.hpp      the series: rows of field points and tracer particles, now or into a ring, the ranks' selection
 //   fes_modes.inc.hpp       the modes: Fourier amplitudes of the node fields at chosen wave vectors, now or into a ring, the ranks' sum
@@ -48,6 +49,7 @@
 #include "fes_fusion_kernels.hpp"
 #include "fes_fusion_spectrum_kernels.hpp"
 #include "fes_remove_kernels.hpp"
+#include "fes_inject_kernels.hpp"
 #include "fes_mom_kernels.hpp"
 #include "fes_series_kernels.hpp"
 #include "fes_modes_kernels.hpp"
@@ -376,6 +378,7 @@ namespace {
 #include "fes_fusion.inc.hpp"
 #include "fes_fusion_spectrum.inc.hpp"
 #include "fes_remove.inc.hpp"
+#include "fes_inject.inc.hpp"
 #include "fes_mom.inc.hpp"
 #include "fes_series.inc.hpp"
 #include "fes_modes.inc.hpp"
@@ -407,6 +410,10 @@ static int diag_after_substep(fpic_handle* h)
     // thinned box.  Each due application waits for one 8-byte count: the host has to learn the new n
     if (!g.remove_ops.empty())
         if (int rc = remove_after_substep(h, g.substep)) return rc;
+    // the particle sources (fes_inject.inc.hpp), after the sinks: a sink beside a source leaves this sub-step's fresh particles
+    // alive, and the rows below count them.  Nothing is read back: the host knows the new n in advance
+    if (!g.inject_ops.empty())
+        if (int rc = inject_after_substep(h, g.substep)) return rc;
     const bool f32 = h->prec == FPIC_F32;
     for (int k = 0; k < kRecorders; ++k) {
         void* row = rec_due(g.rec[k], g.substep);

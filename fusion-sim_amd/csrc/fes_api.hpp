@@ -64,6 +64,13 @@ int remove_register(fpic_handle* h, const fpic_remove_spec* spec, int every, int
 int remove_stats(fpic_handle* h, int index, int scope, fpic_remove_result* out);
 int remove_clear(fpic_handle* h);
 int renumber(fpic_handle* h, int species, uint64_t* n);
+// particle sources, the capacity they grow into and the population's numbers (fes_inject.inc.hpp)
+int reserve(fpic_handle* h, int species, uint64_t capacity, uint64_t* capacity_out);
+int population(fpic_handle* h, int species, uint64_t* n, uint64_t* capacity, uint64_t* id_span);
+int inject(fpic_handle* h, const fpic_inject_spec* spec, fpic_inject_result* out);
+int inject_register(fpic_handle* h, const fpic_inject_spec* spec, int every, int* index);
+int inject_stats(fpic_handle* h, int index, int scope, fpic_inject_result* out);
+int inject_clear(fpic_handle* h);
 // binary Coulomb collisions between the species of the box (fes_pair.inc.hpp)
 int pair(fpic_handle* h, const fpic_pair_spec* spec, fpic_pair_result* out);
 int pair_register(fpic_handle* h, const fpic_pair_spec* spec, int every, int* index);

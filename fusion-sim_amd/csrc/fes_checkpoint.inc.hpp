@@ -298,12 +298,15 @@ int load_checkpoint(fpic_handle* h, const char* path)
         return fail(h, FPIC_ERR_INVALID_ARG, ".spec <- checkpoint was written with different lengths / dt / macro_weight");
     const size_t t = h->prec == FPIC_F32 ? 4 : 8;
     unsigned long long want = sizeof hd + hd.nspecies * sizeof(BoxCheckpointSpecies);
+    std::vector<size_t> counts;
     for (size_t k = 0; k < st->sp.size(); ++k) {
         BoxCheckpointSpecies bs{};
         if (std::fread(&bs, sizeof bs, 1, bf.f) != 1) return fail(h, FPIC_ERR_STATE, "checkpoint is truncated");
-        if (bs.n != st->sp[k].n || bs.mass != st->sp[k].mass || bs.charge != st->sp[k].charge)
-            return fail(h, FPIC_ERR_INVALID_ARG, ".species <- species %zu of the checkpoint (%llu particles, mass %g, charge %g) is not the pusher's", k,
-                        static_cast<unsigned long long>(bs.n), bs.mass, bs.charge);
+        // (a species that sources or sinks have resized: the file's count is restored, into a capacity that holds it — fpic_reserve)
+        if (bs.n > st->sp[k].cap || bs.mass != st->sp[k].mass || bs.charge != st->sp[k].charge)
+            return fail(h, FPIC_ERR_INVALID_ARG, ".species <- species %zu of the checkpoint (%llu particles, mass %g, charge %g) is not the pusher's (capacity %zu; fpic_reserve raises it)", k,
+                        static_cast<unsigned long long>(bs.n), bs.mass, bs.charge, st->sp[k].cap);
+        counts.push_back(static_cast<size_t>(bs.n));
         want += 6ull * bs.n * t;
     }
     for (const auto& a : checkpoint_fields(h)) want += a.second;
@@ -315,6 +318,9 @@ int load_checkpoint(fpic_handle* h, const char* path)
     if (std::fseek(bf.f, at, SEEK_SET) != 0) return fail(h, FPIC_ERR_STATE, "cannot seek in %s", path);
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     for (Species& s : st->sp) { // the arrays are about to hold the caller's order: bins and census are void
+        s.n = counts[&s - st->sp.data()];
+        s.thinned = false;      // (the file's particles are 0 .. n - 1)
+        s.id_span = 0;
         s.binned = s.census_fresh = s.rebin_pending = s.chunk_census_fresh = false;
         s.tail_first = s.tail_count = s.n_after = 0;
         s.ids_identity = true; // (ckpt_scatter_kernel writes slot = index)
@@ -323,6 +329,7 @@ int load_checkpoint(fpic_handle* h, const char* path)
     st->last_spill = 0;
     st->substeps_since_bin = 0;
     st->fields_ready = false;
+    h->n = st->sp[0].n;
     if (int rc = h->prec == FPIC_F32 ? checkpoint_particles<float>(h, bf.f, false) : checkpoint_particles<double>(h, bf.f, false)) return rc;
     if (int rc = checkpoint_arrays(h, bf.f, false)) return rc;
     for (int a = 0; a < 3; ++a) st->B0[a] = hd.B0[a];

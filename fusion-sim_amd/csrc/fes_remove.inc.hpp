@@ -244,7 +244,7 @@ int renumber(fpic_handle* h, int species, uint64_t* n_out)
     if (!s.thinned) return FPIC_OK;
     if (g.rec[kRecSeries].every)
         return fail(h, FPIC_ERR_STATE, "fpic_renumber while a series is being recorded: its tracers are named by id, and the ids are about to change; stop the recording first");
-    if (!g.coll_ops.empty() || !g.force_ops.empty() || !g.gas_ops.empty() || !g.pair_ops.empty() || !g.fusion_ops.empty() || !g.fspec_ops.empty() || !g.remove_ops.empty())
+    if (!g.coll_ops.empty() || !g.force_ops.empty() || !g.gas_ops.empty() || !g.pair_ops.empty() || !g.fusion_ops.empty() || !g.fspec_ops.empty() || !g.remove_ops.empty() || !g.inject_ops.empty())
         return fail(h, FPIC_ERR_STATE, "fpic_renumber while an operator is registered: registered operators draw per-id random words or thin by id, and the ids are about to change; clear the registrations first");
     const size_t n = s.n;
     if (n) {

@@ -116,6 +116,14 @@ struct RemoveOp {
     uint64_t applications, scanned;
 };
 
+// a registered particle source (fes_inject.inc.hpp): the request, its period in sub-steps, the applications so far (the
+// totals are a row on the device)
+struct InjectOp {
+    fpic_inject_spec spec;
+    int every;
+    uint64_t applications;
+};
+
 // a registered binary collision operator (fes_pair.inc.hpp): the request, its period in sub-steps, the applications so far
 struct PairOp {
     fpic_pair_spec spec;
@@ -196,6 +204,10 @@ struct Diag {
     // application, one whose first word is the mark pass's counter, then the move pass's partial rows (kRemoveBlocks of them)
     unsigned long long* remove = nullptr;
     std::vector<RemoveOp> remove_ops;   // the registered sinks, in registration order
+    // fpic_inject (fes_inject.inc.hpp): rows of kDiagWords words - the totals of each registered source, one more for the last
+    // application, then the generation pass's partial rows (kInjectBlocks of them)
+    unsigned long long* inject = nullptr;
+    std::vector<InjectOp> inject_ops;   // the registered sources, in registration order
 };
 inline void diag_release(Diag& g)
 {
@@ -204,7 +216,7 @@ inline void diag_release(Diag& g)
     for (void* p : { g.series_req.block, g.modes_req.block, static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom), g.sel, static_cast<void*>(g.load_tab), static_cast<void*>(g.coll), static_cast<void*>(g.force), static_cast<void*>(g.gas), static_cast<void*>(g.pair),
                      static_cast<void*>(g.pair_seg[0]), static_cast<void*>(g.pair_seg[1]), static_cast<void*>(g.pair_index[0]), static_cast<void*>(g.pair_index[1]),
                      static_cast<void*>(g.fusion), static_cast<void*>(g.fusion_table),
-                     static_cast<void*>(g.fspec), static_cast<void*>(g.fspec_table), static_cast<void*>(g.fspec_words), static_cast<void*>(g.remove) })
+                     static_cast<void*>(g.fspec), static_cast<void*>(g.fspec_table), static_cast<void*>(g.fspec_words), static_cast<void*>(g.remove), static_cast<void*>(g.inject) })
         if (p) (void)hipFree(p);
     for (unsigned long long* p : g.fusion_grid)
         if (p) (void)hipFree(p);

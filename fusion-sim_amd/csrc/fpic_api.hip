@@ -1623,6 +1623,42 @@ int fpic_renumber(fpic_handle* h, int species, uint64_t* n)
     BOX_ONLY(h, "fpic_renumber");
     return fes::renumber(h, species, n);
 }
+int fpic_reserve(fpic_handle* h, int species, uint64_t capacity, uint64_t* capacity_out)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_reserve");
+    return fes::reserve(h, species, capacity, capacity_out);
+}
+int fpic_population(fpic_handle* h, int species, uint64_t* n, uint64_t* capacity, uint64_t* id_span)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_population");
+    return fes::population(h, species, n, capacity, id_span);
+}
+int fpic_inject(fpic_handle* h, const fpic_inject_spec* spec, fpic_inject_result* out)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_inject");
+    return fes::inject(h, spec, out);
+}
+int fpic_inject_register(fpic_handle* h, const fpic_inject_spec* spec, int every, int* index)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_inject_register");
+    return fes::inject_register(h, spec, every, index);
+}
+int fpic_inject_stats(fpic_handle* h, int index, int scope, fpic_inject_result* out)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_inject_stats");
+    return fes::inject_stats(h, index, scope, out);
+}
+int fpic_inject_clear(fpic_handle* h)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_inject_clear");
+    return fes::inject_clear(h);
+}
 int fpic_collide_clear(fpic_handle* h)
 {
     CHECK_HANDLE(h);

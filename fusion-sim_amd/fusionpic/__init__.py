@@ -54,6 +54,7 @@ ABI_FUNCTIONS = [
     "fpic_force", "fpic_force_register", "fpic_force_stats", "fpic_force_clear",
     "fpic_gas", "fpic_gas_register", "fpic_gas_stats", "fpic_gas_clear",
     "fpic_remove", "fpic_remove_register", "fpic_remove_stats", "fpic_remove_clear", "fpic_renumber",
+    "fpic_reserve", "fpic_population", "fpic_inject", "fpic_inject_register", "fpic_inject_stats", "fpic_inject_clear",
 ]
 
 
@@ -829,6 +830,59 @@ _REMOVE_DECOMPOSED = ("%s needs an undecomposed handle: a rank's dead slots and 
                       "would need a protocol of their own to compact")
 
 
+INJECT_VOLUME = 0
+INJECT_FLUX = 1
+INJECT_MAX_OPS = 8
+
+
+class InjectSpec(ctypes.Structure):
+    """mirror of fpic_inject_spec (include/fusionpic.h)"""
+    _fields_ = [
+        ("load", LoadSpec), ("kind", ctypes.c_int32), ("axis", ctypes.c_int32), ("side", ctypes.c_int32), ("reserved_i", ctypes.c_int32),
+        ("plane", ctypes.c_double), ("epoch", ctypes.c_uint64), ("reserved", ctypes.c_double * 4),
+    ]
+
+
+class InjectResult(ctypes.Structure):
+    """mirror of fpic_inject_result"""
+    _fields_ = [("applications", ctypes.c_uint64), ("injected", ctypes.c_uint64),
+                ("energy_fixed", ctypes.c_uint64 * 2), ("momentum_fixed", (ctypes.c_uint64 * 2) * 3),
+                ("energy", ctypes.c_double), ("momentum", ctypes.c_double * 3), ("charge", ctypes.c_double)]
+
+
+def _inject_spec(box, kind="volume", species=0, count=0, first=0, seed=LOAD_SEED, stream=0, lo=None, hi=None, drift=0, vth=0, axis=0, side=0, plane=0.0,
+                 lattice=False, paired=False, mode=None, xamp=0, xphase=0, vamp=0, vphase=0, epoch=0):
+    """InjectSpec of a source: the embedded loader request as load() builds it (_load_spec), then the kind's own fields.  Only
+    what the structure cannot carry is refused here; the library checks the rest."""
+    if kind not in ("volume", "flux"):
+        raise FusionPicError(-1, ".kind <- must be 'volume' or 'flux'")
+    if count is None or isinstance(count, bool):
+        raise FusionPicError(-1, ".count <- must be an unsigned 64-bit integer")
+    s = InjectSpec()
+    s.load = _load_spec(box, species, first, count, seed, stream, lo, hi, drift, vth, mode, xamp, xphase, vamp, vphase, lattice, paired, True, True, False)
+    s.kind = INJECT_VOLUME if kind == "volume" else INJECT_FLUX
+    for name, v, lo_, hi_ in (("axis", axis, -(1 << 31), 1 << 31), ("side", side, -(1 << 31), 1 << 31), ("epoch", epoch, 0, 1 << 64)):
+        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo_ <= int(v) < hi_:
+            raise FusionPicError(-1, ".%s <- must be an integer" % name)
+    s.axis, s.side, s.epoch = int(axis), int(side), int(epoch)
+    try:
+        s.plane = float(plane)
+    except (TypeError, ValueError):
+        raise FusionPicError(-1, ".plane <- must be a number")
+    return s
+
+
+def _inject_dict(r):
+    """energy_fixed and momentum_fixed as Python integers (the 128-bit two's complement sums, units of 2^-80): what the species gained"""
+    return {"applications": int(r.applications), "injected": int(r.injected),
+            "energy_fixed": _force_signed(r.energy_fixed), "momentum_fixed": [_force_signed(r.momentum_fixed[a]) for a in range(3)],
+            "energy": float(r.energy), "momentum": [float(r.momentum[a]) for a in range(3)], "charge": float(r.charge)}
+
+
+_INJECT_DECOMPOSED = ("%s needs an undecomposed handle: a rank's arrivals ride on its next push, and its message buffers were sized "
+                      "from the capacity it had")
+
+
 PAIR_MAX_OPS = 8
 PAIR_CELL_MAX = 2048
 PAIR_SEED = 0x7A1C12ABE
@@ -1306,6 +1360,12 @@ def load_library(path=None):
     lib.fpic_remove_stats.argtypes = [vp, ci, ci, ctypes.POINTER(RemoveResult)]
     lib.fpic_remove_clear.argtypes = [vp]
     lib.fpic_renumber.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_uint64)]
+    lib.fpic_reserve.argtypes = [vp, ci, ctypes.c_uint64, ctypes.POINTER(ctypes.c_uint64)]
+    lib.fpic_population.argtypes = [vp, ci, ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64), ctypes.POINTER(ctypes.c_uint64)]
+    lib.fpic_inject.argtypes = [vp, ctypes.POINTER(InjectSpec), ctypes.POINTER(InjectResult)]
+    lib.fpic_inject_register.argtypes = [vp, ctypes.POINTER(InjectSpec), ci, ctypes.POINTER(ctypes.c_int)]
+    lib.fpic_inject_stats.argtypes = [vp, ci, ci, ctypes.POINTER(InjectResult)]
+    lib.fpic_inject_clear.argtypes = [vp]
     lib.fpic_pair.argtypes = [vp, ctypes.POINTER(PairSpec), ctypes.POINTER(PairResult)]
     lib.fpic_pair_register.argtypes = [vp, ctypes.POINTER(PairSpec), ci, ctypes.POINTER(ctypes.c_int)]
     lib.fpic_pair_stats.argtypes = [vp, ci, ci, ctypes.POINTER(PairResult)]
@@ -1648,6 +1708,64 @@ class CylindricalParticlePusher:
         if int(species) == 0:
             self.n = int(n.value)
         return int(n.value)
+
+    # ---- particle sources: a species gains particles generated on the device, exactly accounted for (fpic_inject*, fpic_reserve)
+    def population(self, species=0):
+        """{n, capacity, id_span} of one species now (fpic_population): the live particles, the particles its arrays hold
+        (reserve() raises it) and one past the largest id it can hold.  Also refreshes the wrapper's own count, which a
+        registered source or sink changes behind its back."""
+        n, cap, span = ctypes.c_uint64(), ctypes.c_uint64(), ctypes.c_uint64()
+        self._check(self._lib.fpic_population(self._h, int(species), ctypes.byref(n), ctypes.byref(cap), ctypes.byref(span)))
+        if hasattr(self, "counts") and 0 <= int(species) < len(self.counts):
+            self.counts[int(species)] = int(n.value)
+        if int(species) == 0:
+            self.n = int(n.value)
+        return {"n": int(n.value), "capacity": int(cap.value), "id_span": int(span.value)}
+
+    def reserve(self, species, capacity):
+        """Raises the capacity of one species of a CART3D box to at least `capacity` particles (fpic_reserve) and returns the
+        capacity it has now; a smaller request changes nothing.  Every particle keeps its bits, its id and its slot."""
+        out = ctypes.c_uint64()
+        self._check(self._lib.fpic_reserve(self._h, int(species), int(capacity), ctypes.byref(out)))
+        return int(out.value)
+
+    def inject(self, kind="volume", **request):
+        """Adds, now, `count` particles to one species of a CART3D box (fpic_inject; an (r,z) handle and a decomposed handle
+        are refused), generated on the device by load()'s rule from the sequence numbers first .. first + count - 1:
+        kind="volume" — uniform in [lo, hi) or on the lattice, a drifting Maxwellian (species=, count=, first=, seed=,
+        stream=, lo=, hi=, drift=, vth=, lattice=, paired=, mode=, xamp=, xphase=, vamp=, vphase= as load() takes them) — or
+        kind="flux" — emission through the plane x[axis] = plane (metres) towards side = +1 / -1 with the flux-weighted
+        half-Maxwellian of vth[axis].  The new particles take the ids after the species' id span and the slots after its
+        particles; reserve() makes the room.  epoch= counts applications made before (a resumed registration).  Returns
+        {applications, injected, energy_fixed, momentum_fixed (exact integers, units of 2**-80), energy (J), momentum
+        (kg m/s), charge (C)}: what the species gained.  With the electrostatic solver the call re-deposits and re-solves;
+        under full EM the fields stay (inject a neutral pair on one seed, stream and sequence)."""
+        s = _inject_spec(self._box_lengths(), kind, **request)
+        out = InjectResult()
+        self._check(self._lib.fpic_inject(self._h, ctypes.byref(s), ctypes.byref(out)))
+        self.population(s.load.species)
+        return _inject_dict(out)
+
+    def injectEvery(self, period, kind="volume", **request):
+        """Registers a source (see inject) to run at the end of every `period`-th sub-step, after the sinks and before the
+        recorders: application k draws the sequence numbers first + (epoch + k) count + l.  Returns its index
+        (fpic_inject_register).  population() reads the count a source has changed."""
+        if isinstance(period, bool) or not isinstance(period, (int, np.integer)):
+            raise FusionPicError(-1, ".every <- must be an integer")
+        s = _inject_spec(self._box_lengths(), kind, **request)
+        index = ctypes.c_int(-1)
+        self._check(self._lib.fpic_inject_register(self._h, ctypes.byref(s), int(period), ctypes.byref(index)))
+        return index.value
+
+    def injectStats(self, index, scope="global"):
+        """the totals of a registered source since its registration (fpic_inject_stats)"""
+        out = InjectResult()
+        self._check(self._lib.fpic_inject_stats(self._h, int(index), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope], ctypes.byref(out)))
+        return _inject_dict(out)
+
+    def clearInjections(self):
+        """drops every registered source (fpic_inject_clear)"""
+        self._check(self._lib.fpic_inject_clear(self._h))
 
     # ---- the loader: a population generated on the device (fpic_load)
     def _box_lengths(self):
@@ -2097,11 +2215,22 @@ class ElectrostaticBoxPusher:
     def addB(self, bx, by, bz):
         self._check(self._lib.fpic_add_b(self._h, float(bx), float(by), float(bz)))
 
+    def _live(self, species):
+        """the particles the species holds now, from the library (fpic_population): sources and sinks change it behind the
+        wrapper; a species the handle does not have keeps the wrapper's own answer (the call then names the mistake)"""
+        n, span = ctypes.c_uint64(), ctypes.c_uint64()
+        if (isinstance(species, (int, np.integer)) and self._lib.fpic_population(self._h, int(species), ctypes.byref(n), None, ctypes.byref(span)) == 0
+                and span.value == n.value):      # (a thinned species has no caller's order: the library refuses the call by name)
+            self.counts[int(species)] = int(n.value)
+            if int(species) == 0:
+                self.n = int(n.value)
+        return self.counts[species]
+
     def set(self, value=None, species=0, **kw):
         """out.set({position, velocity, E}): positions in metres, velocities in units of c (empic.js:1199-1244);
         E is value[i][j][k][3] in V/m (a static field with solver 'none', or a field injected for a test)."""
         value = dict(value or {}, **kw)
-        n = self.counts[species]
+        n = self._live(species)
         for key in ("position", "velocity"):
             if value.get(key) is not None:
                 a = _as_float_array(value[key])
@@ -2168,13 +2297,13 @@ class ElectrostaticBoxPusher:
 
     def getParticles(self, dtype=None, species=0):
         code = self.precision if dtype is None else (F32 if np.dtype(dtype) == np.float32 else F64)
-        n = self.counts[species]
+        n = self._live(species)
         out = {"position": np.empty((n, 3), dtype=_np_dtype(code)), "velocity": np.empty((n, 3), dtype=_np_dtype(code))}
         self._check(self._lib.fpic_get_particles_of(self._h, species, out["position"].ctypes.data, out["velocity"].ctypes.data, code))
         return out
 
     def getCells(self, species=0):
-        out = np.empty(self.counts[species], dtype=np.int32)
+        out = np.empty(self._live(species), dtype=np.int32)
         self._check(self._lib.fpic_get_cells_of(self._h, species, out.ctypes.data))
         return out
 
@@ -2251,6 +2380,12 @@ class ElectrostaticBoxPusher:
     removeStats = CylindricalParticlePusher.removeStats
     clearRemovals = CylindricalParticlePusher.clearRemovals
     renumber = CylindricalParticlePusher.renumber
+    population = CylindricalParticlePusher.population
+    reserve = CylindricalParticlePusher.reserve
+    inject = CylindricalParticlePusher.inject
+    injectEvery = CylindricalParticlePusher.injectEvery
+    injectStats = CylindricalParticlePusher.injectStats
+    clearInjections = CylindricalParticlePusher.clearInjections
     collidePair = CylindricalParticlePusher.collidePair
     collidePairEvery = CylindricalParticlePusher.collidePairEvery
     pairStats = CylindricalParticlePusher.pairStats
@@ -2440,6 +2575,27 @@ class BoxGroup:
     def renumber(self, species=0):
         """refused, see remove"""
         raise FusionPicError(-5, _REMOVE_DECOMPOSED % "renumber")
+
+    def inject(self, kind="volume", **request):
+        """refused (FPIC_ERR_STATE), as by every member: a rank's arrivals ride on its next push and its message buffers were
+        sized from its capacity, so a source needs a protocol of its own there.  Inject before domainInit"""
+        raise FusionPicError(-5, _INJECT_DECOMPOSED % "inject")
+
+    def injectEvery(self, period, kind="volume", **request):
+        """refused, see inject"""
+        raise FusionPicError(-5, _INJECT_DECOMPOSED % "injectEvery")
+
+    def injectStats(self, index, scope="global"):
+        """refused, see inject"""
+        raise FusionPicError(-5, _INJECT_DECOMPOSED % "injectStats")
+
+    def clearInjections(self):
+        """refused, see inject"""
+        raise FusionPicError(-5, _INJECT_DECOMPOSED % "clearInjections")
+
+    def reserve(self, species=0, capacity=0):
+        """refused, see inject"""
+        raise FusionPicError(-5, _INJECT_DECOMPOSED % "reserve")
 
     def collidePair(self, a=0, b=None, **request):
         """refused (FPIC_ERR_STATE), as by every member: between two migrations the particles of a cell can sit on two

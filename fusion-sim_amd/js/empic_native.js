@@ -156,12 +156,20 @@ function makeBox(spec, lib) {
         spec.count || 0, fp64 ? 1 : 0, spec.device || 0, 0, spec.sort_interval || 0, 0, 0, 0, 0,
         1, spec.solver === 'none' ? 0 : (spec.solver === 'yee' ? 2 : 1), spec.ny, spec.length_y, spec.macro_weight === undefined ? 1 : spec.macro_weight, 0, 0);
     const nx = spec.nr, ny = spec.ny, nz = spec.nz, nodes = nx * ny * nz;
-    const counts = [n0];
+    const counts = [n0];      // per species: the particles it holds, as last learnt; on a rank of a decomposition its capacity
+    let decomposed = false;
+    // the particles a species holds NOW, from the library (fpic_population): registered sources and sinks change it inside step(),
+    // and the caller-order reads write that many rows.  A rank of a decomposition keeps its capacity; a library without the
+    // call keeps the count last learnt
+    const live = function (sp) {
+        if (!decomposed) { try { counts[sp] = lib.population(h, sp).n; } catch (err) { /* the call below names what is wrong */ } }
+        return counts[sp];
+    };
     const Real = fp64 ? Float64Array : Float32Array;
     const out = {};
     out.addSpecies = function (mass, charge, count) { const s = lib.addSpecies(h, mass, charge, count); counts.push(count); return s; };
     out.set = function (value, species) {                                      // empic.js:1157: position [N][3] m, velocity [N][3] in c
-        const sp = species || 0, n = counts[sp];
+        const sp = species || 0, n = live(sp);
         if (value.position) lib.setParticlesRange(h, sp, 0, flattenParticles(value.position, n, 'position'), null);
         if (value.velocity) lib.setParticlesRange(h, sp, 0, null, flattenParticles(value.velocity, n, 'velocity'));
         if (value.E) {
@@ -188,13 +196,13 @@ function makeBox(spec, lib) {
         return lib.readField3(h, FIELD3[name], checkLength(buf, len, 'out') || fresh);
     };
     out.getParticles = function (into, species) {
-        const sp = species || 0, n = counts[sp];
+        const sp = species || 0, n = live(sp);
         const r = into || { position: new Real(3 * n), velocity: new Real(3 * n) };
         checkLength(r.position, 3 * n, 'position'); checkLength(r.velocity, 3 * n, 'velocity');
         lib.getParticlesOf(h, sp, r.position || null, r.velocity || null);
         return r;
     };
-    out.getCells = function (buf, species) { const n = counts[species || 0]; return lib.getCellsOf(h, species || 0, checkLength(buf, n, 'cells') || new Int32Array(n)); };
+    out.getCells = function (buf, species) { const n = live(species || 0); return lib.getCellsOf(h, species || 0, checkLength(buf, n, 'cells') || new Int32Array(n)); };
     // the mirror of setRange, and a sampled read-back: the caller's particles first, first + stride, ... (count of them;
     // stride 1 = the range [first, first + count)); 2e9 particles do not fit one typed array
     out.getRange = function (first, count, into, species, stride) {
@@ -213,6 +221,7 @@ function makeBox(spec, lib) {
         const o = options || {};
         lib.domainInit(h, rank, world, o.ghost_planes === undefined ? 2 : o.ghost_planes, o.migrate_every === undefined ? 4 : o.migrate_every,
                        o.distributed_solve === 'interface' || o.distributed_solve === 2 ? 2 : (o.distributed_solve ? 1 : 0));
+        decomposed = true;      // (counts[] is the rank's capacity from now on: domainGet sizes its arrays by it)
     };
     out.domainSet = function (value, firstId, species) {
         const sp = species || 0;
@@ -314,12 +323,59 @@ function makeBox(spec, lib) {
         counts[sp] = n;      // (getParticles and set size their arrays by it)
         return n;
     };
-    // the loader (fpic_load): particles [first, first + count) of one species generated on the GPU.  request = { species, first,
-    // count (default: to the end), seed (an integer up to 2^53 or a BigInt up to 2^64), stream, lo, hi (metres; default the whole
-    // box), drift, vth (units of c), mode (three integers), xamp (metres), xphase, vamp (c), vphase (turns), lattice, paired,
-    // position, velocity (default true), append, density, thermal, shear (tabulated profiles along the axes: below) }; a number
-    // where three are expected is taken for all three -> the particles written (kept, on a rank of a decomposition)
-    out.load = function (request) {
+    // particle sources (fpic_reserve, fpic_population, fpic_inject*): a species gains particles generated on the GPU by load()'s
+    // rule.  request = load()'s keys (species, count: the particles per application, first: the sequence number of application
+    // 0, seed, stream, lo, hi, drift, vth, lattice, paired, mode, xamp, xphase, vamp, vphase) and kind: 'volume' (default) |
+    // 'flux', axis (0 .. 2), side (+1 | -1), plane (metres), epoch (applications made before: a resumed registration).
+    // inject -> { applications, injected, energyFixed, momentumFixed (BigInt, units of 2^-80 c^2 and c: what the species gained),
+    // energy (J), momentum (kg m/s), charge (C) }; injectEvery(period, request) -> the source's index (it runs after every
+    // period-th sub-step, after the sinks); injectStats(index, scope) -> its totals; clearInjections() drops every source;
+    // reserve(species, capacity) makes the room and returns the capacity; population(species) -> { n, capacity, id_span }
+    // (a registered source changes n behind the host: getParticles, getCells and set ask for it themselves)
+    const injectArgs = function (request) {
+        if (request === null || typeof request !== 'object' || Array.isArray(request)) throw new TypeError('.request <- expected { kind, species, count, first, seed, ... }');
+        const kind = request.kind === undefined || request.kind === 'volume' ? 0 : request.kind === 'flux' ? 1 : -1;
+        if (kind < 0) throw new RangeError(".kind <- must be 'volume' or 'flux'");
+        if (!Number.isInteger(request.count) || request.count < 0) throw new RangeError('.count <- expected the particles per application, a non-negative integer');
+        const int32 = function (name, v) {
+            if (v === undefined || v === null) v = 0;
+            if (!Number.isInteger(v) || v < -0x80000000 || v > 0x7fffffff) throw new RangeError('.' + name + ' <- expected a 32-bit integer');
+            return v;
+        };
+        const plane = request.plane === undefined || request.plane === null ? 0 : request.plane;
+        if (typeof plane !== 'number') throw new RangeError('.plane <- expected a number');
+        let epoch = request.epoch === undefined || request.epoch === null ? 0n : request.epoch;
+        if (typeof epoch === 'number' && Number.isInteger(epoch) && epoch >= 0) epoch = BigInt(epoch);
+        if (typeof epoch !== 'bigint' || epoch < 0n || epoch >= (1n << 64n)) throw new RangeError('.epoch <- expected a non-negative integer, or a BigInt up to 2^64');
+        const la = loadArgs(Object.assign({}, request, { position: true, velocity: true, append: false }));
+        return [la.species, Float64Array.from(la.words), Float64Array.from(la.reals), Float64Array.from([kind, int32('axis', request.axis), int32('side', request.side), plane, Number(epoch & 0xffffffffn), Number(epoch >> 32n)])];
+    };
+    out.inject = function (request) {
+        const a = injectArgs(request), r = lib.inject(h, a[0], a[1], a[2], a[3]);
+        live(a[0]);
+        return r;
+    };
+    out.injectEvery = function (period, request) {
+        if (!Number.isInteger(period)) throw new RangeError('.every <- must be an integer');
+        const a = injectArgs(request);
+        return lib.injectEvery(h, a[0], a[1], a[2], a[3], period);
+    };
+    out.injectStats = function (index, scope) {
+        if (!Number.isInteger(index)) throw new RangeError('.index <- must be an integer');
+        return lib.injectStats(h, index, scopeOf(scope));
+    };
+    out.clearInjections = function () { lib.clearInjections(h); };
+    out.reserve = function (species, capacity) {
+        if (!Number.isInteger(capacity) || capacity < 0) throw new RangeError('.capacity <- expected a non-negative integer');
+        return lib.reserve(h, species || 0, capacity);
+    };
+    out.population = function (species) {
+        const sp = species || 0, p = lib.population(h, sp);
+        if (!decomposed) counts[sp] = p.n;
+        return p;
+    };
+    // the loader's request as the addon takes it: { species, words, reals, three, whole, real } (load, inject)
+    const loadArgs = function (request) {
         if (request === null || typeof request !== 'object') throw new TypeError('.request <- expected { species, first, count, seed, ... }');
         const three = function (name, v, dflt) {
             if (v === undefined || v === null) v = dflt;
@@ -350,6 +406,15 @@ function makeBox(spec, lib) {
         const reals = [].concat(three('lo', request.lo, 0), three('hi', request.hi, [spec.radius, spec.length_y, spec.height]), three('drift', request.drift, 0),
             three('vth', request.vth, 0), three('xamp', request.xamp, 0), [real('xphase', request.xphase)], three('vamp', request.vamp, 0), [real('vphase', request.vphase)]);
         const species = whole('species', request.species, 0, 0, 0x7fffffff);
+        return { species: species, words: words, reals: reals, three: three, whole: whole, real: real };
+    };
+    // the loader (fpic_load): particles [first, first + count) of one species generated on the GPU.  request = { species, first,
+    // count (default: to the end), seed (an integer up to 2^53 or a BigInt up to 2^64), stream, lo, hi (metres; default the whole
+    // box), drift, vth (units of c), mode (three integers), xamp (metres), xphase, vamp (c), vphase (turns), lattice, paired,
+    // position, velocity (default true), append, density, thermal, shear (tabulated profiles along the axes: below) }; a number
+    // where three are expected is taken for all three -> the particles written (kept, on a rank of a decomposition)
+    out.load = function (request) {
+        const la = loadArgs(request), species = la.species, words = la.words, reals = la.reals, three = la.three, whole = la.whole, real = la.real;
         // profiles (fpic_load_profile): density, thermal = [x, y, z], each null or a table (an array of numbers or a typed array:
         // 2 .. 1025 nodes over [lo, hi] on its axis, linear between them); shear = { axis, component, values }.  Without any
         // of the three keys the call is fpic_load itself.

@@ -40,6 +40,7 @@ typedef struct {
     size_t nodes;
     int nspecies;
     size_t count[MAX_SPECIES];
+    int decomposed;   /* after domainInit count[] is the rank's CAPACITY (domainGetParticles), not a live count */
     /* the request fpic_series_record armed: how many entries a recorded row has (seriesHistory sizes its arrays by them) */
     size_t series_points, series_tracers;
     /* the request fpic_modes_record armed: the doubles of a recorded row (modesHistory sizes its array by them) */
@@ -93,6 +94,21 @@ static int get_args(napi_env env, napi_callback_info info, size_t want, napi_val
         g_box = b;
     }
     return 1;
+}
+
+/* The particles species sp of a CART3D box holds NOW, from the library (fpic_population): registered sources and sinks change it
+ * inside step(), and fpic_get_particles_of / fpic_get_cells_of write that many rows whatever the caller's array holds — so every
+ * caller-order length check asks first.  A rank of a decomposition keeps count[] as its capacity; a library without the symbol
+ * (the sanitizer build's stub) keeps the cached count. */
+#pragma weak fpic_population
+static size_t live_count(fpic_handle* h, int sp)
+{
+    uint64_t n = 0;
+    if (!g_box->decomposed && fpic_population && fpic_population(h, sp, &n, NULL, NULL) == FPIC_OK) {
+        g_box->count[sp] = (size_t)n;
+        if (sp == 0) g_box->n = (size_t)n;
+    }
+    return g_box->count[sp];
 }
 
 static int get_double(napi_env env, napi_value v, double* out)
@@ -167,6 +183,7 @@ static napi_value n_create(napi_env env, napi_callback_info info)
     b->nodes = b->cells * (size_t)(s.ny > 0 ? s.ny : 1);
     b->nspecies = 1;
     b->count[0] = b->n;
+    b->decomposed = 0;
     b->series_points = b->series_tracers = 0;
     b->modes_width = 0;
     napi_value ext;
@@ -503,7 +520,8 @@ static napi_value n_set_particles_range(napi_env env, napi_callback_info info)
     if (dtype < 0) return undefined(env);
     if (p[0] && p[1] && len[0] != len[1]) { napi_throw_range_error(env, NULL, ".velocity <- must be as long as .position"); return NULL; }
     const size_t m = (p[0] ? len[0] : len[1]) / 3;
-    if (first < 0 || (size_t)first > g_box->count[sp] || m > g_box->count[sp] - (size_t)first) {
+    const size_t live = live_count(h, sp);
+    if (first < 0 || (size_t)first > live || m > live - (size_t)first) {
         napi_throw_range_error(env, NULL, ".position <- range lies outside the species");
         return NULL;
     }
@@ -518,6 +536,7 @@ static napi_value n_get_particles_of(napi_env env, napi_callback_info info)
     if (!get_args(env, info, 4, argv, &h)) return NULL;
     if (!get_species(env, argv[1], &sp)) return NULL;
     napi_typedarray_type t[2]; void* p[2]; size_t len[2]; int dtype = FPIC_F32, have = 0;
+    const size_t live = live_count(h, sp);
     for (int k = 0; k < 2; ++k) {
         if (!get_typed(env, argv[2 + k], &t[k], &p[k], &len[k])) return NULL;
         if (!p[k]) continue;
@@ -525,7 +544,7 @@ static napi_value n_get_particles_of(napi_env env, napi_callback_info info)
         if (!float_dtype(env, t[k], &d2)) return NULL;
         if (have && d2 != dtype) { napi_throw_type_error(env, NULL, "position and velocity must have the same element type"); return NULL; }
         dtype = d2; have = 1;
-        if (!check_len(env, k == 0 ? "position" : "velocity", len[k], 3 * g_box->count[sp])) return NULL;
+        if (!check_len(env, k == 0 ? "position" : "velocity", len[k], 3 * live)) return NULL;
     }
     if (fpic_get_particles_of(h, sp, p[0], p[1], dtype) != FPIC_OK) return throw_fpic(env, h);
     return undefined(env);
@@ -550,7 +569,7 @@ static napi_value n_get_particles_range(napi_env env, napi_callback_info info)
     }
     if (dtype < 0) return undefined(env);
     if (p[0] && p[1] && len[0] != len[1]) { napi_throw_range_error(env, NULL, ".velocity <- must be as long as .position"); return NULL; }
-    const size_t m = (p[0] ? len[0] : len[1]) / 3, have = g_box->count[sp];
+    const size_t m = (p[0] ? len[0] : len[1]) / 3, have = live_count(h, sp);
     if (first < 0 || stride < 1 || (m && ((size_t)first >= have || (m - 1) > (have - 1 - (size_t)first) / (size_t)stride))) {
         napi_throw_range_error(env, NULL, ".position <- range lies outside the species");
         return NULL;
@@ -581,7 +600,7 @@ static napi_value n_get_cells_of(napi_env env, napi_callback_info info)
     napi_typedarray_type t; void* p; size_t len;
     if (!get_typed(env, argv[2], &t, &p, &len)) return NULL;
     if (!p || t != napi_int32_array) { napi_throw_type_error(env, NULL, "expected an Int32Array"); return NULL; }
-    if (!check_len(env, "cells", len, g_box->count[sp])) return NULL;
+    if (!check_len(env, "cells", len, live_count(h, sp))) return NULL;
     if (fpic_get_cells_of(h, sp, (int32_t*)p) != FPIC_OK) return throw_fpic(env, h);
     return argv[2];
 }
@@ -663,6 +682,7 @@ static napi_value n_domain_init(napi_env env, napi_callback_info info)
     for (int k = 0; k < 5; ++k)
         if (!get_double(env, argv[1 + k], &v[k])) return NULL;
     if (fpic_domain_init(h, (int)v[0], (int)v[1], (int)v[2], (int)v[3], (int)v[4]) != FPIC_OK) return throw_fpic(env, h);
+    g_box->decomposed = 1;
     return undefined(env);
 }
 
@@ -855,21 +875,17 @@ static napi_value n_histogram(napi_env env, napi_callback_info info)
     return out;
 }
 
-/* load(h, species, words: Float64Array [first, count (-1: to the end), seed low word, seed high word, stream, flags, mode x, y, z],
- * reals: Float64Array [lo 3, hi 3, drift 3, vth 3, xamp 3, xphase, vamp 3, vphase]) -> the particles written (kept on a rank of a
- * decomposition).  The arrays' lengths and the words' ranges are checked here, the request itself by the library.
- * load(h, species, words, reals, shape, tables): the same with the tables of a profile (fpic_load_profile; see below). */
-static napi_value n_load(napi_env env, napi_callback_info info)
+/* the loader's request from words: Float64Array [first, count (-1: to the end), seed low word, seed high word, stream, flags,
+ * mode x, y, z] and reals: Float64Array [lo 3, hi 3, drift 3, vth 3, xamp 3, xphase, vamp 3, vphase] (n_load, n_inject*) */
+static int load_spec_of(napi_env env, napi_value wv, napi_value rv, int sp, fpic_load_spec* s)
 {
-    napi_value argv[4]; fpic_handle* h; int sp;
-    if (!get_args(env, info, 4, argv, &h) || !get_species(env, argv[1], &sp)) return NULL;
     napi_typedarray_type tw, tr; void *pw, *pr; size_t lw, lr;
-    if (!get_typed(env, argv[2], &tw, &pw, &lw) || !get_typed(env, argv[3], &tr, &pr, &lr)) return NULL;
+    if (!get_typed(env, wv, &tw, &pw, &lw) || !get_typed(env, rv, &tr, &pr, &lr)) return 0;
     if (!pw || !pr || tw != napi_float64_array || tr != napi_float64_array) {
         napi_throw_type_error(env, NULL, ".request <- expected two Float64Arrays");
-        return NULL;
+        return 0;
     }
-    if (!check_len(env, "words", lw, 9) || !check_len(env, "reals", lr, 20)) return NULL;
+    if (!check_len(env, "words", lw, 9) || !check_len(env, "reals", lr, 20)) return 0;
     const double* w = (const double*)pw;
     const double* r = (const double*)pr;
     const double most[9] = { 18446744073709549568.0, 18446744073709549568.0, 4294967295.0, 4294967295.0, 4294967295.0, 4294967295.0, 2147483647.0, 2147483647.0, 2147483647.0 };
@@ -878,22 +894,34 @@ static napi_value n_load(napi_env env, napi_callback_info info)
         const double mag = w[k] < 0 ? -w[k] : w[k];
         if (!(w[k] >= least && w[k] <= most[k]) || mag != (double)(uint64_t)mag) {
             napi_throw_range_error(env, NULL, ".request <- first, count, seed, stream and mode must be integers within their fields");
-            return NULL;
+            return 0;
         }
     }
-    fpic_load_spec s;
-    memset(&s, 0, sizeof s);
-    s.species = sp;
-    s.first = (uint64_t)w[0];
-    s.count = w[1] < 0 ? ~(uint64_t)0 : (uint64_t)w[1];
-    s.seed = (uint64_t)(uint32_t)w[2] | (uint64_t)(uint32_t)w[3] << 32;
-    s.stream = (uint32_t)w[4];
-    s.flags = (uint32_t)w[5];
+    memset(s, 0, sizeof *s);
+    s->species = sp;
+    s->first = (uint64_t)w[0];
+    s->count = w[1] < 0 ? ~(uint64_t)0 : (uint64_t)w[1];
+    s->seed = (uint64_t)(uint32_t)w[2] | (uint64_t)(uint32_t)w[3] << 32;
+    s->stream = (uint32_t)w[4];
+    s->flags = (uint32_t)w[5];
     for (int a = 0; a < 3; ++a) {
-        s.mode[a] = (int32_t)w[6 + a];
-        s.lo[a] = r[a]; s.hi[a] = r[3 + a]; s.drift[a] = r[6 + a]; s.vth[a] = r[9 + a]; s.xamp[a] = r[12 + a]; s.vamp[a] = r[16 + a];
+        s->mode[a] = (int32_t)w[6 + a];
+        s->lo[a] = r[a]; s->hi[a] = r[3 + a]; s->drift[a] = r[6 + a]; s->vth[a] = r[9 + a]; s->xamp[a] = r[12 + a]; s->vamp[a] = r[16 + a];
     }
-    s.xphase = r[15]; s.vphase = r[19];
+    s->xphase = r[15]; s->vphase = r[19];
+    return 1;
+}
+
+/* load(h, species, words: Float64Array [first, count (-1: to the end), seed low word, seed high word, stream, flags, mode x, y, z],
+ * reals: Float64Array [lo 3, hi 3, drift 3, vth 3, xamp 3, xphase, vamp 3, vphase]) -> the particles written (kept on a rank of a
+ * decomposition).  The arrays' lengths and the words' ranges are checked here, the request itself by the library.
+ * load(h, species, words, reals, shape, tables): the same with the tables of a profile (fpic_load_profile; see below). */
+static napi_value n_load(napi_env env, napi_callback_info info)
+{
+    napi_value argv[4]; fpic_handle* h; int sp;
+    if (!get_args(env, info, 4, argv, &h) || !get_species(env, argv[1], &sp)) return NULL;
+    fpic_load_spec s;
+    if (!load_spec_of(env, argv[2], argv[3], sp, &s)) return NULL;
     uint64_t loaded = 0;
     /* the optional tables of a profiled load (fpic_load_profile): shape: Float64Array [density nodes x, y, z, thermal nodes x, y, z,
      * shear nodes, shear axis, shear component], tables: Float64Array, the tables one after the other in that order.  The
@@ -1362,37 +1390,44 @@ static int get_remove_spec(napi_env env, const napi_value* argv, fpic_remove_spe
     return 1;
 }
 
-static napi_value remove_object(napi_env env, const fpic_remove_result* c)
+/* the object of a sink's or a source's result: its counts under their names, then the exact tallies and their doubles */
+static napi_value tally_object(napi_env env, int ncounts, const char* const* names, const uint64_t* counts, const uint64_t* energy_fixed,
+                               const uint64_t (*momentum_fixed)[2], double energy, const double* momentum, double charge)
 {
     napi_value o, v, arr;
     NAPI_OK(env, napi_create_object(env, &o));
-    const char* names[3] = { "applications", "scanned", "removed" };
-    const uint64_t counts[3] = { c->applications, c->scanned, c->removed };
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < ncounts; ++k) {
         NAPI_OK(env, napi_create_double(env, (double)counts[k], &v));
         NAPI_OK(env, napi_set_named_property(env, o, names[k], v));
     }
-    v = fixed_bigint(env, c->energy_fixed);
+    v = fixed_bigint(env, energy_fixed);
     if (!v) return NULL;
     NAPI_OK(env, napi_set_named_property(env, o, "energyFixed", v));
     NAPI_OK(env, napi_create_array_with_length(env, 3, &arr));
     for (uint32_t a = 0; a < 3; ++a) {
-        v = fixed_bigint(env, c->momentum_fixed[a]);
+        v = fixed_bigint(env, momentum_fixed[a]);
         if (!v) return NULL;
         NAPI_OK(env, napi_set_element(env, arr, a, v));
     }
     NAPI_OK(env, napi_set_named_property(env, o, "momentumFixed", arr));
-    NAPI_OK(env, napi_create_double(env, c->energy, &v));
+    NAPI_OK(env, napi_create_double(env, energy, &v));
     NAPI_OK(env, napi_set_named_property(env, o, "energy", v));
     NAPI_OK(env, napi_create_array_with_length(env, 3, &arr));
     for (uint32_t a = 0; a < 3; ++a) {
-        NAPI_OK(env, napi_create_double(env, c->momentum[a], &v));
+        NAPI_OK(env, napi_create_double(env, momentum[a], &v));
         NAPI_OK(env, napi_set_element(env, arr, a, v));
     }
     NAPI_OK(env, napi_set_named_property(env, o, "momentum", arr));
-    NAPI_OK(env, napi_create_double(env, c->charge, &v));
+    NAPI_OK(env, napi_create_double(env, charge, &v));
     NAPI_OK(env, napi_set_named_property(env, o, "charge", v));
     return o;
+}
+
+static napi_value remove_object(napi_env env, const fpic_remove_result* c)
+{
+    const char* names[3] = { "applications", "scanned", "removed" };
+    const uint64_t counts[3] = { c->applications, c->scanned, c->removed };
+    return tally_object(env, 3, names, counts, c->energy_fixed, c->momentum_fixed, c->energy, c->momentum, c->charge);
 }
 
 /* remove(h, species, axes, ranges, idMod, idRem, outside) -> { applications, scanned, removed, energyFixed, momentumFixed, energy, momentum, charge } */
@@ -1454,6 +1489,121 @@ static napi_value n_renumber(napi_env env, napi_callback_info info)
     napi_value v;
     NAPI_OK(env, napi_create_double(env, (double)n, &v));
     return v;
+}
+
+/* ---- particle sources (fpic_reserve, fpic_population, fpic_inject*) */
+
+/* the request of inject / injectEvery: species, words, reals as load takes them, extra: Float64Array [kind, axis, side, plane,
+ * epoch low word, epoch high word] */
+static int get_inject_spec(napi_env env, const napi_value* argv, fpic_inject_spec* s)
+{
+    int sp;
+    memset(s, 0, sizeof *s);
+    if (!get_species(env, argv[1], &sp) || !load_spec_of(env, argv[2], argv[3], sp, &s->load)) return 0;
+    napi_typedarray_type te; void* pe; size_t le;
+    if (!get_typed(env, argv[4], &te, &pe, &le)) return 0;
+    if (!pe || te != napi_float64_array) { napi_throw_type_error(env, NULL, ".request <- expected a Float64Array of the source's own fields"); return 0; }
+    if (!check_len(env, "extra", le, 6)) return 0;
+    const double* e = (const double*)pe;
+    for (int k = 0; k < 6; ++k) {
+        if (k == 3) continue;
+        const double least = k < 3 ? -2147483648.0 : 0.0, most = k < 3 ? 2147483647.0 : 4294967295.0;
+        if (!(e[k] >= least && e[k] <= most) || e[k] != (double)(int64_t)e[k]) {
+            napi_throw_range_error(env, NULL, ".request <- kind, axis, side and epoch must be integers within their fields");
+            return 0;
+        }
+    }
+    s->kind = (int32_t)e[0]; s->axis = (int32_t)e[1]; s->side = (int32_t)e[2];
+    s->plane = e[3];
+    s->epoch = (uint64_t)(uint32_t)e[4] | (uint64_t)(uint32_t)e[5] << 32;
+    return 1;
+}
+
+static napi_value inject_object(napi_env env, const fpic_inject_result* c)
+{
+    const char* names[2] = { "applications", "injected" };
+    const uint64_t counts[2] = { c->applications, c->injected };
+    return tally_object(env, 2, names, counts, c->energy_fixed, c->momentum_fixed, c->energy, c->momentum, c->charge);
+}
+
+/* inject(h, species, words, reals, extra) -> { applications, injected, energyFixed, momentumFixed, energy, momentum, charge } */
+static napi_value n_inject(napi_env env, napi_callback_info info)
+{
+    napi_value argv[5]; fpic_handle* h;
+    fpic_inject_spec s;
+    if (!get_args(env, info, 5, argv, &h) || !get_inject_spec(env, argv, &s)) return NULL;
+    fpic_inject_result c;
+    memset(&c, 0, sizeof c);
+    if (fpic_inject(h, &s, &c) != FPIC_OK) return throw_fpic(env, h);
+    (void)live_count(h, s.load.species);
+    return inject_object(env, &c);
+}
+
+/* injectEvery(h, species, words, reals, extra, period) -> the source's index */
+static napi_value n_inject_every(napi_env env, napi_callback_info info)
+{
+    napi_value argv[6]; fpic_handle* h; double every;
+    fpic_inject_spec s;
+    if (!get_args(env, info, 6, argv, &h) || !get_inject_spec(env, argv, &s) || !get_double(env, argv[5], &every)) return NULL;
+    if (!(every >= -2147483648.0 && every <= 2147483647.0) || every != (double)(int)every) { napi_throw_range_error(env, NULL, ".every <- must be a 32-bit integer"); return NULL; }
+    int index = -1;
+    if (fpic_inject_register(h, &s, (int)every, &index) != FPIC_OK) return throw_fpic(env, h);
+    napi_value v;
+    NAPI_OK(env, napi_create_int32(env, index, &v));
+    return v;
+}
+
+/* injectStats(h, index, scope) -> as inject */
+static napi_value n_inject_stats(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3]; fpic_handle* h; double index; int scope;
+    if (!get_args(env, info, 3, argv, &h) || !get_double(env, argv[1], &index) || !get_scope(env, argv[2], &scope)) return NULL;
+    if (!(index >= -2147483648.0 && index <= 2147483647.0) || index != (double)(int)index) { napi_throw_range_error(env, NULL, ".index <- must be a 32-bit integer"); return NULL; }
+    fpic_inject_result c;
+    memset(&c, 0, sizeof c);
+    if (fpic_inject_stats(h, (int)index, scope, &c) != FPIC_OK) return throw_fpic(env, h);
+    return inject_object(env, &c);
+}
+
+/* clearInjections(h) */
+static napi_value n_clear_injections(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1]; fpic_handle* h;
+    if (!get_args(env, info, 1, argv, &h)) return NULL;
+    if (fpic_inject_clear(h) != FPIC_OK) return throw_fpic(env, h);
+    return undefined(env);
+}
+
+/* reserve(h, species, capacity) -> the capacity the species has now */
+static napi_value n_reserve(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3]; fpic_handle* h; int sp; double cap;
+    if (!get_args(env, info, 3, argv, &h) || !get_species(env, argv[1], &sp) || !get_double(env, argv[2], &cap)) return NULL;
+    if (!(cap >= 0 && cap <= 18446744073709549568.0) || cap != (double)(uint64_t)cap) { napi_throw_range_error(env, NULL, ".capacity <- must be a non-negative integer"); return NULL; }
+    uint64_t got = 0;
+    if (fpic_reserve(h, sp, (uint64_t)cap, &got) != FPIC_OK) return throw_fpic(env, h);
+    napi_value v;
+    NAPI_OK(env, napi_create_double(env, (double)got, &v));
+    return v;
+}
+
+/* population(h, species) -> { n, capacity, id_span } */
+static napi_value n_population(napi_env env, napi_callback_info info)
+{
+    napi_value argv[2]; fpic_handle* h; int sp;
+    if (!get_args(env, info, 2, argv, &h) || !get_species(env, argv[1], &sp)) return NULL;
+    uint64_t w[3] = { 0, 0, 0 };
+    if (!fpic_population) { napi_throw_error(env, NULL, "this libfusionpic has no fpic_population"); return NULL; }
+    if (fpic_population(h, sp, &w[0], &w[1], &w[2]) != FPIC_OK) return throw_fpic(env, h);
+    (void)live_count(h, sp);   /* (a rank of a decomposition keeps count[] as its capacity) */
+    const char* names[3] = { "n", "capacity", "id_span" };
+    napi_value o, v;
+    NAPI_OK(env, napi_create_object(env, &o));
+    for (int k = 0; k < 3; ++k) {
+        NAPI_OK(env, napi_create_double(env, (double)w[k], &v));
+        NAPI_OK(env, napi_set_named_property(env, o, names[k], v));
+    }
+    return o;
 }
 
 /* the request of collidePair / collidePairEvery: words: Float64Array [species_a, species_b, seed low word, seed high word,
@@ -2057,6 +2207,8 @@ static napi_value init(napi_env env, napi_value exports)
         { "force", n_force }, { "forceOn", n_force_on }, { "forceStats", n_force_stats }, { "clearForces", n_clear_forces },
         { "collideGas", n_collide_gas }, { "collideGasEvery", n_collide_gas_every }, { "gasStats", n_gas_stats }, { "clearGas", n_clear_gas },
         { "remove", n_remove }, { "removeEvery", n_remove_every }, { "removeStats", n_remove_stats }, { "clearRemovals", n_clear_removals }, { "renumber", n_renumber },
+        { "inject", n_inject }, { "injectEvery", n_inject_every }, { "injectStats", n_inject_stats }, { "clearInjections", n_clear_injections },
+        { "reserve", n_reserve }, { "population", n_population },
         { "collidePair", n_collide_pair }, { "collidePairEvery", n_collide_pair_every }, { "pairStats", n_pair_stats }, { "clearPairs", n_clear_pairs },
         { "fusionYield", n_fusion_yield }, { "fusionYieldEvery", n_fusion_yield_every }, { "fusionStats", n_fusion_stats }, { "fusionGrid", n_fusion_grid }, { "clearFusion", n_clear_fusion },
         { "fusionSpectrum", n_fusion_spectrum }, { "fusionSpectrumEvery", n_fusion_spectrum_every }, { "fusionSpectrumRead", n_fusion_spectrum_read }, { "clearFusionSpectra", n_clear_fusion_spectra },

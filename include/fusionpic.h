@@ -1354,6 +1354,106 @@ int fpic_remove_stats(fpic_handle* h, int index, int scope, fpic_remove_result* 
 int fpic_remove_clear(fpic_handle* h);
 int fpic_renumber(fpic_handle* h, int species, uint64_t* n);
 
+/* ---- CART3D particle sources: ONE species of an undecomposed handle gains particles that are generated on the device by
+ * the loader's counter-based rule — a beam into a target plasma, an emitting wall or electrode, the refilling bulk of a
+ * sheath, an ionisation source against a limiter, a pellet or a gas puff.  The counterpart of fpic_remove.
+ * Capacity.  fpic_reserve raises the capacity of a species (the particles its arrays hold; it starts as the count given to
+ * fpic_create / fpic_add_species) to at least `capacity` and reports the capacity it has now; a smaller request changes
+ * nothing.  Every particle keeps its bits, its id and its slot, the fields and their readiness stay; the species is left
+ * as an upload leaves one (the next sub-step bins it again).  Synchronous; the old arrays are freed.  Refused
+ * (FPIC_ERR_INVALID_ARG): a capacity whose ids would not fit in 32 bits (2^32 - 4096 and above, fpic_add_species's bound).
+ * fpic_population reads n (the live particles), the capacity and the id span (one past the largest id the species can
+ * hold: n unless fpic_remove has thinned it) of a species on the host; any of the three pointers may be null.  It also
+ * works on a rank of a decomposition, where it reports the rank's numbers.  A registered source changes n behind the
+ * caller's back: this is how a host learns it.
+ * The request.  fpic_inject_spec embeds a fpic_load_spec: species, seed, stream, lo, hi, drift, vth, mode, xamp, xphase,
+ * vamp, vphase and the flags LATTICE and PAIRED mean what they mean to fpic_load, and the embedded request passes
+ * fpic_load's own checks.  FPIC_LOAD_POS | FPIC_LOAD_VEL are both required, FPIC_LOAD_APPEND is refused, count must be
+ * given (~0 is refused).  load.count = the particles per application, load.first = the SEQUENCE NUMBER of the first
+ * particle of application 0.  Application k (k = epoch + the applications this registration has made; fpic_inject itself
+ * is application `epoch`) generates the sequence numbers j = first + k count + l, l < count.  j is the loader's index i:
+ * the first Philox counter word and the lattice index.  A host that resumes a run registers again with epoch = the
+ * applications made so far.  Every application keeps fpic_load's bound on 32-bit indices, first_k + count <= 2^32 - 1: application
+ * 0 that breaks it is refused with the request, a later one returns FPIC_ERR_STATE.
+ * Ids and slots.  Particle l of an application takes the id (id span) + l and the slot n + l of the live set; n and — on a
+ * thinned species — the id span grow by count.  A species that is not thinned stays not thinned, ids 0 .. n-1: the
+ * caller-order calls and the checkpoint keep working on the grown species.  An application that does not fit
+ * (n + count > capacity, or id span + count > 2^32 - 1) changes nothing: fpic_inject returns FPIC_ERR_INVALID_ARG (call
+ * fpic_reserve first), a registered application makes the step return FPIC_ERR_STATE.
+ * All arithmetic below is double, every operation rounded once; an fp32 handle stores the float rounding.
+ *   kind = FPIC_INJECT_VOLUME   position and velocity of sequence number j are EXACTLY fpic_load's for i = j (see there:
+ *              words, fractions, position with its displacement and wrap, Box-Muller velocity, PAIRED): uniform in the
+ *              window [lo, hi) or on the Kronecker lattice, a drifting Maxwellian.  fpic_inject(first = N, count = m)
+ *              into a species of N equals fpic_load(first = N, count = m) into a species of N + m, bit for bit.  Two
+ *              species fed the same seed, stream and sequence coincide exactly: an electron-ion source creates no net
+ *              charge.  axis, side and plane must be zero.
+ *   kind = FPIC_INJECT_FLUX     emission through the plane x[axis] = plane (metres) towards side = +1 or -1, the
+ *              flux-weighted half-Maxwellian of thermal speed vth[axis].  With t1 < t2 the two other axes:
+ *              words      W(0) = (w0, w1, w2, .) and W(1) = (u0, u1, u2, u3) as fpic_load (or the lattice words for W(0))
+ *              tangential p_t = lo[t]/L_t + (w_t 2^-32) (hi[t] - lo[t])/L_t for t = t1, t2 (one multiply, one add)
+ *              time       f_t = w_axis 2^-32: the fraction of the step the particle has already flown
+ *              normals    n0 = sqrt(-2 ln((u0 + 0.5) 2^-32)) cospi(2 u1 2^-32), n1 = the same radius times
+ *                         sinpi(2 u1 2^-32) (fpic_load's n0, n1); s = sqrt(-2 ln((u2 + 0.5) 2^-32)), a Rayleigh deviate
+ *                         (fpic_load's radius of n2), 0 < s <= 6.76
+ *              velocity   v_t1 = drift[t1] + vth[t1] n0, v_t2 = drift[t2] + vth[t2] n1 (one multiply, one add each),
+ *                         v_axis = side (vth[axis] s)
+ *              normal     p_axis = plane/L_axis + (v_axis (dt c / L_axis)) f_t (two multiplies, one add), dt the handle's
+ *                         step and c = 2.998e8 as the push has them; stored cast and wrapped into [0, 1) as every position
+ *              lo[axis], hi[axis] must be a valid interval and are not used.  Refused for FLUX: an axis outside 0 .. 2, a
+ *              side that is not +1 or -1, a plane outside [0, L_axis] or not finite, drift[axis] != 0, PAIRED, any
+ *              non-zero xamp, vamp or mode.
+ * The result: applications; injected; energy_fixed, momentum_fixed[a]: exact sums in the fixed point of the energy
+ * diagnostics (units of 2^-80, 128-bit two's complement, low word first) of floor(|v|^2 2^80) and floor(v[a] 2^80) over the
+ * new particles, from the STORED velocity (after the rounding to the handle's precision), by fpic_energy's rule (a term >=
+ * 2^15 in magnitude or not finite adds nothing and makes its double NaN) — what the species GAINED: fpic_energy_now after
+ * the call minus before it, word for word.  energy, momentum[a] and charge = injected x the species' charge x macro_weight
+ * as fpic_remove_result has them.
+ * fpic_inject applies the request now (synchronous) and returns its result (applications 1).  fpic_inject_register makes
+ * it run at the end of every sub-step with substep % every == 0, after the registered sinks and before the recorders: a
+ * sink registered beside a source leaves that sub-step's fresh particles alive, and the recorded rows count them.
+ * Sources run in registration order, at most FPIC_INJECT_MAX_OPS of them; *index names the source.  No count is read back:
+ * the host knows n + count in advance.  fpic_inject_stats reads the totals since registration (scope: LOCAL or GLOBAL, the
+ * same on an undecomposed handle), fpic_inject_clear drops every registered source.  Registrations are not part of a
+ * checkpoint.  count = 0 and an application that is not due change nothing and launch nothing.
+ * What an application leaves: n raised, the species as an upload leaves one (nothing binned, no census: the next sub-step
+ * bins the WHOLE species again).  Electrostatic solver (poisson_fft): if the fields were ready the call itself deposits the
+ * grown population and solves, so the next sub-step gathers its field; fields that were not ready stay so.  Full EM (yee):
+ * E, B and the readiness stay — a charge that appears without a current is a static source in the lattice E, Gauss's law
+ * is not re-imposed; inject a neutral pair of species on one seed, stream and sequence instead.
+ * A checkpoint of a grown, unthinned species is saved as any other and restores into a handle whose species has the
+ * capacity (fpic_reserve first): the restored count is the file's.
+ * fpic_renumber is refused while a source is registered, as for every registered operator.
+ * Refused (FPIC_ERR_INVALID_ARG): a null spec, what fpic_load refuses of the embedded request, the flag and count rules
+ * above, an unknown kind, the FLUX rules above, VOLUME with a non-zero axis, side or plane, a reserved word that is not
+ * zero, every below 1, a ninth registration, an index outside the registered sources, a null out of fpic_inject_stats;
+ * FPIC_ERR_STATE: a handle that is not CART3D; a decomposed handle (fpic_reserve and the four fpic_inject calls: a rank's
+ * arrivals ride on its next push and its message buffers were sized from the capacity). */
+#define FPIC_INJECT_VOLUME   0
+#define FPIC_INJECT_FLUX     1
+#define FPIC_INJECT_MAX_OPS  8
+typedef struct fpic_inject_spec {
+    fpic_load_spec load;        /* count: particles per application; first: the sequence number of application 0 */
+    int32_t  kind;              /* FPIC_INJECT_VOLUME or FPIC_INJECT_FLUX */
+    int32_t  axis, side;        /* FLUX: 0 .. 2; +1 or -1 */
+    int32_t  reserved_i;        /* zero */
+    double   plane;             /* FLUX: metres, within [0, L_axis] */
+    uint64_t epoch;             /* the applications made before this registration (a resumed run) */
+    double   reserved[4];       /* zero */
+} fpic_inject_spec;
+typedef struct fpic_inject_result {
+    uint64_t applications, injected;
+    uint64_t energy_fixed[2];      /* low word, high word */
+    uint64_t momentum_fixed[3][2];
+    double   energy, momentum[3];  /* J; kg m/s: what the species gained */
+    double   charge;               /* C */
+} fpic_inject_result;
+int fpic_reserve(fpic_handle* h, int species, uint64_t capacity, uint64_t* capacity_out);
+int fpic_population(fpic_handle* h, int species, uint64_t* n, uint64_t* capacity, uint64_t* id_span);
+int fpic_inject(fpic_handle* h, const fpic_inject_spec* spec, fpic_inject_result* out);
+int fpic_inject_register(fpic_handle* h, const fpic_inject_spec* spec, int every, int* index);
+int fpic_inject_stats(fpic_handle* h, int index, int scope, fpic_inject_result* out);
+int fpic_inject_clear(fpic_handle* h);
+
 int fpic_sync(fpic_handle* h);
 int fpic_profile(fpic_handle* h, int enable);
 int fpic_get_stats(fpic_handle* h, fpic_stats* out);
