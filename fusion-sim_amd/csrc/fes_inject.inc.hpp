@@ -16,8 +16,9 @@
 // column with its ids, the tables sized by the capacity (the work lists, the per-item census) allocated anew, the old ones
 // freed.  Who else reads cap, n_pad or work_cap: the joint work list sizes itself from the species' cap at every launch and
 // regrows (ensure_joint_list; its signature is cleared here), EmPushArgs in Species::em_args are stored anew by every
-// full-EM launch, the kernels' arguments are formed per launch from the Species, and the message buffers of a decomposition
-// (fpic_domain_init) are sized when it is made — after which fpic_reserve is refused.
+// full-EM launch, the kernels' arguments are formed per launch from the Species, the cell index of the binary operators
+// (fpic_pair, fpic_fusion, fpic_fusion_spectrum) is sized from n_pad when one is registered and regrown by reserve() itself,
+// and the message buffers of a decomposition (fpic_domain_init) are sized when it is made — after which fpic_reserve is refused.
 
 // the handle's device block, rows of kDiagWords words: the sources' totals, the row of the last application, the generation
 // pass's partial rows
@@ -280,6 +281,26 @@ int reserve(fpic_handle* h, int species, uint64_t capacity, uint64_t* capacity_o
     Species& s = st->sp[species];
     if (capacity > s.cap) {
         if (const char* why = fesinj::check_capacity(capacity)) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+        // the cell index of the binary operators (fes_pair.inc.hpp; the fusion tallies and spectra share it) holds one slot word
+        // per padded particle and is sized when an operator is registered: the hook never grows it (growing waits for the
+        // stream) and refuses a species it finds larger.  This call is synchronous, so the index buffers that exist follow the
+        // new stride here, and an operator registered before the reserve finds them large enough at its next application.
+        // They grow FIRST, and each new buffer is allocated before the old one is freed: an allocation that fails leaves the
+        // species, the index and every registered operator with what they had (a buffer that has already grown stays larger
+        // than it need be, which nobody reads).  Both sides follow whichever species grows — a side serves species a or b of
+        // any request, so the side that never indexes this species is over-allocated by 4 bytes per slot, knowingly
+        Diag& g = st->diag;
+        const size_t n_pad = (static_cast<size_t>(capacity) + 1023) / 1024 * 1024;   // (reserve_run's stride)
+        for (int k = 0; k < 2; ++k) {
+            if (!g.pair_index[k] || g.pair_index_words[k] >= n_pad) continue;
+            void* fresh = nullptr;
+            if (int rc = dev_alloc(h, &fresh, n_pad * sizeof(uint32_t), &h->bytes_grid)) return rc;
+            HIP_TRY(h, hipStreamSynchronize(h->stream));
+            HIP_TRY(h, hipFree(g.pair_index[k]));
+            h->bytes_grid -= g.pair_index_words[k] * sizeof(uint32_t);
+            g.pair_index[k] = static_cast<uint32_t*>(fresh);
+            g.pair_index_words[k] = n_pad;
+        }
         if (int rc = h->prec == FPIC_F32 ? reserve_run<float>(h, s, static_cast<size_t>(capacity)) : reserve_run<double>(h, s, static_cast<size_t>(capacity))) return rc;
     }
     if (capacity_out) *capacity_out = s.cap;

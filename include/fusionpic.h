@@ -1360,7 +1360,9 @@ int fpic_renumber(fpic_handle* h, int species, uint64_t* n);
  * Capacity.  fpic_reserve raises the capacity of a species (the particles its arrays hold; it starts as the count given to
  * fpic_create / fpic_add_species) to at least `capacity` and reports the capacity it has now; a smaller request changes
  * nothing.  Every particle keeps its bits, its id and its slot, the fields and their readiness stay; the species is left
- * as an upload leaves one (the next sub-step bins it again).  Synchronous; the old arrays are freed.  Refused
+ * as an upload leaves one (the next sub-step bins it again).  Synchronous; the old arrays are freed.  Operators registered
+ * before the call keep running: the cell index that fpic_pair_register, fpic_fusion_register and
+ * fpic_fusion_spectrum_register size from the species follows the new capacity here.  Refused
  * (FPIC_ERR_INVALID_ARG): a capacity whose ids would not fit in 32 bits (2^32 - 4096 and above, fpic_add_species's bound).
  * fpic_population reads n (the live particles), the capacity and the id span (one past the largest id the species can
  * hold: n unless fpic_remove has thinned it) of a species on the host; any of the three pointers may be null.  It also

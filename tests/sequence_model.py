@@ -925,3 +925,541 @@ def resume_scene2(solver, precision):
     sc["generation"] = 2
     _registered2(sc, np.random.default_rng([0x5CE92, 1000]), every=[RESUME2_EVERY["gas"], RESUME2_EVERY["fusion"], RESUME2_EVERY["spectrum"]], envelope=RESUME2_ENVELOPE)
     return sc
+
+
+# ================================================================================================ generation 3
+# The sinks and the sources (remove, removeEvery, renumber, inject, injectEvery, reserve, population) under the random call
+# sequences (tests/test_gpu_sequences3.py): the only operators that change a species' count, its id span and its capacity.
+# Generations 1 and 2 above stay what they are (pinned by digests).  The scene of a generation-3 seed is the generation-2
+# scene of that seed ON A BOX OF UNIT EDGES: select() then returns the stored values exactly (metres = box fractions), so its
+# rows feed the numpy references and an upload without rounding.  What follows from the edge lengths is scaled with them:
+# the electrostatic dt is 5e-9 (the fast fifth of particles() still crosses more than a cell per sub-step), the full-EM dt is
+# em_dt's; the number density is 1e9 m^-3, so that omega_p dt is what it was on the millimetre box (0.009: at 1e15 m^-3 it
+# would be 9, and the leapfrog would run away to infinities within a sequence); macro_weight, dv and the pair times are
+# recomputed from it; the given field of a `none` scene and the amplitudes of the forces are scaled by dt_old / dt (the kick
+# per sub-step stays), the density of a windowed background by tau_old / tau (the candidates stay), the fusion tables by
+# (tau W / dv)_old / (tau W / dv) (the yields stay).
+#
+# A removal's count depends on the pushes, so the CPU cannot know n after the first remove: every parameter that depends on
+# n is carried as a fraction or a rule and resolved by the replay against population() just before the call (resolve_range,
+# resolve_tracers, resolve_inject).  What the CPU does know is WHICH species are thinned: a step carries `thinned` (the
+# species thinned before it) and `thinned_after`; a caller-order operation or read on a thinned species carries
+# refused=True — the replay expects the refusal by name with nothing changed, and holds the model's `thinned` against
+# population() at every step.
+L3 = (1.0, 1.0, 1.0)
+DT3 = 5e-9
+DENSITY3 = 1e9
+REMOVE_KINDS3 = ("remove_window", "remove_outside", "remove_thinned_by_id")          # the removals that must take somebody
+INJECT_KINDS3 = ("inject_volume", "inject_flux", "inject_pair")
+NEW_KINDS3 = REMOVE_KINDS3 + ("remove_nothing",) + INJECT_KINDS3 + ("inject_refused", "reserve", "renumber")
+STATE_KINDS3 = STATE_KINDS2 + NEW_KINDS3
+STATS_KINDS3 = STATS_KINDS2 + ("removeStats", "injectStats")
+CALLER_ORDER_KINDS3 = ("set", "setRange", "load", "load_profile", "load_radial")     # refused on a thinned species
+CALLER_ORDER_READS3 = ("getParticles", "getRange", "getCells")                       # refused on a thinned species; saveCheckpoint: on any
+UNBINNING_KINDS3 = REMOVE_KINDS3 + INJECT_KINDS3 + ("reserve",)                      # leave a species as an upload leaves one
+ID_PRIMES3 = (2, 3, 5, 7)       # the moduli of remove_thinned_by_id: none is used twice on a species (classes of different primes always meet)
+READS3 = 4
+
+# chosen by tests/test_sequence_model.py's conditions (coverage, no vacuous removal on the initial particles); none is
+# skipped at run time.  The replay asserts 0 < removed < n for every removal of REMOVE_KINDS3 on the GPU: a seed that fails
+# that there is to be replaced by another one, not skipped, and the replacement noted here.
+SEEDS3 = [8, 24, 82, 89, 176, 648, 1986, 2568, 3060, 3317, 3975, 4778]
+
+
+def particles3(seed, tag, n):
+    return particles(seed, tag, n, lengths=L3)
+
+
+def given_field3(seed):
+    return given_field(seed) * (5e-12 / DT3)
+
+
+def _unit_box(kw):
+    """lo, hi of a request drawn on the millimetre box, in the unit box"""
+    for key in ("lo", "hi"):
+        if key in kw:
+            kw[key] = [float(kw[key][a] / L[a]) for a in range(3)]
+    return kw
+
+
+def _to_unit(sc):
+    """a generation-1/2 scene on the box of unit edges (see the head of this generation)"""
+    old = dict(dt=sc["dt"], W=sc["macro_weight"], dv=sc["dv"])
+    dt = em_dt(SHAPE, L3) if sc["solver"] == "yee" else DT3
+    W = DENSITY3 * float(np.prod(L3)) / N0
+    dv = float(np.prod(L3)) / float(np.prod(SHAPE))
+    sc.update(generation=3, L=L3, dt=dt, macro_weight=W, dv=dv, kick_scale=old["dt"] / dt, sigma_scale=(old["dt"] * old["W"] / old["dv"]) / (dt * W / dv))
+    sc["spec"] = dict(sc["spec"], radius=L3[0], length_y=L3[1], height=L3[2], dt=dt, macro_weight=W)
+    sc["tau_like"] = [pair_tau(W, dv, sc["masses"][a], sc["charges"][a], sc["masses"][a], sc["charges"][a]) for a in range(2)]
+    sc["tau_unlike"] = pair_tau(W, dv, ME, QE, MP, -QE, n_l=1)
+    if sc["registered"]:
+        pe = sc["pair_every"]
+        pe["kw"]["tau"] = sc["tau_like"][0] if pe["b"] is None else sc["tau_unlike"]
+        if "recorders" in sc:
+            sc["recorders"]["series"]["points"] = sc["recorders"]["series"]["points"] / np.array(L)
+        for kw in sc.get("force_on", []):
+            _unit_box(kw)
+            for w in kw["waves"]:
+                w["amp"] = [x * sc["kick_scale"] for x in w["amp"]]
+        if "gas_every" in sc:
+            ge = sc["gas_every"]
+            _unit_box(ge["kw"])
+            ge["kw"]["density"] *= ge["kw"]["tau"] / (ge["every"] * dt)
+            ge["kw"]["tau"] = ge["every"] * dt
+            for key in ("fusion_every", "spectrum_every"):
+                sc[key]["kw"]["tau"] = sc[key]["every"] * dt
+                sc[key]["kw"]["sigma"] = sc[key]["kw"]["sigma"] * sc["sigma_scale"]
+    return sc
+
+
+def _brick(rng, widths, axes=None):
+    """{axis: (lo, lo + w)} on 1 .. 3 spatial axes (or the given number), w drawn from `widths`"""
+    out = {}
+    for a in rng.permutation(3)[:int(rng.integers(1, 4)) if axes is None else axes]:
+        w = float(rng.uniform(*widths))
+        lo = float(rng.uniform(0.0, 1.0 - w))
+        out["xyz"[int(a)]] = (lo, lo + w)
+    return out
+
+
+def _source3(rng, kind, count):
+    """the keywords of a source but its species: sequence numbers from `first`, a sub-box of the unit box; a flux source's
+    plane lies on a face of the box on four draws of ten"""
+    lo = [float(x) for x in rng.uniform(0, 0.4, 3)]
+    kw = dict(kind=kind, count=int(count), first=int(rng.integers(0, 1 << 20)), seed=int(rng.integers(1, 1 << 40)), stream=int(rng.integers(0, 8)),
+              lo=lo, hi=[float(lo[a] + rng.uniform(0.3, 0.6)) for a in range(3)], lattice=bool(rng.random() < 0.5))
+    if kind == "volume":
+        kw.update(drift=[float(x) for x in rng.normal(0, 0.01, 3)], vth=float(rng.uniform(0.01, 0.05)), paired=bool(rng.random() < 0.5))
+    else:
+        axis = int(rng.integers(0, 3))
+        drift = [float(x) for x in rng.normal(0, 0.01, 3)]
+        drift[axis] = 0.0
+        face = rng.random() < 0.4
+        kw.update(axis=axis, side=int(rng.choice([-1, 1])), plane=float(rng.choice([0.0, 1.0])) if face else float(rng.uniform(0.1, 0.9)), drift=drift,
+                  vth=[float(x) for x in rng.uniform(0.01, 0.05, 3)])
+    return kw
+
+
+def _registered3(sc, rng):
+    """the sinks and the sources of a scene with registered operators, beside generation 2's set: a spatial sink on species
+    0 every 2nd and an every=(3, r) sink on species 1 every 3rd sub-step; a volume source into species 0 and 1 on one seed,
+    stream and sequence every sub-step (a neutral pair) and a flux source into species 0 every 2nd"""
+    sc["remove_every"] = [dict(every=2, species=0, where=_brick(rng, (0.15, 0.3), axes=1), every_id=None, outside=False),
+                          dict(every=3, species=1, where=None, every_id=(3, int(rng.integers(0, 3))), outside=False)]
+    pair = dict(_source3(rng, "volume", rng.integers(20, 61)), epoch=int(rng.integers(0, 50)))
+    flux = dict(_source3(rng, "flux", rng.integers(20, 61)), epoch=int(rng.integers(0, 50)))
+    sc["inject_every"] = [dict(every=1, species=0, kw=pair), dict(every=1, species=1, kw=dict(pair)), dict(every=2, species=0, kw=flux)]
+
+
+def reserved3(sc, total):
+    """the capacities a scene with registered sources reserves up front for `total` sub-steps: count + sum of count_source x
+    ceil(total / every) — no application of the hook can fail"""
+    out = list(sc["counts"])
+    for op in sc.get("inject_every", []):
+        out[op["species"]] += op["kw"]["count"] * -(-total // op["every"])
+    return out
+
+
+def scene3(seed):
+    sc = _to_unit(scene2(seed))
+    if sc["registered"]:
+        _registered3(sc, np.random.default_rng([0x5CE93, seed]))
+    return sc
+
+
+def _fusion_kw3(rng, sc):
+    kw = _fusion_kw(rng, sc["dt"])
+    kw["sigma"] = kw["sigma"] * sc["sigma_scale"]
+    return kw
+
+
+def _read3(rng, kind, sc, saved, index, thinned):
+    """a read of generation 3: what depends on n is a fraction (getRange: first_frac, count_frac; series: tracer_fracs of the
+    id span, and the replay adds a dead id once one exists); refused=True on a caller-order read of a thinned species and on
+    a saveCheckpoint while any species is thinned (that save makes no file)"""
+    if kind in STATS_KINDS3:
+        return dict(kind=kind, species=0)
+    if kind in ("fusionYield", "fusionSpectrum"):
+        like = bool(rng.random() < 0.5)
+        a = int(rng.integers(0, 2))
+        b = None if like else 1 - a
+        r = dict(kind=kind, species=a, a=a, b=b, kw=_fusion_kw3(rng, sc))
+        if kind == "fusionSpectrum":
+            r["form"] = ("product", "los", "cm")[int(rng.integers(0, 3))]
+            r["kw"].update(spectrum_axis(sc["masses"], a, b, r["form"]))
+        return r
+    if kind == "saveCheckpoint":
+        r = dict(kind=kind, species=int(rng.integers(0, len(sc["counts"]))), refused=bool(thinned))
+        if not thinned:
+            r["file"] = len(saved)
+            saved.append(index)
+        return r
+    r = _read(rng, kind, sc, [], index)
+    if kind == "getRange":
+        n = sc["counts"][r["species"]]
+        r.update(first_frac=r.pop("first") / n, count_frac=float(rng.random()))
+        del r["count"]
+    elif kind == "series":
+        n = sc["counts"][r["species"]]
+        r["points"] = r["points"] / np.array(L)
+        r["tracer_fracs"] = [x / n for x in r.pop("tracers")]
+    if kind in CALLER_ORDER_READS3:
+        r["refused"] = r["species"] in thinned
+    return r
+
+
+def resolve_range(first_frac, count_frac, n, stride=1):
+    """(first, count) of a strict sub-range of n particles: 0 < first, first + stride (count - 1) < n - 1 where n allows it"""
+    first = min(max(1, int(first_frac * n)), max(n - 2, 0))
+    most = max(1, (n - 1 - first + stride - 1) // stride)
+    return first, max(1, min(most, 1 + int(count_frac * most)))
+
+
+def resolve_tracers(fracs, id_span, ids):
+    """the tracer ids of a series: the fractions of the id span, and one dead id (the smallest) once one exists"""
+    tr = sorted({min(int(f * id_span), id_span - 1) for f in fracs})
+    dead = np.setdiff1d(np.arange(id_span, dtype=np.int64), np.asarray(ids, dtype=np.int64))
+    if len(dead) and int(dead[0]) not in tr:
+        tr.append(int(dead[0]))
+    return tr
+
+
+def resolve_inject(st, n, capacity):
+    """(capacity to reserve first or None, count): with reserve_first the species grows by the drawn count; otherwise the
+    source injects what fits of it, and reserves only if nothing does"""
+    room = capacity - n
+    if st["reserve_first"] or room == 0:
+        return capacity + st["count"], st["count"]
+    return None, min(st["count"], room)
+
+
+def _step3(rng, sc, kind, used_primes):
+    """a step of a new kind"""
+    st = dict(kind=kind)
+    species = int(rng.integers(0, 2))
+    if kind == "remove_window":
+        where = {}
+        while not 1 <= len(where) <= 3:
+            where = _read(rng, "count", sc, [], 0)["where"]
+        st.update(species=species, where=where, every=None, outside=False)
+    elif kind == "remove_outside":
+        st.update(species=species, where=_brick(rng, (0.62, 0.94)), every=None, outside=True)
+    elif kind == "remove_thinned_by_id":
+        if all(p in used_primes[species] for p in ID_PRIMES3):      # (every modulus used on this species: the other one)
+            species = 1 - species
+        free = [p for p in ID_PRIMES3 if p not in used_primes[species]]
+        if not free:
+            return _step3(rng, sc, "remove_window", used_primes)
+        mod = int(free[int(rng.integers(0, len(free)))])
+        used_primes[species].add(mod)
+        st.update(species=species, where=_brick(rng, (0.5, 0.8), axes=1) if rng.random() < 0.5 else None, every=(mod, int(rng.integers(0, mod))), outside=False)
+    elif kind == "remove_nothing":
+        where = ({"vx": (10.0, None)}, {"v2": (None, 0.0)}, {"x": (0.25, 0.5), "vz": (20.0, 30.0)})[int(rng.integers(0, 3))]
+        st.update(species=species, where=where, every=None, outside=False)
+    elif kind in ("inject_volume", "inject_flux"):
+        st.update(species=species, kw=_source3(rng, kind[len("inject_"):], rng.integers(50, 401)), reserve_first=bool(sc["registered"] or rng.random() < 0.5))
+        st["count"] = st["kw"].pop("count")
+    elif kind == "inject_pair":
+        st.update(species=None, kw=dict(_source3(rng, ("volume", "flux")[int(rng.integers(0, 2))], rng.integers(50, 301)), paired=False), reserve_first=True)
+        st["count"] = st["kw"].pop("count")
+        if st["kw"]["kind"] == "flux":
+            del st["kw"]["paired"]
+    elif kind == "inject_refused":
+        st.update(species=species, kw=dict(kind="volume", seed=int(rng.integers(1, 1 << 40)), vth=0.01))
+    elif kind == "reserve":
+        st.update(species=species, extra=int(rng.choice([1, 7, 333, 1024, 1500])))
+    elif kind == "renumber":
+        st.update(species=None)
+    else:
+        raise AssertionError(kind)
+    return st
+
+
+def sequence3(seed, nsteps=None):
+    """the steps of a generation-3 seed: 14 to 18 state-changing operations of STATE_KINDS3, the first a substeps, each with
+    READS3 reading calls of READ_KINDS2 (six, and every read of STATS_KINDS3, on a scene with registered operators).  The
+    forced opening: after one to three steps comes the seed's first removal (of REMOVE_KINDS3), then a substeps with
+    k >= sort_interval + 1 (a re-binning push on a thinned species), then one of each of collide_*, gas_*, pair_*, force_* in
+    a drawn order, the fusionYield and fusionSpectrum reads among theirs — no renumber and no loadCheckpoint before the block
+    ends.  The other steps take new and old kinds in turn from two shuffled cycles.  A step carries `thinned` /
+    `thinned_after` (see the head of this generation) and, where the library must refuse it, refused=True."""
+    sc = scene3(seed)
+    rng = np.random.default_rng([0x0B53, seed])
+    ns = len(sc["counts"])
+    nsteps = int(rng.integers(14, 19)) if nsteps is None else nsteps
+    olds = [k for k in STATE_KINDS2 if k != "substeps"]
+    news = list(NEW_KINDS3)
+    old_cycle = [olds[i] for i in rng.permutation(len(olds))]
+    new_cycle = [news[i] for i in rng.permutation(len(news))]
+    first_removal = REMOVE_KINDS3[int(rng.integers(0, 3))]
+    forced = [("collide_exchange", "collide_elastic", "collide_relax")[int(rng.integers(0, 3))], ("gas_exchange", "gas_elastic")[int(rng.integers(0, 2))],
+              ("pair_like", "pair_unlike")[int(rng.integers(0, 2))], ("force_field", "force_accel")[int(rng.integers(0, 2))]]
+    forced = [forced[i] for i in rng.permutation(4)]
+    block_at = int(rng.integers(1, 4))
+    ks = [k for k in (1, 2, 3, 5) if k >= sc["sort_interval"] + 1]
+    block = [first_removal, ("substeps", int(ks[int(rng.integers(0, len(ks)))]))]
+    for k in forced:
+        if rng.random() < 0.3:
+            block.append("substeps")
+        block.append(k)
+    reads_per_step = 6 if sc["registered"] else READS3
+    at_old = at_new = t = 0
+    turn = int(rng.integers(0, 2))
+    seen = {k: 0 for k in STATE_KINDS3}
+    saved = []
+    last_substeps = -1
+    thinned = set()
+    used_primes = [set(), set()]
+    steps = []
+    in_block = None      # the index into block while it runs
+    for index in range(nsteps):
+        k_forced, from_block = None, False
+        if index == block_at:
+            in_block = 0
+        if in_block is not None and in_block < len(block):
+            kind = block[in_block]
+            in_block += 1
+            from_block = True
+            if isinstance(kind, tuple):
+                kind, k_forced = kind
+        elif index == 0 or (steps[-1]["kind"] != "substeps" and rng.random() < 0.5) or (steps[-1]["kind"] == "substeps" and rng.random() < 0.1):
+            kind = "substeps"
+        else:
+            while True:
+                if turn:
+                    kind = new_cycle[at_new % len(new_cycle)]
+                    at_new += 1
+                else:
+                    kind = old_cycle[at_old % len(old_cycle)]
+                    at_old += 1
+                before_block = in_block is None
+                if before_block and kind in REMOVE_KINDS3 + ("renumber",):
+                    continue          # (the block's removal is the seed's first; a renumber before it has nothing to do)
+                if kind == "loadCheckpoint" and not any(s < last_substeps for s in saved):
+                    continue          # (a rewind needs a file with a substeps after it)
+                if kind == "loadCheckpoint" and sc["registered"] and thinned:
+                    continue          # (with operators registered a rewind is drawn only before the first removal of the hook)
+                break
+            turn ^= 1
+        st = dict(kind=kind, tag=index + 1, precalc=False)
+        if kind in STATE_KINDS and kind not in ("substeps", "loadCheckpoint"):
+            st = dict(_step1(rng, sc, kind), tag=index + 1, precalc=False)
+            if kind in ("setRange", "load"):
+                n = sc["counts"][st["species"]]
+                st.update(first_frac=st.pop("first") / n, count_frac=st.pop("count") / n)
+            if kind == "load":
+                _unit_box(st)
+        elif kind == "substeps":
+            st["k"] = int(rng.choice([1, 2, 3, 5])) if k_forced is None else k_forced
+            t += st["k"]
+            last_substeps = index
+        elif kind == "loadCheckpoint":
+            files = [f for f, s in enumerate(saved) if s < last_substeps]
+            st["file"] = files[int(rng.integers(0, len(files)))]
+        elif kind.startswith("force_"):
+            species = int(rng.integers(0, ns))
+            window = "whole" if species == 2 else ("whole", "narrow", "wide")[int(rng.integers(0, 3))]
+            epoch = int(rng.integers(0, 1000))
+            envelope, active = None, True
+            if rng.random() < 0.4:
+                s = epoch + t
+                if rng.random() < 0.7:
+                    envelope = dict(start=max(0, s - int(rng.integers(0, 3))), stop=s + int(rng.integers(1, 4)))
+                else:
+                    active = False
+                    start = s + int(rng.integers(1, 4)) if s < 4 or rng.random() < 0.5 else s - int(rng.integers(2, 5))
+                    envelope = dict(start=start, stop=start + 1 if start < s else start + 3)
+                envelope["values"] = _table(rng, 0.2, 1.2, int(rng.integers(3, 6))) if rng.random() < 0.6 else None
+            st.update(what=kind[len("force_"):], window=window, active=active, t=t,
+                      kw=_force_kw(rng, kind[len("force_"):], species, window, epoch, envelope, scale=sc["kick_scale"], lengths=L3))
+        elif kind.startswith("gas_"):
+            what = kind[len("gas_"):]
+            K, side = _gas_side(rng)
+            low = side.endswith("_lo")
+            species = 0 if low else int(rng.integers(0, 2))
+            window = ("whole", "wide")[int(rng.integers(0, 2))] if low else ("whole", "narrow", "wide")[int(rng.integers(0, 3))]
+            st.update(what=what, side=side, window=window, kw=_gas_kw(rng, what, species, window, sc["dt"], K, BACKGROUND, lengths=L3, taper_min=0.9 if low else 0.6))
+        elif kind in ("load_profile", "load_radial"):
+            species = int(rng.integers(0, 2))
+            lo = [float(x) for x in rng.uniform(0, 0.4, 3)]
+            st.update(species=species, first_frac=float(rng.uniform(0.001, 0.9)), count_frac=float(rng.random()), what=("position", "velocity", "both")[int(rng.integers(0, 3))],
+                      seed=int(rng.integers(1, 1 << 40)), stream=int(rng.integers(0, 8)), lo=lo, hi=[float(lo[a] + rng.uniform(0.3, 0.6)) for a in range(3)],
+                      drift=[float(x) for x in rng.normal(0, 0.01, 3)], vth=float(rng.uniform(0.01, 0.05)), lattice=bool(rng.random() < 0.5))
+            if kind == "load_profile":
+                axes = rng.permutation(3)[:int(rng.integers(1, 4))]
+                st["density"] = [_table(rng, 0.1, 1.0) if a in axes else None for a in range(3)]
+                st["thermal"] = [_table(rng, 0.5, 1.5) if rng.random() < 0.5 else None for a in range(3)] if rng.random() < 0.6 else None
+                st["shear"] = dict(axis=int(rng.integers(0, 3)), component=int(rng.integers(0, 3)), values=[float(x) for x in rng.normal(0, 0.01, int(rng.integers(2, 8)))]) \
+                    if rng.random() < 0.6 else None
+            else:
+                st["radial"] = _radial(rng, lengths=L3)
+        else:
+            st = dict(_step3(rng, sc, kind, used_primes), tag=index + 1, precalc=False)
+            kind = st["kind"]
+        st["thinned"] = sorted(thinned)
+        st["refused"] = (kind in CALLER_ORDER_KINDS3 and st["species"] in thinned) or (kind == "renumber" and sc["registered"] and bool(thinned))
+        if kind in POSITION_KINDS2 and st["what"] != "velocity" and not st["refused"]:
+            st["precalc"] = sc["solver"] != "none" or bool(rng.random() < 0.5)
+        # who is thinned after the step: the sinks of the hook thin species 0 from the 2nd and species 1 from the 3rd sub-step on
+        if kind in REMOVE_KINDS3:
+            thinned.add(st["species"])
+        elif kind == "loadCheckpoint":
+            thinned.clear()
+            used_primes[0].clear(), used_primes[1].clear()
+        elif kind == "renumber" and not st["refused"]:
+            thinned.clear()
+            used_primes[0].clear(), used_primes[1].clear()
+        elif kind == "substeps" and sc["registered"]:
+            thinned |= {op["species"] for op in sc["remove_every"] if t >= op["every"]}
+        st["thinned_after"] = sorted(thinned)
+        off = (seed * 4 + STATE_KINDS3.index(kind) * 5 + seen[kind] * reads_per_step) % len(READ_KINDS2)
+        seen[kind] += 1
+        kinds = [READ_KINDS2[(off + i) % len(READ_KINDS2)] for i in range(reads_per_step)]
+        if from_block and kind == forced[0]:      # the block's first old kind carries both fusion reads
+            for want, slot in (("fusionYield", 0), ("fusionSpectrum", 1)):
+                if want not in kinds:
+                    kinds[[i for i, k in enumerate(kinds) if k not in ("fusionYield", "fusionSpectrum")][slot]] = want
+        st["reads"] = [_read3(rng, k, sc, saved, index, thinned) for k in kinds]
+        if sc["registered"]:
+            st["reads"] += [_read3(rng, k, sc, saved, index, thinned) for k in STATS_KINDS3]
+        steps.append(st)
+    return steps
+
+
+def can_have_rebinned3(sc, steps):
+    """can_have_rebinned with the new kinds: per step, True for a substeps that can leave a species reordered by a fused
+    re-binning push.  A removal that takes somebody, an injection and a reserve leave the species as an upload does (the next
+    sub-step bins afresh) and reset the count like a position write; a refused step changes nothing.  The sinks and sources of
+    the hook do the same from inside substeps(): a sub-step on which one is due ends with its species un-binned, so the count
+    is followed sub-step by sub-step — on a scene with registered operators, whose pair source is due every sub-step, no
+    substeps ever qualifies, and the condition rests on the scenes without."""
+    hook = [op["every"] for op in sc.get("remove_every", []) + sc.get("inject_every", [])] if sc["registered"] else []
+    out, since, t = [], 0, 0
+    for st in steps:
+        if st["kind"] == "substeps":
+            pushed = False
+            for _ in range(st["k"]):
+                t += 1
+                since += 1
+                pushed = pushed or since > sc["sort_interval"]
+                if any(t % every == 0 for every in hook):
+                    since, pushed = 0, False
+            out.append(sc["solver"] != "yee" and sc["sort_interval"] > 0 and pushed)
+        else:
+            if not st["refused"] and ((st["kind"] in POSITION_KINDS2 and st["what"] != "velocity") or st["kind"] in ("loadCheckpoint", "sort") + UNBINNING_KINDS3):
+                since = 0
+            out.append(False)
+    return out
+
+
+def initial_state3(sc):
+    """initial_state on the unit box"""
+    out = []
+    for sp, n in enumerate(sc["counts"]):
+        pos, vel = particles3(sc["seed"], 1000 + sp, n)
+        out.append(dict(frac=pos, vel=vel, cell=cells_of(pos, sc["shape"]), ids=np.arange(n)))
+    return out
+
+
+def cells_of(frac, shape):
+    """the deposit's cells of stored box fractions, as initial_state computes them — in the arithmetic of the stored type,
+    whose one rounding of u n decides the cell (tests/em_reference.py: cells_and_weights), n itself folding to 0
+    (tests/load_reference.py: plane); in float64 no fraction below 1 reaches n and this is initial_state's number"""
+    frac, shape = np.asarray(frac), np.array(shape)
+    ijk = (frac * shape.astype(frac.dtype)).astype(np.int64)
+    ijk = np.where(ijk >= shape, 0, ijk)
+    return ijk[:, 0] + shape[0] * (ijk[:, 1] + shape[1] * ijk[:, 2])
+
+
+# ---- the named sequences of generation 3: plain programs (lists of tuples) the GPU module runs line by line
+TURNOVER_CASES = [("poisson_fft", "fp32"), ("yee", "fp64"), ("none", "fp64")]
+TURNOVER_PIECES = (1, 2, 3, 5, 5, 3, 2, 1, 1, 2, 3, 5, 5, 2)           # forty sub-steps
+TURNOVER = dict(capacity=1500, count=96, sink_every=2, sink=dict(where={"x": (0.0, 0.5)}, species=1))
+
+
+def _plain3(seed, solver, precision, name, sort_interval=2, staged=False):
+    sc = scene(seed)
+    dt = em_dt(SHAPE, L) if solver == "yee" else 5e-12
+    sc.update(solver=solver, precision=precision, dt=dt, sort_interval=sort_interval, staged=staged, registered=False, name=name, addB=None if solver == "none" else sc["addB"])
+    sc["spec"] = dict(sc["spec"], solver=solver, dt=dt)
+    for key in ("collide_every", "pair_every", "recorders"):
+        sc.pop(key, None)
+    return _to_unit(sc)
+
+
+def turnover(solver, precision):
+    """Source against sink over forty sub-steps in pieces of 1, 2, 3 and 5, on species 1: its capacity reserved to 1500, a
+    volume source of 96 every sub-step, a sink x in [0, 0.5) every second.  The id span ends at 750 + 40 x 96 = 4590, three
+    times the capacity, while n stays in the hundreds.  Under full EM the same source (seed, stream, sequence) also feeds
+    species 0: a neutral pair.  The `none` case has E = 0 and no addB — no velocity ever changes — and carries the ledger."""
+    sc = _plain3(310, solver, precision, "turnover")
+    rng = np.random.default_rng([0x9E9D, 310])
+    src = dict(_source3(rng, "volume", TURNOVER["count"]), paired=False, epoch=3)
+    src["lo"][0], src["hi"][0] = 0.05, 0.55      # (nine tenths inside the sink: under full EM nobody crosses the box in forty sub-steps, and n must stay below the capacity)
+    sc["turnover"] = dict(TURNOVER, source=src, pieces=TURNOVER_PIECES, feeds=[0, 1] if solver == "yee" else [1], zero_field=solver == "none")
+    sc["zero_field"] = solver == "none"
+    sc["capacities"] = [N0 + (40 * TURNOVER["count"] if solver == "yee" else 0), TURNOVER["capacity"]] + sc["counts"][2:]
+    # reads of every kind after every piece: those by id and per particle on the turned-over species 1, the caller-order ones on
+    # species 0 (never thinned); a save is refused from the second sub-step on
+    reads = []
+    for index in range(len(TURNOVER_PIECES)):
+        row = [_read3(rng, k, sc, [], index, {1}) for k in READ_KINDS2]
+        for r in row:
+            if r["kind"] in ("count", "select", "histogram_lds", "histogram_global", "moments", "series"):
+                r["species"] = 1
+            elif r["kind"] in CALLER_ORDER_READS3:
+                r.update(species=0, refused=False)
+        reads.append(row)
+    return sc, reads
+
+
+REWINDS = dict(grow=(500, 200), substeps=(3, 4, 3, 5))
+
+
+def rewinds():
+    """An unregistered electrostatic fp32 scene with sort_interval = 2 and the staged binning forced; the program is
+    tests/test_gpu_sequences3.py's test_rewinds (the issue's list, line by line): files of three sizes loaded into a thinned
+    and into a grown handle, stale slots behind n after each."""
+    sc = _plain3(311, "poisson_fft", "fp32", "rewinds", sort_interval=2, staged=True)
+    rng = np.random.default_rng([0x9E9D, 311])
+    sc["rewinds"] = dict(REWINDS, sources=[dict(_source3(rng, "volume", REWINDS["grow"][0]), paired=False), dict(_source3(rng, "flux", REWINDS["grow"][1]))],
+                         remove=dict(where={"y": (0.1, 0.15)}), odd=dict(where={"vz": (None, 0.0)}))
+    return sc
+
+
+HOOK_OVERFLOW = dict(count=(40, 96), room=2 * 96 + 95)      # species 1 holds two applications of 96 and 95 more: the third is the first that does not fit
+
+
+def hook_overflow():
+    """A source registered on species 1 whose third application does not fit, behind a sink, a background operator and a
+    source into species 0 that does: substeps(5) raises FPIC_ERR_STATE naming fpic_reserve after the third sub-step's hook
+    has run up to that source."""
+    sc = _plain3(312, "poisson_fft", "fp64", "hook_overflow", sort_interval=1)
+    rng = np.random.default_rng([0x9E9D, 312])
+    sc["hook"] = dict(collide=dict(kind="relax", species=0, kw=dict(nu_tau=0.3, seed=91, stream=1, epoch=4, **BACKGROUND)),
+                      sink=dict(species=0, where={"z": (0.2, 0.5)}),      # (on the other species: a sink on species 1 would make the room)
+                      sources=[dict(species=0, kw=dict(_source3(rng, "flux", HOOK_OVERFLOW["count"][0]), epoch=2)),
+                               dict(species=1, kw=dict(_source3(rng, "volume", HOOK_OVERFLOW["count"][1]), paired=False, epoch=0))])
+    sc["capacities"] = [N0 + 5 * HOOK_OVERFLOW["count"][0], N1 + HOOK_OVERFLOW["room"]] + sc["counts"][2:]
+    return sc
+
+
+NAMED3 = {"turnover": turnover, "rewinds": rewinds, "hook_overflow": hook_overflow}
+
+
+# ---- the resumes of generation 3: the generation-2 families registered, and (i) a source alone — the species grows and is
+# never thinned, so the cut goes through a file into a fresh handle that reserves and registers with epoch = the applications
+# made so far — or (ii) a sink as well: a thinned species has no file, so both runs clear every registration at T, renumber
+# and register again (epochs + T); only one of them then goes through the file.
+RESUME3_SOURCE = dict(every=2, count=64)
+RESUME3_SINK = dict(every=3, species=0, where={"x": (0.25, 0.5)})
+
+
+def resume_scene3(solver, precision, sink):
+    sc = _to_unit(resume_scene2(solver, precision))
+    rng = np.random.default_rng([0x5CE93, 1000])
+    src = dict(_source3(rng, "volume", RESUME3_SOURCE["count"]), paired=False, epoch=7)
+    sc["inject_every"] = [dict(every=RESUME3_SOURCE["every"], species=s, kw=dict(src)) for s in (0, 1)]      # a neutral pair on one seed, stream and sequence
+    sc["remove_every"] = [dict(RESUME3_SINK, every_id=None, outside=False)] if sink else []
+    sc["capacities"] = reserved3(sc, RESUME_N)
+    return sc

@@ -424,6 +424,35 @@ def test_reserve_preserves_a_stepped_box(fp, precision, solver):
         s.destroy()
 
 
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_reserve_under_registered_cell_operators(fp, precision):
+    """the cell index of collidePairEvery / fusionYieldEvery / fusionSpectrumEvery is sized from the species' stride when they
+    are registered and the hook never grows it: a reserve() across a stride AFTER the registration regrows it (the next due
+    sub-step used to fail with "found species 1 larger than at its registration"), and the run equals the one that reserved first"""
+    fusion = dict(sigma=np.linspace(1e-28, 4e-28, 16), g_lo=0.0, g_hi=0.5, tau=1e-9, seed=5, stream=2)
+    sims = [unit_box(fp, precision, "poisson_fft", 1500, ni=900, weight=2e9)[0] for _ in range(2)]
+    a, b = sims
+    for k in range(2):
+        b.reserve(k, 2100)
+    for s in sims:
+        s.precalc()
+        assert s.collidePairEvery(1, 0, 1, log_lambda=10.0, tau=1e-9, seed=3) == 0 and s.fusionYieldEvery(1, 1, **fusion) == 0
+        assert s.fusionSpectrumEvery(2, 0, 1, axis="cm", bins=8, lo=0.0, hi=400 * fp.KEV, **fusion) == 0
+        s.substeps(1)
+    for k in range(2):
+        assert a.reserve(k, 2100) == 2100            # 1500 and 900 pad to 2048 and 1024: both strides grow
+    for s in sims:
+        for k in range(2):
+            s.inject("volume", species=k, seed=32, stream=3, vth=0.01, first=50, count=600)
+        s.substeps(2)
+    for k in range(2):
+        assert same_rows(rows(a, k), rows(b, k)) and a.population(k) == dict(n=(2100, 1500)[k], capacity=2100, id_span=(2100, 1500)[k])
+    assert a.pairStats(0) == b.pairStats(0) and a.pairStats(0)["applications"] == 3 and a.fusionStats(0)["pairs"] == b.fusionStats(0)["pairs"]
+    assert a.fusionSpectrumRead(0)["pairs"] == b.fusionSpectrumRead(0)["pairs"]
+    for s in sims:
+        s.destroy()
+
+
 # ---- (i) capacity and id refusals change nothing
 def test_refusals_change_nothing(fp):
     sim, spec = unit_box(fp, "fp32", "poisson_fft", 1000, weight=2e9)

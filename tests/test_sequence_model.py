@@ -466,3 +466,240 @@ def test_the_second_resume_scene():
         assert 0 < got["collided"] < got["candidates"]
         assert model.fusion_want(sc, state, sc["fusion_every"]["a"], sc["fusion_every"]["b"], sc["fusion_every"]["kw"])[1]["reactions_exact"] > 0
         assert np.count_nonzero(model.spectrum_want(sc, state, sc["spectrum_every"]["a"], sc["spectrum_every"]["b"], sc["spectrum_every"]["kw"])["bins"]) >= 2
+
+
+# ================================================================================================ generation 3
+def facts3(seed):
+    """(bad, cover) of a generation-3 seed: the conditions it breaks that every seed must meet (well-formed steps, the forced
+    opening, no vacuous removal on the scene's initial particles, the registered operators' windows and periods), and what it
+    adds to the coverage"""
+    import remove_reference as rr
+    sc, steps = model.scene3(seed), model.sequence3(seed)
+    state = model.initial_state3(sc)
+    bad, cover = [], set()
+    total = model.substeps_of(steps)
+    ok = (sc["shape"] == model.SHAPE and sc["L"] == (1.0, 1.0, 1.0) and sc["counts"][:2] == [model.N0, model.N1] and sc["staged"] == (seed % 3 == 0)
+          and sc["dt"] == (model.em_dt(model.SHAPE, model.L3) if sc["solver"] == "yee" else 5e-9) and 14 <= len(steps) <= 18 and steps[0]["kind"] == "substeps"
+          and sc["macro_weight"] == model.DENSITY3 / model.N0 and sc["dv"] == 1.0 / np.prod(model.SHAPE))
+    if not ok:
+        bad.append("scene")
+    cover |= {("scene", sc["solver"], sc["registered"]), ("scene", sc["precision"], sc["registered"])} | ({("scene", "staged", sc["registered"])} if sc["staged"] else set())
+    re = model.can_have_rebinned3(sc, steps)
+    kinds = [st["kind"] for st in steps]
+    want_reads = (6 + len(model.STATS_KINDS3)) if sc["registered"] else model.READS3
+    saved, thinned = 0, set()
+    for i, st in enumerate(steps):
+        kind = st["kind"]
+        reads = [r["kind"] for r in st["reads"]]
+        if kind not in model.STATE_KINDS3 or len(reads) != want_reads or len(set(reads)) != want_reads or not set(reads) <= set(model.READ_KINDS2 + model.STATS_KINDS3):
+            bad.append(("reads", i))
+        if st["thinned"] != sorted(thinned):
+            bad.append(("thinned", i))
+        if kind in model.NEW_KINDS3:
+            cover |= {("new", kind, sc["solver"]), ("new", kind, sc["precision"]), ("new", kind, sc["registered"])} | ({("new", kind, "staged")} if sc["staged"] else set())
+            if i and re[i - 1]:
+                cover.add(("rebinned", kind))
+        if st["thinned"] and kind in model.STATE_KINDS2:
+            cover.add(("on a thinned handle", kind))
+        if st["refused"]:
+            cover.add(("refused", kind))
+            if not (kind in model.CALLER_ORDER_KINDS3 and st["species"] in thinned or kind == "renumber" and sc["registered"] and thinned) or st["precalc"]:
+                bad.append(("refused", i))
+        if st["thinned_after"]:
+            cover |= {("read of a thinned handle", r) for r in reads}
+        if kind in model.INJECT_KINDS3:
+            cover |= {("read after an injection", r) for r in reads}
+            if thinned & ({0, 1} if kind == "inject_pair" else {st["species"]}):      # (new ids from the id span on, not from n)
+                cover.add(("into a thinned species", kind))
+        for r in st["reads"]:
+            if r.get("refused"):
+                cover.add(("refused read", r["kind"]))
+            want = (r["kind"] in model.CALLER_ORDER_READS3 and r["species"] in st["thinned_after"]) or (r["kind"] == "saveCheckpoint" and bool(st["thinned_after"]))
+            if bool(r.get("refused")) != want:
+                bad.append(("refused read", i, r["kind"]))
+        if kind == "loadCheckpoint" and not st["file"] < saved:
+            bad.append(("file", i))
+        saved += sum("file" in r for r in st["reads"])
+        if kind in model.POSITION_KINDS2 and st["what"] != "velocity" and sc["solver"] != "none" and not (st["precalc"] or st["refused"]):
+            bad.append(("precalc", i))
+        # no vacuous removal, as far as the CPU can tell: on the initial particles
+        if kind in model.REMOVE_KINDS3 + ("remove_nothing",):
+            s = state[st["species"]]
+            share = rr.removed_mask(s["ids"], s["frac"], s["vel"], st["where"], st["every"], st["outside"]).mean()
+            if not (share == 0 if kind == "remove_nothing" else 0.05 <= share <= 0.8):
+                bad.append(("share", i, kind, float(share)))
+        if kind == "remove_thinned_by_id":
+            cover.add(("by id with a window", st["where"] is not None))
+        if kind == "reserve" and st["extra"] >= 1024:
+            cover.add(("reserve across a stride",))
+        if kind in ("inject_volume", "inject_pair") and st["kw"]["kind"] == "volume":
+            cover |= {("volume lattice", st["kw"]["lattice"]), ("volume paired", st["kw"].get("paired", False))}
+        if kind in ("inject_flux", "inject_pair") and st["kw"]["kind"] == "flux":
+            cover |= {("flux plane on a face", st["kw"]["plane"] in (0.0, 1.0)), ("flux axis", st["kw"]["axis"]), ("flux side", st["kw"]["side"])}
+        if kind in model.INJECT_KINDS3:
+            cover |= {("reserve first", st["reserve_first"]), ("pair kind", st["kw"]["kind"])} if kind == "inject_pair" else {("reserve first", st["reserve_first"])}
+        if kind.startswith("force_") and st["t"] != model.substeps_of(steps[:i]):
+            bad.append(("force t", i))
+        thinned = set(st["thinned_after"])
+    # the forced opening
+    first = next(i for i, k in enumerate(kinds) if k in model.REMOVE_KINDS3)
+    after = steps[first + 1]
+    end = next((i for i in range(first + 1, len(steps)) if kinds[i] in ("renumber", "loadCheckpoint") and not steps[i]["refused"]), len(steps))
+    within = kinds[first + 2:end]
+    reads_within = {r["kind"] for st in steps[first + 2:end] for r in st["reads"]}
+    if not (after["kind"] == "substeps" and after["k"] >= sc["sort_interval"] + 1 and all(any(k.startswith(f) for k in within) for f in ("collide_", "gas_", "pair_", "force_"))
+            and {"fusionYield", "fusionSpectrum"} <= reads_within and not any(k in model.REMOVE_KINDS3 + ("renumber",) for k in kinds[:first])):
+        bad.append("opening")
+    if re[first + 1]:      # the forced substeps IS a re-binning push on the thinned species (not on every scene: full EM, sort_interval 0, a hook that un-bins)
+        cover.add(("the opening re-bins", seed))
+    if sc["registered"]:
+        rec = sc["recorders"]
+        if not all(total // rec[k]["every"] > rec[k]["capacity"] for k in rec):
+            bad.append("a ring does not wrap")
+        a, b = sc["force_window"]
+        if not (1 < a and b < total and b - a + 1 >= 3):
+            bad.append(("envelope", a, b, total))
+        for key in ("collide_every", "pair_every", "gas_every", "fusion_every", "spectrum_every"):
+            if not total // sc[key]["every"] >= 3:
+                bad.append(("due", key))
+        for op in sc["remove_every"]:      # the hook's sinks take somebody at their first application, on the initial particles
+            s = state[op["species"]]
+            share = rr.removed_mask(s["ids"], s["frac"], s["vel"], op["where"], op["every_id"], op["outside"]).mean()
+            if not 0.05 <= share <= 0.8:
+                bad.append(("sink", float(share)))
+        if any(k == "loadCheckpoint" for k, st in zip(kinds, steps) if st["thinned"]):
+            bad.append("a rewind of a registered, thinned scene")
+        if model.reserved3(sc, total)[0] != sc["counts"][0] + sum(op["kw"]["count"] * -(-total // op["every"]) for op in sc["inject_every"] if op["species"] == 0):
+            bad.append("reserved")
+    return bad, cover
+
+
+def required3():
+    want = {("scene", x, r) for x in model.SOLVERS + ("fp32", "fp64", "staged") for r in (False, True)}
+    want |= {("new", k, x) for k in model.NEW_KINDS3 for x in model.SOLVERS + ("fp32", "fp64", "staged", False, True)}
+    want |= {("rebinned", k) for k in model.NEW_KINDS3}
+    want |= {("on a thinned handle", k) for k in model.STATE_KINDS2}
+    want |= {("read of a thinned handle", r) for r in model.READ_KINDS2} | {("read after an injection", r) for r in model.READ_KINDS2}
+    want |= {("refused", k) for k in model.CALLER_ORDER_KINDS3 + ("renumber",)} | {("refused read", r) for r in model.CALLER_ORDER_READS3 + ("saveCheckpoint",)}
+    want |= {("into a thinned species", k) for k in model.INJECT_KINDS3}
+    want |= {("by id with a window", False), ("by id with a window", True), ("reserve across a stride",), ("volume lattice", False), ("volume lattice", True),
+             ("volume paired", False), ("volume paired", True), ("flux plane on a face", False), ("flux plane on a face", True), ("reserve first", False),
+             ("reserve first", True), ("pair kind", "volume"), ("pair kind", "flux"), ("flux side", -1), ("flux side", 1)} | {("flux axis", a) for a in range(3)}
+    return want
+
+
+_facts3 = {}
+
+
+def facts3_of(seed):
+    if seed not in _facts3:
+        _facts3[seed] = facts3(seed)
+    return _facts3[seed]
+
+
+# sha256 (first 16 hex digits) of plain(scene3) + plain(sequence3) per committed seed, and of the named scenes: generation 3
+# is deterministic, and a change of its generator shows here before it silently moves what the GPU tests replay
+DIGESTS3 = {
+    "seeds": {8: "5d1a7a11c8472116", 24: "816da214419a390e", 82: "4489ae55c586e536", 89: "6675709e3e59e77f", 176: "b83eb494f3315852", 648: "f05884e5226d9abb", 1986: "e52f62a156fe11e0", 2568: "689e1a35ea5eb2a0", 3060: "8ca50ee9cfe9f3a5", 3317: "44e40433fba138da", 3975: "93292da8640468f5", 4778: "7bfe50ae4007d435"},
+    "turnover": ["b55346484b3c4002", "95130b3e002d33c8", "279e4fd4b0cae3bc"],
+    "named": ["751abf78466dfaa9", "a54dc107abaa0519"],
+    "resume": ["b7c49928a6f52434", "adb5290959fc370d", "9f29a2d7d2272552", "2a84f9a9c0dd626f"],
+}
+
+
+def test_generation_3_is_deterministic_and_leaves_generations_1_and_2_alone():
+    assert len(model.SEEDS3) == len(set(model.SEEDS3)) == 12
+    for seed in model.SEEDS3[:3]:
+        assert plain(model.scene3(seed)) == plain(model.scene3(seed)) and plain(model.sequence3(seed)) == plain(model.sequence3(seed))
+    assert plain(model.sequence3(model.SEEDS3[0])) != plain(model.sequence3(model.SEEDS3[1]))
+    assert {seed: digest(model.scene3(seed), model.sequence3(seed)) for seed in model.SEEDS3} == DIGESTS3["seeds"]
+    assert [digest(*model.turnover(*case)) for case in model.TURNOVER_CASES] == DIGESTS3["turnover"]
+    assert [digest(model.rewinds(), []), digest(model.hook_overflow(), [])] == DIGESTS3["named"]
+    assert [digest(model.resume_scene3(*r, sink), []) for r in model.RESUME for sink in (False, True)] == DIGESTS3["resume"]
+    assert model.STATE_KINDS3[:len(model.STATE_KINDS2)] == model.STATE_KINDS2 and len(set(model.STATE_KINDS3)) == len(model.STATE_KINDS2) + 10
+    # the scene is generation 2's but for what follows from the edge lengths
+    for seed in model.SEEDS3[:3]:
+        base, sc = model.scene2(seed), model.scene3(seed)
+        assert all(plain(sc[k]) == plain(base[k]) for k in ("seed", "solver", "precision", "sort_interval", "staged", "counts", "masses", "charges", "shape", "addB", "registered"))
+    # a fast particle still crosses more than a cell per electrostatic sub-step; omega_p dt is what it was on the millimetre box
+    pos, vel = model.particles3(model.SEEDS3[0], 0, model.N0)
+    assert np.all((pos >= 0) & (pos < 1)) and (np.abs(vel).max(axis=1) * model.C * model.DT3 > 1.0 / model.SHAPE[0]).sum() > 10
+    assert abs(np.sqrt(model.DENSITY3) * model.DT3 / (np.sqrt(1e15) * 5e-12) - 1) < 1e-12
+
+
+def test_no_generation_3_seed_breaks_a_condition_every_seed_must_meet():
+    """well-formed steps; the model's own account of which species are thinned and which calls are refused; the forced
+    opening (the first removal, a re-binning substeps on the thinned species, one of each old family and both fusion reads
+    before the next renumber); on the scene's initial particles every remove_window / remove_outside / remove_thinned_by_id
+    takes between 5 % and 80 % of its species and every remove_nothing nobody (remove_reference.removed_mask); the hook's
+    sinks likewise; every ring wraps, every registered family is due three times"""
+    for seed in model.SEEDS3:
+        assert facts3_of(seed)[0] == [], (seed, facts3_of(seed)[0])
+
+
+def test_generation_3_reaches_what_it_is_there_for():
+    """every new kind under every solver, both precisions, with and without registered operators, with the staged binning
+    forced, and directly after a substeps that can have re-binned; every generation-1 and generation-2 state-changing kind
+    and every read kind on a handle that is thinned; every read kind after an injection; every caller-order call refused"""
+    cover = set().union(*[facts3_of(seed)[1] for seed in model.SEEDS3])
+    missing = required3() - cover
+    assert not missing, sorted(missing, key=str)
+    # ("rebinned", kind) can only come from a scene without registered operators, electrostatic or `none`, with sort_interval > 0:
+    # the hook's sources un-bin their species every sub-step (can_have_rebinned3).  On more than a quarter of the seeds the
+    # forced opening is a re-binning push on the species that was just thinned
+    for seed in model.SEEDS3:
+        sc, steps = model.scene3(seed), model.sequence3(seed)
+        if any(model.can_have_rebinned3(sc, steps)):
+            assert not sc["registered"] and sc["solver"] != "yee" and sc["sort_interval"] > 0
+    assert sum(1 for c in cover if c[0] == "the opening re-bins") * 4 > len(model.SEEDS3)
+
+
+def test_the_arithmetic_of_the_generation_3_named_sequences():
+    import inject_reference as ir
+    # turnover: forty sub-steps in pieces of 1, 2, 3 and 5; the id span ends at three times the capacity
+    assert sum(model.TURNOVER_PIECES) == 40 and set(model.TURNOVER_PIECES) == {1, 2, 3, 5}
+    for case in model.TURNOVER_CASES:
+        sc, reads = model.turnover(*case)
+        tv = sc["turnover"]
+        assert model.N1 + 40 * tv["count"] == 4590 >= 3 * tv["capacity"] and sc["capacities"][1] == tv["capacity"] == 1500 and tv["sink_every"] == 2
+        assert tv["feeds"] == ([0, 1] if case[0] == "yee" else [1]) and sc["capacities"][0] >= model.N0 + (40 * tv["count"] if case[0] == "yee" else 0)
+        assert (sc["solver"], sc["precision"]) == case and not sc["registered"] and (case[0] != "none" or (sc["addB"] is None and sc["zero_field"]))
+        assert len(reads) == len(tv["pieces"]) and all({r["kind"] for r in row} == set(model.READ_KINDS2) for row in reads)
+        lo, hi = tv["source"]["lo"][0], tv["source"]["hi"][0]      # nine tenths of the source's window lie inside the sink's
+        assert (min(hi, 0.5) - lo) / (hi - lo) >= 0.9
+    # the scenes with registered operators: the capacity reserved up front covers every application even if no sink took anybody
+    for seed in model.SEEDS3:
+        sc, steps = model.scene3(seed), model.sequence3(seed)
+        if not sc["registered"]:
+            continue
+        total = model.substeps_of(steps)
+        cap, n = model.reserved3(sc, total), list(sc["counts"])
+        for t in range(1, total + 1):
+            for op in sc["inject_every"]:
+                if t % op["every"] == 0:
+                    assert ir.fits(n[op["species"]], cap[op["species"]], n[op["species"]], op["kw"]["count"]), (seed, t)
+                    n[op["species"]] += op["kw"]["count"]
+        assert all(n[s] <= cap[s] < n[s] + sum(op["kw"]["count"] for op in sc["inject_every"] if op["species"] == s) + 1 for s in range(2))
+        pair = [op["kw"] for op in sc["inject_every"] if op["every"] == 1]
+        assert len(pair) == 2 and plain(pair[0]) == plain(pair[1]) and [op["species"] for op in sc["inject_every"]] == [0, 1, 0] and sc["inject_every"][2]["kw"]["kind"] == "flux"
+        assert [(op["every"], op["species"]) for op in sc["remove_every"]] == [(2, 0), (3, 1)] and sc["remove_every"][1]["every_id"][0] == 3
+    # hook_overflow: the third application is the first that does not fit
+    sc = model.hook_overflow()
+    src = sc["hook"]["sources"][1]
+    n = model.N1
+    fits = []
+    for k in range(3):
+        fits.append(ir.fits(n, sc["capacities"][1], n, src["kw"]["count"]))
+        n += src["kw"]["count"] if fits[-1] else 0
+    assert fits == [True, True, False] and src["species"] == 1 and sc["hook"]["sink"]["species"] == 0 and sc["hook"]["sources"][0]["species"] == 0
+    assert sc["capacities"][0] >= model.N0 + 5 * sc["hook"]["sources"][0]["kw"]["count"]
+    # rewinds: unregistered, electrostatic fp32, sort_interval 2, the staged binning forced
+    sc = model.rewinds()
+    assert (sc["solver"], sc["precision"], sc["sort_interval"], sc["staged"], sc["registered"]) == ("poisson_fft", "fp32", 2, True, False)
+    # the resumes: the cut is a multiple of every period, the capacities hold the whole run
+    for solver, precision in model.RESUME:
+        for sink in (False, True):
+            sc = model.resume_scene3(solver, precision, sink)
+            assert all(model.RESUME_T % op["every"] == 0 for op in sc["inject_every"] + sc["remove_every"]) and len(sc["remove_every"]) == int(sink)
+            assert sc["capacities"][:2] == [sc["counts"][s] + sc["inject_every"][s]["kw"]["count"] * -(-model.RESUME_N // sc["inject_every"][s]["every"]) for s in range(2)]
+            assert plain(sc["inject_every"][0]["kw"]) == plain(sc["inject_every"][1]["kw"])
