@@ -24,6 +24,7 @@
 //   fes_hist.inc.hpp        the phase-space histograms: the pass of one request, the ranks' sum
 //   fes_select.inc.hpp      the particle selection: the filter-and-compact pass of one request, the ranks' merge
 //   fes_load.inc.hpp        the particle loader: a population generated on the device, a rank keeping the particles of its planes
+//   fes_ops.inc.hpp         what the registered operators share: the tally rows, the registration, the stats head, the hook's loop over a family
 //   fes_collide.inc.hpp     Monte Carlo collisions with a prescribed background, now or registered to run after sub-steps
 //   fes_force.inc.hpp       prescribed external forces (waves, window, tapers, envelope), now or registered to run after sub-steps
 //   fes_gas.inc.hpp         windowed background collisions with a tabulated cross-section and exact tallies, now or registered
@@ -42,6 +43,7 @@
 #include "fes_hist_kernels.hpp"
 #include "fes_select_kernels.hpp"
 #include "fes_load_kernels.hpp"
+#include "fes_ops_core.hpp"
 #include "fes_collide_kernels.hpp"
 #include "fes_force_kernels.hpp"
 #include "fes_gas_kernels.hpp"
@@ -371,6 +373,7 @@ namespace {
 #include "fes_hist.inc.hpp"
 #include "fes_select.inc.hpp"
 #include "fes_load.inc.hpp"
+#include "fes_ops.inc.hpp"
 #include "fes_collide.inc.hpp"
 #include "fes_force.inc.hpp"
 #include "fes_gas.inc.hpp"
@@ -383,37 +386,31 @@ namespace {
 #include "fes_series.inc.hpp"
 #include "fes_modes.inc.hpp"
 
-// the recording hook, at the end of every sub-step of every path (substeps(), group_run()): counts the sub-step, applies the
-// registered external forces that are active (fes_force.inc.hpp: everything below sees the kicked state), then the
-// registered collision operators that are due (fes_collide.inc.hpp against the background, then fes_gas.inc.hpp against the
-// windowed background, then fes_pair.inc.hpp between the species: the rows below see the collided state), then the fusion yield tallies that are due (fes_fusion.inc.hpp: they read
-// the collided velocities and write no particle) and the fusion product spectra (fes_fusion_spectrum.inc.hpp), then every
-// recorder that is due — the energy rows, the series, the modes, which share the counter and nothing else — enqueues its row
-// into its ring.  No host synchronisation, no collective; recording off: nothing is enqueued.
+// The sub-step hook, at the end of every sub-step of every path (substeps(), group_run()).  It counts the sub-step; then the
+// families of registered operators run in the order of FES_OP_FAMILIES (fes_state.inc.hpp), each its operators that are due in
+// registration order (ops_run_due, fes_ops.inc.hpp), a family with nothing registered costing one emptiness test:
+//   force      the prescribed forces that are active: everything below sees the kicked state
+//   collide    the collisions against the background, then
+//   gas        against the windowed background, then
+//   pair       between the species: everything below sees the collided state
+//   fusion     the yield tallies, which read the collided velocities and write no particle, and
+//   fspec      the product spectra
+//   remove     the sinks: the tallies above saw the particles that leave now, the rows below see the thinned box.  Each due
+//              application waits for one 8-byte count: the host has to learn the new n
+//   inject     the sources, after the sinks: a sink beside a source leaves this sub-step's fresh particles alive, and the rows
+//              below count them.  Nothing is read back (the host knows the new n in advance); one wait per sub-step
+// then every recorder that is due — the energy rows, the series, the modes, which share the counter and nothing else — enqueues
+// its row into its ring.  But for the sinks and sources: no host synchronisation, no collective.  Nothing registered and
+// recording off: nothing is enqueued.
 static int diag_after_substep(fpic_handle* h)
 {
     Diag& g = h->es->diag;
     g.substep++;
-    if (!g.force_ops.empty())
-        if (int rc = force_after_substep(h, g.substep)) return rc;
-    if (!g.coll_ops.empty())
-        if (int rc = collide_after_substep(h, g.substep)) return rc;
-    if (!g.gas_ops.empty())
-        if (int rc = gas_after_substep(h, g.substep)) return rc;
-    if (!g.pair_ops.empty())
-        if (int rc = pair_after_substep(h, g.substep)) return rc;
-    if (!g.fusion_ops.empty())
-        if (int rc = fusion_after_substep(h, g.substep)) return rc;
-    if (!g.fspec_ops.empty())
-        if (int rc = fspec_after_substep(h, g.substep)) return rc;
-    // the particle sinks (fes_remove.inc.hpp): the tallies above saw the particles that leave now, the rows below see the
-    // thinned box.  Each due application waits for one 8-byte count: the host has to learn the new n
-    if (!g.remove_ops.empty())
-        if (int rc = remove_after_substep(h, g.substep)) return rc;
-    // the particle sources (fes_inject.inc.hpp), after the sinks: a sink beside a source leaves this sub-step's fresh particles
-    // alive, and the rows below count them.  Nothing is read back: the host knows the new n in advance
-    if (!g.inject_ops.empty())
-        if (int rc = inject_after_substep(h, g.substep)) return rc;
+#define X(f) \
+    if (!g.f.ops.empty()) \
+        if (int rc = f##_after_substep(h, g.substep)) return rc;
+    FES_OP_FAMILIES(X)
+#undef X
     const bool f32 = h->prec == FPIC_F32;
     for (int k = 0; k < kRecorders; ++k) {
         void* row = rec_due(g.rec[k], g.substep);

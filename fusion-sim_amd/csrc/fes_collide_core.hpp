@@ -176,19 +176,6 @@ inline const char* check(const fpic_collide_spec* p, int nspecies)
     return nullptr;
 }
 
-// a registration: `registered` operators are held already
-inline const char* check_register(int every, int registered)
-{
-    if (every < 1) return ".every <- must be at least 1";
-    if (registered >= FPIC_COLLIDE_MAX_OPS) return ".spec <- FPIC_COLLIDE_MAX_OPS (8) operators are registered already";
-    return nullptr;
-}
-inline const char* check_index(int index, int registered)
-{
-    if (index < 0 || index >= registered) return ".index <- no such registered operator";
-    return nullptr;
-}
-
 // the kernels' form of a checked request, at `epoch`
 inline Rule rule_of(const fpic_collide_spec& s, uint32_t epoch)
 {

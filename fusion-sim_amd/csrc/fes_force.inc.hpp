@@ -3,40 +3,24 @@
 // The rule and the checks of a request are fes_force_core.hpp, the pass fes_force_kernels.hpp.
 //
 // One launch per application over the slots [0, n) and, while a migration rides on the next push, the arrivals behind them
-// (one range, as collide_enqueue).  The handle keeps one device block: fesforce::kWords tally words and room for three taper
-// tables per registered request, and one more of each for the call that is applied now.  A request's tables are copied at
-// the call — the tapers to the device, the envelope to the host, where it is read once per application.  A registered
-// request is enqueued by the hook diag_after_substep with no host synchronisation and no collective; fpic_force_stats
-// reads its words.
+// (one range, as collide_enqueue).  The family's rows (fes_ops.inc.hpp) hold fesforce::kWords tally words and room for three
+// taper tables each.  A request's tables are copied at the call — the tapers to the device, the envelope to the host, where it
+// is read once per application.  A registered request is enqueued by the hook with no host synchronisation and no
+// collective; fpic_force_stats reads its row.  A force has no period: it is due at the sub-steps at which it is active.
 
-constexpr int kForceNow = FPIC_FORCE_MAX_OPS;            // the words and tables of fpic_force
-constexpr size_t kForceTabDoubles = 3 * static_cast<size_t>(FPIC_FORCE_TABLE_MAX);   // per request
+constexpr int kForceNow = FPIC_FORCE_MAX_OPS;            // the row of fpic_force
+constexpr size_t kForceTabDoubles = 3 * static_cast<size_t>(FPIC_FORCE_TABLE_MAX);   // per row
 
-static int force_room(fpic_handle* h)
-{
-    Diag& g = h->es->diag;
-    if (g.force) return FPIC_OK;
-    void* p = nullptr;
-    const size_t words = static_cast<size_t>(FPIC_FORCE_MAX_OPS + 1) * fesforce::kWords * sizeof(unsigned long long);
-    const size_t bytes = words + static_cast<size_t>(FPIC_FORCE_MAX_OPS + 1) * kForceTabDoubles * sizeof(double);
-    if (int rc = dev_alloc(h, &p, bytes, &h->bytes_grid)) return rc;
-    g.force = static_cast<unsigned long long*>(p);
-    g.force_tab = reinterpret_cast<double*>(static_cast<unsigned char*>(p) + words);
-    HIP_TRY(h, hipMemsetAsync(g.force, 0, words, h->stream));
-    return FPIC_OK;
-}
-
-// a checked request into place `at`: its tally words zeroed, its taper tables on the device, the envelope in `op`
+// a checked request into row `at`: its tally words zeroed, its taper tables on the device, the envelope in `op`
 static int force_hold(fpic_handle* h, const fpic_force_spec& spec, int at, ForceOp& op)
 {
-    Diag& g = h->es->diag;
-    if (int rc = force_room(h)) return rc;
+    OpRows& rows = h->es->diag.force.rows;
+    if (int rc = rows.room(h, fesforce::kWords, FPIC_FORCE_MAX_OPS + 1, kForceTabDoubles)) return rc;
     op.spec = spec;
-    op.applications = 0;
     op.envelope.assign(spec.envelope, spec.envelope + spec.envelope_n);
     op.spec.envelope = nullptr;
-    HIP_TRY(h, hipMemsetAsync(g.force + at * fesforce::kWords, 0, fesforce::kWords * sizeof(unsigned long long), h->stream));
-    double* tab = g.force_tab + at * kForceTabDoubles;
+    if (int rc = rows.zero(h, at)) return rc;
+    double* tab = rows.table(at);
     bool any = false;
     for (int a = 0; a < 3; ++a) {
         op.taper[a] = nullptr;
@@ -95,17 +79,16 @@ static const char* force_check(fpic_handle* h, const fpic_force_spec* spec)
 int force(fpic_handle* h, const fpic_force_spec* spec, fpic_force_result* out)
 {
     State* st = h->es;
+    const OpRows& rows = st->diag.force.rows;
     if (const char* why = force_check(h, spec)) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
     if (out) *out = fpic_force_result{};
     const uint64_t at = st->diag.substep + spec->epoch;
     if (!fesforce::active(*spec, at)) return FPIC_OK;
     ForceOp op;
     if (int rc = force_hold(h, *spec, kForceNow, op)) return rc;
-    unsigned long long* words = st->diag.force + kForceNow * fesforce::kWords;
-    if (int rc = force_apply(h, op, at, words)) return rc;
+    if (int rc = force_apply(h, op, at, rows.row(kForceNow))) return rc;
     uint64_t got[fesforce::kWords] = {};
-    HIP_TRY(h, hipMemcpyAsync(got, words, sizeof(got), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (int rc = rows.fetch(h, kForceNow, got)) return rc;
     if (out) {
         out->applications = 1;
         fesforce::result_of(got, st->sp[spec->species].mass, st->W, out);
@@ -115,58 +98,41 @@ int force(fpic_handle* h, const fpic_force_spec* spec, fpic_force_result* out)
 
 int force_register(fpic_handle* h, const fpic_force_spec* spec, int* index)
 {
-    Diag& g = h->es->diag;
+    auto& f = h->es->diag.force;
     if (const char* why = force_check(h, spec)) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
-    if (const char* why = fesforce::check_register(static_cast<int>(g.force_ops.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
-    const int at = static_cast<int>(g.force_ops.size());
+    if (int rc = ops_check_register(h, f, fesops::kForce, 1)) return rc;
     ForceOp op;
-    if (int rc = force_hold(h, *spec, at, op)) return rc;
-    g.force_ops.push_back(std::move(op));
-    if (index) *index = at;
-    return FPIC_OK;
+    if (int rc = force_hold(h, *spec, static_cast<int>(f.ops.size()), op)) return rc;
+    return ops_push(f, std::move(op), 1, index);
 }
 
 int force_stats(fpic_handle* h, int index, int scope, fpic_force_result* out)
 {
     State* st = h->es;
-    Diag& g = st->diag;
-    if (!out) return fail(h, FPIC_ERR_INVALID_ARG, ".out <- Non-optional property is undefined!");
-    if (const char* why = fesforce::check_index(index, static_cast<int>(g.force_ops.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    auto& f = st->diag.force;
     bool collective = false;
-    if (int rc = diag_scope(h, scope, collective)) return rc;
+    if (int rc = ops_stats_head(h, f, fesops::kForce, index, scope, out, collective)) return rc;
     uint64_t got[fesforce::kWords] = {};
-    HIP_TRY(h, hipMemcpyAsync(got, g.force + index * fesforce::kWords, sizeof(got), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (int rc = f.rows.fetch(h, index, got)) return rc;
     if (collective) {
         uint64_t parts[fesforce::kSumWords];
         fesforce::split_words(got, parts);
         if (int rc = diag_sum_ranks(h, parts, fesforce::kSumWords)) return rc;
         fesforce::join_words(parts, got);
     }
-    const ForceOp& op = g.force_ops[index];
+    const ForceOp& op = f.ops[index];
     *out = fpic_force_result{};
     out->applications = op.applications;   // (the same on every rank: not summed)
     fesforce::result_of(got, st->sp[op.spec.species].mass, st->W, out);
     return FPIC_OK;
 }
 
-int force_clear(fpic_handle* h)
-{
-    h->es->diag.force_ops.clear();   // (applications in flight keep their words and tables; a later registration rewrites its own in stream order)
-    return FPIC_OK;
-}
+int force_clear(fpic_handle* h) { return ops_clear(h->es->diag.force); }
 
-// the hook's part (diag_after_substep, directly after the sub-step is counted): every registered request that is active,
-// in registration order; nothing registered: nothing is enqueued
+// the hook's part: every registered request that is active at s = the sub-step + its epoch (64 bits)
 static int force_after_substep(fpic_handle* h, uint64_t substep)
 {
-    Diag& g = h->es->diag;
-    for (size_t k = 0; k < g.force_ops.size(); ++k) {
-        ForceOp& op = g.force_ops[k];
-        const uint64_t at = substep + op.spec.epoch;
-        if (!fesforce::active(op.spec, at)) continue;
-        op.applications++;
-        if (int rc = force_apply(h, op, at, g.force + k * fesforce::kWords)) return rc;
-    }
-    return FPIC_OK;
+    auto& f = h->es->diag.force;
+    return ops_run_due<true>(f, [&](const ForceOp& op) { return fesforce::active(op.spec, substep + op.spec.epoch); },
+                             [&](ForceOp& op, size_t k) { return force_apply(h, op, substep + op.spec.epoch, f.rows.row(k)); });
 }

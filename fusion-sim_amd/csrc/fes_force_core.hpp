@@ -212,18 +212,6 @@ inline const char* check(const fpic_force_spec* p, int nspecies, const double (&
     return nullptr;
 }
 
-// a registration: `registered` requests are held already
-inline const char* check_register(int registered)
-{
-    if (registered >= FPIC_FORCE_MAX_OPS) return ".spec <- FPIC_FORCE_MAX_OPS (8) requests are registered already";
-    return nullptr;
-}
-inline const char* check_index(int index, int registered)
-{
-    if (index < 0 || index >= registered) return ".index <- no such registered request";
-    return nullptr;
-}
-
 // ---- the tallies on the host
 // the double nearest to s 2^-80 (ties to even) of a 128-bit two's complement sum: from_fix of fes_diag_kernels.hpp
 inline double fixed_to_double(uint64_t lo, uint64_t hi)

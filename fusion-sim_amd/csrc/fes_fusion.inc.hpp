@@ -3,46 +3,28 @@
 // namespace fes).  The rule and the checks of a request are fes_fusion_core.hpp, the pass fes_fusion_kernels.hpp.
 //
 // One application: per species of the request fpic_pair's cell index (pair_index<T>, into the Diag's index buffers,
-// unchanged), then the tally pass — all enqueued on the handle's stream, nothing read back.  The count words, the tables and
-// the cell grids belong to the handle's Diag and are released with it: slot k < FPIC_FUSION_MAX_OPS serves the k-th
-// registered operator, slot FPIC_FUSION_MAX_OPS the call.  A table is uploaded at the call or at the registration (which
+// unchanged), then the tally pass — all enqueued on the handle's stream, nothing read back.  The family's rows
+// (fes_ops.inc.hpp) hold eight count words and a table each (the tables an allocation of their own); beside every row the
+// Diag keeps a cell grid, allocated when the row is first used.  A table is uploaded at the call or at the registration (which
 // waits for the copy: the caller's table need not outlive it); the hook never allocates and never waits.
 // A handle with a Domain is refused as fpic_pair refuses it.
 
-constexpr int kFusionWords = 8;                     // per slot: pairs, below, above, cells, overfull_cells, overfull_particles, yield_hi, yield_lo
-constexpr int kFusionNow = FPIC_FUSION_MAX_OPS;     // the slot of fpic_fusion
+constexpr int kFusionWords = 8;                     // per row: pairs, below, above, cells, overfull_cells, overfull_particles, yield_hi, yield_lo
+constexpr int kFusionNow = FPIC_FUSION_MAX_OPS;     // the row of fpic_fusion
 
-static int fusion_slot(fpic_handle* h, int slot)
-{
-    State* st = h->es;
-    Diag& g = st->diag;
-    void* p = nullptr;
-    if (!g.fusion) {
-        const size_t bytes = static_cast<size_t>(FPIC_FUSION_MAX_OPS + 1) * kFusionWords * sizeof(unsigned long long);
-        if (int rc = dev_alloc(h, &p, bytes, &h->bytes_grid)) return rc;
-        g.fusion = static_cast<unsigned long long*>(p);
-        HIP_TRY(h, hipMemsetAsync(g.fusion, 0, bytes, h->stream));
-    }
-    if (!g.fusion_table) {
-        if (int rc = dev_alloc(h, &p, static_cast<size_t>(FPIC_FUSION_MAX_OPS + 1) * FPIC_FUSION_TABLE_MAX * sizeof(double), &h->bytes_grid)) return rc;
-        g.fusion_table = static_cast<double*>(p);
-    }
-    if (!g.fusion_grid[slot]) {
-        if (int rc = dev_alloc(h, &p, pair_cells(st) * sizeof(unsigned long long), &h->bytes_grid)) return rc;
-        g.fusion_grid[slot] = static_cast<unsigned long long*>(p);
-    }
-    return FPIC_OK;
-}
-
-// the slot starts from zero with the request's table, in stream order; returns after the table has been copied
+// the row starts from zero with the request's table, in stream order; returns after the table has been copied
 static int fusion_begin(fpic_handle* h, int slot, const fpic_fusion_spec& spec)
 {
     State* st = h->es;
     Diag& g = st->diag;
-    if (int rc = fusion_slot(h, slot)) return rc;
-    HIP_TRY(h, hipMemsetAsync(g.fusion + slot * kFusionWords, 0, kFusionWords * sizeof(unsigned long long), h->stream));
-    HIP_TRY(h, hipMemsetAsync(g.fusion_grid[slot], 0, pair_cells(st) * sizeof(unsigned long long), h->stream));
-    HIP_TRY(h, hipMemcpyAsync(g.fusion_table + static_cast<size_t>(slot) * FPIC_FUSION_TABLE_MAX, spec.sigma, static_cast<size_t>(spec.n) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    OpRows& rows = g.fusion.rows;
+    const size_t grid_bytes = pair_cells(st) * sizeof(unsigned long long);
+    if (int rc = rows.room(h, kFusionWords, FPIC_FUSION_MAX_OPS + 1, FPIC_FUSION_TABLE_MAX, true)) return rc;
+    if (!g.fusion_grid[slot])
+        if (int rc = dev_alloc(h, reinterpret_cast<void**>(&g.fusion_grid[slot]), grid_bytes, &h->bytes_grid)) return rc;
+    if (int rc = rows.zero(h, slot)) return rc;
+    HIP_TRY(h, hipMemsetAsync(g.fusion_grid[slot], 0, grid_bytes, h->stream));
+    HIP_TRY(h, hipMemcpyAsync(rows.table(slot), spec.sigma, static_cast<size_t>(spec.n) * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return FPIC_OK;
 }
@@ -83,9 +65,9 @@ static int fusion_enqueue(fpic_handle* h, const fpic_fusion_spec& spec, const fe
     a.index_b = g.pair_index[like ? 0 : 1];
     a.ncells = static_cast<uint32_t>(pair_cells(st));
     a.rank_max = (pair_forms() & 2) ? static_cast<uint32_t>(kPairRankMax) : ~0u;
-    a.counts = g.fusion + slot * kFusionWords;
+    a.counts = g.fusion.rows.row(slot);
     a.grid = g.fusion_grid[slot];
-    a.table = g.fusion_table + static_cast<size_t>(slot) * FPIC_FUSION_TABLE_MAX;
+    a.table = g.fusion.rows.table(slot);
     a.r = r;
     const size_t nchunks = (pair_cells(st) + kPairChunk - 1) / kPairChunk;
     const unsigned grid = static_cast<unsigned>(std::min<size_t>(kPairCollideBlocks, nchunks));
@@ -139,9 +121,8 @@ int fusion(fpic_handle* h, const fpic_fusion_spec* spec, fpic_fusion_result* out
     const fesfusion::Rule r = fesfusion::rule_of(*spec, spec->epoch, st->W, fusion_dv(st));
     if (int rc = fusion_apply(h, *spec, r, kFusionNow, true)) return rc;
     uint64_t got[kFusionWords] = {};
-    HIP_TRY(h, hipMemcpyAsync(got, g.fusion + kFusionNow * kFusionWords, sizeof(got), hipMemcpyDeviceToHost, h->stream));
     if (grid) HIP_TRY(h, hipMemcpyAsync(grid, g.fusion_grid[kFusionNow], pair_cells(st) * sizeof(int64_t), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (int rc = g.fusion.rows.fetch(h, kFusionNow, got)) return rc;
     if (out) fusion_result(out, 1, got, r.e);
     return FPIC_OK;
 }
@@ -149,34 +130,30 @@ int fusion(fpic_handle* h, const fpic_fusion_spec* spec, fpic_fusion_result* out
 int fusion_register(fpic_handle* h, const fpic_fusion_spec* spec, int every, int* index)
 {
     State* st = h->es;
-    Diag& g = st->diag;
+    auto& f = st->diag.fusion;
     if (int rc = pair_refuse_decomposed(h, "fpic_fusion_register")) return rc;
     if (int rc = fusion_check(h, spec)) return rc;
-    if (const char* why = fesfusion::check_register(every, static_cast<int>(g.fusion_ops.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    if (int rc = ops_check_register(h, f, fesops::kFusion, every)) return rc;
     if (int rc = fusion_buffers(h, *spec, true)) return rc;   // (sized now: the hook finds them in place and never grows them)
-    const int at = static_cast<int>(g.fusion_ops.size());
-    if (int rc = fusion_begin(h, at, *spec)) return rc;
-    FusionOp op{ *spec, every, 0, fesfusion::rule_of(*spec, spec->epoch, st->W, fusion_dv(st)) };
+    if (int rc = fusion_begin(h, static_cast<int>(f.ops.size()), *spec)) return rc;
+    FusionOp op;
+    op.spec = *spec;
     op.spec.sigma = nullptr;        // (the table is on the device; the caller's need not outlive this call)
-    g.fusion_ops.push_back(op);
-    if (index) *index = at;
-    return FPIC_OK;
+    op.rule = fesfusion::rule_of(*spec, spec->epoch, st->W, fusion_dv(st));
+    return ops_push(f, op, every, index);
 }
 
 int fusion_stats(fpic_handle* h, int index, int scope, fpic_fusion_result* out)
 {
-    Diag& g = h->es->diag;
+    auto& f = h->es->diag.fusion;
     if (int rc = pair_refuse_decomposed(h, "fpic_fusion_stats")) return rc;
-    if (!out) return fail(h, FPIC_ERR_INVALID_ARG, ".out <- Non-optional property is undefined!");
-    if (const char* why = fesfusion::check_index(index, static_cast<int>(g.fusion_ops.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
     bool collective = false;
-    if (int rc = diag_scope(h, scope, collective)) return rc;
+    if (int rc = ops_stats_head(h, f, fesops::kFusion, index, scope, out, collective)) return rc;
     uint64_t got[kFusionWords] = {};
-    HIP_TRY(h, hipMemcpyAsync(got, g.fusion + index * kFusionWords, sizeof(got), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (int rc = f.rows.fetch(h, index, got)) return rc;
     if (collective)
         if (int rc = diag_sum_ranks(h, got, kFusionWords)) return rc;
-    fusion_result(out, g.fusion_ops[index].applications, got, g.fusion_ops[index].rule.e);
+    fusion_result(out, f.ops[index].applications, got, f.ops[index].rule.e);
     return FPIC_OK;
 }
 
@@ -185,14 +162,14 @@ int fusion_grid(fpic_handle* h, int index, int64_t* grid, int reset)
     State* st = h->es;
     Diag& g = st->diag;
     if (int rc = pair_refuse_decomposed(h, "fpic_fusion_grid")) return rc;
-    if (const char* why = fesfusion::check_index(index, static_cast<int>(g.fusion_ops.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    if (int rc = ops_check_index(h, g.fusion, fesops::kFusion, index)) return rc;
     if (!grid && !reset) return fail(h, FPIC_ERR_INVALID_ARG, ".grid <- Non-optional property is undefined!");
     const size_t bytes = pair_cells(st) * sizeof(int64_t);
     if (grid) HIP_TRY(h, hipMemcpyAsync(grid, g.fusion_grid[index], bytes, hipMemcpyDeviceToHost, h->stream));
     if (reset) {   // (behind the copy, in stream order)
         HIP_TRY(h, hipMemsetAsync(g.fusion_grid[index], 0, bytes, h->stream));
-        HIP_TRY(h, hipMemsetAsync(g.fusion + index * kFusionWords, 0, kFusionWords * sizeof(unsigned long long), h->stream));
-        g.fusion_ops[index].applications = 0;
+        if (int rc = g.fusion.rows.zero(h, index)) return rc;
+        g.fusion.ops[index].applications = 0;
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return FPIC_OK;
@@ -201,21 +178,15 @@ int fusion_grid(fpic_handle* h, int index, int64_t* grid, int reset)
 int fusion_clear(fpic_handle* h)
 {
     if (int rc = pair_refuse_decomposed(h, "fpic_fusion_clear")) return rc;
-    h->es->diag.fusion_ops.clear();   // (applications in flight keep their slots; a later registration zeroes its own in stream order)
-    return FPIC_OK;
+    return ops_clear(h->es->diag.fusion);
 }
 
-// the hook's part (diag_after_substep, after the pair operators): every registered tally that is due, in registration order
+// the hook's part: every registered tally that is due — the registered rule at the epoch of the sub-step; nothing grows here
 static int fusion_after_substep(fpic_handle* h, uint64_t substep)
 {
-    Diag& g = h->es->diag;
-    for (size_t k = 0; k < g.fusion_ops.size(); ++k) {
-        FusionOp& op = g.fusion_ops[k];
-        if (substep % static_cast<uint64_t>(op.every)) continue;
-        op.applications++;
+    return ops_run_due<true>(h->es->diag.fusion, OpsEvery{ substep }, [&](FusionOp& op, size_t k) {
         fesfusion::Rule r = op.rule;
         r.epoch = static_cast<uint32_t>(substep + op.spec.epoch);
-        if (int rc = fusion_apply(h, op.spec, r, static_cast<int>(k), false)) return rc;
-    }
-    return FPIC_OK;
+        return fusion_apply(h, op.spec, r, static_cast<int>(k), false);
+    });
 }

@@ -177,19 +177,6 @@ inline const char* check_bound(const fpic_fusion_spec& s, double W, double dV)
     return nullptr;
 }
 
-// a registration: `registered` operators are held already
-inline const char* check_register(int every, int registered)
-{
-    if (every < 1) return ".every <- must be at least 1";
-    if (registered >= FPIC_FUSION_MAX_OPS) return ".spec <- FPIC_FUSION_MAX_OPS (4) operators are registered already";
-    return nullptr;
-}
-inline const char* check_index(int index, int registered)
-{
-    if (index < 0 || index >= registered) return ".index <- no such registered operator";
-    return nullptr;
-}
-
 // the kernel's form of a checked request, at `epoch`: the macro weight and the cell volume (m^3)
 inline Rule rule_of(const fpic_fusion_spec& s, uint32_t epoch, double W, double dV)
 {

@@ -4,46 +4,25 @@
 // fes_fusion_spectrum_core.hpp on top of fes_fusion_core.hpp, the pass fes_fusion_spectrum_kernels.hpp.
 //
 // One application: per species of the request fpic_pair's cell index (pair_index<T>, into the Diag's index buffers,
-// unchanged), then the spectrum pass — all enqueued on the handle's stream, nothing read back.  The count words, the tables
-// and the histogram words belong to the handle's Diag and are released with it: slot k < FPIC_FUSION_SPECTRUM_MAX_OPS serves
-// the k-th registered operator, slot FPIC_FUSION_SPECTRUM_MAX_OPS the call.  A table is uploaded at the call or at the
+// unchanged), then the spectrum pass — all enqueued on the handle's stream, nothing read back.  The family's rows
+// (fes_ops.inc.hpp) hold the tally's eight count words and a table each (the tables an allocation of their own); the
+// histogram words are rows of their own beside them (Diag::fspec_bins).  A table is uploaded at the call or at the
 // registration (which waits for the copy); the hook never allocates, never waits and never reads back.
 // A handle with a Domain is refused as fpic_fusion refuses it.
 
-constexpr int kFspecNow = FPIC_FUSION_SPECTRUM_MAX_OPS;      // the slot of fpic_fusion_spectrum
+constexpr int kFspecNow = FPIC_FUSION_SPECTRUM_MAX_OPS;      // the row of fpic_fusion_spectrum
 constexpr size_t kFspecSlotWords = static_cast<size_t>(kFspecEntriesMax) * 2;
 
-static int fspec_slots(fpic_handle* h)
-{
-    Diag& g = h->es->diag;
-    void* p = nullptr;
-    if (!g.fspec) {
-        const size_t bytes = static_cast<size_t>(FPIC_FUSION_SPECTRUM_MAX_OPS + 1) * kFusionWords * sizeof(unsigned long long);
-        if (int rc = dev_alloc(h, &p, bytes, &h->bytes_grid)) return rc;
-        g.fspec = static_cast<unsigned long long*>(p);
-        HIP_TRY(h, hipMemsetAsync(g.fspec, 0, bytes, h->stream));
-    }
-    if (!g.fspec_table) {
-        if (int rc = dev_alloc(h, &p, static_cast<size_t>(FPIC_FUSION_SPECTRUM_MAX_OPS + 1) * FPIC_FUSION_TABLE_MAX * sizeof(double), &h->bytes_grid)) return rc;
-        g.fspec_table = static_cast<double*>(p);
-    }
-    if (!g.fspec_words) {
-        const size_t bytes = static_cast<size_t>(FPIC_FUSION_SPECTRUM_MAX_OPS + 1) * kFspecSlotWords * sizeof(unsigned long long);
-        if (int rc = dev_alloc(h, &p, bytes, &h->bytes_grid)) return rc;
-        g.fspec_words = static_cast<unsigned long long*>(p);
-        HIP_TRY(h, hipMemsetAsync(g.fspec_words, 0, bytes, h->stream));
-    }
-    return FPIC_OK;
-}
-
-// the slot starts from zero with the request's table, in stream order; returns after the table has been copied
+// the row starts from zero with the request's table, in stream order; returns after the table has been copied
 static int fspec_begin(fpic_handle* h, int slot, const fpic_fusion_spec& tally)
 {
     Diag& g = h->es->diag;
-    if (int rc = fspec_slots(h)) return rc;
-    HIP_TRY(h, hipMemsetAsync(g.fspec + slot * kFusionWords, 0, kFusionWords * sizeof(unsigned long long), h->stream));
-    HIP_TRY(h, hipMemsetAsync(g.fspec_words + slot * kFspecSlotWords, 0, kFspecSlotWords * sizeof(unsigned long long), h->stream));
-    HIP_TRY(h, hipMemcpyAsync(g.fspec_table + static_cast<size_t>(slot) * FPIC_FUSION_TABLE_MAX, tally.sigma, static_cast<size_t>(tally.n) * sizeof(double), hipMemcpyHostToDevice, h->stream));
+    OpRows& rows = g.fspec.rows;
+    if (int rc = rows.room(h, kFusionWords, FPIC_FUSION_SPECTRUM_MAX_OPS + 1, FPIC_FUSION_TABLE_MAX, true)) return rc;
+    if (int rc = g.fspec_bins.room(h, static_cast<int>(kFspecSlotWords), FPIC_FUSION_SPECTRUM_MAX_OPS + 1)) return rc;
+    if (int rc = rows.zero(h, slot)) return rc;
+    if (int rc = g.fspec_bins.zero(h, slot)) return rc;
+    HIP_TRY(h, hipMemcpyAsync(rows.table(slot), tally.sigma, static_cast<size_t>(tally.n) * sizeof(double), hipMemcpyHostToDevice, h->stream));
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     return FPIC_OK;
 }
@@ -84,9 +63,9 @@ static int fspec_enqueue(fpic_handle* h, const fpic_fusion_spec& spec, const fes
     a.index_b = g.pair_index[like ? 0 : 1];
     a.ncells = static_cast<uint32_t>(pair_cells(st));
     a.rank_max = (pair_forms() & 2) ? static_cast<uint32_t>(kPairRankMax) : ~0u;
-    a.counts = g.fspec + slot * kFusionWords;
-    a.words = g.fspec_words + slot * kFspecSlotWords;
-    a.table = g.fspec_table + static_cast<size_t>(slot) * FPIC_FUSION_TABLE_MAX;
+    a.counts = g.fspec.rows.row(slot);
+    a.words = g.fspec_bins.row(slot);
+    a.table = g.fspec.rows.table(slot);
     a.r = r;
     a.s = s;
     const size_t nchunks = (pair_cells(st) + kPairChunk - 1) / kPairChunk;
@@ -115,17 +94,18 @@ static fesfspec::Rule fspec_rule(const State* st, const fpic_fusion_spectrum_spe
     return fesfspec::rule_of(spec, st->sp[spec.tally.species_a].mass, st->sp[spec.tally.species_b].mass);
 }
 
-// the slot's counts and words -> out, words ((bins + 2) x 2, every entry joined); waits for the copies
+// the row's counts and bins -> out, words ((bins + 2) x 2, every entry joined); waits for the copies
 static int fspec_fetch(fpic_handle* h, int slot, int bins, uint64_t applications, int e, fpic_fusion_result* out, uint64_t* words, bool reset)
 {
     Diag& g = h->es->diag;
     uint64_t got[kFusionWords] = {};
     const size_t nwords = static_cast<size_t>(bins + 2) * 2;
-    HIP_TRY(h, hipMemcpyAsync(got, g.fspec + slot * kFusionWords, sizeof(got), hipMemcpyDeviceToHost, h->stream));
-    if (words) HIP_TRY(h, hipMemcpyAsync(words, g.fspec_words + slot * kFspecSlotWords, nwords * sizeof(uint64_t), hipMemcpyDeviceToHost, h->stream));
+    if (int rc = g.fspec.rows.copy(h, slot, got, kFusionWords)) return rc;
+    if (words)
+        if (int rc = g.fspec_bins.copy(h, slot, words, nwords)) return rc;
     if (reset) {   // (behind the copies, in stream order)
-        HIP_TRY(h, hipMemsetAsync(g.fspec + slot * kFusionWords, 0, kFusionWords * sizeof(unsigned long long), h->stream));
-        HIP_TRY(h, hipMemsetAsync(g.fspec_words + slot * kFspecSlotWords, 0, kFspecSlotWords * sizeof(unsigned long long), h->stream));
+        if (int rc = g.fspec.rows.zero(h, slot)) return rc;
+        if (int rc = g.fspec_bins.zero(h, slot)) return rc;
     }
     HIP_TRY(h, hipStreamSynchronize(h->stream));
     if (out) fusion_result(out, applications, got, e);
@@ -149,27 +129,27 @@ int fusion_spectrum(fpic_handle* h, const fpic_fusion_spectrum_spec* spec, fpic_
 int fusion_spectrum_register(fpic_handle* h, const fpic_fusion_spectrum_spec* spec, int every, int* index)
 {
     State* st = h->es;
-    Diag& g = st->diag;
+    auto& f = st->diag.fspec;
     if (int rc = pair_refuse_decomposed(h, "fpic_fusion_spectrum_register")) return rc;
     if (int rc = fspec_check(h, spec)) return rc;
-    if (const char* why = fesfspec::check_register(every, static_cast<int>(g.fspec_ops.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    if (int rc = ops_check_register(h, f, fesops::kFspec, every)) return rc;
     if (int rc = fusion_buffers(h, spec->tally, true)) return rc;   // (sized now: the hook finds them in place and never grows them)
-    const int at = static_cast<int>(g.fspec_ops.size());
-    if (int rc = fspec_begin(h, at, spec->tally)) return rc;
-    FspecOp op{ *spec, every, 0, fesfusion::rule_of(spec->tally, spec->tally.epoch, st->W, fusion_dv(st)), fspec_rule(st, *spec) };
+    if (int rc = fspec_begin(h, static_cast<int>(f.ops.size()), spec->tally)) return rc;
+    FspecOp op;
+    op.spec = *spec;
     op.spec.tally.sigma = nullptr;  // (the table is on the device; the caller's need not outlive this call)
-    g.fspec_ops.push_back(op);
-    if (index) *index = at;
-    return FPIC_OK;
+    op.rule = fesfusion::rule_of(spec->tally, spec->tally.epoch, st->W, fusion_dv(st));
+    op.axis = fspec_rule(st, *spec);
+    return ops_push(f, op, every, index);
 }
 
 int fusion_spectrum_read(fpic_handle* h, int index, fpic_fusion_result* out, uint64_t* words, int reset)
 {
-    Diag& g = h->es->diag;
+    auto& f = h->es->diag.fspec;
     if (int rc = pair_refuse_decomposed(h, "fpic_fusion_spectrum_read")) return rc;
-    if (const char* why = fesfusion::check_index(index, static_cast<int>(g.fspec_ops.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    if (int rc = ops_check_index(h, f, fesops::kFspec, index)) return rc;
     if (!out && !words && !reset) return fail(h, FPIC_ERR_INVALID_ARG, ".out <- Non-optional property is undefined!");
-    FspecOp& op = g.fspec_ops[index];
+    FspecOp& op = f.ops[index];
     const uint64_t applications = op.applications;
     if (reset) op.applications = 0;
     return fspec_fetch(h, index, op.spec.bins, applications, op.rule.e, out, words, reset != 0);
@@ -178,21 +158,15 @@ int fusion_spectrum_read(fpic_handle* h, int index, fpic_fusion_result* out, uin
 int fusion_spectrum_clear(fpic_handle* h)
 {
     if (int rc = pair_refuse_decomposed(h, "fpic_fusion_spectrum_clear")) return rc;
-    h->es->diag.fspec_ops.clear();   // (applications in flight keep their slots; a later registration zeroes its own in stream order)
-    return FPIC_OK;
+    return ops_clear(h->es->diag.fspec);
 }
 
-// the hook's part (diag_after_substep, after the fusion tallies): every registered spectrum that is due, in registration order
+// the hook's part: every registered spectrum that is due — the registered rules at the epoch of the sub-step
 static int fspec_after_substep(fpic_handle* h, uint64_t substep)
 {
-    Diag& g = h->es->diag;
-    for (size_t k = 0; k < g.fspec_ops.size(); ++k) {
-        FspecOp& op = g.fspec_ops[k];
-        if (substep % static_cast<uint64_t>(op.every)) continue;
-        op.applications++;
+    return ops_run_due<true>(h->es->diag.fspec, OpsEvery{ substep }, [&](FspecOp& op, size_t k) {
         fesfusion::Rule r = op.rule;
         r.epoch = static_cast<uint32_t>(substep + op.spec.tally.epoch);
-        if (int rc = fspec_apply(h, op.spec.tally, r, op.axis, static_cast<int>(k), false)) return rc;
-    }
-    return FPIC_OK;
+        return fspec_apply(h, op.spec.tally, r, op.axis, static_cast<int>(k), false);
+    });
 }

@@ -168,13 +168,6 @@ inline const char* check(const fpic_fusion_spectrum_spec* p, int nspecies)
     return nullptr;
 }
 
-inline const char* check_register(int every, int registered)
-{
-    if (every < 1) return ".every <- must be at least 1";
-    if (registered >= FPIC_FUSION_SPECTRUM_MAX_OPS) return ".spec <- FPIC_FUSION_SPECTRUM_MAX_OPS (4) operators are registered already";
-    return nullptr;
-}
-
 // the kernel's form of a checked request: m_a, m_b the masses of species_a and species_b (kg)
 inline Rule rule_of(const fpic_fusion_spectrum_spec& s, double m_a, double m_b)
 {

@@ -4,20 +4,18 @@
 // fes_gas_kernels.hpp.
 //
 // One launch per application over the slots [0, n) and, while a migration rides on the next push, the arrivals behind them
-// (one range, as collide_enqueue).  The handle keeps one device block: fesgas::kWords tally words and room for the
-// cross-section table and three taper tables per registered operator, and one more of each for the call that is applied now.
-// A request's tables are copied at the call: to the device, and the cross-sections to the host too, where the candidate
+// (one range, as collide_enqueue).  The family's rows (fes_ops.inc.hpp) hold fesgas::kWords tally words and room for the
+// cross-section table and three taper tables each.  A request's tables are copied at the call: to the device, and the cross-sections to the host too, where the candidate
 // bound is formed.  Per request the host chooses which test the pass makes first (gas_window_first) and whether its
 // candidates go through the LDS queue (gas_compacts); DESIGN 4.23 has the measurements behind the thresholds.  A registered
-// operator is enqueued by the hook diag_after_substep with no host synchronisation and no collective; fpic_gas_stats reads
-// its words.
+// operator is enqueued by the hook with no host synchronisation and no collective; fpic_gas_stats reads its row.
 //
 // TEST SWITCH (FPIC_GAS_FORMS, read once): which form runs, for measuring one against the other.  A sum of 1 (the word
 // first), 2 (the window first), 4 (the wave-shared loop), 8 (the LDS queue); 0 or unset: the host's choices.  Every form
 // gives the same particles.
 
-constexpr int kGasNow = FPIC_GAS_MAX_OPS;                // the words and tables of fpic_gas
-constexpr size_t kGasTabDoubles = static_cast<size_t>(FPIC_GAS_TABLE_MAX) + 3 * static_cast<size_t>(FPIC_GAS_TAPER_MAX);   // per request
+constexpr int kGasNow = FPIC_GAS_MAX_OPS;                // the row of fpic_gas
+constexpr size_t kGasTabDoubles = static_cast<size_t>(FPIC_GAS_TABLE_MAX) + 3 * static_cast<size_t>(FPIC_GAS_TAPER_MAX);   // per row
 
 static int gas_forms()
 {
@@ -25,32 +23,16 @@ static int gas_forms()
     return forms;
 }
 
-static int gas_room(fpic_handle* h)
+// a checked request into row `at`: its tally words zeroed, its tables on the device, the cross-sections in `op` too
+static int gas_hold(fpic_handle* h, const fpic_gas_spec& spec, int at, GasOp& op)
 {
-    Diag& g = h->es->diag;
-    if (g.gas) return FPIC_OK;
-    void* p = nullptr;
-    const size_t words = static_cast<size_t>(FPIC_GAS_MAX_OPS + 1) * fesgas::kWords * sizeof(unsigned long long);
-    const size_t bytes = words + static_cast<size_t>(FPIC_GAS_MAX_OPS + 1) * kGasTabDoubles * sizeof(double);
-    if (int rc = dev_alloc(h, &p, bytes, &h->bytes_grid)) return rc;
-    g.gas = static_cast<unsigned long long*>(p);
-    g.gas_tab = reinterpret_cast<double*>(static_cast<unsigned char*>(p) + words);
-    HIP_TRY(h, hipMemsetAsync(g.gas, 0, words, h->stream));
-    return FPIC_OK;
-}
-
-// a checked request into place `at`: its tally words zeroed, its tables on the device, the cross-sections in `op` too
-static int gas_hold(fpic_handle* h, const fpic_gas_spec& spec, int every, int at, GasOp& op)
-{
-    Diag& g = h->es->diag;
-    if (int rc = gas_room(h)) return rc;
+    OpRows& rows = h->es->diag.gas.rows;
+    if (int rc = rows.room(h, fesgas::kWords, FPIC_GAS_MAX_OPS + 1, kGasTabDoubles)) return rc;
     op.spec = spec;
-    op.every = every;
-    op.applications = 0;
     op.sigma.assign(spec.sigma, spec.sigma + spec.n);
     op.spec.sigma = nullptr;
-    HIP_TRY(h, hipMemsetAsync(g.gas + at * fesgas::kWords, 0, fesgas::kWords * sizeof(unsigned long long), h->stream));
-    double* tab = g.gas_tab + at * kGasTabDoubles;
+    if (int rc = rows.zero(h, at)) return rc;
+    double* tab = rows.table(at);
     HIP_TRY(h, hipMemcpyAsync(tab, op.sigma.data(), op.sigma.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
     op.dev_sigma = tab;
     tab += spec.n;
@@ -116,17 +98,16 @@ static const char* gas_check(fpic_handle* h, const fpic_gas_spec* spec)
 int gas(fpic_handle* h, const fpic_gas_spec* spec, fpic_gas_result* out)
 {
     State* st = h->es;
+    const OpRows& rows = st->diag.gas.rows;
     if (const char* why = gas_check(h, spec)) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
     if (out) *out = fpic_gas_result{};
     const double p_max = -std::expm1(-fesgas::x_max_of(*spec));
     if (static_cast<uint64_t>(std::ldexp(p_max, 32)) == 0) return FPIC_OK;   // (K = 0: nothing is launched, nothing is held)
     GasOp op;
-    if (int rc = gas_hold(h, *spec, 1, kGasNow, op)) return rc;
-    unsigned long long* words = st->diag.gas + kGasNow * fesgas::kWords;
-    if (int rc = gas_apply(h, op, spec->epoch, words)) return rc;
+    if (int rc = gas_hold(h, *spec, kGasNow, op)) return rc;
+    if (int rc = gas_apply(h, op, spec->epoch, rows.row(kGasNow))) return rc;
     uint64_t got[fesgas::kWords] = {};
-    HIP_TRY(h, hipMemcpyAsync(got, words, sizeof(got), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (int rc = rows.fetch(h, kGasNow, got)) return rc;
     if (out) {
         out->applications = 1;
         fesgas::result_of(got, st->sp[spec->species].mass, st->W, out);
@@ -136,57 +117,40 @@ int gas(fpic_handle* h, const fpic_gas_spec* spec, fpic_gas_result* out)
 
 int gas_register(fpic_handle* h, const fpic_gas_spec* spec, int every, int* index)
 {
-    Diag& g = h->es->diag;
+    auto& f = h->es->diag.gas;
     if (const char* why = gas_check(h, spec)) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
-    if (const char* why = fesgas::check_register(every, static_cast<int>(g.gas_ops.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
-    const int at = static_cast<int>(g.gas_ops.size());
+    if (int rc = ops_check_register(h, f, fesops::kGas, every)) return rc;
     GasOp op;
-    if (int rc = gas_hold(h, *spec, every, at, op)) return rc;
-    g.gas_ops.push_back(std::move(op));
-    if (index) *index = at;
-    return FPIC_OK;
+    if (int rc = gas_hold(h, *spec, static_cast<int>(f.ops.size()), op)) return rc;
+    return ops_push(f, std::move(op), every, index);
 }
 
 int gas_stats(fpic_handle* h, int index, int scope, fpic_gas_result* out)
 {
     State* st = h->es;
-    Diag& g = st->diag;
-    if (!out) return fail(h, FPIC_ERR_INVALID_ARG, ".out <- Non-optional property is undefined!");
-    if (const char* why = fesgas::check_index(index, static_cast<int>(g.gas_ops.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    auto& f = st->diag.gas;
     bool collective = false;
-    if (int rc = diag_scope(h, scope, collective)) return rc;
+    if (int rc = ops_stats_head(h, f, fesops::kGas, index, scope, out, collective)) return rc;
     uint64_t got[fesgas::kWords] = {};
-    HIP_TRY(h, hipMemcpyAsync(got, g.gas + index * fesgas::kWords, sizeof(got), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (int rc = f.rows.fetch(h, index, got)) return rc;
     if (collective) {
         uint64_t parts[fesgas::kSumWords];
         fesgas::split_words(got, parts);
         if (int rc = diag_sum_ranks(h, parts, fesgas::kSumWords)) return rc;
         fesgas::join_words(parts, got);
     }
-    const GasOp& op = g.gas_ops[index];
+    const GasOp& op = f.ops[index];
     *out = fpic_gas_result{};
     out->applications = op.applications;   // (the same on every rank: not summed)
     fesgas::result_of(got, st->sp[op.spec.species].mass, st->W, out);
     return FPIC_OK;
 }
 
-int gas_clear(fpic_handle* h)
-{
-    h->es->diag.gas_ops.clear();   // (applications in flight keep their words and tables; a later registration rewrites its own in stream order)
-    return FPIC_OK;
-}
+int gas_clear(fpic_handle* h) { return ops_clear(h->es->diag.gas); }
 
-// the hook's part (diag_after_substep, after the operators of fpic_collide_register): every registered operator that is due,
-// in registration order; nothing registered: nothing is enqueued
+// the hook's part: every registered operator that is due, at the epoch of the sub-step
 static int gas_after_substep(fpic_handle* h, uint64_t substep)
 {
-    Diag& g = h->es->diag;
-    for (size_t k = 0; k < g.gas_ops.size(); ++k) {
-        GasOp& op = g.gas_ops[k];
-        if (substep % static_cast<uint64_t>(op.every)) continue;
-        op.applications++;
-        if (int rc = gas_apply(h, op, static_cast<uint32_t>(substep + op.spec.epoch), g.gas + k * fesgas::kWords)) return rc;
-    }
-    return FPIC_OK;
+    auto& f = h->es->diag.gas;
+    return ops_run_due<true>(f, OpsEvery{ substep }, [&](GasOp& op, size_t k) { return gas_apply(h, op, static_cast<uint32_t>(substep + op.spec.epoch), f.rows.row(k)); });
 }

@@ -234,19 +234,6 @@ inline const char* check(const fpic_gas_spec* p, int nspecies, const double (&L)
     return nullptr;
 }
 
-// a registration: `registered` operators are held already
-inline const char* check_register(int every, int registered)
-{
-    if (every < 1) return ".every <- must be at least 1";
-    if (registered >= FPIC_GAS_MAX_OPS) return ".spec <- FPIC_GAS_MAX_OPS (8) operators are registered already";
-    return nullptr;
-}
-inline const char* check_index(int index, int registered)
-{
-    if (index < 0 || index >= registered) return ".index <- no such registered operator";
-    return nullptr;
-}
-
 // the kernels' form of a checked request at `epoch`: sigma, taper[a] = where the kernels read the tables; host_sigma = the
 // host's copy of the cross-sections (s.sigma may have been dropped)
 inline Rule rule_of(const fpic_gas_spec& s, const double (&L)[3], uint32_t epoch, const double* host_sigma, const double* sigma, const double* const* taper)

@@ -20,10 +20,10 @@
 // (fpic_pair, fpic_fusion, fpic_fusion_spectrum) is sized from n_pad when one is registered and regrown by reserve() itself,
 // and the message buffers of a decomposition (fpic_domain_init) are sized when it is made — after which fpic_reserve is refused.
 
-// the handle's device block, rows of kDiagWords words: the sources' totals, the row of the last application, the generation
-// pass's partial rows
+// the family's rows (fes_ops.inc.hpp), kDiagWords words each: the sources' totals, the row of the last application (the call's
+// row), behind it the generation pass's partial rows
 constexpr int kInjectLast = FPIC_INJECT_MAX_OPS;
-constexpr size_t kInjectRows = static_cast<size_t>(FPIC_INJECT_MAX_OPS) + 1 + kInjectBlocks;
+constexpr int kInjectPartial = kInjectLast + 1;
 
 static int inject_refuse_decomposed(fpic_handle* h, const char* name)
 {
@@ -31,16 +31,7 @@ static int inject_refuse_decomposed(fpic_handle* h, const char* name)
     return fail(h, FPIC_ERR_STATE, "%s needs an undecomposed handle: a rank's arrivals ride on its next push, and its message buffers were sized from the capacity it had", name);
 }
 
-static int inject_room(fpic_handle* h)
-{
-    Diag& g = h->es->diag;
-    if (g.inject) return FPIC_OK;
-    void* p = nullptr;
-    const size_t bytes = kInjectRows * kDiagWords * sizeof(unsigned long long);
-    if (int rc = dev_alloc(h, &p, bytes, &h->bytes_grid)) return rc;
-    g.inject = static_cast<unsigned long long*>(p);
-    return FPIC_OK;
-}
+static int inject_room(fpic_handle* h) { return h->es->diag.inject.rows.room(h, kDiagWords, static_cast<size_t>(kInjectPartial) + kInjectBlocks); }
 
 // what follows the applications of a call or of a sub-step.  The electrostatic cycle gathers E of the last solve at the start
 // of the next sub-step: that field lacks the new charge.  The tail of precalc(): bin where it would, deposit the grown
@@ -77,7 +68,7 @@ static int inject_run(fpic_handle* h, const fpic_inject_spec& spec, uint64_t k, 
                     ".count <- species %d holds %zu particles (ids below %llu) of a capacity of %zu: %llu more do not fit; call fpic_reserve first; nothing was changed",
                     spec.load.species, s.n, static_cast<unsigned long long>(span), s.cap, static_cast<unsigned long long>(count));
     if (int rc = inject_room(h)) return rc;
-    unsigned long long* last = g.inject + static_cast<size_t>(kInjectLast) * kDiagWords;
+    const OpRows& rows = g.inject.rows;
     const double L[3] = { st->lx, st->ly, st->lz };
     InjectArgs<T> a{};
     a.slab = static_cast<T*>(s.slab[s.cur]);
@@ -87,13 +78,13 @@ static int inject_run(fpic_handle* h, const fpic_inject_spec& spec, uint64_t k, 
     a.s1 = s.n + static_cast<size_t>(count);
     a.first = static_cast<uint32_t>(first);
     a.id0 = static_cast<uint32_t>(span);
-    a.partial = g.inject + static_cast<size_t>(FPIC_INJECT_MAX_OPS + 1) * kDiagWords;
+    a.partial = rows.row(kInjectPartial);
     a.q = fesinj::rule_of(spec, first, L, h->spec.dt);
     const size_t groups = (a.s1 + kInjectGroup - 1) / kInjectGroup - a.s0 / kInjectGroup;
     const unsigned grid = static_cast<unsigned>(std::min<size_t>(kInjectBlocks, (groups + kInjectThreads - 1) / kInjectThreads));
     if (spec.kind == FPIC_INJECT_FLUX) inject_kernel<T, true><<<grid, kInjectThreads, 0, h->stream>>>(a);
     else inject_kernel<T, false><<<grid, kInjectThreads, 0, h->stream>>>(a);
-    remove_combine_kernel<<<1, kDiagThreads, 0, h->stream>>>(a.partial, static_cast<int>(grid), last, total_row < 0 ? nullptr : g.inject + static_cast<size_t>(total_row) * kDiagWords);
+    remove_combine_kernel<<<1, kDiagThreads, 0, h->stream>>>(a.partial, static_cast<int>(grid), rows.row(kInjectLast), total_row < 0 ? nullptr : rows.row(total_row));
     HIP_TRY(h, hipGetLastError());
     // the state load_keep leaves after an append: the live set holds the particles in slot order with their ids, the other
     // set's ids are the slot numbers (the next binning writes both anew)
@@ -126,8 +117,7 @@ static int inject_fetch(fpic_handle* h, int row, const Species& sp, fpic_inject_
 {
     State* st = h->es;
     uint64_t got[kDiagWords] = {};
-    HIP_TRY(h, hipMemcpyAsync(got, st->diag.inject + static_cast<size_t>(row) * kDiagWords, sizeof(got), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (int rc = st->diag.inject.rows.fetch(h, row, got)) return rc;
     fesinj::result_of(got, sp.mass, sp.charge, st->W, out);
     return FPIC_OK;
 }
@@ -148,28 +138,25 @@ int inject(fpic_handle* h, const fpic_inject_spec* spec, fpic_inject_result* out
 
 int inject_register(fpic_handle* h, const fpic_inject_spec* spec, int every, int* index)
 {
-    Diag& g = h->es->diag;
+    auto& f = h->es->diag.inject;
     if (int rc = inject_refuse_decomposed(h, "fpic_inject_register")) return rc;
     if (int rc = inject_check(h, spec)) return rc;
-    if (const char* why = fesinj::check_register(every, static_cast<int>(g.inject_ops.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    if (int rc = ops_check_register(h, f, fesops::kInject, every)) return rc;
     if (int rc = inject_room(h)) return rc;
-    const int at = static_cast<int>(g.inject_ops.size());
-    HIP_TRY(h, hipMemsetAsync(g.inject + static_cast<size_t>(at) * kDiagWords, 0, kDiagWords * sizeof(unsigned long long), h->stream));
-    g.inject_ops.push_back(InjectOp{ *spec, every, 0 });
-    if (index) *index = at;
-    return FPIC_OK;
+    if (int rc = f.rows.zero(h, f.ops.size())) return rc;
+    InjectOp op;
+    op.spec = *spec;
+    return ops_push(f, op, every, index);
 }
 
 int inject_stats(fpic_handle* h, int index, int scope, fpic_inject_result* out)
 {
     State* st = h->es;
-    Diag& g = st->diag;
+    auto& f = st->diag.inject;
     if (int rc = inject_refuse_decomposed(h, "fpic_inject_stats")) return rc;
-    if (!out) return fail(h, FPIC_ERR_INVALID_ARG, ".out <- Non-optional property is undefined!");
-    if (const char* why = fesinj::check_index(index, static_cast<int>(g.inject_ops.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
     bool collective = false;
-    if (int rc = diag_scope(h, scope, collective)) return rc;   // (undecomposed: GLOBAL is LOCAL)
-    const InjectOp& op = g.inject_ops[index];
+    if (int rc = ops_stats_head(h, f, fesops::kInject, index, scope, out, collective)) return rc;   // (undecomposed: GLOBAL is LOCAL)
+    const InjectOp& op = f.ops[index];
     *out = fpic_inject_result{};
     if (int rc = inject_fetch(h, index, st->sp[op.spec.load.species], out)) return rc;
     out->applications = op.applications;
@@ -179,26 +166,22 @@ int inject_stats(fpic_handle* h, int index, int scope, fpic_inject_result* out)
 int inject_clear(fpic_handle* h)
 {
     if (int rc = inject_refuse_decomposed(h, "fpic_inject_clear")) return rc;
-    h->es->diag.inject_ops.clear();   // (every application has ended synchronised: nothing is in flight)
-    return FPIC_OK;
+    return ops_clear(h->es->diag.inject);   // (every application has ended synchronised: nothing is in flight)
 }
 
-// the hook's part (diag_after_substep, after the sinks and before the recorders): every registered source that is due, in
-// registration order, their launches queued one behind the other; then ONE re-deposit and solve for all of them and one wait
-// (the charge grid is a function of the positions: the result is that of settling after each).  A source of count 0 is never
-// due.  A source that fails leaves what the ones before it did, settled.
+// the hook's part: every registered source that is due — a source of count 0 never is —, its applications so far the
+// application number, counted once it has succeeded; their launches queued one behind the other, then ONE re-deposit and solve
+// for all of them and one wait (the charge grid is a function of the positions: the result is that of settling after each).
+// A source that fails leaves what the ones before it did, settled.
 static int inject_after_substep(fpic_handle* h, uint64_t substep)
 {
-    Diag& g = h->es->diag;
     bool applied = false;
-    int rc = FPIC_OK;
-    for (size_t k = 0; k < g.inject_ops.size() && rc == FPIC_OK; ++k) {
-        InjectOp& op = g.inject_ops[k];
-        if (substep % static_cast<uint64_t>(op.every) || !op.spec.load.count) continue;
-        if ((rc = inject_apply(h, op.spec, op.applications, static_cast<int>(k), true)) != FPIC_OK) break;
-        op.applications++;
-        applied = true;
-    }
+    int rc = ops_run_due<false>(h->es->diag.inject, [&](const InjectOp& op) { return OpsEvery{ substep }(op) && op.spec.load.count != 0; },
+                                [&](InjectOp& op, size_t k) {
+                                    const int e = inject_apply(h, op.spec, op.applications, static_cast<int>(k), true);
+                                    if (e == FPIC_OK) applied = true;
+                                    return e;
+                                });
     if (applied) {
         const std::string why = h->err;          // (the settling must not lose the message of the source that failed)
         const int settled = inject_settle(h);

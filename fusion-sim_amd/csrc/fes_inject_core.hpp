@@ -104,18 +104,6 @@ inline const char* check(const fpic_inject_spec* p, int nspecies, const double (
     return nullptr;
 }
 
-// a registration: `registered` sources are held already
-inline const char* check_register(int every, int registered)
-{
-    if (every < 1) return ".every <- must be at least 1";
-    if (registered >= FPIC_INJECT_MAX_OPS) return ".spec <- FPIC_INJECT_MAX_OPS (8) sources are registered already";
-    return nullptr;
-}
-inline const char* check_index(int index, int registered)
-{
-    if (index < 0 || index >= registered) return ".index <- no such registered source";
-    return nullptr;
-}
 inline const char* check_capacity(uint64_t capacity)
 {
     if (capacity >= kCapacityEnd) return ".capacity <- at most 2^32 particles per species and device: the ids are 32-bit";

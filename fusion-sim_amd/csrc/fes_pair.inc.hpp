@@ -3,14 +3,14 @@
 // The rule and the checks of a request are fes_pair_core.hpp, the passes fes_pair_kernels.hpp.
 //
 // One application: per species of the request the cell index (count, scan, fill: three launches and one memset), then the
-// pairing pass — all enqueued on the handle's stream, nothing read back.  The index buffers and the count words belong to
-// the handle's Diag, grow to the largest request and are released with it.  A registered operator is enqueued by the hook
-// diag_after_substep, after the operators of fpic_collide_register; fpic_pair_stats reads its words.
+// pairing pass — all enqueued on the handle's stream, nothing read back.  The index buffers belong to the handle's Diag, grow
+// to the largest request and are released with it; the counts go to the family's rows (fes_ops.inc.hpp), eight words per row.
+// A registered operator is enqueued by the hook; fpic_pair_stats reads its row.
 // A handle with a Domain is refused: between two migrations the particles of a cell can sit on two ranks, in the ghost
 // planes, so a rank cannot pair a cell alone.
 
 constexpr int kPairWords = 8;                      // per operator: pairs, strong, cells, overfull_cells, overfull_particles, (unused)
-constexpr int kPairNow = FPIC_PAIR_MAX_OPS;        // the words of fpic_pair
+constexpr int kPairNow = FPIC_PAIR_MAX_OPS;        // the row of fpic_pair
 constexpr int kPairSegLead = 4;                    // words before the first cell's: the counts are 16-byte aligned, the word before them is the zero
 
 // TEST SWITCH (FPIC_PAIR_FORMS, read once): which form of two passes runs, for measuring one against the other
@@ -31,17 +31,7 @@ static int pair_refuse_decomposed(fpic_handle* h, const char* name)
     return fail(h, FPIC_ERR_STATE, "%s needs an undecomposed handle: between two migrations the particles of a cell can sit on two ranks (in the ghost planes), so a rank cannot pair a cell alone", name);
 }
 
-static int pair_words(fpic_handle* h)
-{
-    Diag& g = h->es->diag;
-    if (g.pair) return FPIC_OK;
-    void* p = nullptr;
-    const size_t bytes = static_cast<size_t>(FPIC_PAIR_MAX_OPS + 1) * kPairWords * sizeof(unsigned long long);
-    if (int rc = dev_alloc(h, &p, bytes, &h->bytes_grid)) return rc;
-    g.pair = static_cast<unsigned long long*>(p);
-    HIP_TRY(h, hipMemsetAsync(g.pair, 0, bytes, h->stream));
-    return FPIC_OK;
-}
+static int pair_room(fpic_handle* h) { return h->es->diag.pair.rows.room(h, kPairWords, FPIC_PAIR_MAX_OPS + 1); }
 
 static int pair_grow(fpic_handle* h, uint32_t*& buf, size_t& have, size_t words)
 {
@@ -58,12 +48,12 @@ static int pair_grow(fpic_handle* h, uint32_t*& buf, size_t& have, size_t words)
     return FPIC_OK;
 }
 
-// the buffers of a request: the count words and, per side, the cell words and the slots of the species' capacity
+// the buffers of a request: the rows and, per side, the cell words and the slots of the species' capacity
 static int pair_buffers(fpic_handle* h, const fpic_pair_spec& spec, bool may_grow)
 {
     State* st = h->es;
     Diag& g = st->diag;
-    if (int rc = pair_words(h)) return rc;
+    if (int rc = pair_room(h)) return rc;
     const int sides = spec.species_a == spec.species_b ? 1 : 2;
     for (int s = 0; s < sides; ++s) {
         const Species& sp = st->sp[s ? spec.species_b : spec.species_a];
@@ -161,68 +151,55 @@ static void pair_result(fpic_pair_result* out, uint64_t applications, const uint
 int pair(fpic_handle* h, const fpic_pair_spec* spec, fpic_pair_result* out)
 {
     State* st = h->es;
+    const OpRows& rows = st->diag.pair.rows;
     if (int rc = pair_refuse_decomposed(h, "fpic_pair")) return rc;
     if (const char* why = fespair::check(spec, static_cast<int>(st->sp.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
     if (out) *out = fpic_pair_result{};
-    if (int rc = pair_words(h)) return rc;
-    unsigned long long* words = st->diag.pair + kPairNow * kPairWords;
-    HIP_TRY(h, hipMemsetAsync(words, 0, kPairWords * sizeof(unsigned long long), h->stream));
-    if (int rc = pair_apply(h, *spec, spec->epoch, words, true)) return rc;
+    if (int rc = pair_room(h)) return rc;
+    if (int rc = rows.zero(h, kPairNow)) return rc;
+    if (int rc = pair_apply(h, *spec, spec->epoch, rows.row(kPairNow), true)) return rc;
     uint64_t got[kPairWords] = {};
-    HIP_TRY(h, hipMemcpyAsync(got, words, sizeof(got), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (int rc = rows.fetch(h, kPairNow, got)) return rc;
     if (out) pair_result(out, 1, got);
     return FPIC_OK;
 }
 
 int pair_register(fpic_handle* h, const fpic_pair_spec* spec, int every, int* index)
 {
-    Diag& g = h->es->diag;
+    auto& f = h->es->diag.pair;
     if (int rc = pair_refuse_decomposed(h, "fpic_pair_register")) return rc;
     if (const char* why = fespair::check(spec, static_cast<int>(h->es->sp.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
-    if (const char* why = fespair::check_register(every, static_cast<int>(g.pair_ops.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    if (int rc = ops_check_register(h, f, fesops::kPair, every)) return rc;
     if (int rc = pair_buffers(h, *spec, true)) return rc;   // (sized now: the hook finds them in place and never grows them)
-    const int at = static_cast<int>(g.pair_ops.size());
-    HIP_TRY(h, hipMemsetAsync(g.pair + at * kPairWords, 0, kPairWords * sizeof(unsigned long long), h->stream));
-    g.pair_ops.push_back(PairOp{ *spec, every, 0 });
-    if (index) *index = at;
-    return FPIC_OK;
+    if (int rc = f.rows.zero(h, f.ops.size())) return rc;
+    PairOp op;
+    op.spec = *spec;
+    return ops_push(f, op, every, index);
 }
 
 int pair_stats(fpic_handle* h, int index, int scope, fpic_pair_result* out)
 {
-    Diag& g = h->es->diag;
+    auto& f = h->es->diag.pair;
     if (int rc = pair_refuse_decomposed(h, "fpic_pair_stats")) return rc;
-    if (!out) return fail(h, FPIC_ERR_INVALID_ARG, ".out <- Non-optional property is undefined!");
-    if (const char* why = fespair::check_index(index, static_cast<int>(g.pair_ops.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
     bool collective = false;
-    if (int rc = diag_scope(h, scope, collective)) return rc;
+    if (int rc = ops_stats_head(h, f, fesops::kPair, index, scope, out, collective)) return rc;
     uint64_t got[kPairWords] = {};
-    HIP_TRY(h, hipMemcpyAsync(got, g.pair + index * kPairWords, sizeof(got), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (int rc = f.rows.fetch(h, index, got)) return rc;
     if (collective)
         if (int rc = diag_sum_ranks(h, got, kPairWords)) return rc;
-    pair_result(out, g.pair_ops[index].applications, got);
+    pair_result(out, f.ops[index].applications, got);
     return FPIC_OK;
 }
 
 int pair_clear(fpic_handle* h)
 {
     if (int rc = pair_refuse_decomposed(h, "fpic_pair_clear")) return rc;
-    h->es->diag.pair_ops.clear();   // (applications in flight keep their words; a later registration zeroes its own in stream order)
-    return FPIC_OK;
+    return ops_clear(h->es->diag.pair);
 }
 
-// the hook's part (diag_after_substep, after the background operators): every registered operator that is due, in
-// registration order; nothing registered: nothing is enqueued
+// the hook's part: every registered operator that is due, at the epoch of the sub-step; the cell index does not grow here
 static int pair_after_substep(fpic_handle* h, uint64_t substep)
 {
-    Diag& g = h->es->diag;
-    for (size_t k = 0; k < g.pair_ops.size(); ++k) {
-        PairOp& op = g.pair_ops[k];
-        if (substep % static_cast<uint64_t>(op.every)) continue;
-        op.applications++;
-        if (int rc = pair_apply(h, op.spec, static_cast<uint32_t>(substep + op.spec.epoch), g.pair + k * kPairWords, false)) return rc;
-    }
-    return FPIC_OK;
+    auto& f = h->es->diag.pair;
+    return ops_run_due<true>(f, OpsEvery{ substep }, [&](PairOp& op, size_t k) { return pair_apply(h, op.spec, static_cast<uint32_t>(substep + op.spec.epoch), f.rows.row(k), false); });
 }

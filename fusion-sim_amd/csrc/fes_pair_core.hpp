@@ -151,19 +151,6 @@ inline const char* check(const fpic_pair_spec* p, int nspecies)
     return nullptr;
 }
 
-// a registration: `registered` operators are held already
-inline const char* check_register(int every, int registered)
-{
-    if (every < 1) return ".every <- must be at least 1";
-    if (registered >= FPIC_PAIR_MAX_OPS) return ".spec <- FPIC_PAIR_MAX_OPS (8) operators are registered already";
-    return nullptr;
-}
-inline const char* check_index(int index, int registered)
-{
-    if (index < 0 || index >= registered) return ".index <- no such registered operator";
-    return nullptr;
-}
-
 // the kernels' form of a checked request, at `epoch`: the masses (kg) and charges (C) of the two species, the macro weight,
 // the cell volume (m^3)
 inline Rule rule_of(const fpic_pair_spec& s, uint32_t epoch, double ma, double qa, double mb, double qb, double W, double dV)

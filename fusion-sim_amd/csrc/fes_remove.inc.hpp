@@ -14,10 +14,10 @@
 // and solves again here (the tail of precalc()), so that the next sub-step gathers the field of the survivors; a full-EM
 // handle keeps E, B and its readiness as they are.
 
-// the handle's device block, rows of kDiagWords words: the operators' totals, the row of the last application, a row whose
-// first word is the mark pass's counter, the move pass's partial rows
+// the family's rows (fes_ops.inc.hpp), kDiagWords words each: the operators' totals, the row of the last application (the
+// call's row), behind it a row whose first word is the mark pass's counter, then the move pass's partial rows
 constexpr int kRemoveLast = FPIC_REMOVE_MAX_OPS;
-constexpr size_t kRemoveRows = static_cast<size_t>(FPIC_REMOVE_MAX_OPS) + 2 + kRemoveBlocks;
+constexpr int kRemoveGone = kRemoveLast + 1, kRemovePartial = kRemoveLast + 2;
 
 static int remove_refuse_decomposed(fpic_handle* h, const char* name)
 {
@@ -25,17 +25,7 @@ static int remove_refuse_decomposed(fpic_handle* h, const char* name)
     return fail(h, FPIC_ERR_STATE, "%s needs an undecomposed handle: a rank's dead slots and the arrivals of a migration that rides on its next push would need a protocol of their own to compact", name);
 }
 
-static int remove_room(fpic_handle* h)
-{
-    Diag& g = h->es->diag;
-    if (g.remove) return FPIC_OK;
-    void* p = nullptr;
-    const size_t bytes = kRemoveRows * kDiagWords * sizeof(unsigned long long);
-    if (int rc = dev_alloc(h, &p, bytes, &h->bytes_grid)) return rc;
-    g.remove = static_cast<unsigned long long*>(p);
-    HIP_TRY(h, hipMemsetAsync(g.remove, 0, bytes, h->stream));
-    return FPIC_OK;
-}
+static int remove_room(fpic_handle* h) { return h->es->diag.remove.rows.room(h, kDiagWords, static_cast<size_t>(kRemovePartial) + kRemoveBlocks); }
 
 template <typename T, int NA>
 static void remove_launch(fpic_handle* h, const RemoveArgs<T>& a, unsigned grid, bool move)
@@ -68,9 +58,9 @@ static int remove_run(fpic_handle* h, const fpic_remove_spec& spec, int total_ro
     *scanned = s.n;
     *removed = 0;
     if (int rc = remove_room(h)) return rc;
-    unsigned long long* last = g.remove + static_cast<size_t>(kRemoveLast) * kDiagWords;
-    unsigned long long* gone = last + kDiagWords;   // (the row behind it: its first word is the mark pass's counter)
-    HIP_TRY(h, hipMemsetAsync(last, 0, 2 * kDiagWords * sizeof(unsigned long long), h->stream));
+    const OpRows& rows = g.remove.rows;
+    unsigned long long* gone = rows.row(kRemoveGone);
+    if (int rc = rows.zero(h, kRemoveLast, 2)) return rc;   // (the last application's row and the counter's behind it)
     if (!s.n || fesrem::never(spec)) return FPIC_OK;   // (nothing can leave: nothing is launched)
     const size_t n = s.n, nchunks = (n + kRemoveChunk - 1) / kRemoveChunk;
     // the chunks' counts, then 8 bytes for the scan's total (the selection's buffer, as load_keep)
@@ -109,7 +99,7 @@ static int remove_run(fpic_handle* h, const fpic_remove_spec& spec, int total_ro
     a.chunk = reinterpret_cast<uint32_t*>(dev);
     a.nchunks = nchunks;
     a.gone = gone;
-    a.partial = g.remove + static_cast<size_t>(FPIC_REMOVE_MAX_OPS + 2) * kDiagWords;
+    a.partial = rows.row(kRemovePartial);
     a.dst_slab = static_cast<T*>(s.slab[s.cur ^ 1]);
     a.dst_id = s.id[s.cur ^ 1];
     const unsigned grid = static_cast<unsigned>(std::min<size_t>(kRemoveBlocks, (nchunks + kRemoveThreads / 64 - 1) / (kRemoveThreads / 64)));
@@ -125,7 +115,7 @@ static int remove_run(fpic_handle* h, const fpic_remove_spec& spec, int total_ro
     // (everything removed: the move pass still runs, for the tally; it writes no survivor)
     load_scan_kernel<<<1, 1024, 0, h->stream>>>(a.chunk, nchunks, reinterpret_cast<unsigned long long*>(dev + total_at));
     remove_launch_na<T>(h, a, na, grid, true);
-    remove_combine_kernel<<<1, kDiagThreads, 0, h->stream>>>(a.partial, static_cast<int>(grid), last, total_row < 0 ? nullptr : g.remove + static_cast<size_t>(total_row) * kDiagWords);
+    remove_combine_kernel<<<1, kDiagThreads, 0, h->stream>>>(a.partial, static_cast<int>(grid), rows.row(kRemoveLast), total_row < 0 ? nullptr : rows.row(total_row));
     HIP_TRY(h, hipGetLastError());
     // the state load_keep and fpic_domain_set_particles leave: the live set holds the particles in slot order with their
     // ids, the other set's ids are the slot numbers (the next binning writes both anew)
@@ -158,8 +148,7 @@ static int remove_fetch(fpic_handle* h, int row, const Species& sp, fpic_remove_
 {
     State* st = h->es;
     uint64_t got[kDiagWords] = {};
-    HIP_TRY(h, hipMemcpyAsync(got, st->diag.remove + static_cast<size_t>(row) * kDiagWords, sizeof(got), hipMemcpyDeviceToHost, h->stream));
-    HIP_TRY(h, hipStreamSynchronize(h->stream));
+    if (int rc = st->diag.remove.rows.fetch(h, row, got)) return rc;
     fesrem::result_of(got, sp.mass, sp.charge, st->W, out);
     return FPIC_OK;
 }
@@ -181,28 +170,25 @@ int remove(fpic_handle* h, const fpic_remove_spec* spec, fpic_remove_result* out
 
 int remove_register(fpic_handle* h, const fpic_remove_spec* spec, int every, int* index)
 {
-    Diag& g = h->es->diag;
+    auto& f = h->es->diag.remove;
     if (int rc = remove_refuse_decomposed(h, "fpic_remove_register")) return rc;
     if (const char* why = fesrem::check(spec, static_cast<int>(h->es->sp.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
-    if (const char* why = fesrem::check_register(every, static_cast<int>(g.remove_ops.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    if (int rc = ops_check_register(h, f, fesops::kRemove, every)) return rc;
     if (int rc = remove_room(h)) return rc;
-    const int at = static_cast<int>(g.remove_ops.size());
-    HIP_TRY(h, hipMemsetAsync(g.remove + static_cast<size_t>(at) * kDiagWords, 0, kDiagWords * sizeof(unsigned long long), h->stream));
-    g.remove_ops.push_back(RemoveOp{ *spec, every, 0, 0 });
-    if (index) *index = at;
-    return FPIC_OK;
+    if (int rc = f.rows.zero(h, f.ops.size())) return rc;
+    RemoveOp op;
+    op.spec = *spec;
+    return ops_push(f, op, every, index);
 }
 
 int remove_stats(fpic_handle* h, int index, int scope, fpic_remove_result* out)
 {
     State* st = h->es;
-    Diag& g = st->diag;
+    auto& f = st->diag.remove;
     if (int rc = remove_refuse_decomposed(h, "fpic_remove_stats")) return rc;
-    if (!out) return fail(h, FPIC_ERR_INVALID_ARG, ".out <- Non-optional property is undefined!");
-    if (const char* why = fesrem::check_index(index, static_cast<int>(g.remove_ops.size()))) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
     bool collective = false;
-    if (int rc = diag_scope(h, scope, collective)) return rc;   // (undecomposed: GLOBAL is LOCAL)
-    const RemoveOp& op = g.remove_ops[index];
+    if (int rc = ops_stats_head(h, f, fesops::kRemove, index, scope, out, collective)) return rc;   // (undecomposed: GLOBAL is LOCAL)
+    const RemoveOp& op = f.ops[index];
     *out = fpic_remove_result{};
     if (int rc = remove_fetch(h, index, st->sp[op.spec.species], out)) return rc;
     out->applications = op.applications;
@@ -213,24 +199,19 @@ int remove_stats(fpic_handle* h, int index, int scope, fpic_remove_result* out)
 int remove_clear(fpic_handle* h)
 {
     if (int rc = remove_refuse_decomposed(h, "fpic_remove_clear")) return rc;
-    h->es->diag.remove_ops.clear();   // (every application has ended synchronised: nothing is in flight)
-    return FPIC_OK;
+    return ops_clear(h->es->diag.remove);   // (every application has ended synchronised: nothing is in flight)
 }
 
-// the hook's part (diag_after_substep, after the fusion spectra and before the recorders): every registered sink that is due,
-// in registration order.  Each due application waits for its removed count.
+// the hook's part: every registered sink that is due; an application is counted once it has succeeded.  Each waits for its
+// removed count
 static int remove_after_substep(fpic_handle* h, uint64_t substep)
 {
-    Diag& g = h->es->diag;
-    for (size_t k = 0; k < g.remove_ops.size(); ++k) {
-        RemoveOp& op = g.remove_ops[k];
-        if (substep % static_cast<uint64_t>(op.every)) continue;
+    return ops_run_due<false>(h->es->diag.remove, OpsEvery{ substep }, [&](RemoveOp& op, size_t k) {
         uint64_t scanned = 0, removed = 0;
         if (int rc = remove_apply(h, op.spec, static_cast<int>(k), &scanned, &removed)) return rc;
-        op.applications++;
         op.scanned += scanned;
-    }
-    return FPIC_OK;
+        return static_cast<int>(FPIC_OK);
+    });
 }
 
 int renumber(fpic_handle* h, int species, uint64_t* n_out)
@@ -244,7 +225,7 @@ int renumber(fpic_handle* h, int species, uint64_t* n_out)
     if (!s.thinned) return FPIC_OK;
     if (g.rec[kRecSeries].every)
         return fail(h, FPIC_ERR_STATE, "fpic_renumber while a series is being recorded: its tracers are named by id, and the ids are about to change; stop the recording first");
-    if (!g.coll_ops.empty() || !g.force_ops.empty() || !g.gas_ops.empty() || !g.pair_ops.empty() || !g.fusion_ops.empty() || !g.fspec_ops.empty() || !g.remove_ops.empty() || !g.inject_ops.empty())
+    if (ops_registered(g))
         return fail(h, FPIC_ERR_STATE, "fpic_renumber while an operator is registered: registered operators draw per-id random words or thin by id, and the ids are about to change; clear the registrations first");
     const size_t n = s.n;
     if (n) {

@@ -52,19 +52,6 @@ inline const char* check(const fpic_remove_spec* p, int nspecies)
     return nullptr;
 }
 
-// a registration: `registered` operators are held already
-inline const char* check_register(int every, int registered)
-{
-    if (every < 1) return ".every <- must be at least 1";
-    if (registered >= FPIC_REMOVE_MAX_OPS) return ".spec <- FPIC_REMOVE_MAX_OPS (8) operators are registered already";
-    return nullptr;
-}
-inline const char* check_index(int index, int registered)
-{
-    if (index < 0 || index >= registered) return ".index <- no such registered operator";
-    return nullptr;
-}
-
 // a row of totals -> the result but `applications` and `scanned`; mass, charge: the species'; W: the box's macro-weight
 inline void result_of(const uint64_t* w, double mass, double charge, double W, fpic_remove_result* out)
 {

@@ -81,72 +81,72 @@ struct Recorder {
 };
 enum { kRecEnergy, kRecSeries, kRecModes, kRecorders };
 
-// a registered collision operator (fes_collide.inc.hpp): the request, its period in sub-steps, the applications so far
-struct CollideOp {
-    fpic_collide_spec spec;
-    int every;
-    uint64_t applications;
+// The registered operators (fes_ops.inc.hpp has what they share).  A family keeps one device block of tally rows:
+// `rows` rows of `words` 64-bit words — row k < MAX_OPS the totals of the k-th registered operator, row MAX_OPS the call that
+// is applied now, and behind it whatever rows the family's passes need for themselves — and, where its requests carry tables,
+// `tab` doubles of table room per row (in the same allocation behind the words, or `apart` in one of their own).
+struct OpRows {
+    int words = 0;
+    size_t rows = 0, tab = 0;
+    bool apart = false;
+    unsigned long long* dev = nullptr;
+    double* tab_dev = nullptr;
+    unsigned long long* row(size_t k) const { return dev + k * words; }
+    double* table(size_t k) const { return tab_dev + k * tab; }
+    int room(fpic_handle* h, int words_per_row, size_t nrows, size_t tab_doubles = 0, bool tab_apart = false);   // allocates once, zeroes the words
+    int zero(fpic_handle* h, size_t k, size_t n = 1) const;                                                      // rows [k, k + n), in stream order
+    int copy(fpic_handle* h, size_t k, uint64_t* got, size_t nwords) const;                                      // the head of row k to the host, enqueued
+    int fetch(fpic_handle* h, size_t k, uint64_t* got) const;                                                    // row k to the host; waits
+    void release();
 };
+// what every registered operator has: its period in sub-steps (a force has none and keeps 1) and the applications so far
+struct OpCommon {
+    int every = 1;
+    uint64_t applications = 0;
+};
+// a family: its rows and its registered operators, in registration order
+template <typename Op>
+struct OpFamily {
+    OpRows rows;
+    std::vector<Op> ops;
+};
+// the families as the members of Diag, in the order in which the sub-step hook runs them (diag_after_substep of fes_api.hip
+// states the order and why): member f has the hook's part f##_after_substep
+#define FES_OP_FAMILIES(X) X(force) X(collide) X(gas) X(pair) X(fusion) X(fspec) X(remove) X(inject)
 
-// a prescribed external force (fes_force.inc.hpp): the request (its table pointers are not kept), the host's copy of the
-// envelope table, where its taper tables lie on the device, the applications so far
-struct ForceOp {
-    fpic_force_spec spec;
+// what each family's operator keeps of its own, beside OpCommon
+struct CollideOp : OpCommon {          // fes_collide.inc.hpp
+    fpic_collide_spec spec;
+};
+struct ForceOp : OpCommon {            // fes_force.inc.hpp: the request (its table pointers are not kept), the host's copy of the
+    fpic_force_spec spec;              // envelope table, where its taper tables lie on the device
     std::vector<double> envelope;
     const double* taper[3];
-    uint64_t applications;
 };
-
-// a windowed background collision operator (fes_gas.inc.hpp): the request (its table pointers are not kept), its period in
-// sub-steps, the host's copy of the cross-sections, where its tables lie on the device, the applications so far
-struct GasOp {
-    fpic_gas_spec spec;
-    int every;
+struct GasOp : OpCommon {              // fes_gas.inc.hpp: the request (its table pointers are not kept), the host's copy of the
+    fpic_gas_spec spec;                // cross-sections, where its tables lie on the device
     std::vector<double> sigma;
     const double* dev_sigma;
     const double* taper[3];
-    uint64_t applications;
 };
-
-// a registered particle sink (fes_remove.inc.hpp): the request, its period in sub-steps, the applications and the live
-// particles they scanned so far (the other totals are a row on the device)
-struct RemoveOp {
-    fpic_remove_spec spec;
-    int every;
-    uint64_t applications, scanned;
-};
-
-// a registered particle source (fes_inject.inc.hpp): the request, its period in sub-steps, the applications so far (the
-// totals are a row on the device)
-struct InjectOp {
-    fpic_inject_spec spec;
-    int every;
-    uint64_t applications;
-};
-
-// a registered binary collision operator (fes_pair.inc.hpp): the request, its period in sub-steps, the applications so far
-struct PairOp {
+struct PairOp : OpCommon {             // fes_pair.inc.hpp
     fpic_pair_spec spec;
-    int every;
-    uint64_t applications;
 };
-
-// a registered fusion yield tally (fes_fusion.inc.hpp): the request (its table pointer is not kept: the table is on the
-// device), its period in sub-steps, the applications since registration or the last reset, the kernel's form of the request
-struct FusionOp {
-    fpic_fusion_spec spec;
-    int every;
-    uint64_t applications;
+struct FusionOp : OpCommon {           // fes_fusion.inc.hpp: the request (its table pointer is not kept: the table is on the
+    fpic_fusion_spec spec;             // device), the kernel's form of it; applications: since registration or the last reset
     fesfusion::Rule rule;
 };
-
-// a registered fusion product spectrum (fes_fusion_spectrum.inc.hpp): as FusionOp, with the kernel's form of the axis
-struct FspecOp {
+struct FspecOp : OpCommon {            // fes_fusion_spectrum.inc.hpp: as FusionOp, with the kernel's form of the axis
     fpic_fusion_spectrum_spec spec;
-    int every;
-    uint64_t applications;
     fesfusion::Rule rule;
     fesfspec::Rule axis;
+};
+struct RemoveOp : OpCommon {           // fes_remove.inc.hpp: the live particles the applications scanned so far (the other
+    fpic_remove_spec spec;             // totals are the row on the device)
+    uint64_t scanned = 0;
+};
+struct InjectOp : OpCommon {           // fes_inject.inc.hpp
+    fpic_inject_spec spec;
 };
 
 // the diagnostics of a handle: the sub-step counter the recorders share, the recorders and their requests, the buffers of the
@@ -168,56 +168,36 @@ struct Diag {
     size_t sel_bytes = 0;
     double* load_tab = nullptr;         // the tables of fpic_load_profile (fes_load.inc.hpp), uploaded per call; grows to the largest request
     size_t load_tab_bytes = 0;
-    unsigned long long* coll = nullptr; // the counts of fpic_collide (fes_collide.inc.hpp): four words per registered operator, four for a call
-    std::vector<CollideOp> coll_ops;    // the registered operators, in registration order
-    // fpic_force (fes_force.inc.hpp): one block - per registered request and one more for a call, fesforce::kWords tally words,
-    // then room for three taper tables each (force_tab points into the block)
-    unsigned long long* force = nullptr;
-    double* force_tab = nullptr;
-    std::vector<ForceOp> force_ops;     // the registered requests, in registration order
-    // fpic_gas (fes_gas.inc.hpp): one block - per registered operator and one more for a call, fesgas::kWords tally words,
-    // then room for the cross-section table and three taper tables each (gas_tab points into the block)
-    unsigned long long* gas = nullptr;
-    double* gas_tab = nullptr;
-    std::vector<GasOp> gas_ops;         // the registered operators, in registration order
-    unsigned long long* pair = nullptr; // the counts of fpic_pair (fes_pair.inc.hpp): eight words per registered operator, eight for a call
-    std::vector<PairOp> pair_ops;       // the registered operators, in registration order
+    // the registered operators, a family each (OpFamily above); what a row holds and what lies behind row MAX_OPS is the
+    // family's (its .inc.hpp)
+    OpFamily<ForceOp> force;            // fesforce::kWords tally words and room for three taper tables per row
+    OpFamily<CollideOp> collide;        // four count words per row
+    OpFamily<GasOp> gas;                // fesgas::kWords tally words and room for the cross-section table and three taper tables per row
+    OpFamily<PairOp> pair;              // eight count words per row
+    OpFamily<FusionOp> fusion;          // eight count words and a table of FPIC_FUSION_TABLE_MAX doubles per row
+    OpFamily<FspecOp> fspec;            // as fusion
+    OpFamily<RemoveOp> remove;          // rows of kDiagWords words; behind the totals: the last application, the mark pass's counter, the move pass's partial rows
+    OpFamily<InjectOp> inject;          // rows of kDiagWords words; behind the totals: the last application, the generation pass's partial rows
     // the cell index of fpic_pair, one per side (species_a, species_b): pair_seg[s] = 4 + cells words (zeros, then per cell
     // the count -> the exclusive offset -> the end of the cell's segment), pair_index[s] = the slots by cell; both grow to
-    // the largest request
+    // the largest request.  The fusion tallies and spectra use it too
     uint32_t* pair_seg[2] = {};
     uint32_t* pair_index[2] = {};
     size_t pair_seg_words[2] = {}, pair_index_words[2] = {};
-    // fpic_fusion (fes_fusion.inc.hpp), per registered operator and one more for a call: eight count words, a table of
-    // FPIC_FUSION_TABLE_MAX doubles, and the cell grid (nx ny nz int64, allocated when the operator is first used)
-    unsigned long long* fusion = nullptr;
-    double* fusion_table = nullptr;
-    unsigned long long* fusion_grid[FPIC_FUSION_MAX_OPS + 1] = {};
-    std::vector<FusionOp> fusion_ops;   // the registered tallies, in registration order
-    // fpic_fusion_spectrum (fes_fusion_spectrum.inc.hpp), per registered operator and one more for a call: eight count words, a
-    // table of FPIC_FUSION_TABLE_MAX doubles and (FPIC_FUSION_SPECTRUM_BINS_MAX + 2) x 2 words of the histogram
-    unsigned long long* fspec = nullptr;
-    double* fspec_table = nullptr;
-    unsigned long long* fspec_words = nullptr;
-    std::vector<FspecOp> fspec_ops;     // the registered spectra, in registration order
-    // fpic_remove (fes_remove.inc.hpp): rows of kDiagWords words - the totals of each registered operator, one more for the last
-    // application, one whose first word is the mark pass's counter, then the move pass's partial rows (kRemoveBlocks of them)
-    unsigned long long* remove = nullptr;
-    std::vector<RemoveOp> remove_ops;   // the registered sinks, in registration order
-    // fpic_inject (fes_inject.inc.hpp): rows of kDiagWords words - the totals of each registered source, one more for the last
-    // application, then the generation pass's partial rows (kInjectBlocks of them)
-    unsigned long long* inject = nullptr;
-    std::vector<InjectOp> inject_ops;   // the registered sources, in registration order
+    unsigned long long* fusion_grid[FPIC_FUSION_MAX_OPS + 1] = {};   // per row of `fusion` the cell grid (nx ny nz int64, allocated when the row is first used)
+    OpRows fspec_bins;                  // per row of `fspec` (FPIC_FUSION_SPECTRUM_BINS_MAX + 2) x 2 words of the histogram
 };
 inline void diag_release(Diag& g)
 {
     for (Recorder& r : g.rec)
         if (r.dev) (void)hipFree(r.dev);
-    for (void* p : { g.series_req.block, g.modes_req.block, static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom), g.sel, static_cast<void*>(g.load_tab), static_cast<void*>(g.coll), static_cast<void*>(g.force), static_cast<void*>(g.gas), static_cast<void*>(g.pair),
-                     static_cast<void*>(g.pair_seg[0]), static_cast<void*>(g.pair_seg[1]), static_cast<void*>(g.pair_index[0]), static_cast<void*>(g.pair_index[1]),
-                     static_cast<void*>(g.fusion), static_cast<void*>(g.fusion_table),
-                     static_cast<void*>(g.fspec), static_cast<void*>(g.fspec_table), static_cast<void*>(g.fspec_words), static_cast<void*>(g.remove), static_cast<void*>(g.inject) })
+    for (void* p : { g.series_req.block, g.modes_req.block, static_cast<void*>(g.partial), static_cast<void*>(g.row_dev), g.gather, static_cast<void*>(g.hist), static_cast<void*>(g.mom), g.sel, static_cast<void*>(g.load_tab),
+                     static_cast<void*>(g.pair_seg[0]), static_cast<void*>(g.pair_seg[1]), static_cast<void*>(g.pair_index[0]), static_cast<void*>(g.pair_index[1]) })
         if (p) (void)hipFree(p);
+#define X(f) g.f.rows.release();
+    FES_OP_FAMILIES(X)
+#undef X
+    g.fspec_bins.release();
     for (unsigned long long* p : g.fusion_grid)
         if (p) (void)hipFree(p);
     g = Diag();

@@ -64,6 +64,64 @@ class FusionPicError(RuntimeError):
         self.code = code
 
 
+# ---- what the request builders share: a value the C structure cannot carry is refused here, by the property's name
+def _whole(name, v, bits, signed=False):
+    lo_, hi_ = (-(1 << bits - 1), 1 << bits - 1) if signed else (0, 1 << bits)
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo_ <= int(v) < hi_:
+        raise FusionPicError(-1, ".%s <- must be %s %d-bit integer" % (name, "a signed" if signed else "an unsigned", bits))
+    return int(v)
+
+
+def _three(name, v, kind=float):
+    try:
+        if np.ndim(v) == 0:
+            v = [v, v, v]
+        if len(v) != 3:
+            raise ValueError
+        if kind is float:
+            return [float(x) for x in v]
+        return [_whole(name, x, 32, signed=True) for x in v]
+    except (TypeError, ValueError):
+        raise FusionPicError(-1, ".%s <- must be a number or three of them" % name)
+
+
+def _real(name, v):
+    try:
+        return float(v)
+    except (TypeError, ValueError):
+        raise FusionPicError(-1, ".%s <- must be a number" % name)
+
+
+def _real_given(name, v):
+    """_real of a property that has no default"""
+    if v is None:
+        raise FusionPicError(-1, ".%s <- Non-optional property is undefined!" % name)
+    return _real(name, v)
+
+
+def _table(keep, name, v, most=None):
+    """(pointer, size) of a table of doubles; the array goes to the caller's `keep`, which must outlive the call the pointer
+    is handed to.  most: the entries the count's field can carry (None: a 32-bit count, and the older message)"""
+    try:
+        a = np.asarray(v, dtype=np.float64)
+    except (TypeError, ValueError):
+        a = None
+    if a is None or a.ndim != 1 or a.size > ((1 << 32) - 1 if most is None else most):
+        raise FusionPicError(-1, ".%s <- a table must be a sequence of %snumbers" % (name, "" if most is None else "at most %d " % most))
+    a = np.ascontiguousarray(a)
+    keep.append(a)
+    return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(a.size)
+
+
+def _scope_code(scope):
+    return {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope]
+
+
+def _every_arg(every):
+    """the period of a registration as the C int it is passed as"""
+    return _whole("every", every, 32, signed=True)
+
+
 class Spec(ctypes.Structure):
     _fields_ = [
         ("radius", ctypes.c_double), ("height", ctypes.c_double), ("nr", ctypes.c_int32), ("nz", ctypes.c_int32),
@@ -184,7 +242,7 @@ def _hist_call(sim, s, shape, scope):
     n = int(np.prod([max(b, 0) for b in shape], dtype=np.int64))
     counts = np.zeros(n if 0 < n <= HIST_MAX_BINS else 1, dtype=np.uint64)   # (a refused request writes nothing)
     outside = ctypes.c_uint64()
-    sim._check(sim._lib.fpic_histogram(sim._h, ctypes.byref(s), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope], counts.ctypes.data,
+    sim._check(sim._lib.fpic_histogram(sim._h, ctypes.byref(s), _scope_code(scope), counts.ctypes.data,
                                        ctypes.byref(outside)))
     return counts.reshape(shape), int(outside.value)
 
@@ -241,7 +299,7 @@ def _select_spec(where, species, every):
 def _select_call(sim, s, capacity, scope, dtype):
     """fpic_select of one handle -> {ids, position, velocity, matched}.  capacity None: the count query first, then a call
     with room for exactly that many rows; a given capacity that is too small leaves the three arrays None."""
-    sc = {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope]
+    sc = _scope_code(scope)
     code = sim.precision if dtype is None else (F32 if np.dtype(dtype) == np.float32 else F64)
     matched = ctypes.c_uint64()
     if capacity is None:
@@ -263,7 +321,7 @@ def _select_call(sim, s, capacity, scope, dtype):
 
 def _select_count(sim, s, scope):
     matched = ctypes.c_uint64()
-    sim._check(sim._lib.fpic_select(sim._h, ctypes.byref(s), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope], 0, None, None, None,
+    sim._check(sim._lib.fpic_select(sim._h, ctypes.byref(s), _scope_code(scope), 0, None, None, None,
                                     sim.precision, ctypes.byref(matched)))
     return int(matched.value)
 
@@ -290,43 +348,19 @@ def _load_spec(box, species=0, first=0, count=None, seed=LOAD_SEED, stream=0, lo
     components, an integer outside its field); the library checks the rest."""
     s = LoadSpec()
 
-    def whole(name, v, bits, signed=False):
-        lo_, hi_ = (-(1 << bits - 1), 1 << bits - 1) if signed else (0, 1 << bits)
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo_ <= int(v) < hi_:
-            raise FusionPicError(-1, ".%s <- must be %s %d-bit integer" % (name, "a signed" if signed else "an unsigned", bits))
-        return int(v)
-
-    def three(name, v, kind=float):
-        try:
-            if np.ndim(v) == 0:
-                v = [v, v, v]
-            if len(v) != 3:
-                raise ValueError
-            if kind is float:
-                return [float(x) for x in v]
-            return [whole(name, x, 32, signed=True) for x in v]
-        except (TypeError, ValueError):
-            raise FusionPicError(-1, ".%s <- must be a number or three of them" % name)
-
-    def real(name, v):
-        try:
-            return float(v)
-        except (TypeError, ValueError):
-            raise FusionPicError(-1, ".%s <- must be a number" % name)
-
-    s.species = whole("species", species, 32, signed=True)
-    s.first = whole("first", first, 64)
-    s.count = (1 << 64) - 1 if count is None else whole("count", count, 64)
-    s.seed = whole("seed", seed, 64)
-    s.stream = whole("stream", stream, 32)
+    s.species = _whole("species", species, 32, signed=True)
+    s.first = _whole("first", first, 64)
+    s.count = (1 << 64) - 1 if count is None else _whole("count", count, 64)
+    s.seed = _whole("seed", seed, 64)
+    s.stream = _whole("stream", stream, 32)
     s.flags = ((LOAD_POS if position else 0) | (LOAD_VEL if velocity else 0) | (LOAD_LATTICE if lattice else 0) |
                (LOAD_PAIRED if paired else 0) | (LOAD_APPEND if append else 0))
-    s.lo[:] = three("lo", 0.0 if lo is None else lo)
-    s.hi[:] = [float(x) for x in box] if hi is None else three("hi", hi)
-    s.drift[:], s.vth[:] = three("drift", drift), three("vth", vth)
-    s.mode[:] = three("mode", 0 if mode is None else mode, kind=int)
-    s.xamp[:], s.vamp[:] = three("xamp", xamp), three("vamp", vamp)
-    s.xphase, s.vphase = real("xphase", xphase), real("vphase", vphase)
+    s.lo[:] = _three("lo", 0.0 if lo is None else lo)
+    s.hi[:] = [float(x) for x in box] if hi is None else _three("hi", hi)
+    s.drift[:], s.vth[:] = _three("drift", drift), _three("vth", vth)
+    s.mode[:] = _three("mode", 0 if mode is None else mode, kind=int)
+    s.xamp[:], s.vamp[:] = _three("xamp", xamp), _three("vamp", vamp)
+    s.xphase, s.vphase = _real("xphase", xphase), _real("vphase", vphase)
     return s
 
 
@@ -488,48 +522,26 @@ def _collide_spec(dt, kind, species=0, nu=None, sigma_n=None, tau=None, nu_tau=N
     here; the library checks the rest."""
     s = CollideSpec()
 
-    def whole(name, v, bits, signed=False):
-        lo_, hi_ = (-(1 << bits - 1), 1 << bits - 1) if signed else (0, 1 << bits)
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo_ <= int(v) < hi_:
-            raise FusionPicError(-1, ".%s <- must be %s %d-bit integer" % (name, "a signed" if signed else "an unsigned", bits))
-        return int(v)
-
-    def three(name, v):
-        try:
-            if np.ndim(v) == 0:
-                v = [v, v, v]
-            if len(v) != 3:
-                raise ValueError
-            return [float(x) for x in v]
-        except (TypeError, ValueError):
-            raise FusionPicError(-1, ".%s <- must be a number or three of them" % name)
-
-    def real(name, v):
-        try:
-            return float(v)
-        except (TypeError, ValueError):
-            raise FusionPicError(-1, ".%s <- must be a number" % name)
-
     if isinstance(kind, str):
         if kind not in COLLIDE_KINDS:
             raise FusionPicError(-1, ".kind <- must be one of %s" % ", ".join(sorted(COLLIDE_KINDS)))
         kind = COLLIDE_KINDS[kind]
-    s.kind = whole("kind", kind, 32, signed=True)
-    s.species = whole("species", species, 32, signed=True)
-    s.seed, s.stream, s.epoch = whole("seed", seed, 64), whole("stream", stream, 32), whole("epoch", epoch, 32)
+    s.kind = _whole("kind", kind, 32, signed=True)
+    s.species = _whole("species", species, 32, signed=True)
+    s.seed, s.stream, s.epoch = _whole("seed", seed, 64), _whole("stream", stream, 32), _whole("epoch", epoch, 32)
     physical, pair = nu is not None or sigma_n is not None or tau is not None, nu_tau is not None or sigma_tau is not None
     if physical and pair:
         raise FusionPicError(-1, ".nu_tau <- give either nu, sigma_n, tau or nu_tau, sigma_tau, not both")
     if physical:
-        t = real("tau", dt if tau is None else tau)
-        s.nu_tau = real("nu", 0.0 if nu is None else nu) * t
-        s.sigma_tau = real("sigma_n", 0.0 if sigma_n is None else sigma_n) * SPEED_OF_LIGHT * t
+        t = _real("tau", dt if tau is None else tau)
+        s.nu_tau = _real("nu", 0.0 if nu is None else nu) * t
+        s.sigma_tau = _real("sigma_n", 0.0 if sigma_n is None else sigma_n) * SPEED_OF_LIGHT * t
     else:
-        s.nu_tau = real("nu_tau", 0.0 if nu_tau is None else nu_tau)
-        s.sigma_tau = real("sigma_tau", 0.0 if sigma_tau is None else sigma_tau)
-    s.g_max = real("g_max", g_max)
-    s.drift[:], s.vth[:] = three("drift", drift), three("vth", vth)
-    s.mass_ratio = (float("inf") if s.kind == COLLIDE_ELASTIC else 0.0) if mass_ratio is None else real("mass_ratio", mass_ratio)
+        s.nu_tau = _real("nu_tau", 0.0 if nu_tau is None else nu_tau)
+        s.sigma_tau = _real("sigma_tau", 0.0 if sigma_tau is None else sigma_tau)
+    s.g_max = _real("g_max", g_max)
+    s.drift[:], s.vth[:] = _three("drift", drift), _three("vth", vth)
+    s.mass_ratio = (float("inf") if s.kind == COLLIDE_ELASTIC else 0.0) if mass_ratio is None else _real("mass_ratio", mass_ratio)
     return s
 
 
@@ -576,76 +588,43 @@ def _force_spec(dt, L, waves=None, species=0, kind="field", lo=None, hi=None, ta
     s = ForceSpec()
     keep = []
 
-    def whole(name, v, bits, signed=False):
-        lo_, hi_ = (-(1 << bits - 1), 1 << bits - 1) if signed else (0, 1 << bits)
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo_ <= int(v) < hi_:
-            raise FusionPicError(-1, ".%s <- must be %s %d-bit integer" % (name, "a signed" if signed else "an unsigned", bits))
-        return int(v)
-
-    def three(name, v):
-        try:
-            if np.ndim(v) == 0:
-                v = [v, v, v]
-            if len(v) != 3:
-                raise ValueError
-            return [float(x) for x in v]
-        except (TypeError, ValueError):
-            raise FusionPicError(-1, ".%s <- must be a number or three of them" % name)
-
-    def real(name, v):
-        try:
-            return float(v)
-        except (TypeError, ValueError):
-            raise FusionPicError(-1, ".%s <- must be a number" % name)
-
-    def table(name, v):
-        try:
-            a = np.asarray(v, dtype=np.float64)
-        except (TypeError, ValueError):
-            a = None
-        if a is None or a.ndim != 1 or a.size >= 1 << 32:
-            raise FusionPicError(-1, ".%s <- a table must be a sequence of numbers" % name)
-        a = np.ascontiguousarray(a)
-        keep.append(a)
-        return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(a.size)
-
     if isinstance(kind, str):
         if kind not in FORCE_KINDS:
             raise FusionPicError(-1, ".kind <- must be one of %s" % ", ".join(sorted(FORCE_KINDS)))
         kind = FORCE_KINDS[kind]
-    s.kind = whole("kind", kind, 32, signed=True)
-    s.species = whole("species", species, 32, signed=True)
-    s.epoch = whole("epoch", epoch, 64)
+    s.kind = _whole("kind", kind, 32, signed=True)
+    s.species = _whole("species", species, 32, signed=True)
+    s.epoch = _whole("epoch", epoch, 64)
     if waves is None or isinstance(waves, dict) or not hasattr(waves, "__len__"):
         raise FusionPicError(-1, ".waves <- must be a list of 1 .. 4 waves")
-    s.nwaves = whole("nwaves", len(waves), 32, signed=True)
+    s.nwaves = _whole("nwaves", len(waves), 32, signed=True)
     for k, w in enumerate(list(waves)[:FORCE_MAX_WAVES]):
         if not isinstance(w, dict) or set(w) - {"amp", "mode", "nu", "frequency", "phase"} or "amp" not in w:
             raise FusionPicError(-1, ".waves <- a wave is {amp, mode, nu | frequency, phase}")
         if "nu" in w and "frequency" in w:
             raise FusionPicError(-1, ".nu <- give either nu or frequency, not both")
-        s.wave[k].amp[:] = three("amp", w["amp"])
+        s.wave[k].amp[:] = _three("amp", w["amp"])
         mode = w.get("mode", (0, 0, 0))
         if np.ndim(mode) != 1 or len(mode) != 3:
             raise FusionPicError(-1, ".mode <- must be three integers")
-        s.wave[k].mode[:] = [whole("mode", m, 32, signed=True) for m in mode]
-        s.wave[k].nu = real("frequency", w["frequency"]) * dt if "frequency" in w else real("nu", w.get("nu", 0.0))
-        s.wave[k].phase = real("phase", w.get("phase", 0.0))
-    s.lo[:] = three("lo", 0.0 if lo is None else lo)
-    s.hi[:] = three("hi", L if hi is None else hi)
+        s.wave[k].mode[:] = [_whole("mode", m, 32, signed=True) for m in mode]
+        s.wave[k].nu = _real("frequency", w["frequency"]) * dt if "frequency" in w else _real("nu", w.get("nu", 0.0))
+        s.wave[k].phase = _real("phase", w.get("phase", 0.0))
+    s.lo[:] = _three("lo", 0.0 if lo is None else lo)
+    s.hi[:] = _three("hi", L if hi is None else hi)
     if not isinstance(taper, (list, tuple)) or len(taper) != 3:
         raise FusionPicError(-1, ".taper <- must be three tables (None: no table)")
     for a, t in enumerate(taper):
         if t is not None:
-            s.taper[a], s.taper_n[a] = table("taper", t)
+            s.taper[a], s.taper_n[a] = _table(keep, "taper", t)
     s.start, s.stop = 0, FORCE_FOREVER
     if envelope is not None:
         if not isinstance(envelope, dict) or set(envelope) - {"start", "stop", "values"}:
             raise FusionPicError(-1, ".envelope <- must be {start, stop, values}")
-        s.start = whole("start", envelope.get("start", 0), 64)
-        s.stop = whole("stop", envelope.get("stop", FORCE_FOREVER), 64)
+        s.start = _whole("start", envelope.get("start", 0), 64)
+        s.stop = _whole("stop", envelope.get("stop", FORCE_FOREVER), 64)
         if envelope.get("values") is not None:
-            s.envelope, s.envelope_n = table("envelope", envelope["values"])
+            s.envelope, s.envelope_n = _table(keep, "envelope", envelope["values"])
     return s, keep
 
 
@@ -709,63 +688,28 @@ def _gas_spec(tau_default, L, kind, species=0, density=None, tau=None, sigma=Non
     s = GasSpec()
     keep = []
 
-    def whole(name, v, bits, signed=False):
-        lo_, hi_ = (-(1 << bits - 1), 1 << bits - 1) if signed else (0, 1 << bits)
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo_ <= int(v) < hi_:
-            raise FusionPicError(-1, ".%s <- must be %s %d-bit integer" % (name, "a signed" if signed else "an unsigned", bits))
-        return int(v)
-
-    def three(name, v):
-        try:
-            if np.ndim(v) == 0:
-                v = [v, v, v]
-            if len(v) != 3:
-                raise ValueError
-            return [float(x) for x in v]
-        except (TypeError, ValueError):
-            raise FusionPicError(-1, ".%s <- must be a number or three of them" % name)
-
-    def real(name, v):
-        if v is None:
-            raise FusionPicError(-1, ".%s <- Non-optional property is undefined!" % name)
-        try:
-            return float(v)
-        except (TypeError, ValueError):
-            raise FusionPicError(-1, ".%s <- must be a number" % name)
-
-    def table(name, v, most):
-        try:
-            a = np.asarray(v, dtype=np.float64)
-        except (TypeError, ValueError):
-            a = None
-        if a is None or a.ndim != 1 or a.size > most:
-            raise FusionPicError(-1, ".%s <- a table must be a sequence of at most %d numbers" % (name, most))
-        a = np.ascontiguousarray(a)
-        keep.append(a)
-        return a.ctypes.data_as(ctypes.POINTER(ctypes.c_double)), int(a.size)
-
     if isinstance(kind, str):
         if kind not in GAS_KINDS:
             raise FusionPicError(-1, ".kind <- must be one of %s" % ", ".join(sorted(GAS_KINDS)))
         kind = GAS_KINDS[kind]
-    s.kind = whole("kind", kind, 32, signed=True)
-    s.species = whole("species", species, 32, signed=True)
-    s.seed, s.stream, s.epoch = whole("seed", seed, 64), whole("stream", stream, 32), whole("epoch", epoch, 32)
-    s.density = real("density", density)
-    s.tau = real("tau", tau_default if tau is None else tau)
-    s.g_lo, s.g_hi = real("g_lo", g_lo), real("g_hi", g_hi)
+    s.kind = _whole("kind", kind, 32, signed=True)
+    s.species = _whole("species", species, 32, signed=True)
+    s.seed, s.stream, s.epoch = _whole("seed", seed, 64), _whole("stream", stream, 32), _whole("epoch", epoch, 32)
+    s.density = _real_given("density", density)
+    s.tau = _real_given("tau", tau_default if tau is None else tau)
+    s.g_lo, s.g_hi = _real_given("g_lo", g_lo), _real_given("g_hi", g_hi)
     if sigma is None:
         raise FusionPicError(-1, ".sigma <- Non-optional property is undefined!")
-    s.sigma, s.n = table("sigma", sigma, (1 << 31) - 1)
-    s.drift[:], s.vth[:] = three("drift", drift), three("vth", vth)
-    s.mass_ratio = (float("inf") if s.kind == GAS_ELASTIC else 0.0) if mass_ratio is None else real("mass_ratio", mass_ratio)
-    s.lo[:] = three("lo", 0.0 if lo is None else lo)
-    s.hi[:] = three("hi", L if hi is None else hi)
+    s.sigma, s.n = _table(keep, "sigma", sigma, (1 << 31) - 1)
+    s.drift[:], s.vth[:] = _three("drift", drift), _three("vth", vth)
+    s.mass_ratio = (float("inf") if s.kind == GAS_ELASTIC else 0.0) if mass_ratio is None else _real_given("mass_ratio", mass_ratio)
+    s.lo[:] = _three("lo", 0.0 if lo is None else lo)
+    s.hi[:] = _three("hi", L if hi is None else hi)
     if not isinstance(taper, (list, tuple)) or len(taper) != 3:
         raise FusionPicError(-1, ".taper <- must be three tables (None: no table)")
     for a, t in enumerate(taper):
         if t is not None:
-            s.taper[a], s.taper_n[a] = table("taper", t, (1 << 32) - 1)
+            s.taper[a], s.taper_n[a] = _table(keep, "taper", t, (1 << 32) - 1)
     return s, keep
 
 
@@ -908,25 +852,11 @@ def _pair_spec(tau_default, a=0, b=None, log_lambda=None, tau=None, seed=PAIR_SE
     library checks the rest."""
     s = PairSpec()
 
-    def whole(name, v, bits, signed=False):
-        lo_, hi_ = (-(1 << bits - 1), 1 << bits - 1) if signed else (0, 1 << bits)
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo_ <= int(v) < hi_:
-            raise FusionPicError(-1, ".%s <- must be %s %d-bit integer" % (name, "a signed" if signed else "an unsigned", bits))
-        return int(v)
-
-    def real(name, v):
-        if v is None:
-            raise FusionPicError(-1, ".%s <- Non-optional property is undefined!" % name)
-        try:
-            return float(v)
-        except (TypeError, ValueError):
-            raise FusionPicError(-1, ".%s <- must be a number" % name)
-
-    s.species_a = whole("species_a", a, 32, signed=True)
-    s.species_b = s.species_a if b is None else whole("species_b", b, 32, signed=True)
-    s.seed, s.stream, s.epoch = whole("seed", seed, 64), whole("stream", stream, 32), whole("epoch", epoch, 32)
-    s.log_lambda = real("log_lambda", log_lambda)
-    s.tau = real("tau", tau_default if tau is None else tau)
+    s.species_a = _whole("species_a", a, 32, signed=True)
+    s.species_b = s.species_a if b is None else _whole("species_b", b, 32, signed=True)
+    s.seed, s.stream, s.epoch = _whole("seed", seed, 64), _whole("stream", stream, 32), _whole("epoch", epoch, 32)
+    s.log_lambda = _real_given("log_lambda", log_lambda)
+    s.tau = _real_given("tau", tau_default if tau is None else tau)
     return s
 
 
@@ -966,25 +896,11 @@ def _fusion_spec(tau_default, a=0, b=None, sigma=None, g_lo=None, g_hi=None, tau
     structure cannot carry is refused here; the library checks the rest.  The spec keeps the table alive (spec._table)."""
     s = FusionSpec()
 
-    def whole(name, v, bits, signed=False):
-        lo_, hi_ = (-(1 << bits - 1), 1 << bits - 1) if signed else (0, 1 << bits)
-        if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo_ <= int(v) < hi_:
-            raise FusionPicError(-1, ".%s <- must be %s %d-bit integer" % (name, "a signed" if signed else "an unsigned", bits))
-        return int(v)
-
-    def real(name, v):
-        if v is None:
-            raise FusionPicError(-1, ".%s <- Non-optional property is undefined!" % name)
-        try:
-            return float(v)
-        except (TypeError, ValueError):
-            raise FusionPicError(-1, ".%s <- must be a number" % name)
-
-    s.species_a = whole("species_a", a, 32, signed=True)
-    s.species_b = s.species_a if b is None else whole("species_b", b, 32, signed=True)
-    s.seed, s.stream, s.epoch = whole("seed", seed, 64), whole("stream", stream, 32), whole("epoch", epoch, 32)
-    s.tau = real("tau", tau_default if tau is None else tau)
-    s.g_lo, s.g_hi = real("g_lo", g_lo), real("g_hi", g_hi)
+    s.species_a = _whole("species_a", a, 32, signed=True)
+    s.species_b = s.species_a if b is None else _whole("species_b", b, 32, signed=True)
+    s.seed, s.stream, s.epoch = _whole("seed", seed, 64), _whole("stream", stream, 32), _whole("epoch", epoch, 32)
+    s.tau = _real_given("tau", tau_default if tau is None else tau)
+    s.g_lo, s.g_hi = _real_given("g_lo", g_lo), _real_given("g_hi", g_hi)
     if sigma is None:
         raise FusionPicError(-1, ".sigma <- Non-optional property is undefined!")
     try:
@@ -1069,20 +985,10 @@ def _fusion_spectrum_spec(tau_default, a=0, b=None, axis="product", bins=None, l
     if not isinstance(axis, str) or axis not in FSPEC_AXES:
         raise FusionPicError(-1, ".axis <- must be one of cm, product")
     s.axis = FSPEC_AXES[axis]
-    if isinstance(bins, bool) or not isinstance(bins, (int, np.integer)) or not -(1 << 31) <= int(bins) < 1 << 31:
-        raise FusionPicError(-1, ".bins <- must be a signed 32-bit integer")
-    s.bins = int(bins)
+    s.bins = _whole("bins", bins, 32, signed=True)
 
-    def real(name, v):
-        if v is None:
-            raise FusionPicError(-1, ".%s <- Non-optional property is undefined!" % name)
-        try:
-            return float(v)
-        except (TypeError, ValueError):
-            raise FusionPicError(-1, ".%s <- must be a number" % name)
-
-    s.lo, s.hi, s.q_value = real("lo", lo), real("hi", hi), real("q_value", q_value)
-    s.product_mass, s.other_mass = real("product_mass", product_mass), real("other_mass", other_mass)
+    s.lo, s.hi, s.q_value = _real_given("lo", lo), _real_given("hi", hi), _real_given("q_value", q_value)
+    s.product_mass, s.other_mass = _real_given("product_mass", product_mass), _real_given("other_mass", other_mass)
     if los is not None:
         try:
             v = [float(x) for x in los]
@@ -1248,7 +1154,7 @@ def _moments_call(sim, mask, species, scope):
     nm = bin(mask & 0x3FF).count("1") if 0 < mask < 1 << 10 else 1   # (a refused request writes nothing)
     out = np.zeros((nm, sim.nz, sim.ny, sim.nx), dtype=np.int64)
     info = MomentsInfo()
-    sim._check(sim._lib.fpic_moments(sim._h, ctypes.byref(s), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope], out.ctypes.data, ctypes.byref(info)))
+    sim._check(sim._lib.fpic_moments(sim._h, ctypes.byref(s), _scope_code(scope), out.ctypes.data, ctypes.byref(info)))
     return out, int(info.rejected), int(info.spilled)
 
 
@@ -1681,17 +1587,16 @@ class CylindricalParticlePusher:
         """Registers a sink (see remove) to run at the end of every `period`-th sub-step, after the fusion tallies and
         before the recorders.  Each due application waits for one 8-byte count from the device.  Returns the operator's
         index (fpic_remove_register)."""
-        if isinstance(period, bool) or not isinstance(period, (int, np.integer)) or not -(1 << 31) <= int(period) < 1 << 31:
-            raise FusionPicError(-1, ".every <- must be a signed 32-bit integer")
+        period = _every_arg(period)
         s = _remove_spec(where, species, every, outside)
         index = ctypes.c_int()
-        self._check(self._lib.fpic_remove_register(self._h, ctypes.byref(s), int(period), ctypes.byref(index)))
+        self._check(self._lib.fpic_remove_register(self._h, ctypes.byref(s), period, ctypes.byref(index)))
         return index.value
 
     def removeStats(self, index, scope="global"):
         """the totals of a registered sink since its registration (fpic_remove_stats)"""
         out = RemoveResult()
-        self._check(self._lib.fpic_remove_stats(self._h, int(index), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope], ctypes.byref(out)))
+        self._check(self._lib.fpic_remove_stats(self._h, int(index), _scope_code(scope), ctypes.byref(out)))
         return _remove_dict(out)
 
     def clearRemovals(self):
@@ -1760,7 +1665,7 @@ class CylindricalParticlePusher:
     def injectStats(self, index, scope="global"):
         """the totals of a registered source since its registration (fpic_inject_stats)"""
         out = InjectResult()
-        self._check(self._lib.fpic_inject_stats(self._h, int(index), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope], ctypes.byref(out)))
+        self._check(self._lib.fpic_inject_stats(self._h, int(index), _scope_code(scope), ctypes.byref(out)))
         return _inject_dict(out)
 
     def clearInjections(self):
@@ -1827,18 +1732,17 @@ class CylindricalParticlePusher:
         sub-step number + `epoch`; tau defaults to every * dt.  Returns the operator's index (fpic_collide_register)."""
         if kind is None:
             raise FusionPicError(-1, ".kind <- Non-optional property is undefined!")
-        if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or not -(1 << 31) <= int(every) < 1 << 31:
-            raise FusionPicError(-1, ".every <- must be a signed 32-bit integer")
-        s = _collide_spec(int(every) * float(self.spec["dt"]), kind, **request)
+        every = _every_arg(every)
+        s = _collide_spec(every * float(self.spec["dt"]), kind, **request)
         index = ctypes.c_int(-1)
-        self._check(self._lib.fpic_collide_register(self._h, ctypes.byref(s), int(every), ctypes.byref(index)))
+        self._check(self._lib.fpic_collide_register(self._h, ctypes.byref(s), every, ctypes.byref(index)))
         return index.value
 
     def collisionStats(self, index, scope="global"):
         """the totals of a registered operator since its registration (fpic_collide_stats); 'global' on a rank with a
         communicator sums the ranks' counts (collective)"""
         out = CollideResult()
-        self._check(self._lib.fpic_collide_stats(self._h, int(index), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope], ctypes.byref(out)))
+        self._check(self._lib.fpic_collide_stats(self._h, int(index), _scope_code(scope), ctypes.byref(out)))
         return _collide_counts(out)
 
     def clearCollisions(self):
@@ -1873,7 +1777,7 @@ class CylindricalParticlePusher:
         """the totals of a registered force since its registration (fpic_force_stats); 'global' on a rank with a communicator
         sums the ranks' integers (collective)"""
         out = ForceResult()
-        self._check(self._lib.fpic_force_stats(self._h, int(index), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope], ctypes.byref(out)))
+        self._check(self._lib.fpic_force_stats(self._h, int(index), _scope_code(scope), ctypes.byref(out)))
         return _force_dict(out)
 
     def clearForces(self):
@@ -1902,11 +1806,10 @@ class CylindricalParticlePusher:
         number + `epoch`; tau defaults to every * dt.  Returns the operator's index (fpic_gas_register)."""
         if kind is None:
             raise FusionPicError(-1, ".kind <- Non-optional property is undefined!")
-        if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or not -(1 << 31) <= int(every) < 1 << 31:
-            raise FusionPicError(-1, ".every <- must be a signed 32-bit integer")
-        s, keep = _gas_spec(int(every) * float(self.spec["dt"]), self._box_lengths(), kind, **request)
+        every = _every_arg(every)
+        s, keep = _gas_spec(every * float(self.spec["dt"]), self._box_lengths(), kind, **request)
         index = ctypes.c_int(-1)
-        self._check(self._lib.fpic_gas_register(self._h, ctypes.byref(s), int(every), ctypes.byref(index)))
+        self._check(self._lib.fpic_gas_register(self._h, ctypes.byref(s), every, ctypes.byref(index)))
         del keep
         return index.value
 
@@ -1914,7 +1817,7 @@ class CylindricalParticlePusher:
         """the totals of a registered operator since its registration (fpic_gas_stats); 'global' on a rank with a
         communicator sums the ranks' integers (collective)"""
         out = GasResult()
-        self._check(self._lib.fpic_gas_stats(self._h, int(index), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope], ctypes.byref(out)))
+        self._check(self._lib.fpic_gas_stats(self._h, int(index), _scope_code(scope), ctypes.byref(out)))
         return _gas_dict(out)
 
     def clearGas(self):
@@ -1940,17 +1843,16 @@ class CylindricalParticlePusher:
         """Registers a binary collision operator (see collidePair) to run at the end of every `every`-th sub-step, after the
         operators of collideEvery and before the recorders, with epoch = the sub-step number + `epoch`; tau defaults to
         every * dt.  Returns the operator's index (fpic_pair_register)."""
-        if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or not -(1 << 31) <= int(every) < 1 << 31:
-            raise FusionPicError(-1, ".every <- must be a signed 32-bit integer")
-        s = _pair_spec(int(every) * float(self.spec["dt"]), a, b, **request)
+        every = _every_arg(every)
+        s = _pair_spec(every * float(self.spec["dt"]), a, b, **request)
         index = ctypes.c_int(-1)
-        self._check(self._lib.fpic_pair_register(self._h, ctypes.byref(s), int(every), ctypes.byref(index)))
+        self._check(self._lib.fpic_pair_register(self._h, ctypes.byref(s), every, ctypes.byref(index)))
         return index.value
 
     def pairStats(self, index, scope="global"):
         """the totals of a registered binary collision operator since its registration (fpic_pair_stats)"""
         out = PairResult()
-        self._check(self._lib.fpic_pair_stats(self._h, int(index), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope], ctypes.byref(out)))
+        self._check(self._lib.fpic_pair_stats(self._h, int(index), _scope_code(scope), ctypes.byref(out)))
         return _pair_counts(out)
 
     def clearPairs(self):
@@ -1985,17 +1887,16 @@ class CylindricalParticlePusher:
         """Registers a yield tally (see fusionYield) to run at the end of every `every`-th sub-step, after the operators of
         collidePairEvery and before the recorders, with epoch = the sub-step number + `epoch`; tau defaults to every * dt.
         The table is copied.  Returns the operator's index (fpic_fusion_register); at most FUSION_MAX_OPS."""
-        if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or not -(1 << 31) <= int(every) < 1 << 31:
-            raise FusionPicError(-1, ".every <- must be a signed 32-bit integer")
-        s = _fusion_spec(int(every) * float(self.spec["dt"]), a, b, **request)
+        every = _every_arg(every)
+        s = _fusion_spec(every * float(self.spec["dt"]), a, b, **request)
         index = ctypes.c_int(-1)
-        self._check(self._lib.fpic_fusion_register(self._h, ctypes.byref(s), int(every), ctypes.byref(index)))
+        self._check(self._lib.fpic_fusion_register(self._h, ctypes.byref(s), every, ctypes.byref(index)))
         return index.value
 
     def fusionStats(self, index, scope="global"):
         """the totals of a registered yield tally since its registration or its last reset (fpic_fusion_stats)"""
         out = FusionResult()
-        self._check(self._lib.fpic_fusion_stats(self._h, int(index), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope], ctypes.byref(out)))
+        self._check(self._lib.fpic_fusion_stats(self._h, int(index), _scope_code(scope), ctypes.byref(out)))
         return _fusion_counts(out)
 
     def fusionGrid(self, index, reset=False):
@@ -2030,11 +1931,10 @@ class CylindricalParticlePusher:
         """Registers a spectrum (see fusionSpectrum) to run at the end of every `every`-th sub-step, after the tallies of
         fusionYieldEvery and before the recorders, with epoch = the sub-step number + `epoch`; tau defaults to every * dt.
         The table is copied.  Returns the operator's index (fpic_fusion_spectrum_register); at most FUSION_SPECTRUM_MAX_OPS."""
-        if isinstance(every, bool) or not isinstance(every, (int, np.integer)) or not -(1 << 31) <= int(every) < 1 << 31:
-            raise FusionPicError(-1, ".every <- must be a signed 32-bit integer")
-        s = _fusion_spectrum_spec(int(every) * float(self.spec["dt"]), a, b, **request)
+        every = _every_arg(every)
+        s = _fusion_spectrum_spec(every * float(self.spec["dt"]), a, b, **request)
         index = ctypes.c_int(-1)
-        self._check(self._lib.fpic_fusion_spectrum_register(self._h, ctypes.byref(s), int(every), ctypes.byref(index)))
+        self._check(self._lib.fpic_fusion_spectrum_register(self._h, ctypes.byref(s), every, ctypes.byref(index)))
         if getattr(self, "_fspec_axes", None) is None:
             self._fspec_axes = {}                     # the bins and the range of the registered spectra, by index: what a read needs
         self._fspec_axes[index.value] = (s.bins, s.lo, s.hi)
@@ -2067,7 +1967,7 @@ class CylindricalParticlePusher:
         s, keep = _series_spec(points, tracers, species)
         pts = np.zeros((s.npoints if s.npoints <= SERIES_MAX_POINTS else 0, 8))          # (a refused request writes nothing)
         trs = np.zeros((s.ntracers if s.ntracers <= SERIES_MAX_TRACERS else 0, 8))
-        self._check(self._lib.fpic_series_now(self._h, ctypes.byref(s), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope],
+        self._check(self._lib.fpic_series_now(self._h, ctypes.byref(s), _scope_code(scope),
                                               pts.ctypes.data, trs.ctypes.data))
         return {"points": pts, "tracers": trs}
 
@@ -2081,7 +1981,7 @@ class CylindricalParticlePusher:
     def seriesHistory(self, scope="global"):
         """({substep: uint64 (rows,), points: float64 (rows, P, 8), tracers: float64 (rows, M, 8)}, dropped): the rows
         recorded since the last call, oldest first, and how many older rows the ring overwrote"""
-        sc = {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope]
+        sc = _scope_code(scope)
         P, M = getattr(self, "_series_shape", (0, 0))
         n, dropped = ctypes.c_uint64(), ctypes.c_uint64()
         self._check(self._lib.fpic_series_history(self._h, sc, None, None, None, 0, ctypes.byref(n), ctypes.byref(dropped)))
@@ -2096,7 +1996,7 @@ class CylindricalParticlePusher:
         s, names, keep = _modes_spec(modes, fields)
         rows = np.zeros((s.nmodes if s.nmodes <= MODES_MAX else 0, len(names), 2))      # (a refused request writes nothing)
         spare = np.zeros(2)
-        self._check(self._lib.fpic_modes_now(self._h, ctypes.byref(s), {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope],
+        self._check(self._lib.fpic_modes_now(self._h, ctypes.byref(s), _scope_code(scope),
                                              rows.ctypes.data if rows.size else spare.ctypes.data))
         return rows, names
 
@@ -2117,7 +2017,7 @@ class CylindricalParticlePusher:
         self._modes_shape = (int(s.nmodes), names) if every else (0, [])
 
     def _modes_history_rows(self, scope):
-        sc = {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope]
+        sc = _scope_code(scope)
         M, names = getattr(self, "_modes_shape", (0, []))
         n, dropped = ctypes.c_uint64(), ctypes.c_uint64()
         self._check(self._lib.fpic_modes_history(self._h, sc, None, None, 0, ctypes.byref(n), ctypes.byref(dropped)))
@@ -2335,7 +2235,7 @@ class ElectrostaticBoxPusher:
     # ---- energy and momentum diagnostics (fpic_energy_*), reduced on the device
     def _energy_row(self, scope):
         e = Energy()
-        self._check(self._lib.fpic_energy_now(self._h, {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope], ctypes.byref(e)))
+        self._check(self._lib.fpic_energy_now(self._h, _scope_code(scope), ctypes.byref(e)))
         return np.frombuffer(bytes(e), dtype=ENERGY_DTYPE)[0]
 
     def energy(self, scope="global"):
@@ -2351,7 +2251,7 @@ class ElectrostaticBoxPusher:
     def energyHistory(self, scope="global"):
         """(rows, dropped): the rows recorded since the last call, oldest first, as a numpy structured array of
         ENERGY_DTYPE, and how many older rows the ring overwrote"""
-        sc = {"local": DIAG_LOCAL, "global": DIAG_GLOBAL}[scope]
+        sc = _scope_code(scope)
         n, dropped = ctypes.c_uint64(), ctypes.c_uint64()
         self._check(self._lib.fpic_energy_history(self._h, sc, None, 0, ctypes.byref(n), ctypes.byref(dropped)))
         rows = np.zeros(n.value, dtype=ENERGY_DTYPE)

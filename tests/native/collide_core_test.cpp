@@ -196,13 +196,6 @@ static void refusals()
     s = good(FPIC_COLLIDE_RELAX); s.sigma_tau = 1.0; s.g_max = 1.0; CHECK(says(fescoll::check(&s, 1), ".sigma_tau <- must be 0 for FPIC_COLLIDE_RELAX"));
     s = good(FPIC_COLLIDE_RELAX); s.nu_tau = 0; CHECK(says(fescoll::check(&s, 1), ".nu_tau <- must be positive and finite for FPIC_COLLIDE_RELAX"));
     s = good(FPIC_COLLIDE_RELAX); s.nu_tau = kInf; CHECK(says(fescoll::check(&s, 1), ".nu_tau <- must be positive and finite for FPIC_COLLIDE_RELAX"));
-    // registrations and indices
-    CHECK(fescoll::check_register(1, 0) == nullptr && fescoll::check_register(1000000, 7) == nullptr);
-    CHECK(says(fescoll::check_register(0, 0), ".every <- must be at least 1") && says(fescoll::check_register(-3, 0), ".every <- must be at least 1"));
-    CHECK(says(fescoll::check_register(1, 8), ".spec <- FPIC_COLLIDE_MAX_OPS (8) operators are registered already"));
-    CHECK(fescoll::check_index(0, 1) == nullptr && fescoll::check_index(7, 8) == nullptr);
-    CHECK(says(fescoll::check_index(0, 0), ".index <- no such registered operator") && says(fescoll::check_index(-1, 3), ".index <- no such registered operator") &&
-          says(fescoll::check_index(3, 3), ".index <- no such registered operator"));
 }
 
 int main()

@@ -213,11 +213,6 @@ static void refusals()
         s = good(); s.taper_n[0] = 1024; s.taper[0] = tab.data(); CHECK(fesforce::check(&s, 1, kL) == nullptr);
         tab[1024] = 1.0;
     }
-    CHECK(fesforce::check_register(0) == nullptr && fesforce::check_register(7) == nullptr);
-    CHECK(says(fesforce::check_register(8), ".spec <- FPIC_FORCE_MAX_OPS (8) requests are registered already"));
-    CHECK(fesforce::check_index(0, 1) == nullptr && fesforce::check_index(7, 8) == nullptr);
-    CHECK(says(fesforce::check_index(0, 0), ".index <- no such registered request") && says(fesforce::check_index(-1, 3), ".index <- no such registered request") &&
-          says(fesforce::check_index(3, 3), ".index <- no such registered request"));
 }
 
 // ---- cases from a file.  Per case, little endian: int32 kind, nwaves; uint64 epoch, start, stop, count; double L[3], lo[3],

@@ -207,12 +207,6 @@ static void refusals()
     CHECK(fesfusion::rule_of(s, 0u, 1e10, 1.0).e == 0 && fesfusion::rule_of(s, 0u, 1e10, 1.0).s_max == 0.0);
     s = good(); CHECK(fesfusion::check_bound(s, 1e10, 1.0) == nullptr);
     CHECK(says(fesfusion::check_bound(s, 1e200, 1.0), ".sigma <- the yield bound W W 2048 tau max(sigma) g_hi c / dV is not a finite number"));
-    CHECK(fesfusion::check_register(1, 0) == nullptr && fesfusion::check_register(1000000, 3) == nullptr);
-    CHECK(says(fesfusion::check_register(0, 0), ".every <- must be at least 1") && says(fesfusion::check_register(-3, 0), ".every <- must be at least 1"));
-    CHECK(says(fesfusion::check_register(1, 4), ".spec <- FPIC_FUSION_MAX_OPS (4) operators are registered already"));
-    CHECK(fesfusion::check_index(0, 1) == nullptr && fesfusion::check_index(3, 4) == nullptr);
-    CHECK(says(fesfusion::check_index(0, 0), ".index <- no such registered operator") && says(fesfusion::check_index(-1, 3), ".index <- no such registered operator") &&
-          says(fesfusion::check_index(3, 3), ".index <- no such registered operator"));
 }
 
 // the file's pairs through tally(): see the head of this file

@@ -215,9 +215,6 @@ static void refusals()
     s = good(); s.los[0] = 1e-200; CHECK(says(fesfspec::check(&s, 2), ".los <- must be all zero (isotropic) or have a non-zero, finite norm"));
     s = good(); s.los[1] = 1e200; CHECK(says(fesfspec::check(&s, 2), ".los <- must be all zero (isotropic) or have a non-zero, finite norm"));
     s = good(); s.los[2] = -1.0; CHECK(fesfspec::check(&s, 2) == nullptr);
-    CHECK(fesfspec::check_register(1, 0) == nullptr && fesfspec::check_register(1000000, 3) == nullptr);
-    CHECK(says(fesfspec::check_register(0, 0), ".every <- must be at least 1") && says(fesfspec::check_register(-3, 0), ".every <- must be at least 1"));
-    CHECK(says(fesfspec::check_register(1, 4), ".spec <- FPIC_FUSION_SPECTRUM_MAX_OPS (4) operators are registered already"));
 }
 
 // the file's pairs through the rule: see the head of this file

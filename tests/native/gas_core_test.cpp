@@ -212,12 +212,6 @@ static void refusals()
     s = good(); s.taper_n[0] = 2; s.taper[0] = tab.data(); CHECK(fesgas::check(&s, 1, kL) == nullptr);      // 0 and 1 themselves are allowed
     const double huge[2] = { 1e300, 1e300 };
     s = good(); s.density = 1e300; s.sigma = huge; s.n = 2; CHECK(says(fesgas::check(&s, 1, kL), ".sigma <- the candidate bound density c tau max(sigma g) is not a finite number"));
-    CHECK(fesgas::check_register(1, 0) == nullptr && fesgas::check_register(5, 7) == nullptr);
-    CHECK(says(fesgas::check_register(0, 0), ".every <- must be at least 1") && says(fesgas::check_register(-2, 0), ".every <- must be at least 1"));
-    CHECK(says(fesgas::check_register(1, 8), ".spec <- FPIC_GAS_MAX_OPS (8) operators are registered already"));
-    CHECK(fesgas::check_index(0, 1) == nullptr && fesgas::check_index(7, 8) == nullptr);
-    CHECK(says(fesgas::check_index(0, 0), ".index <- no such registered operator") && says(fesgas::check_index(-1, 3), ".index <- no such registered operator") &&
-          says(fesgas::check_index(3, 3), ".index <- no such registered operator"));
 }
 
 // ---- cases from a file.  Per case, little endian: int32 kind, n, precision (0: float, 1: double), 0; uint64 seed; uint32 stream,

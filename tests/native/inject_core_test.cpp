@@ -1,7 +1,7 @@
 // Host test of fusion-sim_amd/csrc/fes_inject_core.hpp (the rule of the particle sources and the checks of a request): the
 // sequence numbers of an application and their 2^32 bound, the capacity and id rule, every refusal by its message, the kind
-// logic — a VOLUME particle is the loader's, a FLUX particle's exact parts spelled out —, the registration, index and capacity
-// checks, and the conversion of a row of totals to the result, the NaN rule included.  Built with g++ -ffp-contract=off by
+// logic — a VOLUME particle is the loader's, a FLUX particle's exact parts spelled out —, the capacity check (the
+// registration and index checks are fes_ops_core.hpp's: ops_core_test.cpp), and the conversion of a row of totals to the result, the NaN rule included.  Built with g++ -ffp-contract=off by
 // tests/test_inject_host.py; prints "ok" and exits 0, or names the first failed check and exits 1.
 #include <cmath>
 #include <cstdio>
@@ -108,11 +108,6 @@ static void refusals()
     s = flux(); s.load.xamp[1] = 1e-3; CHECK(names(fesinj::check(&s, 1, L), ".xamp <- "));
     s = flux(); s.load.vamp[2] = 1e-3; CHECK(names(fesinj::check(&s, 1, L), ".vamp <- "));
     s = flux(); s.load.mode[0] = 1; CHECK(names(fesinj::check(&s, 1, L), ".mode <- "));
-    CHECK(fesinj::check_register(1, 0) == nullptr && fesinj::check_register(1000, FPIC_INJECT_MAX_OPS - 1) == nullptr);
-    CHECK(names(fesinj::check_register(0, 0), ".every <- ") && names(fesinj::check_register(-3, 0), ".every <- "));
-    CHECK(names(fesinj::check_register(1, FPIC_INJECT_MAX_OPS), ".spec <- "));
-    CHECK(fesinj::check_index(0, 1) == nullptr && names(fesinj::check_index(1, 1), ".index <- ") && names(fesinj::check_index(-1, 1), ".index <- ") &&
-          names(fesinj::check_index(0, 0), ".index <- "));
     CHECK(fesinj::check_capacity(1) == nullptr && fesinj::check_capacity(0xFFFFFFFFull - 4097) == nullptr);
     CHECK(names(fesinj::check_capacity(0xFFFFFFFFull - 4096), ".capacity <- ") && names(fesinj::check_capacity(~0ull), ".capacity <- "));
 }

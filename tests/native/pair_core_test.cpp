@@ -156,12 +156,6 @@ static void refusals()
         s = good(); s.log_lambda = bad; CHECK(says(fespair::check(&s, 2), ".log_lambda <- must be positive and finite"));
         s = good(); s.tau = bad; CHECK(says(fespair::check(&s, 2), ".tau <- must be positive and finite"));
     }
-    CHECK(fespair::check_register(1, 0) == nullptr && fespair::check_register(1000000, 7) == nullptr);
-    CHECK(says(fespair::check_register(0, 0), ".every <- must be at least 1") && says(fespair::check_register(-3, 0), ".every <- must be at least 1"));
-    CHECK(says(fespair::check_register(1, 8), ".spec <- FPIC_PAIR_MAX_OPS (8) operators are registered already"));
-    CHECK(fespair::check_index(0, 1) == nullptr && fespair::check_index(7, 8) == nullptr);
-    CHECK(says(fespair::check_index(0, 0), ".index <- no such registered operator") && says(fespair::check_index(-1, 3), ".index <- no such registered operator") &&
-          says(fespair::check_index(3, 3), ".index <- no such registered operator"));
 }
 
 int main()

@@ -1,6 +1,6 @@
 // Host test of fusion-sim_amd/csrc/fes_remove_core.hpp (the rule of the absorbing particle sinks and the checks of a
-// request): the request as the selection's, who leaves under both flags, every refusal by its message, the registration
-// and index checks, and the conversion of a row of totals to the result, the NaN rule included.  Built with g++
+// request): the request as the selection's, who leaves under both flags, every refusal by its message (the registration
+// and index checks are fes_ops_core.hpp's: ops_core_test.cpp), and the conversion of a row of totals to the result, the NaN rule included.  Built with g++
 // -ffp-contract=off by tests/test_remove_host.py; prints "ok" and exits 0, or names the first failed check and exits 1.
 #include <cmath>
 #include <cstdio>
@@ -82,11 +82,6 @@ static void refusals()
     s = good(); s.reserved_u = 1; CHECK(names(fesrem::check(&s, 1), ".reserved <- "));
     std::memset(&s, 0, sizeof s);
     CHECK(fesrem::check(&s, 1) == nullptr);
-    CHECK(fesrem::check_register(1, 0) == nullptr && fesrem::check_register(1000, FPIC_REMOVE_MAX_OPS - 1) == nullptr);
-    CHECK(names(fesrem::check_register(0, 0), ".every <- ") && names(fesrem::check_register(-3, 0), ".every <- "));
-    CHECK(names(fesrem::check_register(1, FPIC_REMOVE_MAX_OPS), ".spec <- "));
-    CHECK(fesrem::check_index(0, 1) == nullptr && names(fesrem::check_index(1, 1), ".index <- ") && names(fesrem::check_index(-1, 1), ".index <- ") &&
-          names(fesrem::check_index(0, 0), ".index <- "));
 }
 
 static void results()
