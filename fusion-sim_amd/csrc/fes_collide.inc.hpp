@@ -2,10 +2,9 @@
 // fpic_collide_stats, fpic_collide_clear) — part of fes_api.hip's translation unit (included there after fes_load.inc.hpp,
 // inside namespace fes).  The rule and the checks of a request are fes_collide_core.hpp, the passes fes_collide_kernels.hpp.
 //
-// EXCHANGE and ELASTIC have two passes, chosen by P_max = K 2^-32 (collide_compacts): the plain one, and between 2^-8 and 2^-3
-// the one that compacts a workgroup's candidates into LDS (DESIGN 4.16 has the measurements behind the two thresholds).
-// One launch per application over the slots [0, n) and, while a migration rides on the next push, the arrivals behind them
-// (they follow at tail_first = n: one range, as the flat pass of mom_enqueue).  The counts go to the family's rows
+// EXCHANGE and ELASTIC have two hand-outs of their candidates, chosen by P_max = K 2^-32 (collide_compacts): the wave-shared
+// loop, and between 2^-8 and 2^-3 the queue in LDS (DESIGN 4.16 has the measurements behind the two thresholds).
+// One launch per application over the range of pass_head (fes_ops.inc.hpp).  The counts go to the family's rows
 // (fes_ops.inc.hpp): four words per row.  A registered operator is enqueued by the hook with no host synchronisation and no
 // collective; fpic_collide_stats reads its row.
 
@@ -14,41 +13,33 @@ constexpr int kCollideNow = FPIC_COLLIDE_MAX_OPS;        // the row of fpic_coll
 
 static int collide_room(fpic_handle* h) { return h->es->diag.collide.rows.room(h, kCollideWords, FPIC_COLLIDE_MAX_OPS + 1); }
 
+// the instance of KIND for the request's form (null-collision test or not) and hand-out (collide_compacts)
+template <typename T, int KIND>
+static void collide_launch(fpic_handle* h, const CollideArgs<T>& a, unsigned grid)
+{
+    const bool compact = collide_compacts(a.r.K);
+    if (a.r.nullc) {
+        if (compact) collide_kernel<T, KIND, true, true><<<grid, kCollideThreads, 0, h->stream>>>(a);
+        else collide_kernel<T, KIND, true, false><<<grid, kCollideThreads, 0, h->stream>>>(a);
+    } else {
+        if (compact) collide_kernel<T, KIND, false, true><<<grid, kCollideThreads, 0, h->stream>>>(a);
+        else collide_kernel<T, KIND, false, false><<<grid, kCollideThreads, 0, h->stream>>>(a);
+    }
+}
+
 // one application of `r` to species `sp`, its counts added to words[1 .. 4): enqueued, nothing waited for
 template <typename T>
 static int collide_enqueue(fpic_handle* h, const Species& sp, const fescoll::Rule& r, unsigned long long* words)
 {
     const bool relax = r.kind == FPIC_COLLIDE_RELAX;
-    const size_t slots = std::min(sp.n + sp.tail_count, sp.n_pad);   // (the arrivals of a riding migration follow at tail_first = n)
-    if (!slots || (!relax && r.K == 0)) return FPIC_OK;   // (nothing can collide: nothing is launched)
     CollideArgs<T> a{};
-    a.slab = static_cast<T*>(sp.slab[sp.cur]);
-    a.id = sp.ids_identity ? nullptr : sp.id[sp.cur];
-    a.n_pad = sp.n_pad;
-    a.s1 = slots;
-    a.dead = h->es->dom ? 1 : 0;
+    const unsigned grid = pass_head(h, sp, kCollideBlocks, a);
+    if (!grid || (!relax && r.K == 0)) return FPIC_OK;   // (nothing can collide: nothing is launched)
     a.counts = words + 1;
     a.r = r;
-    const size_t groups = (slots + 3) / 4;
-    const unsigned grid = static_cast<unsigned>(std::min<size_t>(kCollideBlocks, (groups + kCollideThreads - 1) / kCollideThreads));
-    const bool compact = collide_compacts(r.K);
     if (relax) relax_kernel<T><<<grid, kCollideThreads, 0, h->stream>>>(a);
-    else if (compact) {
-        if (r.kind == FPIC_COLLIDE_EXCHANGE) {
-            if (r.nullc) collide_compact_kernel<T, FPIC_COLLIDE_EXCHANGE, true><<<grid, kCollideThreads, 0, h->stream>>>(a);
-            else collide_compact_kernel<T, FPIC_COLLIDE_EXCHANGE, false><<<grid, kCollideThreads, 0, h->stream>>>(a);
-        } else {
-            if (r.nullc) collide_compact_kernel<T, FPIC_COLLIDE_ELASTIC, true><<<grid, kCollideThreads, 0, h->stream>>>(a);
-            else collide_compact_kernel<T, FPIC_COLLIDE_ELASTIC, false><<<grid, kCollideThreads, 0, h->stream>>>(a);
-        }
-    }
-    else if (r.kind == FPIC_COLLIDE_EXCHANGE) {
-        if (r.nullc) collide_kernel<T, FPIC_COLLIDE_EXCHANGE, true><<<grid, kCollideThreads, 0, h->stream>>>(a);
-        else collide_kernel<T, FPIC_COLLIDE_EXCHANGE, false><<<grid, kCollideThreads, 0, h->stream>>>(a);
-    } else {
-        if (r.nullc) collide_kernel<T, FPIC_COLLIDE_ELASTIC, true><<<grid, kCollideThreads, 0, h->stream>>>(a);
-        else collide_kernel<T, FPIC_COLLIDE_ELASTIC, false><<<grid, kCollideThreads, 0, h->stream>>>(a);
-    }
+    else if (r.kind == FPIC_COLLIDE_EXCHANGE) collide_launch<T, FPIC_COLLIDE_EXCHANGE>(h, a, grid);
+    else collide_launch<T, FPIC_COLLIDE_ELASTIC>(h, a, grid);
     HIP_TRY(h, hipGetLastError());
     return FPIC_OK;
 }

@@ -161,20 +161,13 @@ __device__ __forceinline__ void diag_block_sum(double (&v)[NQ], double* __restri
     }
 }
 
-template <typename T>
-struct Vec16Of;
-template <>
-struct Vec16Of<float> { using type = float4; };
-template <>
-struct Vec16Of<double> { using type = double2; };
-
 // slots [0, n) of one species; `x` non-null: skip a slot whose x < 0 (dead: fes_kernels.hpp, the migration's pack).
 // Slot arrays are n_pad long (a multiple of 1024), so the 16-byte loads of the last vector stay inside them.
 template <typename T>
 __global__ __launch_bounds__(kDiagThreads) void diag_particles_kernel(const T* __restrict__ x, const T* __restrict__ vx, const T* __restrict__ vy,
                                                                       const T* __restrict__ vz, size_t n, unsigned long long* __restrict__ partial)
 {
-    using V = typename Vec16Of<T>::type;
+    using V = typename Vec16<T>::type;
     constexpr int L = 16 / sizeof(T);
     const size_t nv = (n + L - 1) / L, stride = static_cast<size_t>(gridDim.x) * kDiagThreads;
     const V* __restrict__ px = reinterpret_cast<const V*>(x);

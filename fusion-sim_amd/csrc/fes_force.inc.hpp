@@ -2,8 +2,7 @@
 // fpic_force_clear) — part of fes_api.hip's translation unit (included there after fes_collide.inc.hpp, inside namespace fes).
 // The rule and the checks of a request are fes_force_core.hpp, the pass fes_force_kernels.hpp.
 //
-// One launch per application over the slots [0, n) and, while a migration rides on the next push, the arrivals behind them
-// (one range, as collide_enqueue).  The family's rows (fes_ops.inc.hpp) hold fesforce::kWords tally words and room for three
+// One launch per application over the range of pass_head (fes_ops.inc.hpp).  The family's rows (fes_ops.inc.hpp) hold fesforce::kWords tally words and room for three
 // taper tables each.  A request's tables are copied at the call — the tapers to the device, the envelope to the host, where it
 // is read once per application.  A registered request is enqueued by the hook with no host synchronisation and no
 // collective; fpic_force_stats reads its row.  A force has no period: it is due at the sub-steps at which it is active.
@@ -41,18 +40,12 @@ static int force_enqueue(fpic_handle* h, const ForceOp& op, uint64_t at, unsigne
 {
     State* st = h->es;
     const Species& sp = st->sp[op.spec.species];
-    const size_t slots = std::min(sp.n + sp.tail_count, sp.n_pad);   // (the arrivals of a riding migration follow at tail_first = n)
-    if (!slots) return FPIC_OK;
-    const double L[3] = { st->lx, st->ly, st->lz };
     ForceArgs<T> a{};
-    a.slab = static_cast<T*>(sp.slab[sp.cur]);
-    a.n_pad = sp.n_pad;
-    a.s1 = slots;
-    a.dead = st->dom ? 1 : 0;
+    const unsigned grid = pass_head(h, sp, kForceBlocks, a);
+    if (!grid) return FPIC_OK;
+    const double L[3] = { st->lx, st->ly, st->lz };
     a.words = words;
     a.r = fesforce::rule_of(op.spec, L, sp.charge, sp.mass, h->spec.dt, at, op.envelope.data(), op.taper);
-    const size_t groups = (slots + 3) / 4;
-    const unsigned grid = static_cast<unsigned>(std::min<size_t>(kForceBlocks, (groups + kForceThreads - 1) / kForceThreads));
     if (a.r.whole && !a.r.tapered) {
         force_kernel<T, true><<<grid, kForceThreads, 0, h->stream>>>(a);
     } else {

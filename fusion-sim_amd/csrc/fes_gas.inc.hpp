@@ -3,8 +3,7 @@
 // fes_force.inc.hpp, inside namespace fes).  The rule and the checks of a request are fes_gas_core.hpp, the pass
 // fes_gas_kernels.hpp.
 //
-// One launch per application over the slots [0, n) and, while a migration rides on the next push, the arrivals behind them
-// (one range, as collide_enqueue).  The family's rows (fes_ops.inc.hpp) hold fesgas::kWords tally words and room for the
+// One launch per application over the range of pass_head (fes_ops.inc.hpp).  The family's rows (fes_ops.inc.hpp) hold fesgas::kWords tally words and room for the
 // cross-section table and three taper tables each.  A request's tables are copied at the call: to the device, and the cross-sections to the host too, where the candidate
 // bound is formed.  Per request the host chooses which test the pass makes first (gas_window_first) and whether its
 // candidates go through the LDS queue (gas_compacts); DESIGN 4.23 has the measurements behind the thresholds.  A registered
@@ -61,19 +60,12 @@ static int gas_enqueue(fpic_handle* h, const GasOp& op, uint32_t epoch, unsigned
 {
     State* st = h->es;
     const Species& sp = st->sp[op.spec.species];
-    const size_t slots = std::min(sp.n + sp.tail_count, sp.n_pad);   // (the arrivals of a riding migration follow at tail_first = n)
     const double L[3] = { st->lx, st->ly, st->lz };
     GasArgs<T> a{};
+    const unsigned grid = pass_head(h, sp, kGasBlocks, a);
     a.r = fesgas::rule_of(op.spec, L, epoch, op.sigma.data(), op.dev_sigma, op.taper);
-    if (!slots || a.r.K == 0) return FPIC_OK;   // (nothing can collide: nothing is launched)
-    a.slab = static_cast<T*>(sp.slab[sp.cur]);
-    a.id = sp.ids_identity ? nullptr : sp.id[sp.cur];
-    a.n_pad = sp.n_pad;
-    a.s1 = slots;
-    a.dead = st->dom ? 1 : 0;
+    if (!grid || a.r.K == 0) return FPIC_OK;   // (nothing can collide: nothing is launched)
     a.words = words;
-    const size_t groups = (slots + 3) / 4;
-    const unsigned grid = static_cast<unsigned>(std::min<size_t>(kGasBlocks, (groups + kGasThreads - 1) / kGasThreads));
     const int forms = gas_forms();
     const bool window_first = forms & 2 ? true : forms & 1 ? false : gas_window_first(a.r);
     const bool compact = forms & 8 ? true : forms & 4 ? false : gas_compacts(a.r.K);

@@ -51,7 +51,6 @@ constexpr int kCollided = 1, kBelow = 2, kAbove = 4;   // what an update reports
 constexpr int kCounts = 3;
 constexpr int kWords = kCounts + fesforce::kWords;
 constexpr int kSumWords = kCounts + fesforce::kSumWords;
-constexpr double kFixRange = 0x1p15;      // = fes::kFixRange
 
 // a request as the kernels read it; sigma and win.tab are where the kernels read the tables (device pointers in the library)
 struct Rule {
@@ -136,35 +135,10 @@ inline int apply(const Rule& r, uint32_t i, const double (&p)[3], double (&v)[3]
     return scatter(r, r.sigma, tab, i, p, v);
 }
 
-// ---- the tally terms.  floor(d 2^80) exactly for |d| < kFixRange, as a 128-bit two's complement integer: fes::to_fix
-// (fes_diag_kernels.hpp) restated for the host and the device, so that the host test runs what the kernels run.
-using Fix = unsigned __int128;
-FES_HIST_HD Fix floor_fix(double d)
-{
-    const double y = fabs(d) * 0x1p80;
-    const double h = floor(y * 0x1p-64);
-    const double r = y - h * 0x1p64;
-    const unsigned long long lo = static_cast<unsigned long long>(r);
-    const Fix mag = (static_cast<Fix>(static_cast<unsigned long long>(h)) << 64) + lo;
-    if (!(d < 0)) return mag;
-    return ~mag + (static_cast<double>(lo) != r ? 0 : 1);
-}
-// after - before into `sum`, or — either outside the range — the bit into `out`
-FES_HIST_HD void fix_diff(Fix& sum, unsigned long long& out, double before, double after, int bit)
-{
-    if (fabs(before) < kFixRange && fabs(after) < kFixRange) sum += floor_fix(after) - floor_fix(before);
-    else out |= 1ull << bit;
-}
-// a collided particle's terms: u0 the stored velocity before, w the stored velocity after, both as doubles.  sum[0] energy,
-// sum[1 .. 3] momentum; out: bit 0 energy, bits 1 .. 3 momentum
-FES_HIST_HD void tally(const double (&u0)[3], const double (&w)[3], Fix (&sum)[4], unsigned long long& out)
-{
-    for (int a = 0; a < 3; ++a) fix_diff(sum[1 + a], out, u0[a], w[a], 1 + a);
-    const double b00 = u0[0] * u0[0], b11 = u0[1] * u0[1], b22 = u0[2] * u0[2];
-    const double a00 = w[0] * w[0], a11 = w[1] * w[1], a22 = w[2] * w[2];
-    const double b01 = b00 + b11, a01 = a00 + a11;
-    fix_diff(sum[0], out, b01 + b22, a01 + a22, 0);
-}
+// ---- the tally terms: the forces' (fes_force_core.hpp), energy in the place of work, momentum in the place of impulse
+using fesforce::Fix;
+using fesforce::floor_fix;
+using fesforce::tally;
 
 // ---- the host-side numbers
 inline double column_of(const fpic_gas_spec& s)

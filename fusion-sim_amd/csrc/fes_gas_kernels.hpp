@@ -1,25 +1,21 @@
 // fes_gas_kernels.hpp — the pass of the windowed background collisions of a CART3D handle (fpic_gas; host side
-// fes_gas.inc.hpp, the rule fes_gas_core.hpp).  The launch shape of collide_kernel and force_kernel: a fixed grid and a
-// grid-stride loop over groups of FOUR slots; a lane takes the four ids from id[slot] (one 16-byte load) or, while the
-// species is in the caller's order, the slot numbers.
+// fes_gas.inc.hpp, the rule fes_gas_core.hpp).  Launch shape, group access, the two hand-outs of candidates and the tally
+// are the shared forms of fes_pass.hpp.
 //   gas_kernel<T, WINDOW_FIRST, COMPACT>  A candidate is a live particle inside the window whose word w0 < K: a set,
 //       whichever test is made first.
 //       WINDOW_FIRST = false  per particle the pass reads only the id, runs Philox block 0 and makes the integer test; a
 //           particle whose word passes then gathers its position and is dropped if it is dead or outside.  The cheaper order
 //           at small P_max and on the whole box (where an untapered request reads no position at all, as collide_kernel).
-//       WINDOW_FIRST = true   the pass streams x, y, z of the group with 16-byte loads and runs Philox only for the live slots
+//       WINDOW_FIRST = true   the pass streams x, y, z of the group with load4 and runs Philox only for the live slots
 //           inside; a group wholly outside loads no id.  The cheaper order when the window is a small part of a sorted box.
-//       COMPACT = false  the candidates of a lane are taken one per turn of a loop the wave shares (collide_kernel's form).
-//       COMPACT = true   the candidates of a workgroup's turn (its 1024 slots) go into a queue in LDS and are then taken
-//           densely, one per lane (collide_compact_kernel's form).  What a particle gets does not depend on its place.
+//       COMPACT = false  the candidates are handed out by take_pending, COMPACT = true by take_queued.
 //       The cross-section table and the tapers are read through the caches: the lookups are indexed, not searched, and only
 //       candidates make them.  A form that staged them in the workgroup's LDS first (up to 32 KiB + 24.6 KiB: two workgroups
 //       per CU) lost the measurement and is not kept.
 //       Only a candidate gathers its three velocities, and only a particle that collides is stored: every other particle
 //       keeps its bits.  Positions are never written.
-// The counts (candidates, below, above, collided) and the exact tallies (energy, momentum: fesgas::tally, the forces' fixed
-// point) are kept per lane, reduced over the wave by shuffles and over the workgroup through LDS, and added to the request's
-// device words by one lane with one set of 64-bit atomics per workgroup (force_add128 for the 128-bit sums).  No scratch.
+// The counts (candidates, below, above, collided) and the exact tallies (energy, momentum: fesgas::tally, the forces'
+// before/after terms) are a Tally<4, 4>, whose device words are fesgas::kWords.  No scratch.
 #pragma once
 
 #include "fes_collide_kernels.hpp"
@@ -29,12 +25,13 @@
 namespace fes {
 
 constexpr int kGasThreads = 256;
+static_assert(kGasThreads == kPassThreads, "the shared forms reduce and queue for a workgroup of kPassThreads");
 constexpr int kGasBlocks = 2048;          // 8 workgroups of 4 waves per CU of the 256, as kCollideBlocks
 // The host's choices (gas_window_first, gas_compacts), per request.
 // Window first when the window holds less than kGasWindowFirstMax of the box's volume: below, the Philox blocks the pass
 // saves outweigh the three position arrays it streams (fp64 breaks even near 0.4, fp32 near 0.47: DESIGN 4.23).
 constexpr double kGasWindowFirstMax = 0.4;
-// The queue serves kGasCompactMin <= K <= kGasCompactMax (P_max from 2^-8 to 2^-3), the range collide_compact_kernel serves
+// The queue serves kGasCompactMin <= K <= kGasCompactMax (P_max from 2^-8 to 2^-3), the range collide_kernel's queue serves
 // and for its reasons: below, the barriers cost more than the idle lanes; above, most lanes are busy anyway.
 constexpr unsigned long long kGasCompactMin = 1ull << 24, kGasCompactMax = 1ull << 29;
 inline double gas_window_volume(const fesgas::Rule& r) { return (r.win.w[0] * r.win.w[1]) * r.win.w[2]; }
@@ -42,66 +39,13 @@ inline bool gas_window_first(const fesgas::Rule& r) { return !r.win.whole && gas
 inline bool gas_compacts(unsigned long long K) { return K >= kGasCompactMin && K <= kGasCompactMax; }
 
 template <typename T>
-struct GasArgs {
-    T* slab;                  // x, y, z, vx, vy, vz: six arrays of n_pad
-    const uint32_t* id;       // n_pad words; nullptr: slot = id
-    size_t n_pad;             // a multiple of 1024: a group of four slots stays inside the arrays
-    size_t s1;                // the slots [0, s1) the pass visits
-    int dead;                 // a rank of a decomposition: x < 0 marks a dead slot
+struct GasArgs : PassArgs<T> {
     unsigned long long* words;    // fesgas::kWords of them
     fesgas::Rule r;
 };
 
-struct GasAcc {
-    unsigned long long count[4] = { 0, 0, 0, 0 };   // candidates, below, above, collided
-    unsigned long long out = 0;
-    fesgas::Fix sum[4] = { 0, 0, 0, 0 };            // energy, momentum x, y, z
-};
-
-// the lanes' tallies -> the request's words: every lane of the workgroup calls it once, after its loop
-__device__ __forceinline__ void gas_tally(GasAcc& a, unsigned long long* words)
-{
-    __shared__ unsigned long long part[kGasThreads / 64][fesgas::kWords];
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            a.count[c] += __shfl_xor(a.count[c], off, 64);
-            a.sum[c] += shfl_xor_fix(a.sum[c], off);
-        }
-        a.out |= __shfl_xor(a.out, off, 64);
-    }
-    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
-    if (lane == 0) {
-        unsigned long long* p = part[wave];
-        p[0] = a.count[0];
-        p[1] = a.count[1];
-        p[2] = a.count[2];
-        p[3] = a.count[3];
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-            p[4 + 2 * c] = static_cast<unsigned long long>(a.sum[c]);
-            p[5 + 2 * c] = static_cast<unsigned long long>(a.sum[c] >> 64);
-        }
-        p[12] = a.out;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        unsigned long long count[4] = { 0, 0, 0, 0 }, out = 0;
-        Fix sum[4] = { 0, 0, 0, 0 };
-        for (int w = 0; w < kGasThreads / 64; ++w) {
-            for (int c = 0; c < 4; ++c) {
-                count[c] += part[w][c];
-                sum[c] += (static_cast<Fix>(part[w][5 + 2 * c]) << 64) | part[w][4 + 2 * c];
-            }
-            out |= part[w][12];
-        }
-        for (int c = 0; c < 4; ++c)
-            if (count[c]) atomicAdd(words + c, count[c]);
-        for (int c = 0; c < 4; ++c) force_add128(words + 4 + 2 * c, sum[c]);
-        if (out) atomicOr(words + 12, out);
-    }
-}
+using GasAcc = Tally<4, 4>;               // candidates, below, above, collided | energy, momentum x, y, z
+static_assert(GasAcc::kWords == fesgas::kWords, "the tally's words are the request's");
 
 // One particle whose word has passed (S, tab: r.sigma and r.win.tab).  CHECK: the window and the dead mark are still to be
 // tested (the word came first).
@@ -147,15 +91,7 @@ __global__ __launch_bounds__(kGasThreads) void gas_kernel(GasArgs<T> g)
     const double* const tabs[3] = { r.win.tab[0], r.win.tab[1], r.win.tab[2] };
     const size_t g1 = (g.s1 + 3) / 4, stride = static_cast<size_t>(gridDim.x) * kGasThreads;
     GasAcc acc;
-    [[maybe_unused]] auto load4 = [](const T* src, T (&out)[4]) {
-        if constexpr (sizeof(T) == 4) {
-            const float4 q = *reinterpret_cast<const float4*>(src);
-            out[0] = q.x; out[1] = q.y; out[2] = q.z; out[3] = q.w;
-        } else {
-            const double2 a = *reinterpret_cast<const double2*>(src), b = *reinterpret_cast<const double2*>(src + 2);
-            out[0] = a.x; out[1] = a.y; out[2] = b.x; out[3] = b.y;
-        }
-    };
+    auto one = [&](uint32_t i, size_t slot) { gas_one<T, !WINDOW_FIRST>(g, S, tabs, i, slot, acc); };
     for (size_t vb = static_cast<size_t>(blockIdx.x) * kGasThreads; vb < g1; vb += stride) {   // (the same turns for every lane)
         const size_t v = vb + threadIdx.x;
         const size_t base = 4 * v;                        // (v < g1: base + 3 < n_pad, as s1 <= n_pad, a multiple of 4)
@@ -176,37 +112,15 @@ __global__ __launch_bounds__(kGasThreads) void gas_kernel(GasArgs<T> g)
                 }
             }
             if (in) {
-                collide_ids(g.id, base, idx);
+                ids4(g.id, base, idx);
 #pragma unroll
                 for (int l = 0; l < 4; ++l) pend |= ((in >> l & 1u) && fesgas::drawn(r, idx[l])) ? 1u << l : 0u;
             }
         }
-        if constexpr (!COMPACT) {
-            while (pend) {
-                const int l = __ffs(pend) - 1;
-                pend &= pend - 1;
-                const uint32_t i = l == 0 ? idx[0] : l == 1 ? idx[1] : l == 2 ? idx[2] : idx[3];
-                gas_one<T, !WINDOW_FIRST>(g, S, tabs, i, base + l, acc);
-            }
-        } else {
-            __shared__ uint32_t q_id[4 * kGasThreads], q_rel[4 * kGasThreads];
-            __shared__ uint32_t q_n;
-            if (threadIdx.x == 0) q_n = 0;
-            __syncthreads();
-#pragma unroll
-            for (int l = 0; l < 4; ++l)
-                if (pend >> l & 1u) {
-                    const uint32_t at = atomicAdd(&q_n, 1u);         // (at most 1024 per turn: the queue's size)
-                    q_id[at] = idx[l];
-                    q_rel[at] = 4u * threadIdx.x + l;
-                }
-            __syncthreads();
-            const uint32_t total = q_n;
-            for (uint32_t k = threadIdx.x; k < total; k += kGasThreads) gas_one<T, !WINDOW_FIRST>(g, S, tabs, q_id[k], 4 * vb + q_rel[k], acc);
-            __syncthreads();   // (the queue is rewritten by the next turn)
-        }
+        if constexpr (COMPACT) take_queued([&](int l) { return (pend >> l & 1u) != 0; }, idx, vb, one);
+        else take_pending(pend, idx, base, one);
     }
-    gas_tally(acc, g.words);
+    tally_commit(acc, g.words);
 }
 
 } // namespace fes

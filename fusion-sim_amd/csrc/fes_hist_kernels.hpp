@@ -53,7 +53,7 @@ __global__ __launch_bounds__(kHistThreads) void hist_kernel(HistArgs<T> g, unsig
 {
     extern __shared__ unsigned long long hist_shared[];   // LDS: nbins uint32; afterwards (and without LDS) one word per wave
     uint32_t* lds = reinterpret_cast<uint32_t*>(hist_shared);
-    using V = typename Vec16Of<T>::type;
+    using V = typename Vec16<T>::type;
     constexpr int L = 16 / sizeof(T);
     constexpr int N0 = K0 == HIST_V2 ? 3 : 1, N1 = K1 == HIST_V2 ? 3 : (K1 == HIST_PLAIN ? 1 : 0);
     struct Vecs {

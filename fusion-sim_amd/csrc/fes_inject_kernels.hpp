@@ -4,10 +4,9 @@
 //                            of kInjectGroup = FOUR slots, a group per lane and turn) over the slots [n, n + count) of the
 //                            live set: slot n + l holds sequence number first + l and the id id0 + l.  A lane generates the
 //                            state of its slots (fesinj::state_of: the loader's functions), rounds it to T, and stores the six
-//                            state words and the id: a group that lies whole inside the range with 16-byte stores (one per
-//                            array in float, two in double, one for the ids), the groups at the two edges of the range — n
-//                            need not be a multiple of four — with scalar stores of the new slots only: no slot below n or
-//                            from n + count on is written.  Each lane adds the fixed-point terms of the STORED velocities to the
+//                            state words and the id with store4_masked (fes_pass.hpp): the groups at the two edges of the
+//                            range — n need not be a multiple of four — take scalar stores of the new slots only: no slot below
+//                            n or from n + count on is written.  Each lane adds the fixed-point terms of the STORED velocities to the
 //                            energy diagnostics' accumulator (diag_add: its 128-bit sums, its out-of-range rule), held in
 //                            registers across the loop; the workgroup's are combined in the diagnostics' fixed order
 //                            (diag_acc_combine) into one partial row.  The kind is a template parameter: the volume instance
@@ -60,7 +59,7 @@ __global__ __launch_bounds__(kInjectThreads) void inject_kernel(InjectArgs<T> g)
         uint32_t in = 0;
 #pragma unroll
         for (int l = 0; l < kInjectGroup; ++l) in |= (base + l >= g.s0 && base + l < g.s1) ? 1u << l : 0u;
-        T st[kInjectGroup][6];
+        T st[6][kInjectGroup];
         uint32_t ids[kInjectGroup];
 #pragma unroll
         for (int l = 0; l < kInjectGroup; ++l) {
@@ -71,32 +70,13 @@ __global__ __launch_bounds__(kInjectThreads) void inject_kernel(InjectArgs<T> g)
             fesinj::state_of(q, g.first + off, p, w);
 #pragma unroll
             for (int a = 0; a < 3; ++a) {
-                st[l][a] = wrap01(static_cast<T>(p[a]));
-                st[l][3 + a] = static_cast<T>(w[a]);
+                st[a][l] = wrap01(static_cast<T>(p[a]));
+                st[3 + a][l] = static_cast<T>(w[a]);
             }
-            if (in >> l & 1u) diag_add(acc, static_cast<double>(st[l][3]), static_cast<double>(st[l][4]), static_cast<double>(st[l][5]));
+            if (in >> l & 1u) diag_add(acc, static_cast<double>(st[3][l]), static_cast<double>(st[4][l]), static_cast<double>(st[5][l]));
         }
-        if (in == 0xFu) {
-#pragma unroll
-            for (int c = 0; c < 6; ++c) {
-                T* dst = g.slab + c * g.n_pad + base;
-                if constexpr (sizeof(T) == 4) {
-                    *reinterpret_cast<float4*>(dst) = make_float4(st[0][c], st[1][c], st[2][c], st[3][c]);
-                } else {
-                    *reinterpret_cast<double2*>(dst) = make_double2(st[0][c], st[1][c]);
-                    *reinterpret_cast<double2*>(dst + 2) = make_double2(st[2][c], st[3][c]);
-                }
-            }
-            *reinterpret_cast<uint4*>(g.id + base) = make_uint4(ids[0], ids[1], ids[2], ids[3]);
-        } else {
-#pragma unroll
-            for (int l = 0; l < kInjectGroup; ++l)
-                if (in >> l & 1u) {
-#pragma unroll
-                    for (int c = 0; c < 6; ++c) g.slab[c * g.n_pad + base + l] = st[l][c];
-                    g.id[base + l] = ids[l];
-                }
-        }
+        store4_masked<6>(g.slab + base, g.n_pad, in, st);
+        store4_masked<1>(g.id + base, 0, in, &ids);
     }
     diag_acc_combine(acc);
     if (threadIdx.x == 0) diag_store_acc(acc, g.partial + static_cast<size_t>(blockIdx.x) * kDiagWords);

@@ -2,11 +2,11 @@
 // fes_load_core.hpp).
 //   load_slots_kernel<T, POS, VEL>  an undecomposed handle.  A streaming pass in the launch shape of hist_kernel and
 //       select_kernel (fixed grid, grid-stride) over groups of FOUR slots: a lane takes the four particle indices from
-//       id[slot] (one 16-byte load) or, while the species is in the caller's order, the slot numbers; generates the state of
-//       each index inside [first, first + count); and stores it into the slots.  A group whose four slots are all loaded
-//       is stored with 16-byte stores (one per array in float, two in double); a group at the edge of the range, the tail
-//       of 1-3 slots and a group of a permuted species that holds other particles take scalar stores of the loaded slots
-//       only: every other particle keeps its bits.  Identity order: only the groups of [first, first + count) are visited.
+//       id[slot] or, while the species is in the caller's order, the slot numbers (ids4, fes_pass.hpp); generates the state
+//       of each index inside [first, first + count); and stores it into the slots: a group whose four slots are all loaded
+//       with store4, a group at the edge of the range, the tail of 1-3 slots and a group of a permuted species that holds
+//       other particles with scalar stores of the loaded slots only: every other particle keeps its bits.  Identity order:
+//       only the groups of [first, first + count) are visited.
 //   load_keep_kernel<T, WRITE>      a rank of a decomposition, over the INDICES [first, first + count) in chunks of
 //       kLoadChunk (one index per lane, one chunk per workgroup and turn).  WRITE = false generates the position only and
 //       counts per chunk the particles whose cell plane (axis() of the stored z: cells3_kernel, the migration) lies in the
@@ -29,6 +29,7 @@
 #include "fes_hist_kernels.hpp"
 #include "fes_load_profile_core.hpp"
 #include "fes_load_radial_core.hpp"
+#include "fes_pass.hpp"
 
 namespace fes {
 
@@ -176,13 +177,7 @@ __global__ __launch_bounds__(kLoadThreads) void load_slots_kernel(Args g)
     for (size_t v = g0 + static_cast<size_t>(blockIdx.x) * kLoadThreads + threadIdx.x; v < g1; v += stride) {
         const size_t base = 4 * v;                        // (base + 3 < n_pad: s1 <= n <= n_pad, both multiples of 4 apart)
         uint32_t idx[4];
-        if (g.id) {
-            const uint4 q = *reinterpret_cast<const uint4*>(g.id + base);
-            idx[0] = q.x; idx[1] = q.y; idx[2] = q.z; idx[3] = q.w;
-        } else {
-#pragma unroll
-            for (int l = 0; l < 4; ++l) idx[l] = static_cast<uint32_t>(base + l);
-        }
+        ids4(g.id, base, idx);
         uint32_t in = 0;
 #pragma unroll
         for (int l = 0; l < 4; ++l)
@@ -196,16 +191,12 @@ __global__ __launch_bounds__(kLoadThreads) void load_slots_kernel(Args g)
             else load_state<T, POS, VEL>(g.r, idx[l], st[l]);
         }
         constexpr int C0 = POS ? 0 : 3, C1 = VEL ? 6 : 3;
+        // (not store4_masked per array: the profiled velocity-only instances then hold 179 VGPRs against 150 and lose a wave)
         if (in == 0xFu) {
 #pragma unroll
             for (int c = C0; c < C1; ++c) {
-                T* dst = g.slab + c * g.n_pad + base;
-                if constexpr (sizeof(T) == 4) {
-                    *reinterpret_cast<float4*>(dst) = make_float4(st[0][c], st[1][c], st[2][c], st[3][c]);
-                } else {
-                    *reinterpret_cast<double2*>(dst) = make_double2(st[0][c], st[1][c]);
-                    *reinterpret_cast<double2*>(dst + 2) = make_double2(st[2][c], st[3][c]);
-                }
+                const T col[4] = { st[0][c], st[1][c], st[2][c], st[3][c] };
+                store4(g.slab + c * g.n_pad + base, col);
             }
         } else {
 #pragma unroll

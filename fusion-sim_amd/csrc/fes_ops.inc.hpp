@@ -114,6 +114,21 @@ struct OpsEvery {
     bool operator()(const OpCommon& op) const { return substep % static_cast<uint64_t>(op.every) == 0; }
 };
 
+// the head of a pass's arguments (fes_pass.hpp): the slots [0, n) of `sp` and, while a migration rides on the next push, the
+// arrivals behind them (they follow at tail_first = n: one range, as the flat pass of mom_enqueue).  Returns the pass's grid,
+// at most `blocks` workgroups of kPassThreads lanes with a group of four slots each; 0: no slot, nothing to launch
+template <typename T>
+static unsigned pass_head(const fpic_handle* h, const Species& sp, int blocks, PassArgs<T>& a)
+{
+    a.slab = static_cast<T*>(sp.slab[sp.cur]);
+    a.id = sp.ids_identity ? nullptr : sp.id[sp.cur];
+    a.n_pad = sp.n_pad;
+    a.s1 = std::min(sp.n + sp.tail_count, sp.n_pad);
+    a.dead = h->es->dom ? 1 : 0;
+    const size_t groups = (a.s1 + 3) / 4;
+    return static_cast<unsigned>(std::min<size_t>(blocks, (groups + kPassThreads - 1) / kPassThreads));
+}
+
 static bool ops_registered(const Diag& g)
 {
 #define X(f) || !g.f.ops.empty()

@@ -65,14 +65,14 @@ struct RemoveArgs {
 
 template <typename T, int NA>
 struct RemoveVecs {
-    typename Vec16Of<T>::type a[NA ? NA : 1];
+    typename Vec16<T>::type a[NA ? NA : 1];
     typename SelectIdVec<16 / sizeof(T)>::type id;
 };
 
 template <typename T, int NA>
 __device__ __forceinline__ void remove_load(const RemoveArgs<T>& g, size_t v, RemoveVecs<T, NA>& r)
 {
-    using V = typename Vec16Of<T>::type;
+    using V = typename Vec16<T>::type;
     using IV = typename SelectIdVec<16 / sizeof(T)>::type;
 #pragma unroll
     for (int k = 0; k < NA; ++k) r.a[k] = reinterpret_cast<const V*>(g.src[k])[v];

@@ -53,7 +53,7 @@ struct SelectIdVec<2> { using type = uint2; };
 template <typename T, int NA, bool DELIVER>
 __global__ __launch_bounds__(kSelectThreads) void select_kernel(SelectArgs<T> g, unsigned long long* __restrict__ cursor)
 {
-    using V = typename Vec16Of<T>::type;
+    using V = typename Vec16<T>::type;
     constexpr int L = 16 / sizeof(T);
     using IV = typename SelectIdVec<L>::type;
     struct Vecs {

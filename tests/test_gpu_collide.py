@@ -275,6 +275,37 @@ def test_null_collision(fp, precision):
         assert np.all(np.abs(after["velocity"] - want["v"]) <= value_bound(req, ids, before["velocity"]))
 
 
+# EXCHANGE with the null-collision form, handed out by the wave-shared loop (P_max above 2^-3) and by the LDS queue (inside
+# [2^-8, 2^-3]): 2051 slots are three workgroups' turns, the last group of four partial
+EXCHANGE_NULL = {"loop": dict(nu_tau=0.1, sigma_tau=2.0, g_max=0.15, seed=2028, stream=3, epoch=2, **BACKGROUND),
+                 "queue": dict(nu_tau=0.01, sigma_tau=0.3, g_max=0.15, seed=2029, stream=4, epoch=2, **BACKGROUND)}
+
+
+@pytest.mark.parametrize("form", sorted(EXCHANGE_NULL))
+@pytest.mark.parametrize("precision", PRECISIONS)
+def test_exchange_null_collision_in_both_passes(fp, precision, form):
+    n, ids, kw = 2051, np.arange(2051), EXCHANGE_NULL[form]
+    req = ref.request(ref.EXCHANGE, **kw)
+    lo, hi = compact_range()
+    assert (lo <= req["K"] <= hi) == (form == "queue")
+    sim = filled(fp, precision, n)
+    before = sim.getParticles()
+    want = ref.stored(req, ids, before["velocity"])
+    cand = want["candidate"]
+    x, ux = ref.acceptance(req, ids, want["g"])
+    assert not (np.abs(ux - x)[cand] < 1e-9 * req["x_max"]).any() and not (np.abs(want["g"] - req["g_max"])[cand] < 1e-9 * req["g_max"]).any()
+    assert cand[:1024].any() and cand[1024:2048].any() and 0 < want["clipped"].sum() < want["collided"].sum() < cand.sum() < n
+    got = sim.collide("exchange", **kw)
+    after = sim.getParticles()
+    sim.destroy()
+    assert same_counts(got, want)
+    changed = (after["velocity"] != before["velocity"]).any(axis=1)
+    assert np.array_equal(changed, want["collided"])
+    assert bits(after["velocity"][~changed], before["velocity"][~changed]) and bits(after["position"], before["position"])
+    if precision == "fp64":
+        assert np.all(np.abs(after["velocity"] - want["v"]) <= value_bound(req, ids, before["velocity"]))
+
+
 # ---- 4. independence of the slot: no tolerance
 @pytest.mark.parametrize("precision", PRECISIONS)
 def test_slot_independence(fp, precision):
