@@ -33,6 +33,7 @@
 //   fes_fusion_spectrum.inc.hpp   fusion product spectra: the tally's pairs and yields binned over an energy axis
 //   fes_remove.inc.hpp      absorbing particle sinks: the mark, scan and move passes of one request, the state a removal leaves, renumbering
 //   fes_inject.inc.hpp      particle sources: the capacity a species grows into, the generation pass of one request, the state an injection leaves
+//   fes_ionize.inc.hpp      electron-impact ionisation of a background gas: the deciding pass, the events' ranks, the generation pass, the state an application leaves
 //   fes_mom.inc.hpp         the fluid moment grids: the sweeps of one request, the held planes' places, the ranks' sum
 //   fes_series.inc.hpp      the series: rows of field points and tracer particles, now or into a ring, the ranks' selection
 //   fes_modes.inc.hpp       the modes: Fourier amplitudes of the node fields at chosen wave vectors, now or into a ring, the ranks' sum
@@ -52,6 +53,7 @@
 #include "fes_fusion_spectrum_kernels.hpp"
 #include "fes_remove_kernels.hpp"
 #include "fes_inject_kernels.hpp"
+#include "fes_ionize_kernels.hpp"
 #include "fes_mom_kernels.hpp"
 #include "fes_series_kernels.hpp"
 #include "fes_modes_kernels.hpp"
@@ -382,6 +384,7 @@ namespace {
 #include "fes_fusion_spectrum.inc.hpp"
 #include "fes_remove.inc.hpp"
 #include "fes_inject.inc.hpp"
+#include "fes_ionize.inc.hpp"
 #include "fes_mom.inc.hpp"
 #include "fes_series.inc.hpp"
 #include "fes_modes.inc.hpp"
@@ -399,8 +402,11 @@ namespace {
 //              application waits for one 8-byte count: the host has to learn the new n
 //   inject     the sources, after the sinks: a sink beside a source leaves this sub-step's fresh particles alive, and the rows
 //              below count them.  Nothing is read back (the host knows the new n in advance); one wait per sub-step
+//   ionize     the ionisers, last: a beam injected on this sub-step can ionise on it, and the rows below count the new
+//              electrons and ions.  Each due application waits for one 8-byte count (the events); those that had events
+//              settle once, after the last
 // then every recorder that is due — the energy rows, the series, the modes, which share the counter and nothing else — enqueues
-// its row into its ring.  But for the sinks and sources: no host synchronisation, no collective.  Nothing registered and
+// its row into its ring.  But for the sinks, sources and ionisers: no host synchronisation, no collective.  Nothing registered and
 // recording off: nothing is enqueued.
 static int diag_after_substep(fpic_handle* h)
 {

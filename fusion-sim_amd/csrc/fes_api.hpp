@@ -71,6 +71,11 @@ int inject(fpic_handle* h, const fpic_inject_spec* spec, fpic_inject_result* out
 int inject_register(fpic_handle* h, const fpic_inject_spec* spec, int every, int* index);
 int inject_stats(fpic_handle* h, int index, int scope, fpic_inject_result* out);
 int inject_clear(fpic_handle* h);
+// electron-impact ionisation of a background gas (fes_ionize.inc.hpp)
+int ionize(fpic_handle* h, const fpic_ionize_spec* spec, fpic_ionize_result* out);
+int ionize_register(fpic_handle* h, const fpic_ionize_spec* spec, int every, int* index);
+int ionize_stats(fpic_handle* h, int index, int scope, fpic_ionize_result* out);
+int ionize_clear(fpic_handle* h);
 // binary Coulomb collisions between the species of the box (fes_pair.inc.hpp)
 int pair(fpic_handle* h, const fpic_pair_spec* spec, fpic_pair_result* out);
 int pair_register(fpic_handle* h, const fpic_pair_spec* spec, int every, int* index);

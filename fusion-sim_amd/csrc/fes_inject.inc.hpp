@@ -45,6 +45,23 @@ static int inject_settle(fpic_handle* h)
     return FPIC_OK;
 }
 
+// A species whose live set has just gained `count` particles in the slots [n, n + count) with the ids span + l (a source's
+// generation pass, an ioniser's): the state load_keep leaves after an append — the live set holds the particles in slot order
+// with their ids, the other set's ids are the slot numbers (the next binning writes both anew), nothing binned, no census
+static int species_appended(fpic_handle* h, Species& s, uint64_t span, uint64_t count)
+{
+    if (s.thinned) s.id_span = span + count;   // (not thinned: the ids stay 0 .. n - 1, id_span_of() follows n)
+    s.n += static_cast<size_t>(count);
+    iota3_kernel<<<blocks_for(s.n), 256, 0, h->stream>>>(s.id[s.cur ^ 1], s.n, 0u);
+    HIP_TRY(h, hipGetLastError());
+    s.binned = false;
+    s.census_fresh = s.rebin_pending = s.chunk_census_fresh = false;
+    s.rebin_now = false;
+    s.tail_first = s.tail_count = s.n_after = 0;
+    if (&s == h->es->sp.data()) h->n = s.n;   // (the handle's count is its first species')
+    return FPIC_OK;
+}
+
 // application k (counted from the epoch on) of a checked request: this application's row into row kInjectLast, added to row
 // `total_row` (< 0: to none).  hook: called from the sub-step hook — a request that does not fit is a state error there, and the
 // re-deposit and the wait are the hook's, once (inject_settle); otherwise the call ends settled.  count = 0: nothing is launched,
@@ -86,17 +103,7 @@ static int inject_run(fpic_handle* h, const fpic_inject_spec& spec, uint64_t k, 
     else inject_kernel<T, false><<<grid, kInjectThreads, 0, h->stream>>>(a);
     remove_combine_kernel<<<1, kDiagThreads, 0, h->stream>>>(a.partial, static_cast<int>(grid), rows.row(kInjectLast), total_row < 0 ? nullptr : rows.row(total_row));
     HIP_TRY(h, hipGetLastError());
-    // the state load_keep leaves after an append: the live set holds the particles in slot order with their ids, the other
-    // set's ids are the slot numbers (the next binning writes both anew)
-    if (s.thinned) s.id_span = span + count;   // (not thinned: the ids stay 0 .. n - 1, id_span_of() follows n)
-    s.n = a.s1;
-    iota3_kernel<<<blocks_for(s.n), 256, 0, h->stream>>>(s.id[s.cur ^ 1], s.n, 0u);
-    HIP_TRY(h, hipGetLastError());
-    s.binned = false;
-    s.census_fresh = s.rebin_pending = s.chunk_census_fresh = false;
-    s.rebin_now = false;
-    s.tail_first = s.tail_count = s.n_after = 0;
-    if (&s == st->sp.data()) h->n = s.n;   // (the handle's count is its first species')
+    if (int rc = species_appended(h, s, span, count)) return rc;
     return hook ? FPIC_OK : inject_settle(h);   // (the hook settles once, after the last source that is due)
 }
 

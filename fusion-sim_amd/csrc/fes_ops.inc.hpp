@@ -2,7 +2,7 @@
 // unit (included there before fes_collide.inc.hpp, inside namespace fes).  The types are in fes_state.inc.hpp (OpRows, OpCommon,
 // OpFamily, the list FES_OP_FAMILIES), the checks and the families' messages in fes_ops_core.hpp.
 //
-// Every family (collide, force, gas, pair, fusion, fusion_spectrum, remove, inject) has a call that applies a request now and
+// Every family (collide, force, gas, pair, fusion, fusion_spectrum, remove, inject, ionize) has a call that applies a request now and
 // calls that register it, read its totals and drop the registrations.  Here are the parts that do not depend on the family: the
 // rows (allocation, a row's place, zeroing, the copy back), the registration's checks and its tail, the head of a stats read,
 // the loop of the sub-step hook over the operators that are due, and the question whether anything is registered at all.  A
@@ -52,12 +52,17 @@ inline void OpRows::release()
 }
 
 // a registration after the family's own refusals: the period (a family without one passes 1) and the room
+// (the forms that take the messages themselves serve a family that keeps its own beside the shared table)
+template <typename Op>
+static int ops_check_register(fpic_handle* h, const OpFamily<Op>& f, const fesops::Messages& m, int every)
+{
+    if (const char* why = fesops::check_register(every, static_cast<int>(f.ops.size()), m.max, m.full)) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    return FPIC_OK;
+}
 template <typename Op>
 static int ops_check_register(fpic_handle* h, const OpFamily<Op>& f, int family, int every)
 {
-    const fesops::Messages& m = fesops::messages(family);
-    if (const char* why = fesops::check_register(every, static_cast<int>(f.ops.size()), m.max, m.full)) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
-    return FPIC_OK;
+    return ops_check_register(h, f, fesops::messages(family), every);
 }
 // the tail of a registration: the operator behind the others with nothing applied yet, its place (the row the family has
 // prepared for it) to the caller
@@ -72,18 +77,28 @@ static int ops_push(OpFamily<Op>& f, Op op, int every, int* index)
     return FPIC_OK;
 }
 template <typename Op>
+static int ops_check_index(fpic_handle* h, const OpFamily<Op>& f, const fesops::Messages& m, int index)
+{
+    if (const char* why = fesops::check_index(index, static_cast<int>(f.ops.size()), m.index)) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
+    return FPIC_OK;
+}
+template <typename Op>
 static int ops_check_index(fpic_handle* h, const OpFamily<Op>& f, int family, int index)
 {
-    if (const char* why = fesops::check_index(index, static_cast<int>(f.ops.size()), fesops::messages(family).index)) return fail(h, FPIC_ERR_INVALID_ARG, "%s", why);
-    return FPIC_OK;
+    return ops_check_index(h, f, fesops::messages(family), index);
 }
 // the head of a stats read after the family's own refusals: `out`, then the index, then the scope
 template <typename Op>
-static int ops_stats_head(fpic_handle* h, const OpFamily<Op>& f, int family, int index, int scope, const void* out, bool& collective)
+static int ops_stats_head(fpic_handle* h, const OpFamily<Op>& f, const fesops::Messages& m, int index, int scope, const void* out, bool& collective)
 {
     if (!out) return fail(h, FPIC_ERR_INVALID_ARG, ".out <- Non-optional property is undefined!");
-    if (int rc = ops_check_index(h, f, family, index)) return rc;
+    if (int rc = ops_check_index(h, f, m, index)) return rc;
     return diag_scope(h, scope, collective);
+}
+template <typename Op>
+static int ops_stats_head(fpic_handle* h, const OpFamily<Op>& f, int family, int index, int scope, const void* out, bool& collective)
+{
+    return ops_stats_head(h, f, fesops::messages(family), index, scope, out, collective);
 }
 // (applications in flight keep their rows and tables; a later registration rewrites its own in stream order)
 template <typename Op>

@@ -87,7 +87,9 @@ __device__ __forceinline__ void take_pending(uint32_t pend, const uint32_t (&idx
 // into a queue in LDS (id and slot; LDS atomics give the places) and are then taken densely, one per lane, by as few waves
 // as they fill.  cand(l): is slot l of the lane's group a candidate — asked once per slot, in order, between the queue's
 // first two barriers, so a pass may make its test there (collide_kernel) or hand over bits it has (gas_kernel).  EVERY lane
-// of the workgroup calls it, each turn.  8 KiB of LDS.
+// of the workgroup calls it, each turn.  8 KiB of LDS.  Like take_pending it calls one() at most FOUR times per lane and turn
+// (4 kPassThreads entries over kPassThreads lanes): the ioniser's deciding pass keeps a lane's events of a turn in that many
+// registers (fes_ionize_kernels.hpp, kIonizeKept).
 template <typename C, typename F>
 __device__ __forceinline__ void take_queued(C&& cand, const uint32_t (&idx)[4], size_t vb, F&& one)
 {

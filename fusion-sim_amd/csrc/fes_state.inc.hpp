@@ -112,7 +112,7 @@ struct OpFamily {
 };
 // the families as the members of Diag, in the order in which the sub-step hook runs them (diag_after_substep of fes_api.hip
 // states the order and why): member f has the hook's part f##_after_substep
-#define FES_OP_FAMILIES(X) X(force) X(collide) X(gas) X(pair) X(fusion) X(fspec) X(remove) X(inject)
+#define FES_OP_FAMILIES(X) X(force) X(collide) X(gas) X(pair) X(fusion) X(fspec) X(remove) X(inject) X(ionize)
 
 // what each family's operator keeps of its own, beside OpCommon
 struct CollideOp : OpCommon {          // fes_collide.inc.hpp
@@ -148,6 +148,12 @@ struct RemoveOp : OpCommon {           // fes_remove.inc.hpp: the live particles
 struct InjectOp : OpCommon {           // fes_inject.inc.hpp
     fpic_inject_spec spec;
 };
+struct IonizeOp : OpCommon {           // fes_ionize.inc.hpp: as GasOp
+    fpic_ionize_spec spec;
+    std::vector<double> sigma;
+    const double* dev_sigma;
+    const double* taper[3];
+};
 
 // the diagnostics of a handle: the sub-step counter the recorders share, the recorders and their requests, the buffers of the
 // energy reduction (fes_diag.inc.hpp), of the histograms and of the moments, the ranks' gather
@@ -178,6 +184,7 @@ struct Diag {
     OpFamily<FspecOp> fspec;            // as fusion
     OpFamily<RemoveOp> remove;          // rows of kDiagWords words; behind the totals: the last application, the mark pass's counter, the move pass's partial rows
     OpFamily<InjectOp> inject;          // rows of kDiagWords words; behind the totals: the last application, the generation pass's partial rows
+    OpFamily<IonizeOp> ionize;          // fesion::kWords tally words and the gas operator's table room per row; row MAX_OPS: the application in flight
     // the cell index of fpic_pair, one per side (species_a, species_b): pair_seg[s] = 4 + cells words (zeros, then per cell
     // the count -> the exclusive offset -> the end of the cell's segment), pair_index[s] = the slots by cell; both grow to
     // the largest request.  The fusion tallies and spectra use it too

@@ -1659,6 +1659,30 @@ int fpic_inject_clear(fpic_handle* h)
     BOX_ONLY(h, "fpic_inject_clear");
     return fes::inject_clear(h);
 }
+int fpic_ionize(fpic_handle* h, const fpic_ionize_spec* spec, fpic_ionize_result* out)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_ionize");
+    return fes::ionize(h, spec, out);
+}
+int fpic_ionize_register(fpic_handle* h, const fpic_ionize_spec* spec, int every, int* index)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_ionize_register");
+    return fes::ionize_register(h, spec, every, index);
+}
+int fpic_ionize_stats(fpic_handle* h, int index, int scope, fpic_ionize_result* out)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_ionize_stats");
+    return fes::ionize_stats(h, index, scope, out);
+}
+int fpic_ionize_clear(fpic_handle* h)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_ionize_clear");
+    return fes::ionize_clear(h);
+}
 int fpic_collide_clear(fpic_handle* h)
 {
     CHECK_HANDLE(h);

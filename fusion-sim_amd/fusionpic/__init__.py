@@ -55,6 +55,7 @@ ABI_FUNCTIONS = [
     "fpic_gas", "fpic_gas_register", "fpic_gas_stats", "fpic_gas_clear",
     "fpic_remove", "fpic_remove_register", "fpic_remove_stats", "fpic_remove_clear", "fpic_renumber",
     "fpic_reserve", "fpic_population", "fpic_inject", "fpic_inject_register", "fpic_inject_stats", "fpic_inject_clear",
+    "fpic_ionize", "fpic_ionize_register", "fpic_ionize_stats", "fpic_ionize_clear",
 ]
 
 
@@ -827,6 +828,67 @@ _INJECT_DECOMPOSED = ("%s needs an undecomposed handle: a rank's arrivals ride o
                       "from the capacity it had")
 
 
+IONIZE_MAX_OPS = 8
+IONIZE_SEED = 0x1051E0C0FFEE
+
+
+class IonizeSpec(ctypes.Structure):
+    """mirror of fpic_ionize_spec (include/fusionpic.h)"""
+    _fields_ = [
+        ("species", ctypes.c_int32), ("electron", ctypes.c_int32), ("ion", ctypes.c_int32), ("reserved_i", ctypes.c_int32),
+        ("seed", ctypes.c_uint64), ("stream", ctypes.c_uint32), ("epoch", ctypes.c_uint32),
+        ("density", ctypes.c_double), ("tau", ctypes.c_double), ("g_lo", ctypes.c_double), ("g_hi", ctypes.c_double), ("g_threshold", ctypes.c_double),
+        ("n", ctypes.c_int32), ("reserved_n", ctypes.c_int32), ("sigma", ctypes.POINTER(ctypes.c_double)),
+        ("drift", ctypes.c_double * 3), ("vth", ctypes.c_double * 3),
+        ("lo", ctypes.c_double * 3), ("hi", ctypes.c_double * 3), ("taper_n", ctypes.c_uint32 * 3), ("reserved_u", ctypes.c_uint32),
+        ("taper", ctypes.POINTER(ctypes.c_double) * 3), ("reserved", ctypes.c_double * 4),
+    ]
+
+
+class IonizeGain(ctypes.Structure):
+    """mirror of fpic_ionize_gain"""
+    _fields_ = [("energy_fixed", ctypes.c_uint64 * 2), ("momentum_fixed", (ctypes.c_uint64 * 2) * 3),
+                ("energy", ctypes.c_double), ("momentum", ctypes.c_double * 3), ("charge", ctypes.c_double)]
+
+
+class IonizeResult(ctypes.Structure):
+    """mirror of fpic_ionize_result"""
+    _fields_ = [("applications", ctypes.c_uint64), ("candidates", ctypes.c_uint64), ("below", ctypes.c_uint64), ("above", ctypes.c_uint64),
+                ("ionised", ctypes.c_uint64), ("primary", IonizeGain), ("electron", IonizeGain), ("ion", IonizeGain)]
+
+
+def _ionize_spec(tau_default, L, species=0, electron=None, ion=None, g_threshold=None, density=None, tau=None, sigma=None, g_lo=None, g_hi=None,
+                 drift=0, vth=0, lo=None, hi=None, taper=(None, None, None), seed=IONIZE_SEED, stream=0, epoch=0):
+    """IonizeSpec of an ionisation request, and the arrays its table pointers point into (keep them until the call has
+    returned).  species: the projectile; electron (None: the projectile species), ion: the species that receive the secondary
+    and the ion; g_threshold (units of c): sqrt(2 E_ion / (m c^2)) of the projectile.  The rest as _gas_spec.  Only what the
+    structure cannot carry is refused here; the library checks the rest."""
+    g, keep = _gas_spec(tau_default, L, GAS_EXCHANGE, species, density, tau, sigma, g_lo, g_hi, drift, vth, None, lo, hi, taper, seed, stream, epoch)
+    s = IonizeSpec()
+    s.species = g.species
+    s.electron = s.species if electron is None else _whole("electron", electron, 32, signed=True)
+    if ion is None:
+        raise FusionPicError(-1, ".ion <- Non-optional property is undefined!")
+    s.ion = _whole("ion", ion, 32, signed=True)
+    s.g_threshold = _real_given("g_threshold", g_threshold)
+    for name in ("seed", "stream", "epoch", "density", "tau", "g_lo", "g_hi", "n", "sigma"):
+        setattr(s, name, getattr(g, name))
+    for a in range(3):
+        s.drift[a], s.vth[a], s.lo[a], s.hi[a], s.taper_n[a], s.taper[a] = g.drift[a], g.vth[a], g.lo[a], g.hi[a], g.taper_n[a], g.taper[a]
+    return s, keep
+
+
+def _ionize_dict(r):
+    """the counts, and per group (primary: the projectile species; electron, ion: the targets) what the species gained:
+    energy_fixed and momentum_fixed as Python integers (the 128-bit two's complement sums, units of 2^-80)"""
+    out = {k: int(getattr(r, k)) for k in ("applications", "candidates", "below", "above", "ionised")}
+    for name in ("primary", "electron", "ion"):
+        g = getattr(r, name)
+        out[name] = {"energy_fixed": _force_signed(g.energy_fixed), "momentum_fixed": [_force_signed(g.momentum_fixed[a]) for a in range(3)],
+                     "energy": float(g.energy), "momentum": [float(g.momentum[a]) for a in range(3)], "charge": float(g.charge)}
+    return out
+
+
 PAIR_MAX_OPS = 8
 PAIR_CELL_MAX = 2048
 PAIR_SEED = 0x7A1C12ABE
@@ -1272,6 +1334,10 @@ def load_library(path=None):
     lib.fpic_inject_register.argtypes = [vp, ctypes.POINTER(InjectSpec), ci, ctypes.POINTER(ctypes.c_int)]
     lib.fpic_inject_stats.argtypes = [vp, ci, ci, ctypes.POINTER(InjectResult)]
     lib.fpic_inject_clear.argtypes = [vp]
+    lib.fpic_ionize.argtypes = [vp, ctypes.POINTER(IonizeSpec), ctypes.POINTER(IonizeResult)]
+    lib.fpic_ionize_register.argtypes = [vp, ctypes.POINTER(IonizeSpec), ci, ctypes.POINTER(ctypes.c_int)]
+    lib.fpic_ionize_stats.argtypes = [vp, ci, ci, ctypes.POINTER(IonizeResult)]
+    lib.fpic_ionize_clear.argtypes = [vp]
     lib.fpic_pair.argtypes = [vp, ctypes.POINTER(PairSpec), ctypes.POINTER(PairResult)]
     lib.fpic_pair_register.argtypes = [vp, ctypes.POINTER(PairSpec), ci, ctypes.POINTER(ctypes.c_int)]
     lib.fpic_pair_stats.argtypes = [vp, ci, ci, ctypes.POINTER(PairResult)]
@@ -1671,6 +1737,47 @@ class CylindricalParticlePusher:
     def clearInjections(self):
         """drops every registered source (fpic_inject_clear)"""
         self._check(self._lib.fpic_inject_clear(self._h))
+
+    # ---- electron-impact ionisation of a background gas: an event leaves a new electron and a new ion (fpic_ionize*)
+    def _ionize_refresh(self, s):
+        for k in {int(s.species), int(s.electron), int(s.ion)}:
+            self.population(k)
+
+    def ionize(self, **request):
+        """One application, now, of electron-impact ionisation of a background gas (fpic_ionize; an (r,z) handle and a
+        decomposed handle are refused).  species= the projectile, electron= (default: the projectile species) and ion= the
+        species that receive the new particles, g_threshold= (units of c) sqrt(2 E_ion / (m c^2)); density=, tau=, sigma=,
+        g_lo=, g_hi= (g_lo >= g_threshold), drift=, vth=, lo=, hi=, taper=, seed=, stream=, epoch= as collideGas().  The
+        targets need the room: reserve() makes it, and an application that does not fit changes nothing.  Returns
+        {applications, candidates, below, above, ionised, primary, electron, ion}, each group {energy_fixed, momentum_fixed
+        (exact integers, units of 2**-80), energy (J), momentum (kg m/s), charge (C)}: what the species gained."""
+        s, keep = _ionize_spec(float(self.spec["dt"]), self._box_lengths(), **request)
+        out = IonizeResult()
+        self._check(self._lib.fpic_ionize(self._h, ctypes.byref(s), ctypes.byref(out)))
+        del keep
+        self._ionize_refresh(s)
+        return _ionize_dict(out)
+
+    def ionizeEvery(self, every, **request):
+        """Registers an ioniser (see ionize) to run at the end of every `every`-th sub-step, last among the operators and
+        before the recorders, with epoch = the sub-step number + `epoch`; tau defaults to every * dt.  Returns the ioniser's
+        index (fpic_ionize_register).  population() reads the counts it has changed."""
+        every = _every_arg(every)
+        s, keep = _ionize_spec(every * float(self.spec["dt"]), self._box_lengths(), **request)
+        index = ctypes.c_int(-1)
+        self._check(self._lib.fpic_ionize_register(self._h, ctypes.byref(s), every, ctypes.byref(index)))
+        del keep
+        return index.value
+
+    def ionizeStats(self, index, scope="global"):
+        """the totals of a registered ioniser since its registration (fpic_ionize_stats)"""
+        out = IonizeResult()
+        self._check(self._lib.fpic_ionize_stats(self._h, int(index), _scope_code(scope), ctypes.byref(out)))
+        return _ionize_dict(out)
+
+    def clearIonization(self):
+        """drops every registered ioniser (fpic_ionize_clear); other operators stay"""
+        self._check(self._lib.fpic_ionize_clear(self._h))
 
     # ---- the loader: a population generated on the device (fpic_load)
     def _box_lengths(self):
@@ -2286,6 +2393,11 @@ class ElectrostaticBoxPusher:
     injectEvery = CylindricalParticlePusher.injectEvery
     injectStats = CylindricalParticlePusher.injectStats
     clearInjections = CylindricalParticlePusher.clearInjections
+    _ionize_refresh = CylindricalParticlePusher._ionize_refresh
+    ionize = CylindricalParticlePusher.ionize
+    ionizeEvery = CylindricalParticlePusher.ionizeEvery
+    ionizeStats = CylindricalParticlePusher.ionizeStats
+    clearIonization = CylindricalParticlePusher.clearIonization
     collidePair = CylindricalParticlePusher.collidePair
     collidePairEvery = CylindricalParticlePusher.collidePairEvery
     pairStats = CylindricalParticlePusher.pairStats
@@ -2496,6 +2608,22 @@ class BoxGroup:
     def reserve(self, species=0, capacity=0):
         """refused, see inject"""
         raise FusionPicError(-5, _INJECT_DECOMPOSED % "reserve")
+
+    def ionize(self, **request):
+        """refused (FPIC_ERR_STATE), as by every member, for the sources' reason: an ioniser appends particles"""
+        raise FusionPicError(-5, _INJECT_DECOMPOSED % "ionize")
+
+    def ionizeEvery(self, every, **request):
+        """refused, see ionize"""
+        raise FusionPicError(-5, _INJECT_DECOMPOSED % "ionizeEvery")
+
+    def ionizeStats(self, index, scope="global"):
+        """refused, see ionize"""
+        raise FusionPicError(-5, _INJECT_DECOMPOSED % "ionizeStats")
+
+    def clearIonization(self):
+        """refused, see ionize"""
+        raise FusionPicError(-5, _INJECT_DECOMPOSED % "clearIonization")
 
     def collidePair(self, a=0, b=None, **request):
         """refused (FPIC_ERR_STATE), as by every member: between two migrations the particles of a cell can sit on two

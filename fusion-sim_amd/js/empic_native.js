@@ -684,6 +684,39 @@ function makeBox(spec, lib) {
         return lib.gasStats(h, index, scopeOf(scope));
     };
     out.clearGas = function () { lib.clearGas(h); };
+    // electron-impact ionisation of a background gas (fpic_ionize*).  request = collideGas's without kind and massRatio, plus
+    // { species (the projectile), electron (default: species), ion, gThreshold (units of c; gLo >= gThreshold) }.  ionize ->
+    // { applications, candidates, below, above, ionised, primary, electron, ion }, each group { energyFixed, momentumFixed
+    // (BigInt, units of 2^-80 c^2 and c: what the species gained), energy (J), momentum (kg m/s), charge (C) };
+    // ionizeEvery(every, request) -> the ioniser's index (it runs last among the operators); ionizeStats(index, scope) -> its
+    // totals; clearIonization() drops every ioniser.  The targets need the room: reserve() first
+    const ionizeArgs = function (request, tauDefault) {
+        if (request === null || typeof request !== 'object' || Array.isArray(request)) throw new TypeError('.request <- expected { species, electron, ion, gThreshold, density, tau, sigma, gLo, gHi, drift, vth, lo, hi, taper, seed, stream, epoch }');
+        const given = (v) => v !== undefined && v !== null;
+        const a = gasArgs(Object.assign({}, request, { kind: 0, massRatio: 0, seed: given(request.seed) ? request.seed : 0x1051E0C0FFEE }), tauDefault);
+        const target = function (name, v) {
+            if (!Number.isInteger(v) || v < -0x80000000 || v > 0x7fffffff) throw new RangeError('.' + name + ' <- expected an integer within its field');
+            return v;
+        };
+        if (typeof request.gThreshold !== 'number') throw new RangeError('.gThreshold <- expected a number');
+        a.push(Float64Array.from([target('electron', given(request.electron) ? request.electron : a[0]), target('ion', request.ion), request.gThreshold]));
+        return a;
+    };
+    out.ionize = function (request) {
+        const a = ionizeArgs(request, spec.dt), r = lib.ionize(h, a[0], a[1], a[2], a[3], a[4]);
+        live(a[0]); live(a[4][0]); live(a[4][1]);
+        return r;
+    };
+    out.ionizeEvery = function (every, request) {
+        if (!Number.isInteger(every) || every < -0x80000000 || every > 0x7fffffff) throw new RangeError('.every <- expected a 32-bit integer');
+        const a = ionizeArgs(request, every * spec.dt);
+        return lib.ionizeEvery(h, a[0], a[1], a[2], a[3], a[4], every);
+    };
+    out.ionizeStats = function (index, scope) {
+        if (!Number.isInteger(index) || index < -0x80000000 || index > 0x7fffffff) throw new RangeError('.index <- expected a 32-bit integer');
+        return lib.ionizeStats(h, index, scopeOf(scope));
+    };
+    out.clearIonization = function () { lib.clearIonization(h); };
     // binary Coulomb collisions between the species of the box (Takizuka-Abe; fpic_pair*).  request = { a, b (default a: like
     // particles), logLambda, tau (s; default the sub-step dt, every * dt for collidePairEvery), seed (an integer up to 2^53 or a
     // BigInt up to 2^64), stream, epoch }.  collidePair -> { applications, pairs, strong, cells, overfullCells,

@@ -1574,6 +1574,111 @@ static napi_value n_clear_injections(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* ---- electron-impact ionisation of a background gas (fpic_ionize*) */
+
+/* the request of ionize / ionizeEvery: species (the projectile), words, reals, tables as collideGas takes them (kind 0, massRatio
+ * 0), extra: Float64Array [electron, ion, g_threshold] */
+static int get_ionize_spec(napi_env env, const napi_value* argv, fpic_ionize_spec* s)
+{
+    int sp;
+    fpic_gas_spec g;
+    if (!get_species(env, argv[1], &sp) || !get_gas_spec(env, sp, argv[2], argv[3], argv[4], &g)) return 0;
+    napi_typedarray_type te; void* pe; size_t le;
+    if (!get_typed(env, argv[5], &te, &pe, &le)) return 0;
+    if (!pe || te != napi_float64_array) { napi_throw_type_error(env, NULL, ".request <- expected a Float64Array of the targets and the threshold"); return 0; }
+    if (!check_len(env, "extra", le, 3)) return 0;
+    const double* e = (const double*)pe;
+    for (int k = 0; k < 2; ++k)
+        if (!(e[k] >= -2147483648.0 && e[k] <= 2147483647.0) || e[k] != (double)(int32_t)e[k]) {
+            napi_throw_range_error(env, NULL, ".request <- electron and ion must be 32-bit integers");
+            return 0;
+        }
+    memset(s, 0, sizeof *s);
+    s->species = g.species;
+    s->electron = (int32_t)e[0];
+    s->ion = (int32_t)e[1];
+    s->g_threshold = e[2];
+    s->seed = g.seed; s->stream = g.stream; s->epoch = g.epoch;
+    s->density = g.density; s->tau = g.tau; s->g_lo = g.g_lo; s->g_hi = g.g_hi;
+    s->n = g.n; s->sigma = g.sigma;
+    for (int a = 0; a < 3; ++a) {
+        s->drift[a] = g.drift[a]; s->vth[a] = g.vth[a]; s->lo[a] = g.lo[a]; s->hi[a] = g.hi[a];
+        s->taper_n[a] = g.taper_n[a]; s->taper[a] = g.taper[a];
+    }
+    return 1;
+}
+
+/* { applications, candidates, below, above, ionised, primary, electron, ion }, each group { energyFixed, momentumFixed, energy,
+ * momentum, charge } */
+static napi_value ionize_object(napi_env env, const fpic_ionize_result* c)
+{
+    const char* names[5] = { "applications", "candidates", "below", "above", "ionised" };
+    const uint64_t counts[5] = { c->applications, c->candidates, c->below, c->above, c->ionised };
+    const fpic_ionize_gain* gains[3] = { &c->primary, &c->electron, &c->ion };
+    const char* groups[3] = { "primary", "electron", "ion" };
+    napi_value o, v;
+    NAPI_OK(env, napi_create_object(env, &o));
+    for (int k = 0; k < 5; ++k) {
+        NAPI_OK(env, napi_create_double(env, (double)counts[k], &v));
+        NAPI_OK(env, napi_set_named_property(env, o, names[k], v));
+    }
+    for (int k = 0; k < 3; ++k) {
+        v = tally_object(env, 0, NULL, NULL, gains[k]->energy_fixed, gains[k]->momentum_fixed, gains[k]->energy, gains[k]->momentum, gains[k]->charge);
+        if (!v) return NULL;
+        NAPI_OK(env, napi_set_named_property(env, o, groups[k], v));
+    }
+    return o;
+}
+
+/* ionize(h, species, words, reals, tables, extra) -> the result */
+static napi_value n_ionize(napi_env env, napi_callback_info info)
+{
+    napi_value argv[6]; fpic_handle* h;
+    fpic_ionize_spec s;
+    if (!get_args(env, info, 6, argv, &h) || !get_ionize_spec(env, argv, &s)) return NULL;
+    fpic_ionize_result c;
+    memset(&c, 0, sizeof c);
+    if (fpic_ionize(h, &s, &c) != FPIC_OK) return throw_fpic(env, h);
+    (void)live_count(h, s.electron);          /* (the targets have grown: the caller-order length checks ask the library) */
+    (void)live_count(h, s.ion);
+    return ionize_object(env, &c);
+}
+
+/* ionizeEvery(h, species, words, reals, tables, extra, every) -> the ioniser's index */
+static napi_value n_ionize_every(napi_env env, napi_callback_info info)
+{
+    napi_value argv[7]; fpic_handle* h; double every;
+    fpic_ionize_spec s;
+    if (!get_args(env, info, 7, argv, &h) || !get_ionize_spec(env, argv, &s) || !get_double(env, argv[6], &every)) return NULL;
+    if (!(every >= -2147483648.0 && every <= 2147483647.0) || every != (double)(int)every) { napi_throw_range_error(env, NULL, ".every <- must be a 32-bit integer"); return NULL; }
+    int index = -1;
+    if (fpic_ionize_register(h, &s, (int)every, &index) != FPIC_OK) return throw_fpic(env, h);
+    napi_value v;
+    NAPI_OK(env, napi_create_int32(env, index, &v));
+    return v;
+}
+
+/* ionizeStats(h, index, scope) -> as ionize */
+static napi_value n_ionize_stats(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3]; fpic_handle* h; double index; int scope;
+    if (!get_args(env, info, 3, argv, &h) || !get_double(env, argv[1], &index) || !get_scope(env, argv[2], &scope)) return NULL;
+    if (!(index >= -2147483648.0 && index <= 2147483647.0) || index != (double)(int)index) { napi_throw_range_error(env, NULL, ".index <- must be a 32-bit integer"); return NULL; }
+    fpic_ionize_result c;
+    memset(&c, 0, sizeof c);
+    if (fpic_ionize_stats(h, (int)index, scope, &c) != FPIC_OK) return throw_fpic(env, h);
+    return ionize_object(env, &c);
+}
+
+/* clearIonization(h) */
+static napi_value n_clear_ionization(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1]; fpic_handle* h;
+    if (!get_args(env, info, 1, argv, &h)) return NULL;
+    if (fpic_ionize_clear(h) != FPIC_OK) return throw_fpic(env, h);
+    return undefined(env);
+}
+
 /* reserve(h, species, capacity) -> the capacity the species has now */
 static napi_value n_reserve(napi_env env, napi_callback_info info)
 {
@@ -2209,6 +2314,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "remove", n_remove }, { "removeEvery", n_remove_every }, { "removeStats", n_remove_stats }, { "clearRemovals", n_clear_removals }, { "renumber", n_renumber },
         { "inject", n_inject }, { "injectEvery", n_inject_every }, { "injectStats", n_inject_stats }, { "clearInjections", n_clear_injections },
         { "reserve", n_reserve }, { "population", n_population },
+        { "ionize", n_ionize }, { "ionizeEvery", n_ionize_every }, { "ionizeStats", n_ionize_stats }, { "clearIonization", n_clear_ionization },
         { "collidePair", n_collide_pair }, { "collidePairEvery", n_collide_pair_every }, { "pairStats", n_pair_stats }, { "clearPairs", n_clear_pairs },
         { "fusionYield", n_fusion_yield }, { "fusionYieldEvery", n_fusion_yield_every }, { "fusionStats", n_fusion_stats }, { "fusionGrid", n_fusion_grid }, { "clearFusion", n_clear_fusion },
         { "fusionSpectrum", n_fusion_spectrum }, { "fusionSpectrumEvery", n_fusion_spectrum_every }, { "fusionSpectrumRead", n_fusion_spectrum_read }, { "clearFusionSpectra", n_clear_fusion_spectra },

@@ -1456,6 +1456,97 @@ int fpic_inject_register(fpic_handle* h, const fpic_inject_spec* spec, int every
 int fpic_inject_stats(fpic_handle* h, int index, int scope, fpic_inject_result* out);
 int fpic_inject_clear(fpic_handle* h);
 
+/* ---- CART3D electron-impact ionisation of a background gas: a projectile species (the electrons) collides with the gas of
+ * fpic_gas — a window of the box, a separable density profile, a cross-section tabulated over the relative speed — and every
+ * collision is an EVENT that leaves a new electron and a new ion behind, on the device: a gas puff, a breakdown, a beam that
+ * strikes a neutral target, a cold edge layer.  A source and a sink's bookkeeping coupled per event; undecomposed handles
+ * only.  What happens to projectile i (the id the box carries) depends on the request, the epoch, the ids and the stored
+ * state alone — not on the slots, the binning or the order any atomic took.  All arithmetic is double, every operation
+ * rounded once; p is the stored position in box fractions, v the stored velocity in units of c, T the handle's precision.
+ *   request    species (the projectile), seed, stream, epoch, density, tau, g_lo, g_hi, n, sigma, drift, vth, lo, hi, taper_n,
+ *              taper mean what they mean to fpic_gas (there is no kind and no mass_ratio).  electron: the species that
+ *              receives the secondary, which may be the projectile species itself; ion: the species that receives the ion,
+ *              different from both; g_threshold (units of c): g_threshold^2 = 2 E_ion / (m c^2) of the projectile, >= 0 and
+ *              finite, and g_lo >= g_threshold: the table starts at or above the threshold, so an event always has energy
+ *              to share.
+ *   words      W(b) = Philox4x32-10(counter (i, epoch, stream, 0x1051E0 + b), key (seed_lo, seed_hi)): a tag of its own
+ *              beside 0x10AD, 0xC0110/1, 0xC0120.., 0xF0510 and 0x6A500.  W(0) = (w0, w1, w2, w3): candidate, acceptance,
+ *              the two direction words of the primary; W(1): the partner's normals; W(2) = (r0, r1, r2, .): the energy
+ *              share and the two direction words of the secondary (the fourth word is unused).
+ *   candidate, partner, table, acceptance   fpic_gas's, operation for operation, on these words: the window and (uint64) w0 <
+ *              K; vb[a] = drift[a] + vth[a] n[a], d = v - vb, g = sqrt((d0 d0 + d1 d1) + d2 d2); g < g_lo counted `below`,
+ *              g >= g_hi (or NaN) `above`; the lookup with its hold, the tapers, x = min(((column rho) sigma) g, x_max), u =
+ *              (w1 + 0.5) 2^-32; an EVENT iff u x_max < x.
+ *   outcome    gp2 = g g - g_threshold g_threshold; r = (r0 + 0.5) 2^-32; a1 = r gp2; a2 = gp2 - a1; g1 = sqrt(a1), g2 =
+ *              sqrt(a2); n1 = fpic_gas ELASTIC's nhat on (w2, w3), n2 the same formula on (r1, r2);
+ *              primary v'[a] = vb[a] + g1 n1[a]; secondary vs[a] = vb[a] + g2 n2[a]; ion vi[a] = vb[a].
+ *              The gas atom is heavy: it keeps its velocity, and the two electrons share g^2 - g_threshold^2 in its frame,
+ *              isotropically and with a uniform share.  The RECOIL of the ion IS NEGLECTED (momentum is not conserved by
+ *              m_e / m_i of the electrons' change; the tallies below say exactly what each species gained).  Each velocity is
+ *              cast to T when stored.  The secondary and the ion take the primary's stored position, bit for bit.  A
+ *              projectile without an event keeps every bit; positions of existing particles are never written.
+ *   placement  the events of one application in ascending id of their primary: event number l gives the electron in slot
+ *              n_e + l with id (id span of `electron`) + l, and the ion in slot n_i + l with id (id span of `ion`) + l, n
+ *              and the id spans those before the application.  With electron == species only the old [0, n) is scanned.  A
+ *              species that is not thinned stays not thinned; a thinned one stays thinned and its id span grows
+ *              (fpic_inject's rule).
+ *   fit        with M events: n + M beyond either target's capacity, or an id span beyond 2^32 - 1, refuses the
+ *              application and NOTHING has changed — no velocity, no slot, no tally: fpic_ionize returns
+ *              FPIC_ERR_INVALID_ARG (call fpic_reserve first), a registered application makes the step return FPIC_ERR_STATE.
+ * The result: applications, candidates, below, above, ionised (= M); primary: the projectile species' gains, fpic_gas's
+ * before/after terms of the stored velocities of the primaries; electron, ion: what each target gained, fpic_inject's terms
+ * of the STORED velocities of the new particles, and charge = ionised x the species' charge x macro_weight (primary.charge
+ * is 0).  Sums are exact, in the fixed point of the energy diagnostics (units of 2^-80, 128-bit two's complement, low word
+ * first); a term outside its range adds nothing and makes its double NaN.
+ * fpic_ionize applies the request now (synchronous) and settles itself; K = 0 launches nothing and returns zeros.
+ * fpic_ionize_register makes it run at the end of every sub-step with substep % every == 0, LAST among the operators — after
+ * the sources, before the recorders: a beam injected on a sub-step can ionise on it, and the recorded rows count the new
+ * particles —, in registration order, with epoch (uint32)(substep + spec.epoch); at most FPIC_IONIZE_MAX_OPS ionisers.  The
+ * tables are copied at the call.  A due application reads ONE 8-byte count back (the events: the host has to learn the new
+ * n) and is counted once it has succeeded.  fpic_ionize_stats reads the totals since registration, fpic_ionize_clear drops
+ * every ioniser (other operators stay).  Registrations are not part of a checkpoint; fpic_renumber is refused while one exists.
+ * What an application leaves.  M = 0: nothing changes, nothing is re-binned.  Else the projectile species has new velocities
+ * only and keeps its binning (unless it is also the electron target); each target is as fpic_inject leaves one (n raised,
+ * nothing binned: the next sub-step bins the whole species).  Electrostatic solver with ready fields: the call — or the
+ * hook, once per sub-step after the last ioniser due — deposits and solves again.  Full EM: E, B and the readiness stay; an
+ * electron and an ion of opposite charge at one position add no net charge.
+ * Refused (FPIC_ERR_INVALID_ARG): a null spec, everything fpic_gas refuses of the shared fields, an electron or ion the
+ * handle does not have, ion equal to species or electron, a g_threshold that is negative or not finite, g_lo < g_threshold,
+ * a reserved word that is not zero, every below 1, a ninth registration, an index outside the registered ionisers, a null
+ * out of fpic_ionize_stats; FPIC_ERR_STATE: a handle that is not CART3D; a decomposed handle (all four calls). */
+#define FPIC_IONIZE_MAX_OPS 8
+typedef struct fpic_ionize_spec {
+    int32_t  species, electron;    /* the projectile; the species that receives the secondary (may equal species) */
+    int32_t  ion, reserved_i;      /* the species that receives the ion (differs from both); zero */
+    uint64_t seed;
+    uint32_t stream, epoch;
+    double   density;              /* m^-3, as fpic_gas_spec */
+    double   tau;                  /* s */
+    double   g_lo, g_hi;           /* units of c; g_lo >= g_threshold */
+    double   g_threshold;          /* units of c: sqrt(2 E_ion / (m c^2)) of the projectile; >= 0 and finite */
+    int32_t  n, reserved_n;        /* table entries, 2 .. FPIC_GAS_TABLE_MAX; zero */
+    const double* sigma;           /* n ionisation cross-sections, m^2 */
+    double   drift[3], vth[3];     /* the gas, units of c; vth >= 0 */
+    double   lo[3], hi[3];         /* the window, metres */
+    uint32_t taper_n[3], reserved_u;   /* nodes, 0 = no table, else 2 .. FPIC_GAS_TAPER_MAX; zero */
+    const double* taper[3];
+    double   reserved[4];          /* zero */
+} fpic_ionize_spec;
+typedef struct fpic_ionize_gain {
+    uint64_t energy_fixed[2];      /* low word, high word */
+    uint64_t momentum_fixed[3][2];
+    double   energy, momentum[3];  /* J; kg m/s: what the species gained */
+    double   charge;               /* C */
+} fpic_ionize_gain;
+typedef struct fpic_ionize_result {
+    uint64_t applications, candidates, below, above, ionised;
+    fpic_ionize_gain primary, electron, ion;
+} fpic_ionize_result;
+int fpic_ionize(fpic_handle* h, const fpic_ionize_spec* spec, fpic_ionize_result* out);
+int fpic_ionize_register(fpic_handle* h, const fpic_ionize_spec* spec, int every, int* index);
+int fpic_ionize_stats(fpic_handle* h, int index, int scope, fpic_ionize_result* out);
+int fpic_ionize_clear(fpic_handle* h);
+
 int fpic_sync(fpic_handle* h);
 int fpic_profile(fpic_handle* h, int enable);
 int fpic_get_stats(fpic_handle* h, fpic_stats* out);
