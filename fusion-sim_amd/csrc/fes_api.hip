@@ -34,6 +34,7 @@
 //   fes_remove.inc.hpp      absorbing particle sinks: the mark, scan and move passes of one request, the state a removal leaves, renumbering
 //   fes_inject.inc.hpp      particle sources: the capacity a species grows into, the generation pass of one request, the state an injection leaves
 //   fes_ionize.inc.hpp      electron-impact ionisation of a background gas: the deciding pass, the events' ranks, the generation pass, the state an application leaves
+//   fes_burn.inc.hpp        fusion burn: the deciding pass over fes_pair's cell index, the events' ranks, the generation pass, the compaction of the reactants
 //   fes_mom.inc.hpp         the fluid moment grids: the sweeps of one request, the held planes' places, the ranks' sum
 //   fes_series.inc.hpp      the series: rows of field points and tracer particles, now or into a ring, the ranks' selection
 //   fes_modes.inc.hpp       the modes: Fourier amplitudes of the node fields at chosen wave vectors, now or into a ring, the ranks' sum
@@ -54,6 +55,7 @@
 #include "fes_remove_kernels.hpp"
 #include "fes_inject_kernels.hpp"
 #include "fes_ionize_kernels.hpp"
+#include "fes_burn_kernels.hpp"
 #include "fes_mom_kernels.hpp"
 #include "fes_series_kernels.hpp"
 #include "fes_modes_kernels.hpp"
@@ -385,12 +387,13 @@ namespace {
 #include "fes_remove.inc.hpp"
 #include "fes_inject.inc.hpp"
 #include "fes_ionize.inc.hpp"
+#include "fes_burn.inc.hpp"
 #include "fes_mom.inc.hpp"
 #include "fes_series.inc.hpp"
 #include "fes_modes.inc.hpp"
 
 // The sub-step hook, at the end of every sub-step of every path (substeps(), group_run()).  It counts the sub-step; then the
-// families of registered operators run in the order of FES_OP_FAMILIES (fes_state.inc.hpp), each its operators that are due in
+// families of registered operators run in the order of FES_OP_FAMILIES_ALL (fes_state.inc.hpp), each its operators that are due in
 // registration order (ops_run_due, fes_ops.inc.hpp), a family with nothing registered costing one emptiness test:
 //   force      the prescribed forces that are active: everything below sees the kicked state
 //   collide    the collisions against the background, then
@@ -402,11 +405,13 @@ namespace {
 //              application waits for one 8-byte count: the host has to learn the new n
 //   inject     the sources, after the sinks: a sink beside a source leaves this sub-step's fresh particles alive, and the rows
 //              below count them.  Nothing is read back (the host knows the new n in advance); one wait per sub-step
-//   ionize     the ionisers, last: a beam injected on this sub-step can ionise on it, and the rows below count the new
-//              electrons and ions.  Each due application waits for one 8-byte count (the events); those that had events
-//              settle once, after the last
+//   ionize     the ionisers, after the sources: a beam injected on this sub-step can ionise on it, and the rows below count
+//              the new electrons and ions.  Each due application waits for one 8-byte count (the events); those that had
+//              events settle once, after the last
+//   burn       the burners, last: the fusion tallies above saw the unburnt plasma of this sub-step, the rows below see the
+//              burnt one.  Each due application waits for one 8-byte count (the events); those that had events settle once
 // then every recorder that is due — the energy rows, the series, the modes, which share the counter and nothing else — enqueues
-// its row into its ring.  But for the sinks, sources and ionisers: no host synchronisation, no collective.  Nothing registered and
+// its row into its ring.  But for the sinks, sources, ionisers and burners: no host synchronisation, no collective.  Nothing registered and
 // recording off: nothing is enqueued.
 static int diag_after_substep(fpic_handle* h)
 {
@@ -415,7 +420,7 @@ static int diag_after_substep(fpic_handle* h)
 #define X(f) \
     if (!g.f.ops.empty()) \
         if (int rc = f##_after_substep(h, g.substep)) return rc;
-    FES_OP_FAMILIES(X)
+    FES_OP_FAMILIES_ALL(X)
 #undef X
     const bool f32 = h->prec == FPIC_F32;
     for (int k = 0; k < kRecorders; ++k) {

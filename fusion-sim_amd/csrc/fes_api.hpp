@@ -76,6 +76,11 @@ int ionize(fpic_handle* h, const fpic_ionize_spec* spec, fpic_ionize_result* out
 int ionize_register(fpic_handle* h, const fpic_ionize_spec* spec, int every, int* index);
 int ionize_stats(fpic_handle* h, int index, int scope, fpic_ionize_result* out);
 int ionize_clear(fpic_handle* h);
+// fusion burn: reactants consumed, products born (fes_burn.inc.hpp)
+int burn(fpic_handle* h, const fpic_burn_spec* spec, fpic_burn_result* out);
+int burn_register(fpic_handle* h, const fpic_burn_spec* spec, int every, int* index);
+int burn_stats(fpic_handle* h, int index, int scope, fpic_burn_result* out);
+int burn_clear(fpic_handle* h);
 // binary Coulomb collisions between the species of the box (fes_pair.inc.hpp)
 int pair(fpic_handle* h, const fpic_pair_spec* spec, fpic_pair_result* out);
 int pair_register(fpic_handle* h, const fpic_pair_spec* spec, int every, int* index);

@@ -2,7 +2,7 @@
 // unit (included there before fes_collide.inc.hpp, inside namespace fes).  The types are in fes_state.inc.hpp (OpRows, OpCommon,
 // OpFamily, the list FES_OP_FAMILIES), the checks and the families' messages in fes_ops_core.hpp.
 //
-// Every family (collide, force, gas, pair, fusion, fusion_spectrum, remove, inject, ionize) has a call that applies a request now and
+// Every family (collide, force, gas, pair, fusion, fusion_spectrum, remove, inject, ionize, burn) has a call that applies a request now and
 // calls that register it, read its totals and drop the registrations.  Here are the parts that do not depend on the family: the
 // rows (allocation, a row's place, zeroing, the copy back), the registration's checks and its tail, the head of a stats read,
 // the loop of the sub-step hook over the operators that are due, and the question whether anything is registered at all.  A
@@ -147,6 +147,6 @@ static unsigned pass_head(const fpic_handle* h, const Species& sp, int blocks, P
 static bool ops_registered(const Diag& g)
 {
 #define X(f) || !g.f.ops.empty()
-    return false FES_OP_FAMILIES(X);
+    return false FES_OP_FAMILIES_ALL(X);
 #undef X
 }

@@ -113,6 +113,9 @@ struct OpFamily {
 // the families as the members of Diag, in the order in which the sub-step hook runs them (diag_after_substep of fes_api.hip
 // states the order and why): member f has the hook's part f##_after_substep
 #define FES_OP_FAMILIES(X) X(force) X(collide) X(gas) X(pair) X(fusion) X(fspec) X(remove) X(inject) X(ionize)
+// ... and behind the nine of DESIGN 4.26 the burners, which couple a sink and a source per event and so run after
+// both: the list the hook, the release and ops_registered go through
+#define FES_OP_FAMILIES_ALL(X) FES_OP_FAMILIES(X) X(burn)
 
 // what each family's operator keeps of its own, beside OpCommon
 struct CollideOp : OpCommon {          // fes_collide.inc.hpp
@@ -154,6 +157,11 @@ struct IonizeOp : OpCommon {           // fes_ionize.inc.hpp: as GasOp
     const double* dev_sigma;
     const double* taper[3];
 };
+struct BurnOp : OpCommon {             // fes_burn.inc.hpp: the request (its table pointer is not kept), the host's copy of the
+    fpic_burn_spec spec;               // cross-sections, where the table lies on the device
+    std::vector<double> sigma;
+    const double* table;
+};
 
 // the diagnostics of a handle: the sub-step counter the recorders share, the recorders and their requests, the buffers of the
 // energy reduction (fes_diag.inc.hpp), of the histograms and of the moments, the ranks' gather
@@ -185,6 +193,7 @@ struct Diag {
     OpFamily<RemoveOp> remove;          // rows of kDiagWords words; behind the totals: the last application, the mark pass's counter, the move pass's partial rows
     OpFamily<InjectOp> inject;          // rows of kDiagWords words; behind the totals: the last application, the generation pass's partial rows
     OpFamily<IonizeOp> ionize;          // fesion::kWords tally words and the gas operator's table room per row; row MAX_OPS: the application in flight
+    OpFamily<BurnOp> burn;              // fesburn::kWords tally words and a table of FPIC_FUSION_TABLE_MAX doubles per row; row MAX_OPS: the application in flight
     // the cell index of fpic_pair, one per side (species_a, species_b): pair_seg[s] = 4 + cells words (zeros, then per cell
     // the count -> the exclusive offset -> the end of the cell's segment), pair_index[s] = the slots by cell; both grow to
     // the largest request.  The fusion tallies and spectra use it too
@@ -202,7 +211,7 @@ inline void diag_release(Diag& g)
                      static_cast<void*>(g.pair_seg[0]), static_cast<void*>(g.pair_seg[1]), static_cast<void*>(g.pair_index[0]), static_cast<void*>(g.pair_index[1]) })
         if (p) (void)hipFree(p);
 #define X(f) g.f.rows.release();
-    FES_OP_FAMILIES(X)
+    FES_OP_FAMILIES_ALL(X)
 #undef X
     g.fspec_bins.release();
     for (unsigned long long* p : g.fusion_grid)

@@ -1683,6 +1683,30 @@ int fpic_ionize_clear(fpic_handle* h)
     BOX_ONLY(h, "fpic_ionize_clear");
     return fes::ionize_clear(h);
 }
+int fpic_burn(fpic_handle* h, const fpic_burn_spec* spec, fpic_burn_result* out)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_burn");
+    return fes::burn(h, spec, out);
+}
+int fpic_burn_register(fpic_handle* h, const fpic_burn_spec* spec, int every, int* index)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_burn_register");
+    return fes::burn_register(h, spec, every, index);
+}
+int fpic_burn_stats(fpic_handle* h, int index, int scope, fpic_burn_result* out)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_burn_stats");
+    return fes::burn_stats(h, index, scope, out);
+}
+int fpic_burn_clear(fpic_handle* h)
+{
+    CHECK_HANDLE(h);
+    BOX_ONLY(h, "fpic_burn_clear");
+    return fes::burn_clear(h);
+}
 int fpic_collide_clear(fpic_handle* h)
 {
     CHECK_HANDLE(h);

@@ -56,6 +56,7 @@ ABI_FUNCTIONS = [
     "fpic_remove", "fpic_remove_register", "fpic_remove_stats", "fpic_remove_clear", "fpic_renumber",
     "fpic_reserve", "fpic_population", "fpic_inject", "fpic_inject_register", "fpic_inject_stats", "fpic_inject_clear",
     "fpic_ionize", "fpic_ionize_register", "fpic_ionize_stats", "fpic_ionize_clear",
+    "fpic_burn", "fpic_burn_register", "fpic_burn_stats", "fpic_burn_clear",
 ]
 
 
@@ -889,6 +890,60 @@ def _ionize_dict(r):
     return out
 
 
+BURN_MAX_OPS = 4
+BURN_SEED = 0xB0510C0FFEE
+
+
+class BurnSpec(ctypes.Structure):
+    """mirror of fpic_burn_spec (include/fusionpic.h)"""
+    _fields_ = [
+        ("species_a", ctypes.c_int32), ("species_b", ctypes.c_int32), ("product_a", ctypes.c_int32), ("product_b", ctypes.c_int32),
+        ("seed", ctypes.c_uint64), ("stream", ctypes.c_uint32), ("epoch", ctypes.c_uint32),
+        ("tau", ctypes.c_double), ("g_lo", ctypes.c_double), ("g_hi", ctypes.c_double),
+        ("n", ctypes.c_int32), ("reserved_i", ctypes.c_int32), ("sigma", ctypes.POINTER(ctypes.c_double)),
+        ("q_value", ctypes.c_double), ("other_mass", ctypes.c_double), ("reserved", ctypes.c_double * 4),
+    ]
+
+
+class BurnResult(ctypes.Structure):
+    """mirror of fpic_burn_result"""
+    _fields_ = [(k, ctypes.c_uint64) for k in ("applications", "pairs", "below", "above", "cells", "overfull_cells", "overfull_particles",
+                                               "accepted", "blocked", "saturated", "burnt")] + \
+               [("reactant_a", IonizeGain), ("reactant_b", IonizeGain), ("product_a", IonizeGain), ("product_b", IonizeGain)]
+
+
+def _burn_spec(tau_default, a=0, b=None, products=None, q_value=0.0, other_mass=0.0, seed=BURN_SEED, **request):
+    """BurnSpec of a burn request: the reactants a and b (None: a with itself), products = (p3, p4) the species that receive
+    the two products, p4 None: the fourth particle leaves the box and other_mass (kg) is its mass; q_value (J); the rest as
+    _fusion_spec.  Only what the structure cannot carry is refused here; the library checks the rest.  The spec keeps the
+    table alive (spec._table)."""
+    f = _fusion_spec(tau_default, a, b, seed=seed, **request)
+    s = BurnSpec()
+    s._table = f._table
+    for name in ("species_a", "species_b", "seed", "stream", "epoch", "tau", "g_lo", "g_hi", "n", "sigma"):
+        setattr(s, name, getattr(f, name))
+    try:
+        p3, p4 = products
+    except (TypeError, ValueError):
+        raise FusionPicError(-1, ".products <- must be (product_a, product_b or None)")
+    s.product_a = _whole("product_a", p3, 32, signed=True)
+    s.product_b = -1 if p4 is None else _whole("product_b", p4, 32, signed=True)
+    s.q_value, s.other_mass = _real_given("q_value", q_value), _real_given("other_mass", other_mass)
+    return s
+
+
+def _burn_dict(r):
+    """the counts, and per group what the species lost (reactant_a, reactant_b) or gained (product_a, product_b):
+    energy_fixed and momentum_fixed as Python integers (the 128-bit two's complement sums, units of 2^-80)"""
+    out = {k: int(getattr(r, k)) for k in ("applications", "pairs", "below", "above", "cells", "overfull_cells", "overfull_particles",
+                                           "accepted", "blocked", "saturated", "burnt")}
+    for name in ("reactant_a", "reactant_b", "product_a", "product_b"):
+        g = getattr(r, name)
+        out[name] = {"energy_fixed": _force_signed(g.energy_fixed), "momentum_fixed": [_force_signed(g.momentum_fixed[a]) for a in range(3)],
+                     "energy": float(g.energy), "momentum": [float(g.momentum[a]) for a in range(3)], "charge": float(g.charge)}
+    return out
+
+
 PAIR_MAX_OPS = 8
 PAIR_CELL_MAX = 2048
 PAIR_SEED = 0x7A1C12ABE
@@ -1338,6 +1393,10 @@ def load_library(path=None):
     lib.fpic_ionize_register.argtypes = [vp, ctypes.POINTER(IonizeSpec), ci, ctypes.POINTER(ctypes.c_int)]
     lib.fpic_ionize_stats.argtypes = [vp, ci, ci, ctypes.POINTER(IonizeResult)]
     lib.fpic_ionize_clear.argtypes = [vp]
+    lib.fpic_burn.argtypes = [vp, ctypes.POINTER(BurnSpec), ctypes.POINTER(BurnResult)]
+    lib.fpic_burn_register.argtypes = [vp, ctypes.POINTER(BurnSpec), ci, ctypes.POINTER(ctypes.c_int)]
+    lib.fpic_burn_stats.argtypes = [vp, ci, ci, ctypes.POINTER(BurnResult)]
+    lib.fpic_burn_clear.argtypes = [vp]
     lib.fpic_pair.argtypes = [vp, ctypes.POINTER(PairSpec), ctypes.POINTER(PairResult)]
     lib.fpic_pair_register.argtypes = [vp, ctypes.POINTER(PairSpec), ci, ctypes.POINTER(ctypes.c_int)]
     lib.fpic_pair_stats.argtypes = [vp, ci, ci, ctypes.POINTER(PairResult)]
@@ -1778,6 +1837,49 @@ class CylindricalParticlePusher:
     def clearIonization(self):
         """drops every registered ioniser (fpic_ionize_clear); other operators stay"""
         self._check(self._lib.fpic_ionize_clear(self._h))
+
+    # ---- fusion burn: the pairs of the yield tally react — reactants consumed, products born (fpic_burn*)
+    def _burn_refresh(self, s):
+        for k in {int(s.species_a), int(s.species_b), int(s.product_a), int(s.product_b)} - {-1}:
+            self.population(k)
+
+    def burn(self, a=0, b=None, **request):
+        """One application, now, of fusion burn between species a and species b of a CART3D box (b None or b == a: a species
+        with itself; fpic_burn; an (r,z) handle and a decomposed handle are refused).  The pairs, the table and the yield y
+        of a pair are fusionYield()'s; a pair reacts with the probability y / macro_weight, a particle at most once.  Both
+        reactants leave their species as remove() takes a particle out (the species is thinned), and one new particle each
+        is born in products=(p3, p4) with fusionSpectrum()'s product kinematics: q_value= (J), isotropic emission; p4 None:
+        the fourth particle leaves the box and other_mass= (kg) is its mass.  sigma=, g_lo=, g_hi=, tau=, seed=, stream=,
+        epoch= as fusionYield().  The products need the room: reserve() makes it, and an application that does not fit
+        changes nothing.  Returns {applications, pairs, below, above, cells, overfull_cells, overfull_particles, accepted,
+        blocked, saturated, burnt, reactant_a, reactant_b, product_a, product_b}, each group {energy_fixed, momentum_fixed
+        (exact integers, units of 2**-80), energy (J), momentum (kg m/s), charge (C)}: what the reactants lost and the
+        products gained."""
+        s = _burn_spec(float(self.spec["dt"]), a, b, **request)
+        out = BurnResult()
+        self._check(self._lib.fpic_burn(self._h, ctypes.byref(s), ctypes.byref(out)))
+        self._burn_refresh(s)
+        return _burn_dict(out)
+
+    def burnEvery(self, every, a=0, b=None, **request):
+        """Registers a burner (see burn) to run at the end of every `every`-th sub-step, after the ionisers and before the
+        recorders, with epoch = the sub-step number + `epoch`; tau defaults to every * dt.  The table is copied.  Returns
+        the burner's index (fpic_burn_register); at most BURN_MAX_OPS.  population() reads the counts it has changed."""
+        every = _every_arg(every)
+        s = _burn_spec(every * float(self.spec["dt"]), a, b, **request)
+        index = ctypes.c_int(-1)
+        self._check(self._lib.fpic_burn_register(self._h, ctypes.byref(s), every, ctypes.byref(index)))
+        return index.value
+
+    def burnStats(self, index, scope="global"):
+        """the totals of a registered burner since its registration (fpic_burn_stats)"""
+        out = BurnResult()
+        self._check(self._lib.fpic_burn_stats(self._h, int(index), _scope_code(scope), ctypes.byref(out)))
+        return _burn_dict(out)
+
+    def clearBurn(self):
+        """drops every registered burner (fpic_burn_clear); other operators stay"""
+        self._check(self._lib.fpic_burn_clear(self._h))
 
     # ---- the loader: a population generated on the device (fpic_load)
     def _box_lengths(self):
@@ -2398,6 +2500,11 @@ class ElectrostaticBoxPusher:
     ionizeEvery = CylindricalParticlePusher.ionizeEvery
     ionizeStats = CylindricalParticlePusher.ionizeStats
     clearIonization = CylindricalParticlePusher.clearIonization
+    _burn_refresh = CylindricalParticlePusher._burn_refresh
+    burn = CylindricalParticlePusher.burn
+    burnEvery = CylindricalParticlePusher.burnEvery
+    burnStats = CylindricalParticlePusher.burnStats
+    clearBurn = CylindricalParticlePusher.clearBurn
     collidePair = CylindricalParticlePusher.collidePair
     collidePairEvery = CylindricalParticlePusher.collidePairEvery
     pairStats = CylindricalParticlePusher.pairStats
@@ -2624,6 +2731,22 @@ class BoxGroup:
     def clearIonization(self):
         """refused, see ionize"""
         raise FusionPicError(-5, _INJECT_DECOMPOSED % "clearIonization")
+
+    def burn(self, a=0, b=None, **request):
+        """refused (FPIC_ERR_STATE), as by every member, for the sources' reason: a burner appends particles"""
+        raise FusionPicError(-5, _INJECT_DECOMPOSED % "burn")
+
+    def burnEvery(self, every, a=0, b=None, **request):
+        """refused, see burn"""
+        raise FusionPicError(-5, _INJECT_DECOMPOSED % "burnEvery")
+
+    def burnStats(self, index, scope="global"):
+        """refused, see burn"""
+        raise FusionPicError(-5, _INJECT_DECOMPOSED % "burnStats")
+
+    def clearBurn(self):
+        """refused, see burn"""
+        raise FusionPicError(-5, _INJECT_DECOMPOSED % "clearBurn")
 
     def collidePair(self, a=0, b=None, **request):
         """refused (FPIC_ERR_STATE), as by every member: between two migrations the particles of a cell can sit on two

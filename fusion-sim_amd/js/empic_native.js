@@ -688,7 +688,7 @@ function makeBox(spec, lib) {
     // { species (the projectile), electron (default: species), ion, gThreshold (units of c; gLo >= gThreshold) }.  ionize ->
     // { applications, candidates, below, above, ionised, primary, electron, ion }, each group { energyFixed, momentumFixed
     // (BigInt, units of 2^-80 c^2 and c: what the species gained), energy (J), momentum (kg m/s), charge (C) };
-    // ionizeEvery(every, request) -> the ioniser's index (it runs last among the operators); ionizeStats(index, scope) -> its
+    // ionizeEvery(every, request) -> the ioniser's index (it runs after the sources, before the burners); ionizeStats(index, scope) -> its
     // totals; clearIonization() drops every ioniser.  The targets need the room: reserve() first
     const ionizeArgs = function (request, tauDefault) {
         if (request === null || typeof request !== 'object' || Array.isArray(request)) throw new TypeError('.request <- expected { species, electron, ion, gThreshold, density, tau, sigma, gLo, gHi, drift, vth, lo, hi, taper, seed, stream, epoch }');
@@ -831,6 +831,47 @@ function makeBox(spec, lib) {
         return grid;
     };
     out.clearFusion = function () { lib.clearFusion(h); };
+    // fusion burn (fpic_burn*): the pairs of fusionYield react — both reactants leave their species and one new particle each is
+    // born in the product species.  request = the request of fusionYield and { products: [p3, p4 or null (the fourth particle
+    // leaves the box)], qValue (J), otherMass (kg; with p4 null) }.  burn -> { applications, pairs, below, above, cells,
+    // overfullCells, overfullParticles, accepted, blocked, saturated, burnt, reactantA, reactantB (what the species lost),
+    // productA, productB (what they gained) }, each group { energyFixed, momentumFixed (BigInt, units of 2^-80 c^2 and c),
+    // energy (J), momentum (kg m/s), charge (C) }; burnEvery(every, request) -> the burner's index (it runs after the ionisers);
+    // burnStats(index, scope) -> its totals; clearBurn() drops every burner.  The products need the room: reserve() first
+    const burnArgs = function (request, tauDefault) {
+        if (request === null || typeof request !== 'object' || Array.isArray(request)) throw new TypeError('.request <- expected { a, b, products, sigma, gLo, gHi, tau, qValue, otherMass, seed, stream, epoch }');
+        const given = (v) => v !== undefined && v !== null;
+        const a = fusionArgs(Object.assign({}, request, { seed: given(request.seed) ? request.seed : 0xB0510C0FFEE }), tauDefault);
+        const products = request.products;
+        if (!Array.isArray(products) || products.length !== 2) throw new RangeError('.products <- expected [productA, productB or null]');
+        const target = function (name, v) {
+            if (!Number.isInteger(v) || v < -0x80000000 || v > 0x7fffffff) throw new RangeError('.' + name + ' <- expected an integer within its field');
+            return v;
+        };
+        const real = function (name, v) {
+            if (!given(v)) v = 0;
+            if (typeof v !== 'number') throw new RangeError('.' + name + ' <- expected a number');
+            return v;
+        };
+        const extra = Float64Array.from([target('productA', products[0]), given(products[1]) ? target('productB', products[1]) : -1, real('qValue', request.qValue), real('otherMass', request.otherMass)]);
+        return [a[0], a[1], a[2], extra];
+    };
+    out.burn = function (request) {
+        const a = burnArgs(request, spec.dt), r = lib.burn(h, a[0], a[1], a[2], a[3]);
+        live(a[0][0]); live(a[0][1]); live(a[3][0]);
+        if (a[3][1] >= 0) live(a[3][1]);
+        return r;
+    };
+    out.burnEvery = function (every, request) {
+        if (!Number.isInteger(every) || every < -0x80000000 || every > 0x7fffffff) throw new RangeError('.every <- expected a 32-bit integer');
+        const a = burnArgs(request, every * spec.dt);
+        return lib.burnEvery(h, a[0], a[1], a[2], a[3], every);
+    };
+    out.burnStats = function (index, scope) {
+        if (!Number.isInteger(index) || index < -0x80000000 || index > 0x7fffffff) throw new RangeError('.index <- expected a 32-bit integer');
+        return lib.burnStats(h, index, scopeOf(scope));
+    };
+    out.clearBurn = function () { lib.clearBurn(h); };
     // fusion product spectra (fpic_fusion_spectrum*): the yield of a fusionYield request distributed over an energy axis.
     // request = the request of fusionYield and { axis: 'product' (default) or 'cm', bins (1 .. 256), lo, hi (J), qValue (J),
     // productMass, otherMass (kg; axis 'product'), los: [x, y, z] (absent or zeros: isotropic emission) }.  fusionSpectrum ->

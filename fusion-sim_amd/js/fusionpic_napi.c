@@ -1935,6 +1935,108 @@ static napi_value n_clear_fusion(napi_env env, napi_callback_info info)
     return undefined(env);
 }
 
+/* ---- fusion burn: reactants consumed, products born (fpic_burn*) */
+
+/* the request of burn / burnEvery: words, reals, sigma as fusionYield takes them, extra: Float64Array [product_a, product_b
+ * (-1: not tracked), q_value, other_mass] */
+static int get_burn_spec(napi_env env, const napi_value* argv, fpic_burn_spec* s)
+{
+    fpic_fusion_spec f;
+    if (!get_fusion_spec(env, argv[1], argv[2], argv[3], &f)) return 0;
+    napi_typedarray_type te; void* pe; size_t le;
+    if (!get_typed(env, argv[4], &te, &pe, &le)) return 0;
+    if (!pe || te != napi_float64_array) { napi_throw_type_error(env, NULL, ".request <- expected a Float64Array of the products, the q-value and the other mass"); return 0; }
+    if (!check_len(env, "extra", le, 4)) return 0;
+    const double* e = (const double*)pe;
+    for (int k = 0; k < 2; ++k)
+        if (!(e[k] >= -2147483648.0 && e[k] <= 2147483647.0) || e[k] != (double)(int32_t)e[k]) {
+            napi_throw_range_error(env, NULL, ".request <- the products must be 32-bit integers");
+            return 0;
+        }
+    memset(s, 0, sizeof *s);
+    s->species_a = f.species_a; s->species_b = f.species_b;
+    s->product_a = (int32_t)e[0]; s->product_b = (int32_t)e[1];
+    s->seed = f.seed; s->stream = f.stream; s->epoch = f.epoch;
+    s->tau = f.tau; s->g_lo = f.g_lo; s->g_hi = f.g_hi;
+    s->n = f.n; s->sigma = f.sigma;
+    s->q_value = e[2];
+    s->other_mass = e[3];
+    return 1;
+}
+
+/* { applications, pairs, below, above, cells, overfullCells, overfullParticles, accepted, blocked, saturated, burnt, reactantA,
+ * reactantB, productA, productB }, each group { energyFixed, momentumFixed, energy, momentum, charge } */
+static napi_value burn_object(napi_env env, const fpic_burn_result* c)
+{
+    const char* names[11] = { "applications", "pairs", "below", "above", "cells", "overfullCells", "overfullParticles", "accepted", "blocked", "saturated", "burnt" };
+    const uint64_t counts[11] = { c->applications, c->pairs, c->below, c->above, c->cells, c->overfull_cells, c->overfull_particles, c->accepted, c->blocked, c->saturated, c->burnt };
+    const fpic_ionize_gain* gains[4] = { &c->reactant_a, &c->reactant_b, &c->product_a, &c->product_b };
+    const char* groups[4] = { "reactantA", "reactantB", "productA", "productB" };
+    napi_value o, v;
+    NAPI_OK(env, napi_create_object(env, &o));
+    for (int k = 0; k < 11; ++k) {
+        NAPI_OK(env, napi_create_double(env, (double)counts[k], &v));
+        NAPI_OK(env, napi_set_named_property(env, o, names[k], v));
+    }
+    for (int k = 0; k < 4; ++k) {
+        v = tally_object(env, 0, NULL, NULL, gains[k]->energy_fixed, gains[k]->momentum_fixed, gains[k]->energy, gains[k]->momentum, gains[k]->charge);
+        if (!v) return NULL;
+        NAPI_OK(env, napi_set_named_property(env, o, groups[k], v));
+    }
+    return o;
+}
+
+/* burn(h, words, reals, sigma, extra) -> the result */
+static napi_value n_burn(napi_env env, napi_callback_info info)
+{
+    napi_value argv[5]; fpic_handle* h;
+    fpic_burn_spec s;
+    if (!get_args(env, info, 5, argv, &h) || !get_burn_spec(env, argv, &s)) return NULL;
+    fpic_burn_result c;
+    memset(&c, 0, sizeof c);
+    if (fpic_burn(h, &s, &c) != FPIC_OK) return throw_fpic(env, h);
+    (void)live_count(h, s.species_a);         /* (every species of the request has changed: the caller-order length checks ask the library) */
+    (void)live_count(h, s.species_b);
+    (void)live_count(h, s.product_a);
+    if (s.product_b >= 0) (void)live_count(h, s.product_b);
+    return burn_object(env, &c);
+}
+
+/* burnEvery(h, words, reals, sigma, extra, every) -> the burner's index */
+static napi_value n_burn_every(napi_env env, napi_callback_info info)
+{
+    napi_value argv[6]; fpic_handle* h; double every;
+    fpic_burn_spec s;
+    if (!get_args(env, info, 6, argv, &h) || !get_burn_spec(env, argv, &s) || !get_double(env, argv[5], &every)) return NULL;
+    if (!(every >= -2147483648.0 && every <= 2147483647.0) || every != (double)(int)every) { napi_throw_range_error(env, NULL, ".every <- must be a 32-bit integer"); return NULL; }
+    int index = -1;
+    if (fpic_burn_register(h, &s, (int)every, &index) != FPIC_OK) return throw_fpic(env, h);
+    napi_value v;
+    NAPI_OK(env, napi_create_int32(env, index, &v));
+    return v;
+}
+
+/* burnStats(h, index, scope) -> as burn */
+static napi_value n_burn_stats(napi_env env, napi_callback_info info)
+{
+    napi_value argv[3]; fpic_handle* h; double index; int scope;
+    if (!get_args(env, info, 3, argv, &h) || !get_double(env, argv[1], &index) || !get_scope(env, argv[2], &scope)) return NULL;
+    if (!(index >= -2147483648.0 && index <= 2147483647.0) || index != (double)(int)index) { napi_throw_range_error(env, NULL, ".index <- must be a 32-bit integer"); return NULL; }
+    fpic_burn_result c;
+    memset(&c, 0, sizeof c);
+    if (fpic_burn_stats(h, (int)index, scope, &c) != FPIC_OK) return throw_fpic(env, h);
+    return burn_object(env, &c);
+}
+
+/* clearBurn(h) */
+static napi_value n_clear_burn(napi_env env, napi_callback_info info)
+{
+    napi_value argv[1]; fpic_handle* h;
+    if (!get_args(env, info, 1, argv, &h)) return NULL;
+    if (fpic_burn_clear(h) != FPIC_OK) return throw_fpic(env, h);
+    return undefined(env);
+}
+
 /* the request of fusionSpectrum / fusionSpectrumEvery: the tally's three arrays (get_fusion_spec) and axis: Float64Array
  * [axis, bins, lo, hi, q_value, product_mass, other_mass, los x, los y, los z].  The array's type and length and the two
  * integers' ranges are checked here, the request itself by the library. */
@@ -2315,6 +2417,7 @@ static napi_value init(napi_env env, napi_value exports)
         { "inject", n_inject }, { "injectEvery", n_inject_every }, { "injectStats", n_inject_stats }, { "clearInjections", n_clear_injections },
         { "reserve", n_reserve }, { "population", n_population },
         { "ionize", n_ionize }, { "ionizeEvery", n_ionize_every }, { "ionizeStats", n_ionize_stats }, { "clearIonization", n_clear_ionization },
+        { "burn", n_burn }, { "burnEvery", n_burn_every }, { "burnStats", n_burn_stats }, { "clearBurn", n_clear_burn },
         { "collidePair", n_collide_pair }, { "collidePairEvery", n_collide_pair_every }, { "pairStats", n_pair_stats }, { "clearPairs", n_clear_pairs },
         { "fusionYield", n_fusion_yield }, { "fusionYieldEvery", n_fusion_yield_every }, { "fusionStats", n_fusion_stats }, { "fusionGrid", n_fusion_grid }, { "clearFusion", n_clear_fusion },
         { "fusionSpectrum", n_fusion_spectrum }, { "fusionSpectrumEvery", n_fusion_spectrum_every }, { "fusionSpectrumRead", n_fusion_spectrum_read }, { "clearFusionSpectra", n_clear_fusion_spectra },

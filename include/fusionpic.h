@@ -1499,8 +1499,8 @@ int fpic_inject_clear(fpic_handle* h);
  * is 0).  Sums are exact, in the fixed point of the energy diagnostics (units of 2^-80, 128-bit two's complement, low word
  * first); a term outside its range adds nothing and makes its double NaN.
  * fpic_ionize applies the request now (synchronous) and settles itself; K = 0 launches nothing and returns zeros.
- * fpic_ionize_register makes it run at the end of every sub-step with substep % every == 0, LAST among the operators — after
- * the sources, before the recorders: a beam injected on a sub-step can ionise on it, and the recorded rows count the new
+ * fpic_ionize_register makes it run at the end of every sub-step with substep % every == 0, after
+ * the sources, before the burners: a beam injected on a sub-step can ionise on it, and the recorded rows count the new
  * particles —, in registration order, with epoch (uint32)(substep + spec.epoch); at most FPIC_IONIZE_MAX_OPS ionisers.  The
  * tables are copied at the call.  A due application reads ONE 8-byte count back (the events: the host has to learn the new
  * n) and is counted once it has succeeded.  fpic_ionize_stats reads the totals since registration, fpic_ionize_clear drops
@@ -1546,6 +1546,96 @@ int fpic_ionize(fpic_handle* h, const fpic_ionize_spec* spec, fpic_ionize_result
 int fpic_ionize_register(fpic_handle* h, const fpic_ionize_spec* spec, int every, int* index);
 int fpic_ionize_stats(fpic_handle* h, int index, int scope, fpic_ionize_result* out);
 int fpic_ionize_clear(fpic_handle* h);
+
+/* ---- CART3D fusion burn: the pairs of fpic_fusion REACT — a macro-particle of species_a and one of species_b leave their
+ * species, and one new particle of product_a and one of product_b are born, on the device: burn-up, alpha heating, a
+ * fast-ion tail.  The handle has one macro_weight W for all species, so one macro-reactant of each kind becomes exactly one
+ * macro-product of each kind; nothing is weighted.  Undecomposed handles only.  What an application does depends on the
+ * request, the epoch, the ids and the stored state alone — not on the slots, the binning or the order any atomic took.  All
+ * arithmetic is double, every operation one of + - x / sqrt and rounded once; v is the stored velocity in units of c, T the
+ * handle's precision; non-relativistic kinematics, as fpic_fusion_spectrum's.
+ *   pairs      the cells, the order inside a cell (ascending (key, id)), the pair sets and N_L are fpic_fusion's: unlike
+ *              species the Nm pairs many[j] with few[j mod Nf] (`many` the species with more, a tie: species_a), N_L = Nf;
+ *              like species (s[2t], s[2t+1]) with N_L = N, an odd cell (s0,s1), (s1,s2), (s2,s0) with N_L = N / 2 and then
+ *              (s[3+2t], s[4+2t]); a cell with more than FPIC_PAIR_CELL_MAX particles of either species is skipped and
+ *              counted.  The pair's OWNER is its `many` particle, or s[q] of the place q that fpic_fusion's like_pair names.
+ *              The key is word 0 of Philox4x32-10(counter (id, epoch, stream, 0xB0510), key (seed_lo, seed_hi)): a tag of
+ *              its own, so a burner never correlates with a tally (0xF0510) or a Coulomb operator (0xC0120) on the same seed.
+ *   g, table   u = v_o - v_p, g = sqrt((ux ux + uy uy) + uz uz); g < g_lo counted `below`, g >= g_hi (or NaN) `above`, both
+ *              do nothing; else the lookup of fpic_fusion with its hold at max sigma, operation for operation.
+ *   probability   y = ((((W W) N_L) tau) / dV) (sigma (g c)), fpic_fusion's yield of the pair before its floor; P = y / W.
+ *              The pair is ACCEPTED iff (u + 0.5) 2^-32 < P, u = word 0 of the owner's block Philox4x32-10(counter (id_o,
+ *              epoch, stream, 0xB0511 + [the owner is of species_b and a != b]), key seed).  P >= 1 always accepts and is
+ *              counted `saturated`.  max sigma = 0 launches nothing.
+ *   conflicts  a particle burns at most once.  Unlike species: few[f] is the partner of the many places f, f + Nf, f + 2 Nf,
+ *              ...: of the accepted pairs of that chain only the one with the lowest place REACTS, the others are counted
+ *              `blocked`.  Like species: the pairs are disjoint but for the triple of an odd cell, where the first accepted
+ *              pair in the order (s0,s1), (s1,s2), (s2,s0) reacts.  accepted = burnt + blocked.
+ *   outcome    host numbers as fpic_fusion_spectrum's with m3 = the mass of product_a and m4 = the mass of product_b (or
+ *              other_mass): M = m_a + m_b, f_a = m_a / M, f_b = m_b / M, hk = (0.5 ((m_a m_b) / M)) (c c),
+ *              kf = ((2 m4) / (m3 (m3 + m4))) / (c c), r34 = m3 / m4.  With a the species_a reactant and b the species_b
+ *              reactant (like species: owner and partner): K = hk (g g); Et = q_value + K, held to 0 from below;
+ *              u3 = sqrt(Et kf); u4 = r34 u3; V_i = (f_a v_a,i) + (f_b v_b,i); n the exact isotropic direction of
+ *              fpic_fusion_spectrum (two tries per block, x = ((w + 0.5) 2^-31) - 1, s = x1 x1 + x2 x2 < 1, n = ((2 x1) r,
+ *              (2 x2) r, 1 - (2 s)) with r = sqrt(1 - s); after sixteen rejections (0, 0, 1)) on the blocks
+ *              Philox4x32-10(counter (id_a, epoch, stream, 0xB0520 + k), key seed), k = 0 .. 7, of the species_a reactant (a
+ *              reactant is in one event at most, so every event has blocks of its own); w3_i = V_i + (u3 n_i);
+ *              w4_i = V_i - (u4 n_i).  Product 3 takes the stored position of the species_a reactant bit for bit and the
+ *              velocity (T) w3; product 4 the position of the species_b reactant and (T) w4.
+ *   placement  the events of one application in ascending id of their species_a reactant (like species: of the owner): event
+ *              number l puts product 3 in slot n3 + l with id (id span of product_a) + l and product 4 in slot n4 + l with
+ *              id (id span of product_b) + l, n and the id spans those before the application (fpic_ionize's rule).
+ *   removal    both reactants of every event leave their species exactly as fpic_remove takes a particle out: the survivors
+ *              keep every bit, their ids and their order, the species is THINNED (fpic_renumber is refused while a burner
+ *              is registered), the handle's n follows the first species.
+ *   fit        with M events: n + M beyond a product's capacity, or an id span beyond 2^32 - 1, refuses the application and
+ *              NOTHING has changed — no slot, no velocity, no tally, no thinned mark: fpic_burn returns FPIC_ERR_INVALID_ARG
+ *              (call fpic_reserve first), a registered application makes the step return FPIC_ERR_STATE.
+ * The result: applications; pairs (inside the table), below, above, cells, overfull_cells, overfull_particles as fpic_fusion
+ * counts them; accepted, blocked, saturated, burnt (= M).  reactant_a, reactant_b: what the species LOST, fpic_remove's
+ * terms of the stored velocities of the particles that left (like species: reactant_a carries both members of every pair
+ * and reactant_b is zeros); product_a, product_b: what each GAINED, fpic_inject's terms of the stored velocities of the new
+ * particles.  With product_b = -1 the fourth particle leaves the box: nothing is stored, and product_b of the result carries
+ * what it took away, from its double velocity w4 with mass other_mass and charge 0 — the books stay closed.  charge = the
+ * count x the species' charge x macro_weight.  Sums are exact, in the fixed point of the energy diagnostics (units of 2^-80,
+ * 128-bit two's complement, low word first); a term outside its range adds nothing and makes its double NaN.
+ * fpic_burn applies the request now (synchronous) and settles itself.  fpic_burn_register makes it run at the end of every
+ * sub-step with substep % every == 0, after the ionisers and before the recorders, in registration order, with epoch
+ * (uint32)(substep + spec.epoch): a tally registered beside a burner sees the unburnt plasma of that sub-step, the recorded
+ * rows the burnt one; at most FPIC_BURN_MAX_OPS burners.  The table is copied at the call.  A due application reads ONE
+ * 8-byte count back (the events) and is counted once it has succeeded.  fpic_burn_stats reads the totals since
+ * registration, fpic_burn_clear drops every burner (other operators stay).  Registrations are not part of a checkpoint.
+ * What an application leaves.  M = 0: nothing changes, nothing is re-binned, no species is thinned.  Else each reactant
+ * species is as fpic_remove leaves one and each product as fpic_inject leaves one.  Electrostatic solver with ready fields:
+ * the call — or the hook, once per sub-step after the last burner due — deposits and solves again.  Full EM: E, B and the
+ * readiness stay; an event moves charge within a cell without a current (the static-source caveat of the sinks and sources).
+ * Refused (FPIC_ERR_INVALID_ARG): a null spec, everything fpic_fusion refuses of the shared fields (species_a, species_b,
+ * tau, n, sigma, g_lo, g_hi, the yield bound), a product_a the handle does not have, a product_b that is neither -1 nor a
+ * species of the handle, a product equal to a reactant or to the other product, other_mass not positive and finite with
+ * product_b = -1 or not zero otherwise, a q_value that is not finite, a reserved word that is not zero, every below 1, a
+ * fifth registration, an index outside the registered burners, a null out of fpic_burn_stats; FPIC_ERR_STATE: a handle that
+ * is not CART3D; a decomposed handle (all four calls). */
+#define FPIC_BURN_MAX_OPS 4
+typedef struct fpic_burn_spec {
+    int32_t  species_a, species_b;     /* the reactants; equal: like species (D-D) */
+    int32_t  product_a, product_b;     /* the species receiving product 3 / product 4; product_b = -1: not tracked (it leaves the box) */
+    uint64_t seed;
+    uint32_t stream, epoch;
+    double   tau, g_lo, g_hi;          /* as fpic_fusion_spec */
+    int32_t  n, reserved_i;            /* table entries; zero */
+    const double* sigma;               /* n cross-sections, m^2 */
+    double   q_value;                  /* J, as fpic_fusion_spectrum_spec */
+    double   other_mass;               /* kg: m4 when product_b = -1; zero otherwise */
+    double   reserved[4];              /* zero */
+} fpic_burn_spec;
+typedef struct fpic_burn_result {
+    uint64_t applications, pairs, below, above, cells, overfull_cells, overfull_particles, accepted, blocked, saturated, burnt;
+    fpic_ionize_gain reactant_a, reactant_b, product_a, product_b;   /* a, b: what the species LOST; the products: GAINED */
+} fpic_burn_result;
+int fpic_burn(fpic_handle* h, const fpic_burn_spec* spec, fpic_burn_result* out);
+int fpic_burn_register(fpic_handle* h, const fpic_burn_spec* spec, int every, int* index);
+int fpic_burn_stats(fpic_handle* h, int index, int scope, fpic_burn_result* out);
+int fpic_burn_clear(fpic_handle* h);
 
 int fpic_sync(fpic_handle* h);
 int fpic_profile(fpic_handle* h, int enable);
