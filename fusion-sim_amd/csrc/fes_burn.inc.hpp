@@ -117,18 +117,7 @@ static int burn_run(fpic_handle* h, const BurnOp& op, uint32_t epoch, int total_
     if (!like)
         if (int rc = pair_index<T>(h, sb, 1)) return rc;
     BurnDecideArgs<T> a{};
-    a.slab_a = static_cast<const T*>(sa.slab[sa.cur]);
-    a.slab_b = static_cast<const T*>(sb.slab[sb.cur]);
-    a.id_a = sa.ids_identity ? nullptr : sa.id[sa.cur];
-    a.id_b = sb.ids_identity ? nullptr : sb.id[sb.cur];
-    a.n_pad_a = sa.n_pad;
-    a.n_pad_b = sb.n_pad;
-    a.seg_a = g.pair_seg[0] + kPairSegLead - 1;
-    a.seg_b = g.pair_seg[like ? 0 : 1] + kPairSegLead - 1;
-    a.index_a = g.pair_index[0];
-    a.index_b = g.pair_index[like ? 0 : 1];
-    a.ncells = static_cast<uint32_t>(pair_cells(st));
-    a.rank_max = (pair_forms() & 2) ? static_cast<uint32_t>(kPairRankMax) : ~0u;
+    const unsigned grid = pair_head(st, sa, sb, a);
     a.words = rows.row(kBurnNow);
     a.cursor = total + 1;
     a.events = reinterpret_cast<BurnEvent*>(dev + events_at);
@@ -138,8 +127,6 @@ static int burn_run(fpic_handle* h, const BurnOp& op, uint32_t epoch, int total_
     a.marked = bitmap;
     a.table = op.table;
     a.r = r;
-    const size_t cell_chunks = (pair_cells(st) + kPairChunk - 1) / kPairChunk;
-    const unsigned grid = static_cast<unsigned>(std::min<size_t>(kPairCollideBlocks, cell_chunks));
     // (kBurnLdsBytes is below the 64 KiB a launch may ask for without an attribute: the header asserts it)
     if (like) burn_decide_kernel<T, true><<<grid, kPairThreads, kBurnLdsBytes, h->stream>>>(a);
     else burn_decide_kernel<T, false><<<grid, kPairThreads, kBurnLdsBytes, h->stream>>>(a);

@@ -110,8 +110,7 @@ FES_HIST_HD bool accepts(uint32_t u, double p)
     return x < p;
 }
 
-// unlike species: the place in the `few` segment of the partner of the `many` place p — the chain p belongs to
-FES_HIST_HD uint32_t few_of(uint32_t p, uint32_t nf) { return p % nf; }
+using fesfusion::few_of;   // the chain a `many` place belongs to
 // whether the accepted pair of place (pair number) p reacts, given the least accepted place of its chain
 FES_HIST_HD bool wins(uint32_t least, uint32_t p) { return least == p; }
 

@@ -1,8 +1,8 @@
 // fes_burn_kernels.hpp — the passes of the fusion burn of a CART3D handle (fpic_burn; host side fes_burn.inc.hpp, the rule
 // fes_burn_core.hpp).  The cell index is fpic_pair's (pair_index<T>), the ranks of the events come from fpic_renumber's
 // popcount scan (renumber_count_kernel, load_scan_kernel); this header adds
-//   burn_decide_kernel<T, LIKE>   fusion_tally_kernel's run planning, loads and in-LDS sort (pair_segment_of, pair_bitonic,
-//       pair_load; only the key's tag differs), then two sweeps over the run's places, a lane per pair.  FIRST sweep: the
+//   burn_decide_kernel<T, LIKE>   the runs of sorted cells are pair_walk's (fes_pair_kernels.hpp) with this family's key, the
+//       pair of a place pair_of's (fes_fusion_kernels.hpp); per run two sweeps over its places, a lane per pair.  FIRST sweep: the
 //       lookup, P and the acceptance; an accepted pair that shares a particle with others — the chain of a `few` particle,
 //       the triple of an odd like cell — takes an integer atomicMin with its place on the chain's word in LDS.  The words lie
 //       where the sort keys lay (a key is dead once its segment is sorted), one per place, so a chain's word is the place of
@@ -55,14 +55,7 @@ static_assert(kBurnTurnsMax <= 32 && kBurnStage >= 2 * kPairThreads, "a lane's a
 static_assert(kPairThreads == kPassThreads, "tally_commit reduces a workgroup of kPassThreads");
 
 template <typename T>
-struct BurnDecideArgs {
-    const T *slab_a, *slab_b;         // six arrays of n_pad each; like species: b = a
-    const uint32_t *id_a, *id_b;      // nullptr: slot = id
-    size_t n_pad_a, n_pad_b;
-    const uint32_t *seg_a, *seg_b;    // cells + 1 words: cell c is index[seg[c] .. seg[c + 1])
-    const uint32_t *index_a, *index_b;
-    uint32_t ncells;
-    uint32_t rank_max;                // a segment of more entries is sorted by the bitonic network, not by counting
+struct BurnDecideArgs : PairHead<const T> {
     unsigned long long* words;        // fesburn::kDecideCounts of them are added here
     unsigned long long* cursor;       // the rows taken of `events`: the event count
     BurnEvent* events;                // room for max_events rows
@@ -72,52 +65,7 @@ struct BurnDecideArgs {
     const double* table;              // r.f.n cross-sections
     fesburn::Rule r;
 };
-
-// the pair that the place e of a run owns
-struct BurnPair {
-    bool has, isb;                    // it owns one; unlike species: the owner is of species_b
-    uint32_t eo, ep;                  // the entries of the owner and of the partner
-    uint32_t chain, p;                // the place of the chain's word (kNoPlace: the pair shares no particle) and what it writes there
-    double nl;
-};
-template <bool LIKE>
-__device__ __forceinline__ BurnPair burn_pair_of(uint32_t e, uint32_t na, uint32_t len, const uint32_t* seg_a, const uint32_t* seg_b, const uint16_t* sorted, bool& first)
-{
-    BurnPair q{};
-    q.chain = fesburn::kNoPlace;
-    q.isb = !LIKE && e >= na;
-    const uint32_t local = q.isb ? e - na : e;
-    const uint32_t l = pair_segment_of(q.isb ? seg_b : seg_a, len, local);
-    first = false;
-    if (LIKE) {
-        const uint32_t lo = seg_a[l], n = seg_a[l + 1] - lo, p = e - lo;
-        uint32_t partner;
-        q.has = fesfusion::like_pair(n, p, partner, q.nl);
-        if (q.has) {
-            first = p == 0;
-            q.eo = sorted[e];
-            q.ep = sorted[lo + partner];
-            if ((n & 1u) && p < 3u) q.chain = lo;       // the triple
-            q.p = p;
-        }
-    } else {
-        const uint32_t alo = seg_a[l], blo = seg_b[l];
-        const uint32_t ca = seg_a[l + 1] - alo, cb = seg_b[l + 1] - blo;
-        const bool a_many = fesfusion::many_is_a(ca, cb);
-        const uint32_t nf = a_many ? cb : ca;
-        q.has = q.isb != a_many && nf > 0;              // (this entry is of the `many` species)
-        if (q.has) {
-            const uint32_t p = local - (q.isb ? blo : alo);
-            first = p == 0;
-            q.nl = static_cast<double>(nf);
-            q.eo = sorted[e];
-            q.chain = (a_many ? na + blo : alo) + fesburn::few_of(p, nf);
-            q.ep = sorted[q.chain];
-            q.p = p;
-        }
-    }
-    return q;
-}
+static_assert(fesburn::kNoPlace == kPairAlone, "a chain's untouched word is the chain of a pair that shares no particle");
 
 // The lanes' rows of this turn -> the workgroup's stage, and the stage -> rows of the list when another turn might not fit
 // (last: whatever it holds).  EVERY lane of the workgroup calls it, once per turn and once after the loop
@@ -152,95 +100,20 @@ template <typename T, bool LIKE>
 __global__ __launch_bounds__(kPairThreads) void burn_decide_kernel(BurnDecideArgs<T> g)
 {
     extern __shared__ unsigned long long burn_lds[];
-    uint32_t* st_key = reinterpret_cast<uint32_t*>(burn_lds);   // the entries as loaded: species a's of the run, then species b's
-    uint32_t* st_id = st_key + kPairEntries;
-    uint32_t* st_slot = st_id + kPairEntries;
-    uint32_t* seg_a = st_slot + kPairEntries;        // [len + 1] the segments of the run's cells, from 0
-    uint32_t* seg_b = seg_a + (kPairChunk + 1);
-    uint32_t* plan = seg_b + (kPairChunk + 1);       // [0]: the cells of the run
-    uint16_t* sorted = reinterpret_cast<uint16_t*>(plan + 2);   // the entries' places, sorted inside their cells' segments
+    const PairRun t(burn_lds);                       // the run's tables, and behind them the stage
     BurnStageHead& stage = *reinterpret_cast<BurnStageHead*>(reinterpret_cast<unsigned char*>(burn_lds) + kPairLdsBytes);
     BurnEvent* rows = reinterpret_cast<BurnEvent*>(&stage + 1);
-    uint32_t* chain = st_key;                        // after the sort: the chains' words, a place each
+    uint32_t* chain = t.st_key;                      // after the sort: the chains' words, a place each
     BurnDecideCounts acc;
     if (threadIdx.x == 0) { stage.n = 0; stage.flush = 0; }
     __syncthreads();
-    const uint32_t nchunks = (g.ncells + kPairChunk - 1) / kPairChunk;
-    for (uint32_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
-        uint32_t c0 = chunk * kPairChunk;
-        const uint32_t cend = min(c0 + static_cast<uint32_t>(kPairChunk), g.ncells);
-        while (c0 < cend) {
-            // the run [c0, c0 + len): the cells from c0 on that are not overfull and fit the LDS together (wave 0 decides)
-            if (threadIdx.x < 64) {
-                const uint32_t c = c0 + threadIdx.x;
-                bool ok = false;
-                uint32_t na = 0, nb = 0;
-                if (c < cend) {
-                    const uint32_t ae = g.seg_a[c + 1];
-                    na = ae - g.seg_a[c];
-                    unsigned long long tot = ae - g.seg_a[c0];
-                    if (!LIKE) {
-                        const uint32_t be = g.seg_b[c + 1];
-                        nb = be - g.seg_b[c];
-                        tot += be - g.seg_b[c0];
-                    }
-                    ok = na <= static_cast<uint32_t>(kPairCellMax) && nb <= static_cast<uint32_t>(kPairCellMax) && tot <= static_cast<unsigned long long>(kPairEntries);
-                }
-                const unsigned long long fits = __ballot(ok);
-                const uint32_t len = fits == ~0ull ? 64u : static_cast<uint32_t>(__ffsll(~fits)) - 1u;
-                if (threadIdx.x == 0) {
-                    plan[0] = len;
-                    if (len == 0) {      // (a cell that is not overfull fits alone: c0 is overfull)
-                        acc.count[4] += 1;
-                        acc.count[5] += static_cast<unsigned long long>(na) + nb;
-                    }
-                }
-            }
-            __syncthreads();
-            const uint32_t len = plan[0];
-            if (len == 0) {
-                c0 += 1;
-                __syncthreads();   // (plan is rewritten by the next turn)
-                continue;
-            }
-            const uint32_t a0 = g.seg_a[c0], b0 = LIKE ? 0u : g.seg_b[c0];
-            if (threadIdx.x <= len) {
-                seg_a[threadIdx.x] = g.seg_a[c0 + threadIdx.x] - a0;
-                if (!LIKE) seg_b[threadIdx.x] = g.seg_b[c0 + threadIdx.x] - b0;
-            }
-            __syncthreads();
-            const uint32_t na = seg_a[len], nb = LIKE ? 0u : seg_b[len], total = na + nb;   // (total <= kPairEntries)
-            for (uint32_t e = threadIdx.x; e < total; e += kPairThreads) {
-                const bool isb = !LIKE && e >= na;
-                const uint32_t slot = isb ? g.index_b[b0 + (e - na)] : g.index_a[a0 + e];
-                const uint32_t* ids = isb ? g.id_b : g.id_a;
-                const uint32_t id = ids ? ids[slot] : slot;
-                st_key[e] = fesburn::key_of(g.r, id);
-                st_id[e] = id;
-                st_slot[e] = slot;
-            }
-            __syncthreads();
-            // the sort: an entry's place in its cell's segment is the number of entries of the segment before it
-            for (uint32_t e = threadIdx.x; e < total; e += kPairThreads) {
-                const bool isb = !LIKE && e >= na;
-                const uint32_t base = isb ? na : 0u;
-                const uint32_t* seg = isb ? seg_b : seg_a;
-                const uint32_t l = pair_segment_of(seg, len, e - base);
-                const uint32_t lo = base + seg[l], hi = base + seg[l + 1];
-                if (hi - lo > g.rank_max) {        // (the network below sorts this segment)
-                    sorted[e] = static_cast<uint16_t>(e);
-                    continue;
-                }
-                const uint32_t key = st_key[e], id = st_id[e];
-                uint32_t rank = 0;
-                for (uint32_t j = lo; j < hi; ++j) rank += fespair::before(st_key[j], st_id[j], key, id) ? 1u : 0u;
-                sorted[lo + rank] = static_cast<uint16_t>(e);
-            }
-            __syncthreads();
-            for (uint32_t l = 0; l < len; ++l) {   // (the same segments for every lane: the tables are in LDS)
-                if (seg_a[l + 1] - seg_a[l] > g.rank_max) pair_bitonic(sorted, st_key, st_id, seg_a[l], seg_a[l + 1] - seg_a[l]);
-                if (!LIKE && seg_b[l + 1] - seg_b[l] > g.rank_max) pair_bitonic(sorted, st_key, st_id, na + seg_b[l], seg_b[l + 1] - seg_b[l]);
-            }
+    pair_walk<LIKE>(
+        g, t, [&](uint32_t id) { return fesburn::key_of(g.r, id); },
+        [&](unsigned long long particles) {
+            acc.count[4] += 1;
+            acc.count[5] += particles;
+        },
+        [&](uint32_t, uint32_t len, uint32_t na, uint32_t, uint32_t total) {
             // (every read of a key lies before a barrier: the counting sort's, or the last step's of the network)
             for (uint32_t e = threadIdx.x; e < total; e += kPairThreads) chain[e] = fesburn::kNoPlace;
             __syncthreads();
@@ -250,20 +123,20 @@ __global__ __launch_bounds__(kPairThreads) void burn_decide_kernel(BurnDecideArg
             for (uint32_t turn = 0; turn < turns; ++turn) {
                 const uint32_t e = turn * kPairThreads + threadIdx.x;
                 if (e >= total) continue;
-                bool first;
-                const BurnPair q = burn_pair_of<LIKE>(e, na, len, seg_a, seg_b, sorted, first);
+                const PairOf q = pair_of<LIKE>(t, e, na, len);
                 if (!q.has) continue;
-                if (first) acc.count[3] += 1;
+                if (q.first) acc.count[3] += 1;
+                const uint32_t eo = t.sorted[e];   // the owner's entry
                 double vo[3], vp[3];
-                pair_load(q.isb ? g.slab_b : g.slab_a, q.isb ? g.n_pad_b : g.n_pad_a, st_slot[q.eo], vo);
-                pair_load(LIKE || q.isb ? g.slab_a : g.slab_b, LIKE || q.isb ? g.n_pad_a : g.n_pad_b, st_slot[q.ep], vp);
+                pair_load(q.isb ? g.slab_b : g.slab_a, q.isb ? g.n_pad_b : g.n_pad_a, t.st_slot[eo], vo);
+                pair_load(LIKE || q.isb ? g.slab_a : g.slab_b, LIKE || q.isb ? g.n_pad_a : g.n_pad_b, t.st_slot[t.sorted[q.pp]], vp);
                 double p;
                 const int what = fesburn::probability(g.r, g.table, q.nl, vo, vp, &p);
                 acc.count[0] += what == fesburn::kInside ? 1 : 0;
                 acc.count[1] += what == fesburn::kBelow ? 1 : 0;
                 acc.count[2] += what == fesburn::kAbove ? 1 : 0;
                 if (what != fesburn::kInside) continue;
-                if (!fesburn::accepts(fesburn::accept_word(g.r, st_id[q.eo], q.isb), p)) continue;
+                if (!fesburn::accepts(fesburn::accept_word(g.r, t.st_id[eo], q.isb), p)) continue;
                 acc.count[6] += 1;
                 acc.count[8] += p >= 1.0 ? 1 : 0;
                 accepted |= 1u << turn;
@@ -276,14 +149,14 @@ __global__ __launch_bounds__(kPairThreads) void burn_decide_kernel(BurnDecideArg
                 bool reacts = false;
                 BurnEvent row{};
                 if (accepted >> turn & 1u) {
-                    bool first;
-                    const BurnPair q = burn_pair_of<LIKE>(e, na, len, seg_a, seg_b, sorted, first);
+                    const PairOf q = pair_of<LIKE>(t, e, na, len);
                     reacts = q.chain == fesburn::kNoPlace || fesburn::wins(chain[q.chain], q.p);
                     if (reacts) {
-                        const uint32_t ea = q.isb ? q.ep : q.eo, eb = q.isb ? q.eo : q.ep;   // the entries of species_a's and of species_b's reactant
-                        row.slot_a = st_slot[ea];
-                        row.slot_b = st_slot[eb];
-                        row.id_a = st_id[ea];
+                        const uint32_t eo = t.sorted[e], ep = t.sorted[q.pp];
+                        const uint32_t ea = q.isb ? ep : eo, eb = q.isb ? eo : ep;   // the entries of species_a's and of species_b's reactant
+                        row.slot_a = t.st_slot[ea];
+                        row.slot_b = t.st_slot[eb];
+                        row.id_a = t.st_id[ea];
                         atomicOr(g.gone_a + (row.slot_a >> 5), 1u << (row.slot_a & 31u));
                         atomicOr(g.gone_b + (row.slot_b >> 5), 1u << (row.slot_b & 31u));
                         atomicOr(g.marked + (row.id_a >> 5), 1u << (row.id_a & 31u));
@@ -293,10 +166,7 @@ __global__ __launch_bounds__(kPairThreads) void burn_decide_kernel(BurnDecideArg
                 }
                 burn_stage(g, stage, rows, reacts, row, false);
             }
-            __syncthreads();   // (the run's tables are rewritten by the next)
-            c0 += len;
-        }
-    }
+        });
     burn_stage(g, stage, rows, false, BurnEvent{}, true);
     tally_commit(acc, g.words);
 }

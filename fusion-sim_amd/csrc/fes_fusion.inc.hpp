@@ -53,24 +53,11 @@ static int fusion_enqueue(fpic_handle* h, const fpic_fusion_spec& spec, const fe
     if (!like)
         if (int rc = pair_index<T>(h, sb, 1)) return rc;
     FusionArgs<T> a{};
-    a.slab_a = static_cast<const T*>(sa.slab[sa.cur]);
-    a.slab_b = static_cast<const T*>(sb.slab[sb.cur]);
-    a.id_a = sa.ids_identity ? nullptr : sa.id[sa.cur];
-    a.id_b = sb.ids_identity ? nullptr : sb.id[sb.cur];
-    a.n_pad_a = sa.n_pad;
-    a.n_pad_b = sb.n_pad;
-    a.seg_a = g.pair_seg[0] + kPairSegLead - 1;
-    a.seg_b = g.pair_seg[like ? 0 : 1] + kPairSegLead - 1;
-    a.index_a = g.pair_index[0];
-    a.index_b = g.pair_index[like ? 0 : 1];
-    a.ncells = static_cast<uint32_t>(pair_cells(st));
-    a.rank_max = (pair_forms() & 2) ? static_cast<uint32_t>(kPairRankMax) : ~0u;
+    const unsigned grid = pair_head(st, sa, sb, a);
     a.counts = g.fusion.rows.row(slot);
     a.grid = g.fusion_grid[slot];
     a.table = g.fusion.rows.table(slot);
     a.r = r;
-    const size_t nchunks = (pair_cells(st) + kPairChunk - 1) / kPairChunk;
-    const unsigned grid = static_cast<unsigned>(std::min<size_t>(kPairCollideBlocks, nchunks));
     // (kFusionLdsBytes is below the 64 KiB a launch may ask for without an attribute: the header asserts it)
     if (like) fusion_tally_kernel<T, true><<<grid, kPairThreads, kFusionLdsBytes, h->stream>>>(a);
     else fusion_tally_kernel<T, false><<<grid, kPairThreads, kFusionLdsBytes, h->stream>>>(a);

@@ -70,6 +70,8 @@ FES_HIST_HD uint32_t key_of(const Rule& r, uint32_t id)
 
 // unlike species: whether species_a is the `many` one of a cell with na and nb particles
 FES_HIST_HD bool many_is_a(uint32_t na, uint32_t nb) { return na >= nb; }
+// unlike species: the place in the `few` segment of the partner of the `many` place p — the chain p belongs to
+FES_HIST_HD uint32_t few_of(uint32_t p, uint32_t nf) { return p % nf; }
 
 // like species: the pair that the place q of a cell's n sorted particles owns — false: none; else (s[q], s[partner]) with n_l
 FES_HIST_HD bool like_pair(uint32_t n, uint32_t q, uint32_t& partner, double& n_l)

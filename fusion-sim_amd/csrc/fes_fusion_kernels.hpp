@@ -1,10 +1,12 @@
 // fes_fusion_kernels.hpp — the pass of the fusion yield tally of a CART3D handle (fpic_fusion; host side
 // fes_fusion.inc.hpp, the rule fes_fusion_core.hpp).  The cell index is fpic_pair's, built by the same three passes
 // (pair_count*, pair_scan, pair_fill* of fes_pair_kernels.hpp) into the same buffers; this header adds
-//   fusion_tally_kernel<T, LIKE>   A workgroup takes chunks of kPairChunk consecutive cells and cuts each into runs that fit
-//       kPairEntries places of LDS, loads (key, id, slot) per entry and sorts every cell's segment in (key, id), all as
-//       pair_collide_kernel does and with its helpers (pair_segment_of, pair_bitonic, pair_load) — only the key's tag differs.
-//       Then EVERY PAIR HAS A LANE OF ITS OWN: nothing is written back, so the chain of a `few` particle has no sequential
+//   pair_of<LIKE>   the pair that a place of a sorted run owns; the spectrum and the burn take it from here.
+//   fusion_tally_kernel<T, LIKE>   The runs of sorted cells are those of pair_walk (fes_pair_kernels.hpp) with this family's
+//       key, but this kernel KEEPS ITS OWN COPY of the walk and of the pair's derivation: with the shared ones its like
+//       instance in fp32 measured 1.2 - 2 % slower, in every form that was tried (DESIGN 4.30 has the numbers).  A change
+//       to pair_walk's planning or sort has to be made here as well.
+//       Per run EVERY PAIR HAS A LANE OF ITS OWN: nothing is written back, so the chain of a `few` particle has no sequential
 //       dependence; the lane of a `many` entry (unlike species) or of a pair's owner (like species; the three places of an odd
 //       cell's triple own one pair each) gathers the two velocities, interpolates the table and floors the yield.
 //       The table (at most 32 KiB of doubles) is gathered from global memory: beside the run's 56.5 KiB it would leave one
@@ -30,19 +32,59 @@ static_assert(kFusionLdsBytes <= 64 * 1024, "two workgroups per CU");
 static_assert(fesfusion::kCellMax == kPairCellMax, "the bound's N_L is the cap");
 
 template <typename T>
-struct FusionArgs {
-    const T *slab_a, *slab_b;         // six arrays of n_pad each; like species: b = a
-    const uint32_t *id_a, *id_b;      // nullptr: slot = id
-    size_t n_pad_a, n_pad_b;
-    const uint32_t *seg_a, *seg_b;    // cells + 1 words: cell c is index[seg[c] .. seg[c + 1])
-    const uint32_t *index_a, *index_b;
-    uint32_t ncells;
-    uint32_t rank_max;                // a segment of more entries is sorted by the bitonic network, not by counting
+struct FusionArgs : PairHead<const T> {
     unsigned long long* counts;       // pairs, below, above, cells, overfull_cells, overfull_particles, yield_hi, yield_lo
     unsigned long long* grid;         // ncells words (int64 in two's complement)
     const double* table;              // r.n cross-sections
     fesfusion::Rule r;
 };
+
+// The pair that the place e of a sorted run owns (the tally, the spectrum and the burn: every pair has a lane of its own).
+// Unlike species: the owner is the `many` particle, its partner few[p mod Nf]; like species: fesfusion::like_pair.
+constexpr uint32_t kPairAlone = 0xFFFFFFFFu;
+struct PairOf {
+    bool has, isb, first;             // it owns one; unlike species: the owner is of species_b; the owner is the first of its cell
+    uint32_t cell;                    // the run's cell of the place, whether it owns a pair or not
+    uint32_t pp;                      // the partner's place: the owner's entry is sorted[e], the partner's sorted[pp]
+    uint32_t chain, p;                // the place of the particle the pair shares with others — the `few` particle, the first of an
+                                      // odd like cell's triple; kPairAlone: it shares none — and the owner's place in its segment
+    double nl;
+};
+template <bool LIKE>
+__device__ __forceinline__ PairOf pair_of(const PairRun& t, uint32_t e, uint32_t na, uint32_t len)
+{
+    PairOf q{};
+    q.chain = kPairAlone;
+    q.isb = !LIKE && e >= na;
+    const uint32_t local = q.isb ? e - na : e;
+    const uint32_t l = pair_segment_of(q.isb ? t.seg_b : t.seg_a, len, local);
+    q.cell = l;
+    if (LIKE) {
+        const uint32_t lo = t.seg_a[l], n = t.seg_a[l + 1] - lo, p = e - lo;
+        uint32_t partner;
+        q.has = fesfusion::like_pair(n, p, partner, q.nl);
+        if (q.has) {
+            q.first = p == 0;
+            q.pp = lo + partner;
+            if ((n & 1u) && p < 3u) q.chain = lo;       // the triple
+            q.p = p;
+        }
+    } else {
+        const uint32_t alo = t.seg_a[l], blo = t.seg_b[l];
+        const uint32_t ca = t.seg_a[l + 1] - alo, cb = t.seg_b[l + 1] - blo;
+        const bool a_many = fesfusion::many_is_a(ca, cb);
+        const uint32_t nf = a_many ? cb : ca;
+        q.has = q.isb != a_many && nf > 0;              // (this entry is of the `many` species)
+        if (q.has) {
+            const uint32_t p = local - (q.isb ? blo : alo);
+            q.first = p == 0;
+            q.nl = static_cast<double>(nf);
+            q.pp = q.chain = (a_many ? na + blo : alo) + fesfusion::few_of(p, nf);
+            q.p = p;
+        }
+    }
+    return q;
+}
 
 template <typename T, bool LIKE>
 __global__ __launch_bounds__(kPairThreads) void fusion_tally_kernel(FusionArgs<T> g)
@@ -171,7 +213,7 @@ __global__ __launch_bounds__(kPairThreads) void fusion_tally_kernel(FusionArgs<T
                             if (p == 0) count[3] += 1;
                             nl = static_cast<double>(nf);
                             so = st_slot[sorted[e]];
-                            sp = st_slot[sorted[(a_many ? na + blo : alo) + p % nf]];
+                            sp = st_slot[sorted[(a_many ? na + blo : alo) + fesfusion::few_of(p, nf)]];
                         }
                     }
                     if (has) {

@@ -94,12 +94,34 @@ static int pair_index(fpic_handle* h, const Species& sp, int s)
     return FPIC_OK;
 }
 
+// The head of the arguments of a pass that walks the cell index (pair_walk), from the two species — like species: the same
+// one — and the index pair_index has left in Diag: side 0 is species a's, side 1 species b's.  Returns the grid.
+template <typename S>
+static unsigned pair_head(State* st, const Species& sa, const Species& sb, PairHead<S>& a)
+{
+    Diag& g = st->diag;
+    const int side_b = &sa == &sb ? 0 : 1;
+    a.slab_a = static_cast<S*>(sa.slab[sa.cur]);
+    a.slab_b = static_cast<S*>(sb.slab[sb.cur]);
+    a.id_a = sa.ids_identity ? nullptr : sa.id[sa.cur];
+    a.id_b = sb.ids_identity ? nullptr : sb.id[sb.cur];
+    a.n_pad_a = sa.n_pad;
+    a.n_pad_b = sb.n_pad;
+    a.seg_a = g.pair_seg[0] + kPairSegLead - 1;
+    a.seg_b = g.pair_seg[side_b] + kPairSegLead - 1;
+    a.index_a = g.pair_index[0];
+    a.index_b = g.pair_index[side_b];
+    a.ncells = static_cast<uint32_t>(pair_cells(st));
+    a.rank_max = (pair_forms() & 2) ? static_cast<uint32_t>(kPairRankMax) : ~0u;
+    const size_t nchunks = (pair_cells(st) + kPairChunk - 1) / kPairChunk;
+    return static_cast<unsigned>(std::min<size_t>(kPairCollideBlocks, nchunks));
+}
+
 // one application at `epoch`, its counts added to words[0 .. 5): enqueued, nothing waited for
 template <typename T>
 static int pair_enqueue(fpic_handle* h, const fpic_pair_spec& spec, uint32_t epoch, unsigned long long* words, bool may_grow)
 {
     State* st = h->es;
-    Diag& g = st->diag;
     if (int rc = pair_buffers(h, spec, may_grow)) return rc;
     const Species& sa = st->sp[spec.species_a];
     const Species& sb = st->sp[spec.species_b];
@@ -110,22 +132,9 @@ static int pair_enqueue(fpic_handle* h, const fpic_pair_spec& spec, uint32_t epo
     if (!like)
         if (int rc = pair_index<T>(h, sb, 1)) return rc;
     PairArgs<T> a{};
-    a.slab_a = static_cast<T*>(sa.slab[sa.cur]);
-    a.slab_b = static_cast<T*>(sb.slab[sb.cur]);
-    a.id_a = sa.ids_identity ? nullptr : sa.id[sa.cur];
-    a.id_b = sb.ids_identity ? nullptr : sb.id[sb.cur];
-    a.n_pad_a = sa.n_pad;
-    a.n_pad_b = sb.n_pad;
-    a.seg_a = g.pair_seg[0] + kPairSegLead - 1;
-    a.seg_b = g.pair_seg[like ? 0 : 1] + kPairSegLead - 1;
-    a.index_a = g.pair_index[0];
-    a.index_b = g.pair_index[like ? 0 : 1];
-    a.ncells = static_cast<uint32_t>(pair_cells(st));
-    a.rank_max = (pair_forms() & 2) ? static_cast<uint32_t>(kPairRankMax) : ~0u;
+    const unsigned grid = pair_head(st, sa, sb, a);
     a.counts = words;
     a.r = fespair::rule_of(spec, epoch, sa.mass, sa.charge, sb.mass, sb.charge, st->W, dv);
-    const size_t nchunks = (pair_cells(st) + kPairChunk - 1) / kPairChunk;
-    const unsigned grid = static_cast<unsigned>(std::min<size_t>(kPairCollideBlocks, nchunks));
     // (kPairLdsBytes is below the 64 KiB a launch may ask for without an attribute: the header asserts it)
     if (like) pair_collide_kernel<T, true><<<grid, kPairThreads, kPairLdsBytes, h->stream>>>(a);
     else pair_collide_kernel<T, false><<<grid, kPairThreads, kPairLdsBytes, h->stream>>>(a);

@@ -13,13 +13,16 @@
 //       scanned count is the cursor: afterwards it is the END of the cell's segment, and the word before it the beginning).
 //       The LDS form gives the particles of the turn's tile their places inside the turn from the table and reserves a cell's
 //       run with one global atomic.  The order inside a segment is arbitrary.
-//   pair_collide_kernel<T, LIKE>   A workgroup takes chunks of kPairChunk consecutive cells (fixed grid, grid-stride) and
-//       cuts each into runs of cells whose entries, both species together, fit kPairEntries places of LDS.  It loads
-//       (key, id, slot) per entry, sorts every cell's segment in (key, id) — up to kPairRankMax = 64 entries by counting the
-//       entries before each, longer ones by a bitonic network (pair_bitonic) —, and then gives one lane to every `few` particle (unlike species) or to every
-//       pair / triple (like species).  The lane walks its chain sequentially with its own particle in registers and casts
-//       both velocities to T after every pair; inside a cell no two lanes touch the same particle, so there are no atomics
-//       on velocities and no barrier between rounds.  Only velocities that changed are stored.
+//   pair_walk<LIKE>   the walk over the index that this pass, the fusion tally, the fusion spectrum and the burn's deciding
+//       pass share (PairHead: the head of their arguments; PairRun: the run's tables in LDS).  A workgroup takes chunks of
+//       kPairChunk consecutive cells (fixed grid, grid-stride) and cuts each into runs of cells whose entries, both species
+//       together, fit kPairEntries places of LDS.  It loads (key, id, slot) per entry, sorts every cell's segment in
+//       (key, id) — up to kPairRankMax = 64 entries by counting the entries before each, longer ones by a bitonic network
+//       (pair_bitonic) —, and hands the run to the pass's body.
+//   pair_collide_kernel<T, LIKE>   per run one lane to every `few` particle (unlike species) or to every pair / triple (like
+//       species).  The lane walks its chain sequentially with its own particle in registers and casts both velocities to T
+//       after every pair; inside a cell no two lanes touch the same particle, so there are no atomics on velocities and no
+//       barrier between rounds.  Only velocities that changed are stored.
 // A cell with more than kPairCellMax = 2048 particles of either species is not collided and counted as overfull: two full
 // species of a cell are the kPairEntries = 4096 places, 14 bytes each (the unsorted triple, and 16 bits for the place of the
 // entry that is sorted to here) = 56.5 KiB with the run's tables: two workgroups on a CU's 160 KiB.
@@ -56,20 +59,39 @@ struct PairIndexArgs {
     uint32_t* index;          // the slots by cell
 };
 
-// the deposit's cell of slot s; false: the stored position is no number of [0, 1)
+// the deposit's cell (i, j, k) of slot s; false: the stored position is no number of [0, 1)
+template <typename T>
+__device__ __forceinline__ bool pair_ijk(const PairIndexArgs<T>& a, size_t s, int& i, int& j, int& k)
+{
+    int w;
+    axis(a.slab[s], a.nx, i, w);
+    axis(a.slab[a.n_pad + s], a.ny, j, w);
+    axis(a.slab[2 * a.n_pad + s], a.nz, k, w);
+    return static_cast<unsigned>(i) < static_cast<unsigned>(a.nx) && static_cast<unsigned>(j) < static_cast<unsigned>(a.ny) &&
+           static_cast<unsigned>(k) < static_cast<unsigned>(a.nz);
+}
+// the cell's number in the grid
+template <typename T>
+__device__ __forceinline__ uint32_t pair_cell_at(const PairIndexArgs<T>& a, uint32_t i, uint32_t j, uint32_t k)
+{
+    return i + static_cast<uint32_t>(a.nx) * (j + static_cast<uint32_t>(a.ny) * k);
+}
 template <typename T>
 __device__ __forceinline__ bool pair_cell_of(const PairIndexArgs<T>& a, size_t s, uint32_t& c)
 {
-    const T x = a.slab[s], y = a.slab[a.n_pad + s], z = a.slab[2 * a.n_pad + s];
-    int i, j, k, w;
-    axis(x, a.nx, i, w);
-    axis(y, a.ny, j, w);
-    axis(z, a.nz, k, w);
-    if (static_cast<unsigned>(i) >= static_cast<unsigned>(a.nx) || static_cast<unsigned>(j) >= static_cast<unsigned>(a.ny) ||
-        static_cast<unsigned>(k) >= static_cast<unsigned>(a.nz))
-        return false;
-    c = static_cast<uint32_t>(i) + static_cast<uint32_t>(a.nx) * (static_cast<uint32_t>(j) + static_cast<uint32_t>(a.ny) * static_cast<uint32_t>(k));
+    int i, j, k;
+    if (!pair_ijk(a, s, i, j, k)) return false;
+    c = pair_cell_at(a, i, j, k);
     return true;
+}
+// lane 0 of the workgroup: the origin of the tile of the turn's first slot (-1: that slot holds no position of the box)
+template <typename T>
+__device__ __forceinline__ void pair_tile_origin(const PairIndexArgs<T>& a, size_t base, int mx, int my, int mz, int (&origin)[3])
+{
+    if (threadIdx.x != 0) return;
+    int i, j, k;
+    const bool ok = pair_ijk(a, base, i, j, k);
+    origin[0] = ok ? i & ~mx : -1; origin[1] = ok ? j & ~my : -1; origin[2] = ok ? k & ~mz : -1;
 }
 
 template <typename T>
@@ -94,39 +116,27 @@ __global__ __launch_bounds__(kPairThreads) void pair_count_lds_kernel(PairIndexA
     __shared__ int origin[3];
     const uint32_t tcells = 1u << (a.ltx + a.lty + a.ltz);
     const int mx = (1 << a.ltx) - 1, my = (1 << a.lty) - 1, mz = (1 << a.ltz) - 1;
-    auto ijk = [&](size_t s, int& i, int& j, int& k) {
-        int w;
-        axis(a.slab[s], a.nx, i, w);
-        axis(a.slab[a.n_pad + s], a.ny, j, w);
-        axis(a.slab[2 * a.n_pad + s], a.nz, k, w);
-        return static_cast<unsigned>(i) < static_cast<unsigned>(a.nx) && static_cast<unsigned>(j) < static_cast<unsigned>(a.ny) &&
-               static_cast<unsigned>(k) < static_cast<unsigned>(a.nz);
-    };
     for (size_t base = static_cast<size_t>(blockIdx.x) * kPairCountTurn; base < a.n; base += static_cast<size_t>(gridDim.x) * kPairCountTurn) {
         for (uint32_t t = threadIdx.x; t < tcells; t += kPairThreads) table[t] = 0;
-        if (threadIdx.x == 0) {
-            int i, j, k;
-            const bool ok = ijk(base, i, j, k);
-            origin[0] = ok ? i & ~mx : -1; origin[1] = ok ? j & ~my : -1; origin[2] = ok ? k & ~mz : -1;
-        }
+        pair_tile_origin(a, base, mx, my, mz, origin);
         __syncthreads();
         const int ox = origin[0], oy = origin[1], oz = origin[2];
 #pragma unroll
         for (int q = 0; q < kPairCountTurn / kPairThreads; ++q) {
             const size_t s = base + static_cast<size_t>(q) * kPairThreads + threadIdx.x;
             int i, j, k;
-            if (s >= a.n || !ijk(s, i, j, k)) continue;
+            if (s >= a.n || !pair_ijk(a, s, i, j, k)) continue;
             if ((i & ~mx) == ox && (j & ~my) == oy && (k & ~mz) == oz)
                 atomicAdd(&table[(i & mx) | ((j & my) << a.ltx) | ((k & mz) << (a.ltx + a.lty))], 1u);
             else
-                atomicAdd(a.cell + (static_cast<uint32_t>(i) + static_cast<uint32_t>(a.nx) * (static_cast<uint32_t>(j) + static_cast<uint32_t>(a.ny) * static_cast<uint32_t>(k))), 1u);
+                atomicAdd(a.cell + pair_cell_at(a, i, j, k), 1u);
         }
         __syncthreads();
         for (uint32_t t = threadIdx.x; t < tcells; t += kPairThreads) {
             const uint32_t c = table[t];
             if (!c) continue;     // (a cell that was hit lies inside the grid: a particle was there)
             const uint32_t i = ox + (t & mx), j = oy + ((t >> a.ltx) & my), k = oz + (t >> (a.ltx + a.lty));
-            atomicAdd(a.cell + (i + static_cast<uint32_t>(a.nx) * (j + static_cast<uint32_t>(a.ny) * k)), c);
+            atomicAdd(a.cell + pair_cell_at(a, i, j, k), c);
         }
         __syncthreads();   // (the table is zeroed by the next turn)
     }
@@ -212,21 +222,9 @@ __global__ __launch_bounds__(kPairThreads) void pair_fill_lds_kernel(PairIndexAr
     constexpr int kPer = kPairCountTurn / kPairThreads;
     const uint32_t tcells = 1u << (a.ltx + a.lty + a.ltz);
     const int mx = (1 << a.ltx) - 1, my = (1 << a.lty) - 1, mz = (1 << a.ltz) - 1;
-    auto ijk = [&](size_t s, int& i, int& j, int& k) {
-        int w;
-        axis(a.slab[s], a.nx, i, w);
-        axis(a.slab[a.n_pad + s], a.ny, j, w);
-        axis(a.slab[2 * a.n_pad + s], a.nz, k, w);
-        return static_cast<unsigned>(i) < static_cast<unsigned>(a.nx) && static_cast<unsigned>(j) < static_cast<unsigned>(a.ny) &&
-               static_cast<unsigned>(k) < static_cast<unsigned>(a.nz);
-    };
     for (size_t base = static_cast<size_t>(blockIdx.x) * kPairCountTurn; base < a.n; base += static_cast<size_t>(gridDim.x) * kPairCountTurn) {
         for (uint32_t t = threadIdx.x; t < tcells; t += kPairThreads) table[t] = 0;
-        if (threadIdx.x == 0) {
-            int i, j, k;
-            const bool ok = ijk(base, i, j, k);
-            origin[0] = ok ? i & ~mx : -1; origin[1] = ok ? j & ~my : -1; origin[2] = ok ? k & ~mz : -1;
-        }
+        pair_tile_origin(a, base, mx, my, mz, origin);
         __syncthreads();
         const int ox = origin[0], oy = origin[1], oz = origin[2];
         uint32_t where[kPer], place[kPer];      // the cell within the tile (~0: none) and the place inside the turn
@@ -236,12 +234,12 @@ __global__ __launch_bounds__(kPairThreads) void pair_fill_lds_kernel(PairIndexAr
             int i, j, k;
             where[q] = ~0u;
             place[q] = 0;
-            if (s >= a.n || !ijk(s, i, j, k)) continue;
+            if (s >= a.n || !pair_ijk(a, s, i, j, k)) continue;
             if ((i & ~mx) == ox && (j & ~my) == oy && (k & ~mz) == oz) {
                 where[q] = (i & mx) | ((j & my) << a.ltx) | ((k & mz) << (a.ltx + a.lty));
                 place[q] = atomicAdd(&table[where[q]], 1u);
             } else {
-                const uint32_t c = static_cast<uint32_t>(i) + static_cast<uint32_t>(a.nx) * (static_cast<uint32_t>(j) + static_cast<uint32_t>(a.ny) * static_cast<uint32_t>(k));
+                const uint32_t c = pair_cell_at(a, i, j, k);
                 a.index[atomicAdd(a.cell + c, 1u)] = static_cast<uint32_t>(s);
             }
         }
@@ -250,7 +248,7 @@ __global__ __launch_bounds__(kPairThreads) void pair_fill_lds_kernel(PairIndexAr
             const uint32_t c = table[t];
             if (!c) continue;
             const uint32_t i = ox + (t & mx), j = oy + ((t >> a.ltx) & my), k = oz + (t >> (a.ltx + a.lty));
-            first[t] = atomicAdd(a.cell + (i + static_cast<uint32_t>(a.nx) * (j + static_cast<uint32_t>(a.ny) * k)), c);
+            first[t] = atomicAdd(a.cell + pair_cell_at(a, i, j, k), c);
         }
         __syncthreads();
 #pragma unroll
@@ -260,15 +258,21 @@ __global__ __launch_bounds__(kPairThreads) void pair_fill_lds_kernel(PairIndexAr
     }
 }
 
-template <typename T>
-struct PairArgs {
-    T *slab_a, *slab_b;               // six arrays of n_pad each; like species: b = a
+// The head of the arguments of every pass that walks the cell index (pair_walk); S is T where the pass writes velocities,
+// const T where it only reads them.  pair_head (fes_pair.inc.hpp) fills it.
+template <typename S>
+struct PairHead {
+    S *slab_a, *slab_b;               // six arrays of n_pad each; like species: b = a
     const uint32_t *id_a, *id_b;      // nullptr: slot = id
     size_t n_pad_a, n_pad_b;
     const uint32_t *seg_a, *seg_b;    // cells + 1 words: cell c is index[seg[c] .. seg[c + 1])
     const uint32_t *index_a, *index_b;
     uint32_t ncells;
     uint32_t rank_max;                // a segment of more entries is sorted by the bitonic network, not by counting
+};
+
+template <typename T>
+struct PairArgs : PairHead<T> {
     unsigned long long* counts;       // pairs, strong, cells, overfull_cells, overfull_particles
     fespair::Rule r;
 };
@@ -327,18 +331,29 @@ __device__ __forceinline__ void pair_bitonic(uint16_t* sorted, const uint32_t* s
     }
 }
 
-template <typename T, bool LIKE>
-__global__ __launch_bounds__(kPairThreads) void pair_collide_kernel(PairArgs<T> g)
+// The tables of a run, kPairLdsBytes of LDS from `base` on (4-byte aligned).  A kernel's own LDS lies in front of or behind them.
+struct PairRun {
+    uint32_t *st_key, *st_id, *st_slot;   // [kPairEntries] the entries as loaded: species a's of the run, then species b's
+    uint32_t *seg_a, *seg_b;              // [len + 1] the segments of the run's cells, from 0
+    uint32_t* plan;                       // [0]: the cells of the run
+    uint16_t* sorted;                     // [kPairEntries] the entries' places, sorted inside their cells' segments
+    __device__ __forceinline__ explicit PairRun(void* base)
+        : st_key(static_cast<uint32_t*>(base)), st_id(st_key + kPairEntries), st_slot(st_id + kPairEntries), seg_a(st_slot + kPairEntries),
+          seg_b(seg_a + (kPairChunk + 1)), plan(seg_b + (kPairChunk + 1)), sorted(reinterpret_cast<uint16_t*>(plan + 2))
+    {
+    }
+};
+
+// The walk every pairing pass shares (pair_collide_kernel, fusion_tally_kernel, fusion_spectrum_kernel, burn_decide_kernel):
+// a workgroup takes the chunks blockIdx.x, blockIdx.x + gridDim.x, ... of kPairChunk consecutive cells and cuts each into
+// runs of cells that are not overfull and whose entries, both species together, fit kPairEntries places.  Per run it copies
+// the segment tables to LDS, loads (key_of(id), id, slot) per entry, sorts every cell's segment in (key, id) and calls
+// body(c0, len, na, nb, total) — the run is the cells [c0, c0 + len) with na + nb = total entries — between two barriers.
+// A first cell that is overfull is skipped and reported: overfull(its particles), on lane 0 of the workgroup alone.
+// EVERY lane of the workgroup calls it, and body runs on every lane: it may hold barriers of its own.
+template <bool LIKE, typename S, typename Key, typename Overfull, typename Body>
+__device__ __forceinline__ void pair_walk(const PairHead<S>& g, const PairRun& t, Key key_of, Overfull overfull, Body body)
 {
-    extern __shared__ uint32_t pair_lds[];
-    uint32_t* st_key = pair_lds;                     // the entries as loaded: species a's of the run, then species b's
-    uint32_t* st_id = st_key + kPairEntries;
-    uint32_t* st_slot = st_id + kPairEntries;
-    uint32_t* seg_a = st_slot + kPairEntries;        // [len + 1] the segments of the run's cells, from 0
-    uint32_t* seg_b = seg_a + (kPairChunk + 1);
-    uint32_t* plan = seg_b + (kPairChunk + 1);       // [0]: the cells of the run
-    uint16_t* sorted = reinterpret_cast<uint16_t*>(plan + 2);   // the entries' places, sorted inside their cells' segments
-    unsigned long long count[kPairCounts] = { 0, 0, 0, 0, 0 };
     const uint32_t nchunks = (g.ncells + kPairChunk - 1) / kPairChunk;
     for (uint32_t chunk = blockIdx.x; chunk < nchunks; chunk += gridDim.x) {
         uint32_t c0 = chunk * kPairChunk;
@@ -363,15 +378,12 @@ __global__ __launch_bounds__(kPairThreads) void pair_collide_kernel(PairArgs<T> 
                 const unsigned long long fits = __ballot(ok);
                 const uint32_t len = fits == ~0ull ? 64u : static_cast<uint32_t>(__ffsll(~fits)) - 1u;
                 if (threadIdx.x == 0) {
-                    plan[0] = len;
-                    if (len == 0) {      // (a cell that is not overfull fits alone: c0 is overfull)
-                        count[3] += 1;
-                        count[4] += static_cast<unsigned long long>(na) + nb;
-                    }
+                    t.plan[0] = len;
+                    if (len == 0) overfull(static_cast<unsigned long long>(na) + nb);   // (a cell that is not overfull fits alone: c0 is overfull)
                 }
             }
             __syncthreads();
-            const uint32_t len = plan[0];
+            const uint32_t len = t.plan[0];
             if (len == 0) {
                 c0 += 1;
                 __syncthreads();   // (plan is rewritten by the next turn)
@@ -379,42 +391,64 @@ __global__ __launch_bounds__(kPairThreads) void pair_collide_kernel(PairArgs<T> 
             }
             const uint32_t a0 = g.seg_a[c0], b0 = LIKE ? 0u : g.seg_b[c0];
             if (threadIdx.x <= len) {
-                seg_a[threadIdx.x] = g.seg_a[c0 + threadIdx.x] - a0;
-                if (!LIKE) seg_b[threadIdx.x] = g.seg_b[c0 + threadIdx.x] - b0;
+                t.seg_a[threadIdx.x] = g.seg_a[c0 + threadIdx.x] - a0;
+                if (!LIKE) t.seg_b[threadIdx.x] = g.seg_b[c0 + threadIdx.x] - b0;
             }
             __syncthreads();
-            const uint32_t na = seg_a[len], nb = LIKE ? 0u : seg_b[len], total = na + nb;   // (total <= kPairEntries)
+            const uint32_t na = t.seg_a[len], nb = LIKE ? 0u : t.seg_b[len], total = na + nb;   // (total <= kPairEntries)
             for (uint32_t e = threadIdx.x; e < total; e += kPairThreads) {
                 const bool isb = !LIKE && e >= na;
                 const uint32_t slot = isb ? g.index_b[b0 + (e - na)] : g.index_a[a0 + e];
                 const uint32_t* ids = isb ? g.id_b : g.id_a;
                 const uint32_t id = ids ? ids[slot] : slot;
-                st_key[e] = fespair::key_of(g.r, id);
-                st_id[e] = id;
-                st_slot[e] = slot;
+                t.st_key[e] = key_of(id);
+                t.st_id[e] = id;
+                t.st_slot[e] = slot;
             }
             __syncthreads();
             // the sort: an entry's place in its cell's segment is the number of entries of the segment before it
             for (uint32_t e = threadIdx.x; e < total; e += kPairThreads) {
                 const bool isb = !LIKE && e >= na;
                 const uint32_t base = isb ? na : 0u;
-                const uint32_t* seg = isb ? seg_b : seg_a;
+                const uint32_t* seg = isb ? t.seg_b : t.seg_a;
                 const uint32_t l = pair_segment_of(seg, len, e - base);
                 const uint32_t lo = base + seg[l], hi = base + seg[l + 1];
                 if (hi - lo > g.rank_max) {        // (the network below sorts this segment)
-                    sorted[e] = static_cast<uint16_t>(e);
+                    t.sorted[e] = static_cast<uint16_t>(e);
                     continue;
                 }
-                const uint32_t key = st_key[e], id = st_id[e];
+                const uint32_t key = t.st_key[e], id = t.st_id[e];
                 uint32_t rank = 0;
-                for (uint32_t j = lo; j < hi; ++j) rank += fespair::before(st_key[j], st_id[j], key, id) ? 1u : 0u;
-                sorted[lo + rank] = static_cast<uint16_t>(e);
+                for (uint32_t j = lo; j < hi; ++j) rank += fespair::before(t.st_key[j], t.st_id[j], key, id) ? 1u : 0u;
+                t.sorted[lo + rank] = static_cast<uint16_t>(e);
             }
             __syncthreads();
             for (uint32_t l = 0; l < len; ++l) {   // (the same segments for every lane: the tables are in LDS)
-                if (seg_a[l + 1] - seg_a[l] > g.rank_max) pair_bitonic(sorted, st_key, st_id, seg_a[l], seg_a[l + 1] - seg_a[l]);
-                if (!LIKE && seg_b[l + 1] - seg_b[l] > g.rank_max) pair_bitonic(sorted, st_key, st_id, na + seg_b[l], seg_b[l + 1] - seg_b[l]);
+                if (t.seg_a[l + 1] - t.seg_a[l] > g.rank_max) pair_bitonic(t.sorted, t.st_key, t.st_id, t.seg_a[l], t.seg_a[l + 1] - t.seg_a[l]);
+                if (!LIKE && t.seg_b[l + 1] - t.seg_b[l] > g.rank_max) pair_bitonic(t.sorted, t.st_key, t.st_id, na + t.seg_b[l], t.seg_b[l + 1] - t.seg_b[l]);
             }
+            body(c0, len, na, nb, total);
+            __syncthreads();   // (the run's tables are rewritten by the next)
+            c0 += len;
+        }
+    }
+}
+
+template <typename T, bool LIKE>
+__global__ __launch_bounds__(kPairThreads) void pair_collide_kernel(PairArgs<T> g)
+{
+    extern __shared__ uint32_t pair_lds[];
+    const PairRun t(pair_lds);
+    uint32_t *const st_id = t.st_id, *const st_slot = t.st_slot, *const seg_a = t.seg_a, *const seg_b = t.seg_b;
+    uint16_t* const sorted = t.sorted;
+    unsigned long long count[kPairCounts] = { 0, 0, 0, 0, 0 };
+    pair_walk<LIKE>(
+        g, t, [&](uint32_t id) { return fespair::key_of(g.r, id); },
+        [&](unsigned long long particles) {
+            count[3] += 1;
+            count[4] += particles;
+        },
+        [&](uint32_t, uint32_t len, uint32_t na, uint32_t, uint32_t total) {
             for (uint32_t e = threadIdx.x; e < total; e += kPairThreads) {
                 if (LIKE) {
                     const uint32_t l = pair_segment_of(seg_a, len, e);
@@ -489,10 +523,7 @@ __global__ __launch_bounds__(kPairThreads) void pair_collide_kernel(PairArgs<T> 
                     if (changed) pair_store(slab_f, pad_f, sf, vf);
                 }
             }
-            __syncthreads();   // (the run's tables are rewritten by the next)
-            c0 += len;
-        }
-    }
+        });
     collide_counts<kPairCounts>(count, g.counts);
 }
 

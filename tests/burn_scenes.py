@@ -7,6 +7,8 @@ precision stores exactly what the reference is given) and two scenes of their ow
     "unlike"    unlike cells from (1,1) to (130,7), each species the `many` one somewhere, ties
     "full"      six consecutive cells of one chunk: three of 1300 + 700 (the run is cut by the LDS total), one of 2048 + 2048
                 (full) and two overfull ones (2049 of either species)
+    "full_like" the like species' share of that: five consecutive cells of one chunk, 2047, 2048, 2 (the run is cut by the total in
+                front of the third) and an overfull one of 2049 behind it, then 3
     "wide"      a grid with three different edges, 5 x 6 x 7 cells: a wrong linearisation i + nx (j + ny k) aliases its cells.
                 fpic_create takes every axis of 2 nodes or more; 5 x 6 x 7 is the smallest grid with three different edges that the
                 suite already steps under both field solvers (tests/test_gpu_moments.py), so the scene runs with both, like the others
@@ -48,6 +50,9 @@ FULL_COUNTS = [(1300, 700), (1300, 700), (1300, 700), (PAIR_CELL_MAX, PAIR_CELL_
 _full = pair_scene.cell_index(np.array(FULL_CELLS, dtype=np.float64) + 0.5)
 assert sum(a + b for a, b in FULL_COUNTS[:3]) > PAIR_ENTRIES and np.all(np.diff(_full) == 1) and _full[0] // PAIR_CHUNK == _full[-1] // PAIR_CHUNK
 
+FULL_LIKE_COUNTS = [PAIR_CELL_MAX - 1, PAIR_CELL_MAX, 2, PAIR_CELL_MAX + 1, 3]       # (the first is odd: its triple saturates)
+assert sum(FULL_LIKE_COUNTS[:2]) <= PAIR_ENTRIES < sum(FULL_LIKE_COUNTS[:3]) and FULL_LIKE_COUNTS[2] <= RANK_MAX < PAIR_CELL_MAX
+
 WIDE_SHAPE = (5, 6, 7)
 WIDE_L = (5.0, 6.0, 7.0)
 WIDE_COUNTS = {(0, 0, 0): (3, 1), (4, 0, 0): (1, 1), (0, 5, 0): (7, 3), (0, 0, 6): (2, 9), (4, 5, 6): (5, 5), (1, 1, 1): (70, 20), (3, 2, 0): (1, 0)}
@@ -83,6 +88,8 @@ def particles(name):
         out = dict(like=False, a=(s["pos_a"], s["vel_a"]), b=(s["pos_b"], s["vel_b"]))
     elif name == "full":
         out = dict(like=False, a=pair_scene.populate([c[0] for c in FULL_COUNTS], 61, 0.01, FULL_CELLS), b=pair_scene.populate([c[1] for c in FULL_COUNTS], 62, 0.008, FULL_CELLS))
+    elif name == "full_like":
+        out = dict(like=True, a=pair_scene.populate(FULL_LIKE_COUNTS, 65, 0.01, FULL_CELLS[:len(FULL_LIKE_COUNTS)]), b=None)
     elif name == "wide":
         shape, L = WIDE_SHAPE, WIDE_L
         cells = list(WIDE_COUNTS)
@@ -135,4 +142,4 @@ def reference(name, which, dtype=np.float32, tracked_b=False):
     return _reference[key]
 
 
-SCENES = ("like", "unlike", "full", "wide")
+SCENES = ("like", "unlike", "full", "full_like", "wide")

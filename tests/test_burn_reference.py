@@ -221,6 +221,9 @@ def test_the_conditions_of_the_gpu_scenes(name):
     assert sc.RANK_MAX + 1 in np.bincount(sc.stored("like", np.float32)[0]["cell"]) and (like["g"] == 0).sum() == 1 and like["what"][like["g"] == 0][0] == 1
     full = sc.reference("full", "saturated")[1]
     assert full["overfull_cells"] == 2 and full["cells"] == 4 and sc.reference("full", "rare")[1]["m"] > 0
+    full = sc.reference("full_like", "saturated")[1]
+    assert full["overfull_cells"] == 1 and full["overfull_particles"] == sc.PAIR_CELL_MAX + 1 and full["cells"] == 4 and sc.reference("full_like", "rare")[1]["m"] > 0
+    assert np.bincount(sc.stored("full_like", np.float32)[0]["cell"])[sc._full[0]:sc._full[0] + 5].tolist() == sc.FULL_LIKE_COUNTS
     counts = np.bincount(sc.stored("unlike", np.float32)[0]["cell"], minlength=4096), np.bincount(sc.stored("unlike", np.float32)[1]["cell"], minlength=4096)
     pairs = set(zip(counts[0].tolist(), counts[1].tolist()))
     assert {(1, 1), (130, 7), (7, 130), (64, 64), (65, 64)} <= pairs

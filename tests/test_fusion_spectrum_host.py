@@ -88,6 +88,10 @@ def test_the_spectrum_keeps_two_workgroups_on_a_cu():
     assert (bins_max + 3) * 2 * 8 + run <= 64 * 1024 < (2 * bins_max + 2) * 2 * 8 + run            # (the cap is the power of two that fits)
     assert "fusion_tally_kernel" not in code and "pair_collide_kernel" not in code
     assert all(name in code for name in ("pair_segment_of", "pair_bitonic", "pair_load", "collide_counts"))
+    # the sort's two are reached through the walk of the pair header, which the kernel calls
+    walk = re.sub(r"//.*", "", pair)
+    walk = walk[walk.index("void pair_walk("):walk.index("void pair_collide_kernel(")]
+    assert "pair_walk" in code and all(name in walk for name in ("pair_segment_of", "pair_bitonic"))
     core = open(os.path.join(CSRC, "fes_fusion_spectrum_core.hpp")).read()
     assert "2^23" in core and "NOTHING DETECTS AN OVERFLOW" in core
 

@@ -146,7 +146,7 @@ def test_against_the_reference(fp, precision, solver, name):
         app = check_application(box, before, got, sc.TAUS[which], tracked)
         print("%s %s %s %s: %s" % (name, precision, solver, which, {c: got[c] for c in COUNTS}))
         if which == "rare":
-            assert app["m"] > 0 or name != "full"
+            assert app["m"] > 0 or name not in ("full", "full_like")
         if which == "many":
             assert app["blocked"] > 0
         if which == "saturated":
@@ -155,6 +155,8 @@ def test_against_the_reference(fp, precision, solver, name):
             assert app["cells"] == sum(1 for a, b in sc.WIDE_COUNTS.values() if min(a, b) > 0) and (which != "saturated" or app["m"] > 10)
         if name == "full":
             assert app["overfull_cells"] == 2 and app["overfull_particles"] == sc.PAIR_CELL_MAX + 1 + 3 + 10 + sc.PAIR_CELL_MAX + 1
+        if name == "full_like":
+            assert app["overfull_cells"] == 1 and app["overfull_particles"] == sc.PAIR_CELL_MAX + 1 and app["cells"] == 4
         box.sim.destroy()
 
 
