@@ -83,26 +83,25 @@ class Box:
                            like=self.like, **dict(sc.SEEDS, **kw))
 
 
-def same_group(got, want, count, mass, charge):
+def same_group(got, want, count, mass, charge, weight=sc.W):
     """a group of the result against the exact sums of the reference's rows, and the doubles derived from them"""
     assert got["energy_fixed"] == want["energy_fixed"] and got["momentum_fixed"] == want["momentum_fixed"], (got, want)
-    d = iref.derived(want, count, mass, charge, sc.W)
+    d = iref.derived(want, count, mass, charge, weight)
     assert got["energy"] == d["energy"] and got["momentum"] == d["momentum"] and got["charge"] == d["charge"], (got, d)
 
 
-def check_application(box, before, got, tau, tracked=True, **kw):
-    """one application `got` to the state `before` (Box.held()): everything bit for bit.  Returns the reference's application"""
-    sim = box.sim
-    T = DTYPE[box.precision]
-    A, B = box.side(before, box.a), None if box.like else box.side(before, box.b)
-    (_, pop3), (_, pop4) = before[box.p3], before[box.p4]
-    app = ref.application(box.request(tau, tracked, **kw), A, B, pop3["n"], pop3["id_span"], pop4["n"], pop4["id_span"], tracked_b=tracked)
+def check_against(sim, app, species, before, got, mass, charge, weight=sc.W, other=(sc.MN, 0.0)):
+    """one application `got` of a handle against the reference's `app` of the state `before` ({k: (rows, population)}, read
+    before it): everything bit for bit.  species = (a, b or None: a with itself, p3, p4 or None: the fourth particle leaves the
+    box and has other = (mass, charge)); mass, charge: per species"""
+    a, b, p3, p4 = species
+    T = before[a][0][2].dtype
     assert ref.conditions_hold(app)
     assert {k: got[k] for k in COUNTS} == {k: app[k] for k in COUNTS}, ({k: got[k] for k in COUNTS}, {k: app[k] for k in COUNTS})
     assert got["applications"] == 1 and got["accepted"] == got["burnt"] + got["blocked"]
     m = app["m"]
     # the survivors: every bit, their ids, their order
-    for k, keep in ((box.a, app["keep_a"]), (box.b, app["keep_b"])):
+    for k, keep in ((a, app["keep_a"]), (b, app["keep_b"])):
         if k is None:
             continue
         was = before[k][0]
@@ -110,12 +109,11 @@ def check_application(box, before, got, tau, tracked=True, **kw):
         now = sim.population(k)
         assert now["n"] == int(keep.sum()) and now["id_span"] == before[k][1]["id_span"]
     # the products: behind the old rows, ids from the id span on in the order of the species_a reactants' ids
-    for k, name in ((box.p3, "product_a"), (box.p4, "product_b")):
+    for k, name in ((p3, "product_a"), (p4, "product_b")):
+        if k is None:
+            continue
         was, pop = before[k]
         held = rows(sim, k)
-        if name == "product_b" and not tracked:
-            assert same_rows(held, was) and sim.population(k) == pop
-            continue
         new = app[name]
         assert new["velocity"].dtype == T and len(held[0]) == pop["n"] + m
         assert same_rows(tuple(x[:pop["n"]] for x in held), was), name
@@ -124,10 +122,20 @@ def check_application(box, before, got, tau, tracked=True, **kw):
         assert bits(held[2][pop["n"]:], new["velocity"]), (name, int((held[2][pop["n"]:] != new["velocity"]).sum()))
         now = sim.population(k)
         assert now["n"] == pop["n"] + m and now["id_span"] == pop["id_span"] + m
-    same_group(got["reactant_a"], app["lost_a"], app["lost_a"]["count"], sc.MD, sc.QP)
-    same_group(got["reactant_b"], app["lost_b"], app["lost_b"]["count"], sc.MD if box.like else sc.MT, sc.QP)
-    same_group(got["product_a"], app["gain_a"], m, sc.MA, 2 * sc.QP)
-    same_group(got["product_b"], app["gain_b"], m, sc.MP if tracked else sc.MN, sc.QP if tracked else 0.0)
+    same_group(got["reactant_a"], app["lost_a"], app["lost_a"]["count"], mass[a], charge[a], weight)
+    same_group(got["reactant_b"], app["lost_b"], app["lost_b"]["count"], mass[a if b is None else b], charge[a if b is None else b], weight)
+    same_group(got["product_a"], app["gain_a"], m, mass[p3], charge[p3], weight)
+    same_group(got["product_b"], app["gain_b"], m, other[0] if p4 is None else mass[p4], other[1] if p4 is None else charge[p4], weight)
+
+
+def check_application(box, before, got, tau, tracked=True, **kw):
+    """one application `got` to the state `before` (Box.held()): everything bit for bit.  Returns the reference's application"""
+    A, B = box.side(before, box.a), None if box.like else box.side(before, box.b)
+    (_, pop3), (_, pop4) = before[box.p3], before[box.p4]
+    app = ref.application(box.request(tau, tracked, **kw), A, B, pop3["n"], pop3["id_span"], pop4["n"], pop4["id_span"], tracked_b=tracked)
+    check_against(box.sim, app, (box.a, box.b, box.p3, box.p4 if tracked else None), before, got, box.mass, box.charge)
+    if not tracked:      # the species that was not named keeps every row
+        assert same_rows(rows(box.sim, box.p4), before[box.p4][0]) and box.sim.population(box.p4) == before[box.p4][1]
     return app
 
 

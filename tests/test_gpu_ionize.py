@@ -116,27 +116,29 @@ def value_bound(req, ids, v, out):
     return bounds[0], bounds[1], e_vb
 
 
-def same_gain(got, vel, count, mass, charge):
+def same_gain(got, vel, count, mass, charge, weight=WEIGHT):
     """a target's group of the result against the exact sums of the rows it gained, and the doubles derived from them"""
     want = ref.gain(vel)
     assert got["energy_fixed"] == want["energy_fixed"] and got["momentum_fixed"] == want["momentum_fixed"], (got, want)
-    d = ref.derived(want, count, mass, charge, WEIGHT)
+    d = ref.derived(want, count, mass, charge, weight)
     assert got["energy"] == d["energy"] and got["momentum"] == d["momentum"] and got["charge"] == d["charge"], (got, d)
 
 
-def check_application(sim, precision, kw, electron, before, targets, got, figures=None, known=None):
+def check_application(sim, precision, kw, electron, before, targets, got, figures=None, known=None, ion=1, lengths=L, weight=WEIGHT, masses=(ME, ME, MI),
+                      charges=(-QE, -QE, QE), projectile=0):
     """one application `got` of the request kw to the projectile rows `before` (ids, position, velocity of species 0, read
     before it), `targets` the (rows, population) of the electron and the ion species before it: everything exact, and the
-    rounded velocities within the bound"""
+    rounded velocities within the bound.  projectile, ion: the projectile species and the ion target; lengths, weight: the box's;
+    masses, charges: of the projectile, the electron and the ion species (the defaults are this module's box)"""
     T = DTYPE[precision]
-    req = ref.request(L, **kw)
+    req = ref.request(lengths, **kw)
     (rows_e, pop_e), (rows_i, pop_i) = targets
     app = ref.application(req, before[0], before[1], before[2], pop_e["n"], pop_e["id_span"], pop_i["n"], pop_i["id_span"], known=known)
     assert ref.margins_hold(req, app)
     m = app["m"]
     assert {k: got[k] for k in ("candidates", "below", "above", "ionised")} == ref.counts(app) and got["applications"] == 1
-    after = rows(sim, 0)
-    new_e, new_i = rows(sim, electron), rows(sim, 1)
+    after = rows(sim, projectile)
+    new_e, new_i = rows(sim, electron), rows(sim, ion)
     old = slice(0, len(before[0]))
     # the projectiles: the same ids and positions; exactly the primaries have new velocities
     assert bits(after[0][old], before[0]) and bits(after[1][old], before[1])
@@ -145,21 +147,21 @@ def check_application(sim, precision, kw, electron, before, targets, got, figure
     # the new rows: behind the old ones, ids from the id span on in the order of the primaries' ids, the primaries' positions
     for name, held, (was, pop) in (("electron", new_e, targets[0]), ("ion", new_i, targets[1])):
         assert len(held[0]) == pop["n"] + m
-        if not (electron == 0 and name == "electron"):                         # (the projectile species' own old rows: checked above)
+        if not (electron == projectile and name == "electron"):                # (the projectile species' own old rows: checked above)
             assert same_rows(tuple(x[:pop["n"]] for x in held), was), name
         assert bits(held[0][pop["n"]:], (pop["id_span"] + np.arange(m)).astype(np.uint32)), name
         assert bits(held[1][pop["n"]:], app[name]["position"]), name
-        now = sim.population(electron if name == "electron" else 1)
+        now = sim.population(electron if name == "electron" else ion)
         assert now["n"] == pop["n"] + m and now["id_span"] == pop["id_span"] + m
     ve, vi = new_e[2][pop_e["n"]:], new_i[2][pop_i["n"]:]
     # the tallies: the integers Python computes from the read-back rows, and the doubles derived from them
     t = fref.tallies(before[2], after[2][old], app["event"])
     p = got["primary"]
     assert p["energy_fixed"] == t["work_fixed"] and p["momentum_fixed"] == t["impulse_fixed"] and p["charge"] == 0.0
-    d = fref.derived(t, ME, WEIGHT)
+    d = fref.derived(t, masses[0], weight)
     assert p["energy"] == d["work"] and p["momentum"] == d["impulse"]
-    same_gain(got["electron"], ve, m, ME, -QE)
-    same_gain(got["ion"], vi, m, MI, QE)
+    same_gain(got["electron"], ve, m, masses[1], charges[1], weight)
+    same_gain(got["ion"], vi, m, masses[2], charges[2], weight)
     if not m:
         return 0.0
     # the rounded velocities

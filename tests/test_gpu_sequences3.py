@@ -216,9 +216,10 @@ def sinks_and_sources(m, sc, t, sums, applied, held=None):
             applied[i] += 1
 
 
-def manual_substeps3(fp, m, sc, k, t, sums, due, applied, held=None):
+def manual_substeps3(fp, m, sc, k, t, sums, due, applied, held=None, tail=None):
     """the manual equivalent of substeps(k) on the mate, which has run beside A from the start (its own count of sub-steps is
-    A's: a one-shot force needs no shift of its epoch), in the hook's order; returns t"""
+    A's: a one-shot force needs no shift of its epoch), in the hook's order; tail(m, t): the operators a later generation has
+    behind the sources and before the recorder rows; returns t"""
     ce, pe, ge, fe, se, rec = sc["collide_every"], sc["pair_every"], sc["gas_every"], sc["fusion_every"], sc["spectrum_every"], sc["recorders"]
     for _ in range(k):
         m.substeps(1)
@@ -236,6 +237,8 @@ def manual_substeps3(fp, m, sc, k, t, sums, due, applied, held=None):
         if t % se["every"] == 0:
             add_ints(sums["spectrum"], m.fusionSpectrum(se["a"], se["b"], **dict(se["kw"], epoch=t + se["kw"]["epoch"])))
         sinks_and_sources(m, sc, t, sums, applied, held)
+        if tail is not None:
+            tail(m, t)
         if t % rec["energy"]["every"] == 0:
             row = np.zeros(1, dtype=fp.ENERGY_DTYPE)
             row[0] = m._energy_row("global")
@@ -563,6 +566,36 @@ def stats3_of(sim, sc):
     return out
 
 
+def end_of_registered_run(a, c, sc, sums, due, t, families=None, stats=None):
+    """the end of a run with registered operators: A's and C's totals are the sums of the mate's one-shot results, every
+    family was due as often as its period says, A's three histories are the mate's rows"""
+    families, stats = families or families_of, stats or stats3_of
+    have, theirs = stats(a, sc), stats(c, sc)
+    for key in families(sc):
+        assert equal_sums(have[key], sums[key]) and have[key] == theirs[key], (sc["seed"], key, {k: v for k, v in have[key].items() if k != "grid"}, {k: v for k, v in sums[key].items() if k != "grid"})
+    lo, hi = sc["force_window"]
+    assert sums["force0"]["applications"] == hi - lo + 1 and sums["force1"]["applications"] == t
+    assert all(sums[key]["applications"] == t // sc[key + "_every"]["every"] >= 3 for key in ("collide", "pair", "gas", "fusion", "spectrum"))
+    assert all(sums["remove%d" % i]["applications"] == t // op["every"] and sums["remove%d" % i]["removed"] > 0 for i, op in enumerate(sc["remove_every"]))
+    assert all(sums["inject%d" % i]["injected"] == op["kw"]["count"] * (t // op["every"]) > 0 for i, op in enumerate(sc["inject_every"]))
+    rec = sc["recorders"]
+    erows, edropped = a.energyHistory()
+    hist, sdropped = a.seriesHistory()
+    msub, mout, _, mdropped = a._modes_history_rows("global")
+    erows = erows.copy()
+    assert int(erows["substep"][-1]) == t // rec["energy"]["every"] * rec["energy"]["every"]
+    labels = dict(energy=[int(x) for x in erows["substep"]], series=hist["substep"].tolist(), modes=msub.tolist())
+    erows["substep"] = 0
+    got_rows = dict(energy=[erows[i:i + 1].tobytes() for i in range(len(erows))],
+                    series=[hist["points"][i].tobytes() + hist["tracers"][i].tobytes() for i in range(len(hist["substep"]))],
+                    modes=[mout[i].tobytes() for i in range(len(msub))])
+    for name, dropped in (("energy", edropped), ("series", sdropped), ("modes", mdropped)):
+        cap = rec[name]["capacity"]
+        assert dropped == len(due[name]) - cap > 0, (name, dropped, len(due[name]))
+        assert labels[name] == [tt for tt, _ in due[name][-cap:]], (name, labels[name])
+        assert got_rows[name] == [row for _, row in due[name][-cap:]], (sc["seed"], name)
+
+
 def run_sequence3(fp, sc, steps, tmp_path, monkeypatch):
     ns = len(sc["counts"])
     caps = model.reserved3(sc, model.substeps_of(steps)) if sc["registered"] else None
@@ -645,30 +678,7 @@ def run_sequence3(fp, sc, steps, tmp_path, monkeypatch):
             before = sa if end else before
     assert a.stats()["sort_passes"] > passes0 and mated > 0 and (sc["registered"] or twins > 0), (sc["seed"], mated, twins)
     if sc["registered"]:
-        have, theirs = stats3_of(a, sc), stats3_of(c, sc)
-        for key in families_of(sc):
-            assert equal_sums(have[key], sums[key]) and have[key] == theirs[key], (sc["seed"], key, {k: v for k, v in have[key].items() if k != "grid"}, {k: v for k, v in sums[key].items() if k != "grid"})
-        lo, hi = sc["force_window"]
-        assert sums["force0"]["applications"] == hi - lo + 1 and sums["force1"]["applications"] == t
-        assert all(sums[key]["applications"] == t // sc[key + "_every"]["every"] >= 3 for key in ("collide", "pair", "gas", "fusion", "spectrum"))
-        assert all(sums["remove%d" % i]["applications"] == t // op["every"] and sums["remove%d" % i]["removed"] > 0 for i, op in enumerate(sc["remove_every"]))
-        assert all(sums["inject%d" % i]["injected"] == op["kw"]["count"] * (t // op["every"]) > 0 for i, op in enumerate(sc["inject_every"]))
-        rec = sc["recorders"]
-        erows, edropped = a.energyHistory()
-        hist, sdropped = a.seriesHistory()
-        msub, mout, _, mdropped = a._modes_history_rows("global")
-        erows = erows.copy()
-        assert int(erows["substep"][-1]) == t // rec["energy"]["every"] * rec["energy"]["every"]
-        labels = dict(energy=[int(x) for x in erows["substep"]], series=hist["substep"].tolist(), modes=msub.tolist())
-        erows["substep"] = 0
-        got_rows = dict(energy=[erows[i:i + 1].tobytes() for i in range(len(erows))],
-                        series=[hist["points"][i].tobytes() + hist["tracers"][i].tobytes() for i in range(len(hist["substep"]))],
-                        modes=[mout[i].tobytes() for i in range(len(msub))])
-        for name, dropped in (("energy", edropped), ("series", sdropped), ("modes", mdropped)):
-            cap = rec[name]["capacity"]
-            assert dropped == len(due[name]) - cap > 0, (name, dropped, len(due[name]))
-            assert labels[name] == [tt for tt, _ in due[name][-cap:]], (name, labels[name])
-            assert got_rows[name] == [row for _, row in due[name][-cap:]], (sc["seed"], name)
+        end_of_registered_run(a, c, sc, sums, due, t)
     for sim in (a, c, m):
         sim.destroy()
     return held

@@ -703,3 +703,296 @@ def test_the_arithmetic_of_the_generation_3_named_sequences():
             assert all(model.RESUME_T % op["every"] == 0 for op in sc["inject_every"] + sc["remove_every"]) and len(sc["remove_every"]) == int(sink)
             assert sc["capacities"][:2] == [sc["counts"][s] + sc["inject_every"][s]["kw"]["count"] * -(-model.RESUME_N // sc["inject_every"][s]["every"]) for s in range(2)]
             assert plain(sc["inject_every"][0]["kw"]) == plain(sc["inject_every"][1]["kw"])
+
+
+# ================================================================================================ generation 4
+def facts4(seed):
+    """(bad, cover) of a generation-4 seed: the conditions it breaks that every seed must meet, and what it adds to the
+    coverage.  The events are the references' on the scene's initial particles (ionize_reference.application,
+    burn_reference.application with the cells of cells_of)."""
+    import burn_reference as bref
+    import ionize_reference as iref
+    import remove_reference as rr
+    sc, steps = model.scene4(seed), model.sequence4(seed)
+    base = model.scene3(seed)
+    state = model.initial_state3(sc)
+    roles = sc["roles"]
+    bad, cover = [], set()
+    total = model.substeps_of(steps)
+    nb = len(base["counts"])
+    ok = (sc["counts"][:nb] == base["counts"] and sc["masses"][:nb] == base["masses"] and set(sc["counts"][nb:]) == {1} and steps[0]["kind"] == "substeps"
+          and (sc["masses"][roles["p3"]], sc["charges"][roles["p3"]]) == (4 * model.MP, -2 * model.QE) and (sc["masses"][roles["p4"]], sc["charges"][roles["p4"]]) == (model.MP, -model.QE)
+          and (roles["electron"] == 0 or (sc["masses"][roles["electron"]], sc["charges"][roles["electron"]]) == (model.ME, model.QE))
+          and all(plain(sc[k]) == plain(base[k]) for k in ("seed", "solver", "precision", "sort_interval", "staged", "shape", "L", "dt", "macro_weight", "addB", "registered"))
+          and any(r["kind"] == "saveCheckpoint" for r in steps[0]["reads"]) and sc["empty"] == ([roles["p3"]] if sc["registered"] else []))
+    if not ok:
+        bad.append("scene")
+    cover |= {("scene", sc["solver"], sc["registered"]), ("scene", sc["precision"], sc["registered"])} | ({("scene", "staged", sc["registered"])} if sc["staged"] else set())
+    re = model.can_have_rebinned4(sc, steps)
+    kinds = [st["kind"] for st in steps]
+    want_reads = (6 + len(model.STATS_KINDS4)) if sc["registered"] else model.READS3
+    saved, thinned, t = 0, set(sc["empty"]), 0
+    burnt = grown = thins_product = False      # since the last rewind or renumber: a burn has thinned somebody, an ionisation has grown somebody
+    first_removal = next(i for i, k in enumerate(kinds) if k in model.REMOVE_KINDS3)
+    for i, st in enumerate(steps):
+        kind = st["kind"]
+        reads = [r["kind"] for r in st["reads"]]
+        if kind not in model.STATE_KINDS4 or len(reads) != want_reads or len(set(reads)) != want_reads or not set(reads) <= set(model.READ_KINDS2 + model.STATS_KINDS4):
+            bad.append(("reads", i))
+        if st["thinned"] != sorted(thinned):
+            bad.append(("thinned", i))
+        if st["refused"] != ((kind in model.CALLER_ORDER_KINDS3 and st["species"] in thinned) or (kind == "renumber" and sc["registered"] and bool(thinned))) or (st["refused"] and st["precalc"]):
+            bad.append(("refused", i))
+        if kind in model.NEW_KINDS4:
+            cover |= {("new", kind, sc["solver"]), ("new", kind, sc["precision"]), ("new", kind, sc["registered"])} | ({("new", kind, "staged")} if sc["staged"] else set())
+            if i and re[i - 1]:
+                cover.add(("rebinned", kind))
+        elif burnt and grown:
+            cover.add(("burnt and grown", kind))
+        # the events, on the initial particles
+        if kind in model.IONIZE_KINDS4:
+            req, app = model.ionize_want(sc, state, st)
+            share = app["m"] / model.N0
+            if not iref.margins_hold(req, app) or not (app["m"] == 0 if kind == "ionize_nothing" else app["m"] >= 2 if kind == "ionize_refused" else 1 <= app["m"] and share <= 0.5):
+                bad.append(("ionised", i, kind, app["m"]))
+            if kind != "ionize_nothing" and not (st["g_threshold"] <= st["kw"]["g_lo"] < st["kw"]["g_hi"]):
+                bad.append(("threshold", i))
+            if kind == "ionize":
+                cover.add(("ionize into", "a separate species" if st["electron"] != 0 else "its projectiles, thinned" if 0 in thinned else "its projectiles"))
+                cover.add(("ionize at the threshold", st["g_threshold"] == st["kw"]["g_lo"]))
+        elif kind in model.BURN_KINDS4 + ("burn_nothing", "burn_refused"):
+            req, app = model.burn_want(sc, state, st)
+            left = [int(app["keep_a"].sum())] + ([int(app["keep_b"].sum())] if st["b"] is not None else [])
+            if not bref.conditions_hold(app) or not (app["m"] == 0 if kind == "burn_nothing" else app["m"] >= 2 if kind == "burn_refused" else app["m"] >= 4 and min(left) >= 1):
+                bad.append(("burnt", i, kind, app["m"]))
+            if st["saturated"] and not (app["accepted"] > app["burnt"] > 0 and app["saturated"] > 0 and app["blocked"] > 0):
+                bad.append(("saturated", i, app["accepted"], app["burnt"], app["saturated"]))
+            if kind in model.BURN_KINDS4:
+                cover |= {("burn", st["form"]), ("burn tracked", st["products"][1] is not None)}
+            if kind == "burn_nothing":
+                cover.add(("burn_nothing", st["nothing"]))
+        if kind == "reserve" and st["extra"] >= 1024 and st["species"] in (roles["p3"], roles["p4"]):
+            cover.add(("reserve across a stride on a product",))
+        if kind == "loadCheckpoint" and burnt:
+            cover.add(("loadCheckpoint after a burn",))
+        if kind == "loadCheckpoint" and not st["file"] < saved:
+            bad.append(("file", i))
+        if kind in model.POSITION_KINDS2 and st["what"] != "velocity" and sc["solver"] != "none" and not (st["precalc"] or st["refused"]):
+            bad.append(("precalc", i))
+        if kind in model.REMOVE_KINDS3 + ("remove_nothing",) and st["species"] != roles["p3"]:
+            s = state[st["species"]]
+            share = rr.removed_mask(s["ids"], s["frac"], s["vel"], st["where"], st["every"], st["outside"]).mean()
+            if not (share == 0 if kind == "remove_nothing" else 0.05 <= share <= 0.8):
+                bad.append(("share", i, kind, float(share)))
+        if kind in model.REMOVE_KINDS3 and st["species"] == roles["p3"]:      # (the product's removal: one of two of the consecutive ids the block's burn has made)
+            if not (i == first_removal + 6 and st["where"] is None and st["every"][0] == 2 and not st["outside"]):
+                bad.append(("the product's removal", i))
+            thins_product = True
+        if kind in model.BURN_KINDS4 and roles["p3"] in thinned:
+            cover.add(("burn into a thinned product", sc["registered"]))
+        if kind.startswith("force_") and st["t"] != model.substeps_of(steps[:i]):
+            bad.append(("force t", i))
+        # the model's account, restated
+        t += st.get("k", 0)
+        if kind in model.REMOVE_KINDS3:
+            thinned.add(st["species"])
+        elif kind in model.BURN_KINDS4:
+            thinned |= {st["a"]} | ({st["b"]} if st["b"] is not None else set())
+            burnt = True
+        elif kind == "ionize":
+            grown = True
+        elif kind == "loadCheckpoint" or (kind == "renumber" and not st["refused"]):
+            thinned.clear()
+            burnt = grown = False
+        elif kind == "substeps" and sc["registered"]:
+            thinned |= {op["species"] for op in sc["remove_every"] if t >= op["every"]}
+            bu = sc["burn_every"][0]
+            if t >= bu["every"]:
+                thinned |= {bu["a"]} | ({bu["b"]} if bu["b"] is not None else set())
+                burnt = True
+            grown = grown or t >= sc["ionize_every"][0]["every"]
+        if st["thinned_after"] != sorted(thinned):
+            bad.append(("thinned after", i))
+        if burnt and grown:
+            cover |= {("read burnt and grown", r) for r in reads}
+        for r in st["reads"]:
+            want = (r["kind"] in model.CALLER_ORDER_READS3 and r["species"] in thinned) or (r["kind"] == "saveCheckpoint" and bool(thinned))
+            if bool(r.get("refused")) != want:
+                bad.append(("refused read", i, r["kind"]))
+        saved += sum("file" in r for r in st["reads"])
+    if not set(model.NEW_KINDS4) <= set(kinds) or not thins_product:
+        bad.append("a new kind is missing")
+    # the forced block: the first removal, a re-binning substeps, an ionize, such a substeps, the saturated burn, such a substeps; both fusion reads behind each
+    first = next(i for i, k in enumerate(kinds) if k in model.REMOVE_KINDS3)
+    block = steps[first:first + 6]
+    pushes = [block[1], block[3], block[5]]
+    end = next((i for i in range(first + 1, len(steps)) if kinds[i] in ("renumber", "loadCheckpoint") and not steps[i]["refused"]), len(steps))
+    if not (first <= 2 and [b["kind"] for b in block[::2]][1] == "ionize" and block[4]["kind"] in model.BURN_KINDS4 and block[4]["saturated"] and end >= first + 7
+            and all(p["kind"] == "substeps" and p["k"] >= sc["sort_interval"] + 1 and {"fusionYield", "fusionSpectrum"} <= {r["kind"] for r in p["reads"]} for p in pushes)
+            and not any(k in model.REMOVE_KINDS3 + ("renumber", "loadCheckpoint") for k in kinds[:first])):
+        bad.append("block")
+    if re[first + 3] and re[first + 5]:      # the block's burn and the substeps behind it meet a handle that a fused re-binning push has reordered
+        cover.add(("the block re-bins", seed))
+    if sc["registered"]:
+        rec = sc["recorders"]
+        if not all(total // rec[k]["every"] > rec[k]["capacity"] for k in rec):
+            bad.append("a ring does not wrap")
+        a, b = sc["force_window"]
+        if not (1 < a and b < total and b - a + 1 >= 3):
+            bad.append(("envelope", a, b, total))
+        ops = [sc[key] for key in ("collide_every", "pair_every", "gas_every", "fusion_every", "spectrum_every")] + sc["ionize_every"] + sc["burn_every"]
+        if not all(total // op["every"] >= 3 for op in ops):
+            bad.append("due")
+        for op in sc["remove_every"]:
+            s = state[op["species"]]
+            share = rr.removed_mask(s["ids"], s["frac"], s["vel"], op["where"], op["every_id"], op["outside"]).mean()
+            if not 0.05 <= share <= 0.8:
+                bad.append(("sink", float(share)))
+        ionised, burnt0 = model.hook_events4(sc)
+        if not (ionised > 0 and burnt0 > 0):
+            bad.append(("the hook's first applications", ionised, burnt0))
+        # the chain: the first burner's product_a species is a reactant of the second, which is due behind the every-third sink of species 1
+        b1, b2 = sc["burn_every"]
+        if not (b1["products"] == [roles["p3"], roles["p4"]] and b2["a"] == roles["p3"] and b2["b"] == 1 and b2["products"] == [roles["p4"], None] and b2["every"] == 3
+                and any(op["species"] == 1 and op["every"] == 3 for op in sc["remove_every"]) and b1["a"] == 0 and sc["ionize_every"][0]["species"] == 0):
+            bad.append("chain")
+        # the capacities: generation 3's, and HOOK_GROWTH4 times the events on the initial particles per application
+        cap, cap3 = model.reserved4(sc, total), model.reserved3(sc, total)
+        gi = max(model.HOOK_GROWTH4 * ionised, model.HOOK_FLOOR4) * (total // sc["ionize_every"][0]["every"])
+        gb = max(model.HOOK_GROWTH4 * burnt0, model.HOOK_FLOOR4) * (total // b1["every"])
+        want = list(cap3)
+        want[roles["electron"]] += gi
+        want[1] += gi
+        want[roles["p3"]] += gb
+        want[roles["p4"]] += 2 * gb
+        if cap != want:
+            bad.append("reserved")
+    return bad, cover
+
+
+def required4():
+    want = {("scene", x, r) for x in model.SOLVERS + ("fp32", "fp64", "staged") for r in (False, True)}
+    want |= {("new", k, x) for k in model.NEW_KINDS4 for x in model.SOLVERS + ("fp32", "fp64", "staged", False, True)}
+    want |= {("rebinned", k) for k in model.NEW_KINDS4}
+    want |= {("burnt and grown", k) for k in model.STATE_KINDS3} | {("read burnt and grown", r) for r in model.READ_KINDS2 + model.STATS_KINDS4}
+    want |= {("ionize into", "a separate species"), ("ionize into", "its projectiles, thinned"), ("ionize at the threshold", False), ("ionize at the threshold", True),
+             ("burn", "like"), ("burn", "unlike"), ("burn tracked", False), ("burn tracked", True), ("burn_nothing", "above"), ("burn_nothing", "tau"),
+             ("loadCheckpoint after a burn",), ("reserve across a stride on a product",), ("burn into a thinned product", False), ("burn into a thinned product", True)}
+    return want
+
+
+_facts4 = {}
+
+
+def facts4_of(seed):
+    if seed not in _facts4:
+        _facts4[seed] = facts4(seed)
+    return _facts4[seed]
+
+
+# sha256 (first 16 hex digits) of plain(scene4) + plain(sequence4) per committed seed, of the named scenes and of the resumes
+DIGESTS4 = {
+    "seeds": {0: "7e1f27ab466ef938", 2: "4b048f5426925b42", 12: "c82d412f9be55d7d", 13: "5a817ebf65a2f483", 21: "1fc9060b0082b6ed", 59: "4bf89f4c4cd757ed", 111: "6e5907555f46c56e", 129: "a085ce7c92bc6aa4", 131: "be127c67cb049395", 149: "aa9f56720c424ae9", 165: "9ce0e4507a5942a4", 187: "f47df5e105e67d2d"},
+    "chain": ["2c3afeb18b441edc", "0204019995dd81b2"],
+    "named": ["acaf39bfe0d4abaf", "255d8faa414e2e42", "5731d5cadbb794f6"],
+    "resume": ["6f5cf24cf89d3af5", "157131ec783851d1", "33c067b578e6f1dc", "236a096cf98ac261"],
+}
+
+
+def digests4():
+    return {"seeds": {seed: digest(model.scene4(seed), model.sequence4(seed)) for seed in model.SEEDS4},
+            "chain": [digest(model.chain(*case), []) for case in model.CHAIN_CASES],
+            "named": [digest(model.reserve_after_register(), []), digest(model.hook_order(), []), digest(model.burner_fails_behind_an_ioniser(), [])],
+            "resume": [digest(model.resume_scene4(*r, burner), []) for r in model.RESUME for burner in (False, True)]}
+
+
+def test_generation_4_is_deterministic_and_leaves_generations_1_to_3_alone():
+    assert len(model.SEEDS4) == len(set(model.SEEDS4)) == 12
+    for seed in model.SEEDS4[:3]:
+        assert plain(model.scene4(seed)) == plain(model.scene4(seed)) and plain(model.sequence4(seed)) == plain(model.sequence4(seed))
+    assert plain(model.sequence4(model.SEEDS4[0])) != plain(model.sequence4(model.SEEDS4[1]))
+    assert digests4() == DIGESTS4
+    # generations 1 to 3 digest as before (generation 3's scenes are generation 2's on the unit box, its steps use generation 2's draws)
+    assert {seed: digest(model.scene(seed), model.sequence(seed)) for seed in model.SEEDS} == DIGESTS["seeds"]
+    assert {seed: digest(model.scene3(seed), model.sequence3(seed)) for seed in model.SEEDS3} == DIGESTS3["seeds"]
+    assert model.STATE_KINDS4[:len(model.STATE_KINDS3)] == model.STATE_KINDS3 and len(set(model.STATE_KINDS4)) == len(model.STATE_KINDS3) + 8
+    assert model.STATS_KINDS4[:len(model.STATS_KINDS3)] == model.STATS_KINDS3
+    # the scene is generation 3's with more species behind its own
+    for seed in model.SEEDS4[:3]:
+        base, sc = model.scene3(seed), model.scene4(seed)
+        n = len(base["counts"])
+        assert all(plain(sc[k]) == plain(base[k]) for k in base if k not in ("counts", "masses", "charges", "generation"))
+        assert sc["counts"][:n] == base["counts"] and sorted(sc["roles"].values()) == ([0] if sc["roles"]["electron"] == 0 else []) + list(range(n, len(sc["counts"])))
+
+
+def test_no_generation_4_seed_breaks_a_condition_every_seed_must_meet():
+    """well-formed steps; the model's own account of which species are thinned and which calls are refused, restated; the forced
+    block; on the scene's initial particles every ionize has between 1 event and 50 % of its projectiles as events, every burn
+    kind with events at least 4 and a survivor of every reactant, every *_nothing exactly none, every *_refused at least 2
+    (its target can be one slot short), the saturated burn accepted > burnt > 0 and saturated > 0, with
+    burn_reference.conditions_hold and ionize_reference.margins_hold; every registered family due three times, the hook's
+    ioniser and first burner with events at their first application, the chain's shape, the capacities by reserved4's rule"""
+    for seed in model.SEEDS4:
+        assert facts4_of(seed)[0] == [], (seed, facts4_of(seed)[0])
+
+
+def test_generation_4_reaches_what_it_is_there_for():
+    """every new kind under every solver, both precisions, with and without registered operators, with the staged binning
+    forced, and directly after a substeps that can have re-binned; every state-changing kind of generations 1 to 3 and every
+    read kind on a handle that a burn has thinned and an ionisation has grown; ionize into a thinned electron target and into a
+    separate species; a loadCheckpoint after a burn; like, unlike and untracked burns; a reserve across a stride on a product"""
+    cover = set().union(*[facts4_of(seed)[1] for seed in model.SEEDS4])
+    missing = required4() - cover
+    assert not missing, sorted(missing, key=str)
+    assert sum(1 for c in cover if c[0] == "the block re-bins") * 4 > len(model.SEEDS4)
+
+
+def test_the_arithmetic_of_the_generation_4_named_scenes():
+    import burn_reference as bref
+    import ionize_reference as iref
+    # chain: twenty sub-steps in pieces of 1, 2, 3 and 5; species 2 is the first burner's product, the second's reactant and the ioniser's projectile
+    assert sum(model.CHAIN_PIECES) == 20 and set(model.CHAIN_PIECES) == {1, 2, 3, 5}
+    for case in model.CHAIN_CASES:
+        sc = model.chain(*case)
+        b1, b2 = sc["burn_every"]
+        io = sc["ionize_every"][0]
+        assert (sc["solver"], sc["precision"]) == case and (b1["a"], b1["b"], b1["products"]) == (0, None, [2, 3]) and (b2["a"], b2["b"], b2["products"]) == (2, 1, [3, None])
+        assert (io["species"], io["kw"]["species"], io["electron"], io["ion"]) == (2, 2, 4, 1) and (case[0] != "none" or (sc["addB"] is None and sc["zero_field"]))
+        assert model.burn_want(sc, model.initial_state3(sc), b1)[1]["m"] >= 20
+    # reserve_after_register: every reserve crosses a stride of 1024; all four families on species 0 and 1, due every sub-step
+    sc = model.reserve_after_register()
+    plan = sc["plan"]
+    assert plan["reserve"] == [0, sc["roles"]["p3"], 1] and all(sc["capacities"][sp] // 1024 != (sc["capacities"][sp] + plan["extra"]) // 1024 for sp in plan["reserve"])
+    assert all(op["every"] == 1 for op in [sc["pair_every"], sc["fusion_every"]] + sc["ionize_every"] + sc["burn_every"])
+    assert (sc["pair_every"]["a"], sc["pair_every"]["b"]) == (sc["fusion_every"]["a"], sc["fusion_every"]["b"]) == (sc["burn_every"][0]["a"], sc["burn_every"][0]["b"]) == (0, 1)
+    state = model.initial_state3(sc)
+    ionised, burnt = model.hook_events4(sc)
+    # the room up front holds the applications before the reserves at HOOK_GROWTH4 times the first one's events, the room afterwards all five
+    g, p3 = model.HOOK_GROWTH4, sc["roles"]["p3"]
+    assert 0 < plan["before"] * g * ionised <= 400 and 0 < plan["before"] * g * burnt <= sc["capacities"][p3] - 1, (ionised, burnt)
+    assert (plan["before"] + plan["after"]) * g * max(ionised, burnt) <= min(400, sc["capacities"][p3] - 1) + plan["extra"]
+    assert model.fusion_want(sc, state, 0, 1, sc["fusion_every"]["kw"])[1]["reactions_exact"] > 0
+    # hook_order: on the initial particles (no beam yet) the ioniser finds only the fast fifth, and the burner's species holds one particle
+    for precision in ("fp32", "fp64"):
+        sc = model.hook_order(precision)
+        io, bu, src = sc["ionize_every"][0], sc["burn_every"][0], sc["inject_every"][0]
+        assert (src["every"], io["every"], bu["every"], src["species"], io["species"]) == (1, 1, 1, 0, 0) and bu["a"] == io["electron"] == sc["roles"]["electron"] != 0 and bu["b"] is None
+        assert sc["counts"][bu["a"]] == 1 and src["kw"]["drift"][2] == 0.8 and io["kw"]["g_lo"] == io["g_threshold"] == 0.6 and bu["p"] >= 1
+        req, app = model.ionize_want(sc, model.initial_state3(sc), io)
+        assert 0 < app["m"] < 300 and iref.margins_hold(req, app)
+        assert sc["capacities"][0] == model.N0 + sc["substeps"] * src["kw"]["count"]
+    # burner_fails_behind_an_ioniser: on the initial particles the first two applications fit the room of three but one slot and
+    # the third does not; the replay takes the events from the mate, and asserts the same
+    sc = model.burner_fails_behind_an_ioniser()
+    req, app = model.burn_want(sc, model.initial_state3(sc), sc["burn_every"][0])
+    m0 = app["m"]
+    room = model.room_of(1, [m0] * 3)
+    assert m0 >= 20 and bref.fits(1, room, 1, m0) and bref.fits(1 + m0, room, 1 + m0, m0) and not bref.fits(1 + 2 * m0, room, 1 + 2 * m0, m0)
+    assert sc["fails_at"] == 3 and sc["ionize_every"][0]["every"] == sc["burn_every"][0]["every"] == 1 and sc["capacities"][sc["roles"]["p3"]] >= 1 + 5 * 4 * m0
+    # the resumes: the cut is a multiple of every period
+    for solver, precision in model.RESUME:
+        for burner in (False, True):
+            sc = model.resume_scene4(solver, precision, burner)
+            ops = sc["inject_every"] + sc["ionize_every"] + sc["burn_every"]
+            assert all(model.RESUME_T % op["every"] == 0 for op in ops) and len(sc["burn_every"]) == int(burner) and not sc["remove_every"]
+            assert len(sc["capacities"]) == len(sc["counts"]) and sc["roles"]["electron"] != 0
